@@ -9,11 +9,18 @@ A step = the reference's training iteration on one batch (`src/run_GNN.py:99-131
 with the batch resident in HBM.  Per-GPU work is fixed (32 meshes/rank): weak scaling; the only
 collective is the all-reduce of the flat gradient bucket.
 
+The headline is W untimed warm-up steps, then exactly K timed steps between barriers + torch.cuda.synchronize() (max over
+ranks).  `--dump-outputs DIR` then writes what the last of those steps handed back or left behind (rank 0): DIR/out.npy (the
+model's output coordinates), loss.npy, grad.npy (the flat gradient the optimizer applied) and params.npy (the optimizer's flat
+parameter bucket after the update), all float32.  The batch and the initial weights are seeded and the step count before the dump
+is fixed by the arguments, so two builds run with the same arguments can be compared array for array.
+
 Extra objects on the JSON line:
   roofline     - dominant hot kernel: algorithmic bytes per launch / its measured
                  duration (HIP events on the launch stream, second instrumented pass of K steps).
   cpu_baseline - the CPU oracle (PyG-equivalent op sequence in plain torch) on the host cores, rank 0, N=1.
-  windows      - `value` / `ms_per_step` are the MEDIAN of --windows (5) timed windows of exactly K steps; min / max beside it.
+  windows      - the headline's one timed window (K steps).  The secondary timings (dense slots, GAT_plus, other workloads) take the
+                 MEDIAN of --windows windows, each the K-step block repeated until it lasts >= 50 ms; min / max beside it.
   value_dense_slots / ms_per_step_dense_slots - the same run's timing of the literal dense-slot flow.
   train_loop   - N=1: the reference's training loop (src/run_GNN.py:95-131) on SHUFFLED, CHANGING batches through
                  training.GraphedTrainStep + DeviceMeshLoader (the headline steps on one static batch).
@@ -151,7 +158,7 @@ def main():
                          '(DESIGN.md §4) instead of their compact forms')
     ap.add_argument('--cpu-seconds', type=float, default=20.0)
     ap.add_argument('--windows', type=int, default=5,
-                    help='timed windows of --steps steps each; value / ms_per_step are the MEDIAN window (min and max reported beside it)')
+                    help='timed windows of the secondary timings (dense slots, GAT_plus, other workloads); the headline times --steps steps once')
     ap.add_argument('--no-train-loop', action='store_true',
                     help='skip the third measurement: the reference training loop on SHUFFLED, changing batches (GraphedTrainStep)')
     ap.add_argument('--no-gat-plus', action='store_true',
@@ -160,6 +167,8 @@ def main():
                     help='skip the timing of the other single-GPU BASELINE.json configurations (default workload, one GPU only)')
     ap.add_argument('--no-companion', action='store_true',
                     help='skip the second timing of the other slot flow (dense when the headline is compact and vice versa)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write the last step's output, loss, gradient and updated parameters as DIR/<name>.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get('RANK', 0))
@@ -258,6 +267,9 @@ def main():
         model = GNN(ds_, opt).to(dev)
         model.train()
         optim = FlatAdam(model.parameters(), lr=opt['lr'], weight_decay=opt['decay'], capturable=True)
+        # the autograd route's latest out / loss (captured: the graph's own tensors, which every replay rewrites).  Detached: the values
+        # are kept, the step's autograd graph is not - it is released when the step ends, as it is without this record
+        last = {}
 
         def fwd_bwd():
             out = model(data_)
@@ -266,6 +278,7 @@ def main():
                 loss.backward()
             else:
                 loss.backward(gradient=root)
+            last['out'], last['loss'] = out.detach(), loss.detach()
             return loss
 
         def eager_step():
@@ -369,7 +382,14 @@ def main():
             else:
                 step_issued()
 
-        return {'opt': opt, 'model': model, 'optim': optim, 'step': step, 'fwd_bwd': (fused.forward_backward if fused is not None else fwd_bwd), 'graph': graph,
+        def outputs():
+            """What the last step handed back or left behind, as float32 host arrays."""
+            out, loss = (fused.out, fused.loss) if fused is not None else (last['out'], last['loss'])
+            grads = fused.flat if fused is not None else optim.grad_bucket
+            return {k: v.detach().float().cpu().numpy() for k, v in
+                    (('out', out), ('loss', loss), ('grad', grads), ('params', optim.bucket))}
+
+        return {'outputs': outputs, 'opt': opt, 'model': model, 'optim': optim, 'step': step, 'fwd_bwd': (fused.forward_backward if fused is not None else fwd_bwd), 'graph': graph,
                 'capture_all': cap_all, 'fused': fused is not None, 'fused_reason': fused_reason, 'launch_ab': launch_ab}
 
     def barrier():
@@ -415,7 +435,18 @@ def main():
     main_run = build_runner(args.dense_slots)
     model, optim, fwd_bwd, opt = main_run['model'], main_run['optim'], main_run['fwd_bwd'], main_run['opt']
     graph, capture_all = main_run['graph'], main_run['capture_all']
-    elapsed, windows = summarise(timed_windows(main_run['step']))     # the headline: the MEDIAN window
+    # the headline: W warm-up steps, then exactly K timed steps (no repeated blocks: the step count before the dump is the arguments')
+    for _ in range(args.warmup):
+        main_run['step']()
+    elapsed = timed_block(main_run['step'], 1)
+    windows = {'n': 1, 'steps_per_window': args.steps, 'window_ms': round(1e3 * elapsed, 3)}
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        arrays = main_run['outputs']()
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), arr)
     meshes = w['batch'] * world * args.steps
     value = meshes / elapsed
 

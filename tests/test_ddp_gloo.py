@@ -6,6 +6,7 @@ World size 8 runs BASELINE config 3's partition - 256 meshes of 64x64 nodes, 32 
 not depend on the width and the CPU oracle stays quick) - and an uneven 250-mesh split (31 / 32 per rank), each with both
 reductions: 'mean' for the mean-reduced mesh loss (run_GNN.py:106) and 'sum' for the modular pseudo-loss, a SUM over the nodes
 (run_GNN.py:118), which must come out un-scaled."""
+import io
 import os
 import socket
 
@@ -21,6 +22,19 @@ from oracle.pyg_restatement import OracleGNN
 
 def _free_port():
     s = socket.socket(); s.bind(('127.0.0.1', 0)); p = s.getsockname()[1]; s.close(); return p
+
+
+def _by_value(obj):
+    """Serialise a result for the parent.  A tensor put on a multiprocessing queue as it is travels as a shared-memory file
+    descriptor that the parent fetches from the sending process when it unpickles - after rank 0 may have exited (exit code 0,
+    result lost: ConnectionRefusedError in the parent's get).  Bytes carry the values themselves."""
+    buf = io.BytesIO()
+    torch.save(obj, buf)
+    return buf.getvalue()
+
+
+def _from_bytes(b):
+    return torch.load(io.BytesIO(b), weights_only=True)
 
 
 def _loss_grads(model, ds, idx):
@@ -55,7 +69,7 @@ def _worker(rank, world, port, out):
         refused = 'capture_optimizer=False' in str(e)
     assert refused
     if rank == 0:
-        out.put((optim.grad_bucket / n).clone())
+        out.put(_by_value((optim.grad_bucket / n).clone()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -68,7 +82,7 @@ def _run_two_ranks():
     for p in procs:
         p.start()
     try:
-        reduced = q.get(timeout=120)
+        reduced = _from_bytes(q.get(timeout=120))
     except Exception:
         reduced = None
     ok = reduced is not None
@@ -149,7 +163,7 @@ def _w8_worker(rank, world, port, n_meshes, out):
     gathered = [None] * world
     dist.all_gather_object(gathered, {k: (v if k == 'span' else (v[1], v[2])) for k, v in res.items()})
     if rank == 0:
-        out.put({'reduced': {k: res[k][0] for k in ('mesh', 'modular')}, 'per_rank': gathered})
+        out.put(_by_value({'reduced': {k: res[k][0] for k in ('mesh', 'modular')}, 'per_rank': gathered}))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -162,7 +176,7 @@ def _run_w8(n_meshes):
     for p in procs:
         p.start()
     try:
-        got = q.get(timeout=600)                                # eight single-threaded ranks on as many cores: minutes when the box is busy
+        got = _from_bytes(q.get(timeout=600))                   # eight single-threaded ranks on as many cores: minutes when the box is busy
     except Exception:
         got = None
     ok = got is not None

@@ -215,14 +215,16 @@ def test_bench_line_contract(gpu_device):
     assert rf['bound'] == 'hbm' and rf['peak'] == 8000.0 and abs(rf['frac'] - rf['achieved'] / rf['peak']) < 1e-3 and rf['unit'] == 'GB/s'
     assert cb['kind'] == 'port' and cb['cores'] >= 1 and cb['value'] > 0 and 'sample' in cb
     assert abs(d['value'] - 32 * 1000.0 / d['ms_per_step']) / d['value'] < 0.01
-    # median of >= 5 windows of K steps, and the dense-slot flow timed in the same run
+    # the headline times exactly K steps (--steps), once
     wd = d['windows']
-    # a window is the K-step block repeated until it lasts >= 50 ms
-    assert wd['n'] >= 5 and wd['steps_per_window'] == 4 * wd['blocks_per_window'] and wd['ms_per_step_min'] <= wd['ms_per_step_median'] <= wd['ms_per_step_max']
-    assert wd['window_ms_median'] >= 0.9 * wd['min_window_ms'] >= 45.0
-    assert abs(wd['ms_per_step_median'] - d['ms_per_step']) < 1e-3
-    assert d['config']['slots'] == 'compact' and d['value_dense_slots'] > 0 and d['ms_per_step_dense_slots'] >= wd['ms_per_step_min'] * 0.9
-    assert d['windows_dense_slots']['n'] >= 5
+    assert wd['n'] == 1 and wd['steps_per_window'] == 4 and abs(wd['window_ms'] / 4 - d['ms_per_step']) < 1e-3
+    # the dense-slot flow timed in the same run: median of >= 5 windows, a window the K-step block repeated until
+    # it lasts >= 50 ms
+    wdd = d['windows_dense_slots']
+    assert wdd['n'] >= 5 and wdd['steps_per_window'] == 4 * wdd['blocks_per_window'] and wdd['ms_per_step_min'] <= wdd['ms_per_step_median'] <= wdd['ms_per_step_max']
+    assert wdd['window_ms_median'] >= 0.9 * wdd['min_window_ms'] >= 45.0
+    assert abs(wdd['ms_per_step_median'] - d['ms_per_step_dense_slots']) < 1e-3
+    assert d['config']['slots'] == 'compact' and d['value_dense_slots'] > 0 and d['ms_per_step_dense_slots'] >= d['ms_per_step'] * 0.9
     # ... and the reference's training loop on shuffled, changing batches (GraphedTrainStep): same order of speed as the static-batch
     # headline (with real step counts it is within 5 %: profiles/r04_bench.json; this run times 24 steps, so the bar is loose)
     tl = d['train_loop']
@@ -240,6 +242,44 @@ def test_bench_line_contract(gpu_device):
         for k in ('kernel', 'variant', 'frac', 'avg_launch_us', 'alg_bytes_per_launch', 'profile'):
             assert k in orf, (name, k)
         assert abs(orf['frac'] - orf['alg_bytes_per_launch'] / (orf['avg_launch_us'] * 1e-6) / 8e12) < 2e-3, (name, orf)
+
+
+@pytest.mark.one_dispatch
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", [[], ['--no-fused-step']], ids=['fused-iteration', 'autograd-iteration'])
+def test_bench_dump_outputs_follow_the_step_count(gpu_device, tmp_path, route):
+    """`bench.py --dump-outputs DIR`: the last timed step's output, loss, gradient and updated parameters, float32, <= 64 MB.  W warm-up
+    + K timed steps are the steps the dump follows: (K 4, W 2) and (K 2, W 4) run the same six steps on the same seeded batch and
+    weights and dump the same arrays; (K 3, W 2) is one step short and dumps other parameters."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def dump(steps, warmup):
+        out = tmp_path / f'k{steps}_w{warmup}'
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup),
+                            '--no-companion', '--no-gat-plus', '--no-other-workloads', '--no-train-loop', '--no-cpu-baseline',
+                            '--dump-outputs', str(out)] + route, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+        assert d['steps'] == steps and d['warmup'] == warmup and d['windows']['steps_per_window'] == steps
+        assert d['config']['fused_step'] == (not route)
+        names = sorted(p.name for p in out.iterdir())
+        assert names == ['grad.npy', 'loss.npy', 'out.npy', 'params.npy'], names
+        arrays = {n[:-4]: np.load(out / n, allow_pickle=False) for n in names}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays['out'].shape == (32 * 64 * 64, 2) and arrays['loss'].size == 1
+        assert arrays['grad'].shape == arrays['params'].shape == (2 * 64 * 64 + 2 * 64,)
+        return arrays
+
+    def rel(a, b):
+        return float(np.linalg.norm((a - b).ravel()) / np.linalg.norm(b.ravel()))
+
+    a, b, c = dump(4, 2), dump(2, 4), dump(3, 2)
+    for k in a:
+        assert rel(a[k], b[k]) <= 1e-5, (k, rel(a[k], b[k]))
+    assert rel(c['params'], a['params']) > 1e-4, rel(c['params'], a['params'])
 
 
 def _fresh_trainer(ds, opt, gpu_device, state, fused=True):
