@@ -1,5 +1,6 @@
 # Builds the C-ABI shared library of the hot path for gfx950 (MI355X), in-tree.
 #   make -j8        -> g_adaptivity_amd/libgadapt_hip.so   (one object per kernel family: csrc/gadapt_internal.h)
+#                      g_adaptivity_amd/libgadapt_fem.so   (the pde_loss FEM tail: fem_csrc/, include/gadapt_fem.h)
 #   make resources  -> per-kernel VGPR/SGPR/LDS/occupancy report
 #   make DEV_C=64   -> development build: tiled kernels for one hidden size only (never shipped)
 HIPCC      ?= /opt/rocm/bin/hipcc
@@ -7,6 +8,9 @@ ARCH       ?= gfx950
 CSRC       := g_adaptivity_amd/csrc
 OBJDIR     := build/obj
 LIB        := g_adaptivity_amd/libgadapt_hip.so
+FEM_CSRC   := g_adaptivity_amd/fem_csrc
+FEM_LIB    := g_adaptivity_amd/libgadapt_fem.so
+FEM_OBJS   := $(OBJDIR)/fem_kernels.o $(OBJDIR)/fem_topology.o
 HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-variable -Wno-unused-but-set-variable -Wno-unused-function $(EXTRA)
 ifdef DEV_C
 HIPFLAGS   += -DGADAPT_DEV_C=$(DEV_C)
@@ -15,7 +19,20 @@ UNITS      := gadapt_kernels gadapt_tu_fwd gadapt_tu_bwd_target gadapt_tu_bwd_so
 OBJS       := $(UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/csr_build.o
 SHARED     := $(CSRC)/gadapt_internal.h $(CSRC)/gadapt_common.inc include/gadapt_hip.h
 
-all: $(LIB)
+all: $(LIB) $(FEM_LIB)
+
+# the differentiable P1 FEM tail of loss_type='pde_loss' (include/gadapt_fem.h): its own library, built without FMA contraction
+# (fem_csrc/fem_common.h: the reference's edge tests compare rounded sums)
+$(FEM_LIB): $(FEM_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(FEM_OBJS)
+
+$(OBJDIR)/fem_kernels.o: $(FEM_CSRC)/fem_kernels.hip $(FEM_CSRC)/fem_common.h include/gadapt_fem.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+
+$(OBJDIR)/fem_topology.o: $(FEM_CSRC)/fem_topology.cpp include/gadapt_fem.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
@@ -41,6 +58,6 @@ resources:
 	python3 tools/resources.py
 
 clean:
-	rm -rf $(OBJDIR) $(LIB)
+	rm -rf $(OBJDIR) $(LIB) $(FEM_LIB)
 
 .PHONY: all resources clean

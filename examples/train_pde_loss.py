@@ -1,0 +1,69 @@
+#!/usr/bin/env python
+"""Training with loss_type='pde_loss' (`src/run_GNN.py:108-110`): the mesh is trained on the error of a differentiable P1
+FEM solve on the moved mesh, the reference's own `GNN` config (`src/params.py:107-111`: hidden 8, 4 layers, dt 0.1, l1,
+training meshes 15 and 20).  Prints the loss per epoch and ms per step, split into GNN forward / backward and FEM tail
+forward / backward.
+
+    python examples/train_pde_loss.py --epochs 3 --num_train 32 --batch_size 8
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from g_adaptivity_amd import GNN, MeshDataset, collate, fem_poisson, hot_path_opt, l1_loss   # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--epochs', type=int, default=3)
+    ap.add_argument('--num_train', type=int, default=32)
+    ap.add_argument('--batch_size', type=int, default=8)
+    ap.add_argument('--mesh_dims_train', type=int, nargs='+', default=[15, 20])
+    ap.add_argument('--lr', type=float, default=1e-3)
+    a = ap.parse_args()
+    dev = torch.device('cuda:0')
+    for n in a.mesh_dims_train:
+        opt = hot_path_opt(mesh_dims=[n, n], hidden_dim=8, num_layers=4, time_step=0.1, loss_type='pde_loss', loss_fn='l1',
+                           device=str(dev))
+        ds = MeshDataset([n, n], a.num_train, seed=n, pde_loss_fields=True)
+        torch.manual_seed(0)
+        model = GNN(ds, opt).to(dev).train()
+        optim = torch.optim.Adam(model.parameters(), lr=a.lr)
+        batches = [collate(ds.samples[i:i + a.batch_size]).to(dev) for i in range(0, len(ds), a.batch_size)]
+        ev = lambda: torch.cuda.Event(enable_timing=True)
+        for epoch in range(a.epochs):
+            tot, t = 0.0, {'gnn_fwd': 0.0, 'fem_fwd': 0.0, 'fem_bwd': 0.0, 'gnn_bwd': 0.0, 'step': 0.0}
+            for dd in batches:
+                e = [ev() for _ in range(6)]
+                optim.zero_grad()
+                e[0].record()
+                # the model's pde_loss forward split in its two halves: x_phys, then the FEM tail (GNN.forward does both)
+                model.opt['loss_type'] = 'mesh_loss'
+                x_phys = model(dd)
+                model.opt['loss_type'] = 'pde_loss'
+                e[1].record()
+                xd = x_phys.detach().requires_grad_(True)
+                counts = torch.bincount(dd.batch.cpu()).tolist()
+                coeffs, sol = fem_poisson(xd, dd.cells, dd.boundary_nodes, counts, dd.pde_params, model.quad_points)
+                loss = l1_loss(sol.view(-1, 1), dd.u_true_fine_tensor.view(-1, 1))
+                e[2].record()
+                loss.backward()
+                e[3].record()
+                x_phys.backward(xd.grad)
+                e[4].record()
+                optim.step()
+                e[5].record()
+                torch.cuda.synchronize()
+                for k, (i, j) in zip(t, [(0, 1), (1, 2), (2, 3), (3, 4), (0, 5)]):
+                    t[k] += e[i].elapsed_time(e[j]) / len(batches)
+                tot += loss.item() / len(batches)
+            print(f"mesh {n}x{n} epoch {epoch}: loss {tot:.5f} | ms/step {t['step']:.2f} (GNN fwd {t['gnn_fwd']:.2f}, "
+                  f"FEM fwd {t['fem_fwd']:.2f}, FEM bwd {t['fem_bwd']:.2f}, GNN bwd {t['gnn_bwd']:.2f})", flush=True)
+
+
+if __name__ == '__main__':
+    main()

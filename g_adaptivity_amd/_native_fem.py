@@ -1,0 +1,56 @@
+"""ctypes binding of `libgadapt_fem.so`, the FEM tail of loss_type='pde_loss' (C-ABI declared in include/gadapt_fem.h).
+
+There is no CPU fallback: if the library is missing, or a call fails, this raises `NativeError`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+from ._native import NativeError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, 'libgadapt_fem.so')
+
+ABI_VERSION = 1
+META = 8                                   # GADAPT_FEM_META
+M_N_INT, M_BAND = 5, 6                     # GADAPT_FEM_M_N_INT, GADAPT_FEM_M_BAND
+
+_P, _I, _L = C.c_void_p, C.c_int, C.c_int64
+
+# name -> (restype, argtypes); must list every symbol include/gadapt_fem.h declares
+PROTOTYPES = {
+    'gadapt_fem_abi_version': (_I, []),
+    'gadapt_fem_last_error': (C.c_char_p, []),
+    'gadapt_fem_simpson_points': (_I, []),
+    'gadapt_fem_lds_budget': (_I, []),
+    'gadapt_fem_topology_host': (_L, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'gadapt_fem_factor_lds_bytes': (_L, [_I, _I]),
+    'gadapt_fem_eval_lds_bytes': (_L, [_I]),
+    'gadapt_fem_forward': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 5),
+    'gadapt_fem_backward': (_I, [_I, _I, _I] + [_P] * 13 + [_I, _I] + [_P] * 9),
+}
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise NativeError(f"{LIB_PATH} not found: build it with `make` (hipcc --offload-arch=gfx950); "
+                              "there is no CPU fallback for the FEM tail")
+        handle = C.CDLL(LIB_PATH)
+        for name, (res, args) in PROTOTYPES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = res, args
+        if handle.gadapt_fem_abi_version() != ABI_VERSION:
+            raise NativeError(f"{LIB_PATH}: ABI {handle.gadapt_fem_abi_version()}, expected {ABI_VERSION}")
+        _lib = handle
+    return _lib
+
+
+def check(rc: int, what: str):
+    if rc < 0:
+        msg = lib().gadapt_fem_last_error().decode() or f"error {rc}"
+        raise NativeError(f"{what}: {msg} (code {rc})")

@@ -1,0 +1,250 @@
+"""Differentiable P1 FEM tail of loss_type='pde_loss' (2-D Poisson), MI355X-native.
+
+The reference solves the Poisson problem of each sample on the moved mesh with a differentiable P1 FEM
+(`firedrake_difFEM/difFEM_2d.py:320-372`, called from `src/GNN.py:307-342`) and trains on the error of that solve.  Here a
+whole batch is one autograd node over `libgadapt_fem.so` (include/gadapt_fem.h): three launches forward (load vector, banded
+Cholesky solve with the band in LDS, lattice evaluation), four backward (evaluation adjoint, adjoint solve on the kept factor,
+per-triangle chain rule, per-node gather).
+
+    torch_FEM_2D(opt, mesh, mesh_points, quad_points, num_meshpoints, c_list, s_list) -> (coeffs [N,1], mesh_points, sol)
+    fem_poisson(x_phys, cells, boundary, node_counts, pde_params, lattice) -> (coeffs [N,1], sol [B*Q])
+
+Limits: 2-D Poisson only; each mesh's banded factor must fit the LDS budget (`gadapt_fem_lds_budget()`, 64 KB: square
+meshes up to 26 x 26 nodes); the evaluation points must be a uniform tensor-product lattice.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _native_fem as _nf
+from ._native import NativeError, current_stream
+from .graph import content_fingerprint
+
+__all__ = ['FemTopology', 'fem_poisson', 'torch_FEM_2D', 'boundary_from_cells', 'gnn_pde_tail']
+
+
+def _require_gpu(t: torch.Tensor, what: str):
+    if not t.is_cuda:
+        raise NativeError(f"{what}: the FEM tail runs on the MI355X only (got a {t.device} tensor); there is no CPU fallback")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what}: fp32 expected, got {t.dtype}")
+
+
+def boundary_from_cells(cells: np.ndarray, n_nodes: int) -> np.ndarray:
+    """Nodes on an edge that belongs to one triangle only (Firedrake's DirichletBC(V, 0, 'on_boundary').nodes)."""
+    cells = np.asarray(cells, dtype=np.int64)
+    e = np.concatenate([cells[:, [0, 1]], cells[:, [1, 2]], cells[:, [2, 0]]], 0)
+    e.sort(1)
+    uniq, cnt = np.unique(e, axis=0, return_counts=True)
+    out = np.zeros(n_nodes, dtype=bool)
+    out[uniq[cnt == 1].reshape(-1)] = True
+    return out
+
+
+class FemTopology:
+    """Interior numbering, band and node -> triangle CSR of a batch (gadapt_fem_topology_host), on the device."""
+
+    def __init__(self, cells: np.ndarray, boundary: np.ndarray, node_counts: Sequence[int], tri_counts: Sequence[int], device):
+        lib = _nf.lib()
+        B = len(node_counts)
+        cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        bnd = np.ascontiguousarray(boundary, dtype=np.uint8).reshape(-1)
+        node_off = np.zeros(B + 1, np.int32); node_off[1:] = np.cumsum(node_counts)
+        tri_off = np.zeros(B + 1, np.int32); tri_off[1:] = np.cumsum(tri_counts)
+        N, T = int(node_off[-1]), int(tri_off[-1])
+        if cells.shape[0] != T or bnd.shape[0] != N:
+            raise ValueError(f"FEM topology: {cells.shape[0]} cells / {bnd.shape[0]} boundary flags for {T} triangles / {N} nodes")
+        meta = np.zeros((B, _nf.META), np.int32)
+        node_mesh, int_idx, int_node, nt_ptr = (np.zeros(N, np.int32) for _ in range(4))
+        nt_ptr = np.zeros(N + 1, np.int32)
+        tri_mesh, nt_idx = np.zeros(T, np.int32), np.zeros(3 * T, np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = lib.gadapt_fem_topology_host(B, p(node_off), p(tri_off), p(cells), p(bnd), p(meta), p(node_mesh), p(tri_mesh),
+                                          p(int_idx), p(int_node), p(nt_ptr), p(nt_idx))
+        _nf.check(rc, 'gadapt_fem_topology_host')
+        self.band_floats = max(int(rc), 1)
+        self.n_meshes, self.n_nodes, self.n_tris = B, N, T
+        self.n_int = meta[:, _nf.M_N_INT].copy()
+        self.band = meta[:, _nf.M_BAND].copy()
+        budget = int(lib.gadapt_fem_lds_budget())
+        need = [int(lib.gadapt_fem_factor_lds_bytes(int(n), int(w))) for n, w in zip(self.n_int, self.band)]
+        if max(need) > budget:
+            b = int(np.argmax(need))
+            raise NotImplementedError(f"pde_loss FEM tail: mesh {b} ({int(node_counts[b])} nodes, {int(self.n_int[b])} interior, "
+                                      f"half-bandwidth {int(self.band[b])}) needs {need[b]} B of LDS for its banded factor; the "
+                                      f"limit is {budget} B (square meshes up to 26 x 26 nodes)")
+        self.max_tris = int(max(tri_counts))
+        eval_need = int(lib.gadapt_fem_eval_lds_bytes(self.max_tris))
+        if eval_need > budget:
+            raise NotImplementedError(f"pde_loss FEM tail: {self.max_tris} triangles per mesh need {eval_need} B of LDS for the "
+                                      f"evaluation's bin mask; the limit is {budget} B")
+        self.lds_bytes = max(need)
+        self.host = dict(meta=meta, cells=cells, node_mesh=node_mesh, tri_mesh=tri_mesh, int_idx=int_idx, int_node=int_node,
+                         nt_ptr=nt_ptr, nt_idx=nt_idx, boundary=bnd.astype(bool))
+        dev = torch.device(device)
+        self.dev = {k: torch.from_numpy(v).to(dev) for k, v in self.host.items() if k != 'boundary'}
+
+
+_topo_cache: Dict[Tuple, FemTopology] = {}
+
+
+def _topology(cells: torch.Tensor, boundary: torch.Tensor, node_counts, tri_counts, device) -> FemTopology:
+    key = (tuple(int(n) for n in node_counts), tuple(int(t) for t in tri_counts), str(device),
+           content_fingerprint([cells, boundary]))
+    topo = _topo_cache.get(key)
+    if topo is None:
+        topo = FemTopology(cells.detach().cpu().numpy(), boundary.detach().cpu().numpy(), node_counts, tri_counts, device)
+        if len(_topo_cache) >= 32:
+            _topo_cache.pop(next(iter(_topo_cache)))
+        _topo_cache[key] = topo
+    return topo
+
+
+def pack_gaussians(pde_params: Sequence[dict], device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gptr [B+1] int32 and gpar [G,4] fp32 = (c0, c1, s0, s1): per mesh its own number of Gaussians."""
+    counts, rows = [0], []
+    for p in pde_params:
+        cs, ss = p['centers'], p['scales']
+        for c, s in zip(cs, ss):
+            c, s = np.asarray(c, np.float32).reshape(-1), np.asarray(s, np.float32).reshape(-1)
+            rows.append([c[0], c[1], s[0], s[1]])
+        counts.append(len(cs))
+    gptr = torch.tensor(np.cumsum(counts), dtype=torch.int32, device=device)
+    gpar = torch.tensor(np.asarray(rows, np.float32).reshape(-1, 4), device=device)
+    return gptr, gpar
+
+
+def lattice_axes(quad_points, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lat_x, lat_y) of a tensor-product lattice given as [X, Y] = meshgrid(qx, qy, indexing='ij') (GNN.quad_points) or as
+    the pair of axes; sol.view(-1)[i * nlat + j] is the point (lat_x[i], lat_y[j])."""
+    X, Y = quad_points[0], quad_points[1]
+    if X.dim() == 2:
+        lx, ly = X[:, 0], Y[0, :]
+        if not (torch.equal(X, lx[:, None].expand_as(X)) and torch.equal(Y, ly[None, :].expand_as(Y))):
+            raise NotImplementedError("pde_loss FEM tail: quad_points must be meshgrid(qx, qy, indexing='ij') of a lattice")
+    else:
+        lx, ly = X, Y
+    if lx.numel() != ly.numel() or lx.numel() < 2:
+        raise NotImplementedError("pde_loss FEM tail: the evaluation lattice must be square (nlat x nlat, nlat >= 2)")
+    for a in (lx, ly):
+        d = a[1:] - a[:-1]
+        if not bool((d > 0).all()) or float((d - d.mean()).abs().max()) > 1e-5 * float(a[-1] - a[0]):
+            raise NotImplementedError("pde_loss FEM tail: the evaluation lattice must be uniform and increasing")
+    return (lx.detach().to(device=device, dtype=torch.float32).contiguous(),
+            ly.detach().to(device=device, dtype=torch.float32).contiguous())
+
+
+class _FemPoisson(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, topo: FemTopology, gptr, gpar, lat_x, lat_y):
+        _require_gpu(x, 'FEM node coordinates')
+        x = x.contiguous()
+        d, dev = topo.dev, x.device
+        nlat = int(lat_x.numel())
+        N, B = topo.n_nodes, topo.n_meshes
+        rhs = torch.empty(N, device=dev)
+        coeffs = torch.empty(N, device=dev)
+        lfac = torch.empty(topo.band_floats, device=dev)
+        sol = torch.empty(B * nlat * nlat, device=dev)
+        _nf.check(_nf.lib().gadapt_fem_forward(
+            B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
+            d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(), x.data_ptr(),
+            lat_x.data_ptr(), lat_y.data_ptr(), nlat, topo.lds_bytes, topo.max_tris, rhs.data_ptr(), coeffs.data_ptr(),
+            lfac.data_ptr(), sol.data_ptr(), current_stream(dev)), 'gadapt_fem_forward')
+        ctx.topo, ctx.nlat = topo, nlat
+        ctx.save_for_backward(x, coeffs, lfac, gptr, gpar, lat_x, lat_y)
+        return coeffs, sol
+
+    @staticmethod
+    def backward(ctx, g_coeffs, g_sol):
+        x, coeffs, lfac, gptr, gpar, lat_x, lat_y = ctx.saved_tensors
+        topo, d, dev = ctx.topo, ctx.topo.dev, x.device
+        N, T = topo.n_nodes, topo.n_tris
+        gc = torch.empty(N, device=dev)
+        mu = torch.empty(N, device=dev)
+        tgrad = torch.empty(T * 6, device=dev)
+        gx = torch.empty(N, 2, device=dev)
+        g_coeffs = None if g_coeffs is None else g_coeffs.contiguous().float()
+        g_sol = None if g_sol is None else g_sol.contiguous().float()
+        _nf.check(_nf.lib().gadapt_fem_backward(
+            topo.n_meshes, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['tri_mesh'].data_ptr(),
+            d['int_idx'].data_ptr(), d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(),
+            gpar.data_ptr(), x.data_ptr(), lat_x.data_ptr(), lat_y.data_ptr(), ctx.nlat, topo.lds_bytes, coeffs.data_ptr(),
+            lfac.data_ptr(), None if g_coeffs is None else g_coeffs.data_ptr(), None if g_sol is None else g_sol.data_ptr(),
+            gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), current_stream(dev)), 'gadapt_fem_backward')
+        return gx, None, None, None, None, None
+
+
+def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
+                pde_params: Sequence[dict], quad_points, tri_counts: Optional[Sequence[int]] = None):
+    """Batched P1 Poisson solve on the meshes of `x_phys` [N,2] (differentiable wrt x_phys).
+
+    cells [T,3] global node ids, mesh by mesh; boundary [N] bool; node_counts per mesh; pde_params per mesh
+    ({'centers': [...], 'scales': [...]}, any number of Gaussians); quad_points the evaluation lattice (GNN.quad_points).
+    Returns coeffs [N,1] and sol [B*nlat*nlat] (mesh by mesh, lattice row-major)."""
+    _require_gpu(x_phys, 'pde_loss FEM tail')
+    if x_phys.dim() != 2 or x_phys.shape[1] != 2:
+        raise NotImplementedError(f"pde_loss FEM tail: 2-D meshes only (x_phys {tuple(x_phys.shape)})")
+    dev = x_phys.device
+    if tri_counts is None:
+        c0 = cells[:, 0].detach().cpu()
+        ends = torch.tensor(np.cumsum(node_counts), dtype=c0.dtype)
+        tri_counts = np.diff(np.concatenate([[0], torch.searchsorted(c0.contiguous(), ends, right=False).numpy()])).tolist()
+    topo = _topology(cells, boundary, node_counts, tri_counts, dev)
+    gptr, gpar = pack_gaussians(pde_params, dev)
+    lx, ly = lattice_axes(quad_points, dev)
+    coeffs, sol = _FemPoisson.apply(x_phys, topo, gptr, gpar, lx, ly)
+    return coeffs.unsqueeze(1), sol
+
+
+def torch_FEM_2D(opt, mesh, mesh_points, quad_points, num_meshpoints, c_list, s_list):
+    """The reference's entry point (`difFEM_2d.py:320-372`) on one mesh: (coeffs [N,1], mesh_points, sol shaped as
+    quad_points[0])."""
+    cells_np = np.asarray(mesh.coordinates.cell_node_map().values, dtype=np.int64)
+    n = mesh_points.shape[0]
+    if n != num_meshpoints ** 2:
+        raise ValueError(f"torch_FEM_2D: {n} mesh points for num_meshpoints={num_meshpoints}")
+    cells = torch.from_numpy(cells_np)
+    boundary = torch.from_numpy(boundary_from_cells(cells_np, n))
+    params = [{'centers': [np.asarray(c.detach().cpu() if torch.is_tensor(c) else c, np.float32) for c in c_list],
+               'scales': [np.asarray(s.detach().cpu() if torch.is_tensor(s) else s, np.float32) for s in s_list]}]
+    coeffs, sol = fem_poisson(mesh_points, cells, boundary, [n], params, quad_points, tri_counts=[cells_np.shape[0]])
+    shape = quad_points[0].shape if quad_points[0].dim() == 2 else (quad_points[0].numel(), quad_points[1].numel())
+    return coeffs, mesh_points, sol.view(shape)
+
+
+def gnn_pde_tail(model, data, x_phys: torch.Tensor):
+    """`GNN.forward`'s pde_loss branch (`src/GNN.py:307-342`) for a batch: (coeffs [N,1], x_phys, sol [B*Q])."""
+    o = model.opt
+    if model.dim != 2:
+        raise NotImplementedError("loss_type='pde_loss' is built for 2-D Poisson only; the 1-D tail (torch_FEM_1D) is out of scope")
+    if o.get('pde_type', 'Poisson') != 'Poisson':
+        raise NotImplementedError(f"loss_type='pde_loss' is built for 2-D Poisson only (pde_type={o.get('pde_type')!r})")
+    batch = data.batch
+    B = int(data.num_graphs) if hasattr(data, 'num_graphs') else int(batch.max()) + 1
+    if batch is None:
+        node_counts = [x_phys.shape[0]]
+    else:
+        node_counts = torch.bincount(batch.detach().cpu(), minlength=B).tolist()
+    if o.get('data_type') == 'randg_mix' and hasattr(data, 'batch_dict'):
+        params = [data.batch_dict[i]['pde_params'] for i in range(B)]
+    else:
+        params = data.pde_params if isinstance(data.pde_params, (list, tuple)) else [data.pde_params]
+    cells = getattr(data, 'cells', None)
+    tri_counts = None
+    if cells is None:                                    # per-mesh topology objects (the reference's mesh / data.mesh[i])
+        meshes = data.mesh if isinstance(getattr(data, 'mesh', None), (list, tuple)) else [model.dataset.mesh] * B
+        parts, off = [], 0
+        for m, n in zip(meshes, node_counts):
+            parts.append(torch.as_tensor(np.asarray(m.coordinates.cell_node_map().values, np.int64)) + off)
+            off += n
+        cells, tri_counts = torch.cat(parts, 0), [p.shape[0] for p in parts]
+    boundary = getattr(data, 'boundary_nodes', None)
+    if boundary is None:
+        boundary = torch.from_numpy(boundary_from_cells(cells.cpu().numpy(), sum(node_counts)))
+    coeffs, sol = fem_poisson(x_phys, cells, boundary, node_counts, params, model.quad_points, tri_counts=tri_counts)
+    return coeffs, x_phys, sol

@@ -1,0 +1,500 @@
+// fem_kernels.hip - differentiable P1 FEM tail of loss_type='pde_loss' for gfx950 (include/gadapt_fem.h).
+//
+// Forward (three launches): load vector, banded Cholesky solve (one wave per mesh, band in LDS), evaluation on the lattice.
+// Backward (four launches): d L / d c from the evaluation, adjoint solve on the kept factor, per-triangle chain rule
+// (stiffness, load vector, evaluation), per-node gather.  Every sum runs in a fixed order: results are bit-reproducible.
+#include <stdio.h>
+#include <string.h>
+#include "fem_common.h"
+
+#pragma clang fp contract(off)
+
+using fem::V2;
+using fem::ld2;
+
+static thread_local char g_err[256] = "";
+
+static int fail(int code, const char* msg) {
+    snprintf(g_err, sizeof(g_err), "%s", msg);
+    return code;
+}
+
+static int launched(const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
+        return GADAPT_FEM_E_LAUNCH;
+    }
+    return GADAPT_FEM_OK;
+}
+
+extern "C" int gadapt_fem_abi_version(void) { return GADAPT_FEM_ABI; }
+extern "C" const char* gadapt_fem_last_error(void) { return g_err; }
+extern "C" int gadapt_fem_simpson_points(void) { return FEM_SIMPSON_N; }
+extern "C" int gadapt_fem_lds_budget(void) { return GADAPT_FEM_LDS_BUDGET; }
+
+// ---------------------------------------------------------------------------------------------------- triangle bins
+// The evaluation locates lattice points with a per-mesh bin grid over the lattice's square, rebuilt on every call from the
+// current coordinates: bit t of bin (i,j) is set when triangle t's bounding box, widened by one bin, overlaps the bin.  A
+// point scans the triangles of its bin in increasing id, so overlapping (tangled) triangles are all found, in a fixed order.
+#define FEM_NB 16
+
+__host__ __device__ inline int64_t eval_words(int n_tris) { return (n_tris + 31) / 32; }
+
+extern "C" int64_t gadapt_fem_eval_lds_bytes(int n_tris) { return (int64_t)FEM_NB * FEM_NB * eval_words(n_tris) * 4; }
+
+__device__ inline int bin_of(float v, float lo, float scale) {
+    float f = floorf((v - lo) * scale);
+    f = fminf(fmaxf(f, 0.0f), (float)(FEM_NB - 1));           // NaN -> 0
+    return (int)f;
+}
+
+// lattice index range [i0, i1] that may hold points of [lo_v, hi_v] (one index of slack each side); empty if i0 > i1
+__device__ inline void lattice_range(float lo_v, float hi_v, float lo, float hi, int nlat, int& i0, int& i1) {
+    const float inv = (float)(nlat - 1) / (hi - lo);
+    float a = floorf((lo_v - lo) * inv) - 1.0f, b = ceilf((hi_v - lo) * inv) + 1.0f;
+    a = fminf(fmaxf(a, 0.0f), (float)(nlat - 1));
+    b = fminf(fmaxf(b, 0.0f), (float)(nlat - 1));
+    i0 = (int)a;
+    i1 = (int)b;
+}
+
+// ---------------------------------------------------------------------------------------------------- load vector
+// RHS_m = u_true(x_m) on the boundary; inside, the 9 x 9 Simpson rule of phim(., m) f over the bounding box of the vertices of
+// m's incident triangles (difFEM_2d.py:159-203, :298-309), nested as torchquad applies it: the y rule per x row, then x.
+__device__ inline void simpson_box(int m, const int32_t* __restrict__ nt_ptr, const int32_t* __restrict__ nt_idx,
+                                   const int32_t* __restrict__ cells, const float* __restrict__ x, float& x0, float& x1,
+                                   float& y0, float& y1) {
+    x0 = y0 = INFINITY;
+    x1 = y1 = -INFINITY;
+    for (int e = nt_ptr[m]; e < nt_ptr[m + 1]; ++e) {
+        const int t = nt_idx[e] >> 2;
+        for (int k = 0; k < 3; ++k) {
+            const V2 p = ld2(x, cells[3 * t + k]);
+            x0 = fminf(x0, p.x); x1 = fmaxf(x1, p.x);
+            y0 = fminf(y0, p.y); y1 = fmaxf(y1, p.y);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) fem_rhs_kernel(int n_nodes, const int32_t* __restrict__ cells, const int32_t* __restrict__ node_mesh,
+                                                      const int32_t* __restrict__ int_idx, const int32_t* __restrict__ nt_ptr,
+                                                      const int32_t* __restrict__ nt_idx, const int32_t* __restrict__ gptr,
+                                                      const float* __restrict__ gpar, const float* __restrict__ x, float* __restrict__ rhs) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_nodes) return;
+    const int b = node_mesh[m];
+    const int g0 = gptr[b], g1 = gptr[b + 1];
+    const V2 xm = ld2(x, m);
+    if (int_idx[m] < 0) {
+        rhs[m] = fem::u_true(xm.x, xm.y, gpar, g0, g1);
+        return;
+    }
+    constexpr int n = FEM_SIMPSON_N;
+    float bx0, bx1, by0, by1;
+    simpson_box(m, nt_ptr, nt_idx, cells, x, bx0, bx1, by0, by1);
+    const float hx3 = (bx1 - bx0) / (float)(n - 1) / 3.0f, hy3 = (by1 - by0) / (float)(n - 1) / 3.0f;
+    float row[n];
+    for (int i = 0; i < n; ++i) {
+        const float px = fem::linspace_at(bx0, bx1, n, i);
+        float f[n];
+        for (int j = 0; j < n; ++j) {
+            const float py = fem::linspace_at(by0, by1, n, j);
+            float out;
+            const float div = fem::phim_parts(px, py, m, nt_ptr, nt_idx, cells, x, &out);
+            f[j] = out / div * fem::forcing(px, py, gpar, g0, g1);
+        }
+        float s = 0.0f;
+        for (int k = 0; k + 2 < n; k += 2) s = s + hy3 * (f[k] + 4.0f * f[k + 1] + f[k + 2]);
+        row[i] = s;
+    }
+    float s = 0.0f;
+    for (int k = 0; k + 2 < n; k += 2) s = s + hx3 * (row[k] + 4.0f * row[k + 1] + row[k + 2]);
+    rhs[m] = s;
+}
+
+// ---------------------------------------------------------------------------------------------------- banded Cholesky
+// P_II (= -A_II, SPD: a sum of PSD element terms with |area|) in band storage, row r holding P[r][r-d] at r*(w+1)+d.  One
+// wave per mesh; the rank-1 update of column k touches w(w+1)/2 entries, spread over the lanes by a pair table in LDS.
+#define FEM_SOLVE_THREADS 64
+
+__device__ inline void band_factor(float* __restrict__ A, const int32_t* __restrict__ pairs, int n, int w) {
+    const int lane = threadIdx.x, ld = w + 1, np = w * (w + 1) / 2;
+    for (int k = 0; k < n; ++k) {
+        const float d = sqrtf(A[k * ld]);
+        for (int i = 1 + lane; i <= w && k + i < n; i += FEM_SOLVE_THREADS) A[(k + i) * ld + i] = A[(k + i) * ld + i] / d;
+        __syncthreads();
+        if (lane == 0) A[k * ld] = d;
+        for (int p = lane; p < np; p += FEM_SOLVE_THREADS) {
+            const int i = pairs[p] >> 16, j = pairs[p] & 0xffff;
+            if (k + i < n) A[(k + i) * ld + (i - j)] -= A[(k + i) * ld + i] * A[(k + j) * ld + j];
+        }
+        __syncthreads();
+    }
+}
+
+// L L^T y = b in place (column-oriented substitutions)
+__device__ inline void band_solve(const float* __restrict__ A, float* __restrict__ b, int n, int w) {
+    const int lane = threadIdx.x, ld = w + 1;
+    for (int k = 0; k < n; ++k) {
+        const float y = b[k] / A[k * ld];
+        for (int i = 1 + lane; i <= w && k + i < n; i += FEM_SOLVE_THREADS) b[k + i] -= A[(k + i) * ld + i] * y;
+        if (lane == 0) b[k] = y;
+        __syncthreads();
+    }
+    for (int k = n - 1; k >= 0; --k) {
+        const float y = b[k] / A[k * ld];
+        for (int j = 1 + lane; j <= w && k - j >= 0; j += FEM_SOLVE_THREADS) b[k - j] -= A[k * ld + j] * y;
+        if (lane == 0) b[k] = y;
+        __syncthreads();
+    }
+}
+
+__device__ inline void fill_pairs(int32_t* pairs, int w) {
+    for (int i = 1, p = 0; i <= w; ++i)
+        for (int j = 1; j <= i; ++j, ++p)
+            if ((p % FEM_SOLVE_THREADS) == (int)threadIdx.x) pairs[p] = (i << 16) | j;
+}
+
+// element matrix row: P_T[l][k] = area grad(phi_l).grad(phi_k) = r_l.r_k / (2 |D|)  (difFEM_2d.py:66-111)
+__device__ inline void tri_geometry(V2 p0, V2 p1, V2 p2, V2 r[3], float& D) {
+    r[0] = V2{p1.y - p2.y, p2.x - p1.x};
+    r[1] = V2{p2.y - p0.y, p0.x - p2.x};
+    r[2] = V2{p0.y - p1.y, p1.x - p0.x};
+    D = p0.x * (p1.y - p2.y) + p1.x * (p2.y - p0.y) + p2.x * (p0.y - p1.y);
+}
+
+__global__ void __launch_bounds__(FEM_SOLVE_THREADS) fem_factor_kernel(const int32_t* __restrict__ meta, const int32_t* __restrict__ cells,
+                                                                       const int32_t* __restrict__ int_idx, const int32_t* __restrict__ int_node,
+                                                                       const int32_t* __restrict__ nt_ptr, const int32_t* __restrict__ nt_idx,
+                                                                       const float* __restrict__ x, const float* __restrict__ rhs,
+                                                                       float* __restrict__ coeffs, float* __restrict__ lfac) {
+    extern __shared__ float lds[];
+    const int32_t* mt = meta + blockIdx.x * GADAPT_FEM_META;
+    const int n = mt[GADAPT_FEM_M_N_INT], w = mt[GADAPT_FEM_M_BAND], io = mt[GADAPT_FEM_M_INT_OFF];
+    const int ld = w + 1;
+    float* A = lds;
+    float* bv = A + n * ld;
+    int32_t* pairs = (int32_t*)(bv + n);
+    const int lane = threadIdx.x;
+    for (int v = mt[GADAPT_FEM_M_NODE_OFF] + lane; v < mt[GADAPT_FEM_M_NODE_OFF] + mt[GADAPT_FEM_M_N_NODES]; v += FEM_SOLVE_THREADS)
+        if (int_idx[v] < 0) coeffs[v] = rhs[v];                    // c_B = RHS_B (the identity rows, difFEM_2d.py:358-359)
+    fill_pairs(pairs, w);
+    // assembly by rows: row r gathers its incident triangles (each lane owns whole rows: no atomics)
+    for (int r = lane; r < n; r += FEM_SOLVE_THREADS) {
+        for (int d = 0; d < ld; ++d) A[r * ld + d] = 0.0f;
+        const int g = int_node[io + r];
+        float b = -rhs[g];
+        for (int e = nt_ptr[g]; e < nt_ptr[g + 1]; ++e) {
+            const int t = nt_idx[e] >> 2, l = nt_idx[e] & 3;
+            V2 rr[3];
+            float D;
+            tri_geometry(ld2(x, cells[3 * t]), ld2(x, cells[3 * t + 1]), ld2(x, cells[3 * t + 2]), rr, D);
+            const float inv = 1.0f / (2.0f * fabsf(D));
+            for (int k = 0; k < 3; ++k) {
+                const int h = cells[3 * t + k];
+                const float p = (rr[l].x * rr[k].x + rr[l].y * rr[k].y) * inv;
+                const int ih = int_idx[h];
+                if (ih < 0) b -= p * rhs[h];
+                else if (ih <= r) A[r * ld + (r - ih)] += p;
+            }
+        }
+        bv[r] = b;
+    }
+    __syncthreads();
+    band_factor(A, pairs, n, w);
+    band_solve(A, bv, n, w);
+    for (int r = lane; r < n; r += FEM_SOLVE_THREADS) coeffs[int_node[io + r]] = bv[r];
+    float* out = lfac + mt[GADAPT_FEM_M_BAND_OFF];
+    for (int i = lane; i < n * ld; i += FEM_SOLVE_THREADS) out[i] = A[i];
+}
+
+// adjoint: P_II mu = gc_I on the kept factor (lambda_I = -mu); mu = 0 on the boundary
+__global__ void __launch_bounds__(FEM_SOLVE_THREADS) fem_adjoint_kernel(const int32_t* __restrict__ meta, const int32_t* __restrict__ int_idx,
+                                                                        const int32_t* __restrict__ int_node, const float* __restrict__ lfac,
+                                                                        const float* __restrict__ gc, float* __restrict__ mu) {
+    extern __shared__ float lds[];
+    const int32_t* mt = meta + blockIdx.x * GADAPT_FEM_META;
+    const int n = mt[GADAPT_FEM_M_N_INT], w = mt[GADAPT_FEM_M_BAND], io = mt[GADAPT_FEM_M_INT_OFF];
+    const int ld = w + 1, lane = threadIdx.x;
+    float* A = lds;
+    float* bv = A + n * ld;
+    const float* src = lfac + mt[GADAPT_FEM_M_BAND_OFF];
+    for (int i = lane; i < n * ld; i += FEM_SOLVE_THREADS) A[i] = src[i];
+    for (int r = lane; r < n; r += FEM_SOLVE_THREADS) bv[r] = gc[int_node[io + r]];
+    for (int v = mt[GADAPT_FEM_M_NODE_OFF] + lane; v < mt[GADAPT_FEM_M_NODE_OFF] + mt[GADAPT_FEM_M_N_NODES]; v += FEM_SOLVE_THREADS)
+        if (int_idx[v] < 0) mu[v] = 0.0f;
+    __syncthreads();
+    band_solve(A, bv, n, w);
+    for (int r = lane; r < n; r += FEM_SOLVE_THREADS) mu[int_node[io + r]] = bv[r];
+}
+
+// ---------------------------------------------------------------------------------------------------- evaluation
+#define FEM_EVAL_THREADS 256
+#define FEM_EVAL_CHUNKS 8
+
+// sol(p) = sum over triangles T containing p, over their vertices v: c_v aux_T(p; v) / repeat(p, v)  (difFEM_2d.py:312-318)
+__global__ void __launch_bounds__(FEM_EVAL_THREADS) fem_eval_kernel(const int32_t* __restrict__ meta, const int32_t* __restrict__ cells,
+                                                                    const int32_t* __restrict__ nt_ptr, const int32_t* __restrict__ nt_idx,
+                                                                    const float* __restrict__ x, const float* __restrict__ coeffs,
+                                                                    const float* __restrict__ lat_x, const float* __restrict__ lat_y,
+                                                                    int nlat, float* __restrict__ sol) {
+    extern __shared__ uint32_t mask[];
+    const int32_t* mt = meta + blockIdx.x * GADAPT_FEM_META;
+    const int t0 = mt[GADAPT_FEM_M_TRI_OFF], nt = mt[GADAPT_FEM_M_N_TRIS];
+    const int W = (int)eval_words(nt);
+    const float lox = lat_x[0], hix = lat_x[nlat - 1], loy = lat_y[0], hiy = lat_y[nlat - 1];
+    const float scx = (float)FEM_NB / (hix - lox), scy = (float)FEM_NB / (hiy - loy);
+    for (int i = threadIdx.x; i < FEM_NB * FEM_NB * W; i += FEM_EVAL_THREADS) mask[i] = 0u;
+    __syncthreads();
+    for (int t = threadIdx.x; t < nt; t += FEM_EVAL_THREADS) {
+        const V2 p0 = ld2(x, cells[3 * (t0 + t)]), p1 = ld2(x, cells[3 * (t0 + t) + 1]), p2 = ld2(x, cells[3 * (t0 + t) + 2]);
+        const int bx0 = max(bin_of(fminf(fminf(p0.x, p1.x), p2.x), lox, scx) - 1, 0);
+        const int bx1 = min(bin_of(fmaxf(fmaxf(p0.x, p1.x), p2.x), lox, scx) + 1, FEM_NB - 1);
+        const int by0 = max(bin_of(fminf(fminf(p0.y, p1.y), p2.y), loy, scy) - 1, 0);
+        const int by1 = min(bin_of(fmaxf(fmaxf(p0.y, p1.y), p2.y), loy, scy) + 1, FEM_NB - 1);
+        for (int bx = bx0; bx <= bx1; ++bx)
+            for (int by = by0; by <= by1; ++by) atomicOr(&mask[(bx * FEM_NB + by) * W + (t >> 5)], 1u << (t & 31));
+    }
+    __syncthreads();
+    const int Q = nlat * nlat;
+    const int q0 = (int)((int64_t)Q * blockIdx.y / gridDim.y), q1 = (int)((int64_t)Q * (blockIdx.y + 1) / gridDim.y);
+    for (int q = q0 + threadIdx.x; q < q1; q += FEM_EVAL_THREADS) {
+        const float px = lat_x[q / nlat], py = lat_y[q % nlat];
+        const uint32_t* bm = mask + (bin_of(px, lox, scx) * FEM_NB + bin_of(py, loy, scy)) * W;
+        float acc = 0.0f;
+        for (int wd = 0; wd < W; ++wd) {
+            uint32_t bits = bm[wd];
+            while (bits) {
+                const int t = t0 + wd * 32 + __builtin_ctz(bits);
+                bits &= bits - 1;
+                const float ind = fem::inside(px, py, ld2(x, cells[3 * t + 2]), ld2(x, cells[3 * t + 1]), ld2(x, cells[3 * t]));
+                if (ind == 0.0f) continue;
+                for (int l = 0; l < 3; ++l) {
+                    int va, vb, vc;
+                    fem::rotation(cells, t, l, va, vb, vc);
+                    const float inc = fem::aux_value(px, py, ld2(x, va), ld2(x, vb), ld2(x, vc), ind);
+                    if (inc == 0.0f) continue;
+                    const float div = fem::phim_parts(px, py, vc, nt_ptr, nt_idx, cells, x, nullptr);
+                    acc += coeffs[vc] * (inc / div);
+                }
+            }
+        }
+        sol[(int64_t)blockIdx.x * Q + q] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- backward
+// gc[v] = g_coeffs[v] + sum_p g_sol[p] phim(p, v): v's incident triangles, the lattice points of each one's bounding box
+__global__ void __launch_bounds__(256) fem_gc_kernel(int n_nodes, const int32_t* __restrict__ cells, const int32_t* __restrict__ node_mesh,
+                                                     const int32_t* __restrict__ nt_ptr, const int32_t* __restrict__ nt_idx,
+                                                     const float* __restrict__ x, const float* __restrict__ lat_x, const float* __restrict__ lat_y,
+                                                     int nlat, const float* __restrict__ g_coeffs, const float* __restrict__ g_sol,
+                                                     float* __restrict__ gc) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_nodes) return;
+    float acc = g_coeffs ? g_coeffs[v] : 0.0f;
+    if (g_sol) {
+        const float* gs = g_sol + (int64_t)node_mesh[v] * nlat * nlat;
+        for (int e = nt_ptr[v]; e < nt_ptr[v + 1]; ++e) {
+            const int t = nt_idx[e] >> 2, l = nt_idx[e] & 3;
+            int va, vb, vc;
+            fem::rotation(cells, t, l, va, vb, vc);
+            const V2 a = ld2(x, va), b = ld2(x, vb), c = ld2(x, vc);
+            int i0, i1, j0, j1;
+            lattice_range(fminf(fminf(a.x, b.x), c.x), fmaxf(fmaxf(a.x, b.x), c.x), lat_x[0], lat_x[nlat - 1], nlat, i0, i1);
+            lattice_range(fminf(fminf(a.y, b.y), c.y), fmaxf(fmaxf(a.y, b.y), c.y), lat_y[0], lat_y[nlat - 1], nlat, j0, j1);
+            for (int i = i0; i <= i1; ++i)
+                for (int j = j0; j <= j1; ++j) {
+                    const float px = lat_x[i], py = lat_y[j];
+                    const float ind = fem::inside(px, py, a, b, c);
+                    if (ind == 0.0f) continue;
+                    const float inc = fem::aux_value(px, py, a, b, c, ind);
+                    if (inc == 0.0f) continue;
+                    const float div = fem::phim_parts(px, py, v, nt_ptr, nt_idx, cells, x, nullptr);
+                    acc += gs[i * nlat + j] * (inc / div);
+                }
+        }
+    }
+    gc[v] = acc;
+}
+
+__device__ inline void add_rot(V2 g[3], int l, V2 ga, V2 gb, V2 gc) {
+    g[l].x += gc.x; g[l].y += gc.y;
+    g[(l + 2) % 3].x += ga.x; g[(l + 2) % 3].y += ga.y;
+    g[(l + 1) % 3].x += gb.x; g[(l + 1) % 3].y += gb.y;
+}
+
+// d L / d (vertices of t): stiffness (through slopes and |area|), load vector (through phim at the fixed Simpson points)
+// and evaluation (through phim at the lattice points)
+__global__ void __launch_bounds__(256) fem_tri_bwd_kernel(int n_tris, const int32_t* __restrict__ cells, const int32_t* __restrict__ tri_mesh,
+                                                          const int32_t* __restrict__ int_idx, const int32_t* __restrict__ nt_ptr,
+                                                          const int32_t* __restrict__ nt_idx, const int32_t* __restrict__ gptr,
+                                                          const float* __restrict__ gpar, const float* __restrict__ x,
+                                                          const float* __restrict__ lat_x, const float* __restrict__ lat_y, int nlat,
+                                                          const float* __restrict__ coeffs, const float* __restrict__ mu,
+                                                          const float* __restrict__ g_sol, float* __restrict__ tgrad) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tris) return;
+    const int b = tri_mesh[t];
+    const int vtx[3] = {cells[3 * t], cells[3 * t + 1], cells[3 * t + 2]};
+    const V2 p[3] = {ld2(x, vtx[0]), ld2(x, vtx[1]), ld2(x, vtx[2])};
+    V2 g[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+
+    // stiffness: E = sum_ab Abar_ab r_a.r_b / (2|D|), Abar_ab = dL/dP_ab = lambda_a c_b = -mu_a c_b (0 on boundary rows)
+    {
+        V2 r[3];
+        float D;
+        tri_geometry(p[0], p[1], p[2], r, D);
+        float Ab[3][3];
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) Ab[a][c] = -mu[vtx[a]] * coeffs[vtx[c]];
+        float R = 0.0f;
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) R += Ab[a][c] * (r[a].x * r[c].x + r[a].y * r[c].y);
+        const float inv = 1.0f / (2.0f * fabsf(D));
+        for (int a = 0; a < 3; ++a) {
+            V2 s = {0.f, 0.f};
+            for (int c = 0; c < 3; ++c) {
+                const float w = Ab[a][c] + Ab[c][a];
+                s.x += w * r[c].x;
+                s.y += w * r[c].y;
+            }
+            s.x *= inv; s.y *= inv;
+            g[(a + 2) % 3].x += s.y; g[(a + 1) % 3].x -= s.y;
+            g[(a + 1) % 3].y += s.x; g[(a + 2) % 3].y -= s.x;
+        }
+        const float sgn = D > 0.0f ? 1.0f : (D < 0.0f ? -1.0f : 0.0f);
+        const float coef = -R * sgn * inv * inv * 2.0f;          // -R sign(D) / (2 D^2)
+        for (int k = 0; k < 3; ++k) { g[k].x += coef * r[k].x; g[k].y += coef * r[k].y; }
+    }
+
+    // load vector: d L / d RHS_m = lambda_m = -mu_m at each interior vertex m of t; Simpson points are constants
+    const int g0 = gptr[b], g1 = gptr[b + 1];
+    constexpr int n = FEM_SIMPSON_N;
+    for (int l = 0; l < 3; ++l) {
+        const int m = vtx[l];
+        if (int_idx[m] < 0) continue;
+        const float lam = -mu[m];
+        int va, vb, vc;
+        fem::rotation(cells, t, l, va, vb, vc);
+        const V2 a = ld2(x, va), bb = ld2(x, vb), c = ld2(x, vc);
+        float bx0, bx1, by0, by1;
+        simpson_box(m, nt_ptr, nt_idx, cells, x, bx0, bx1, by0, by1);
+        const float hx3 = (bx1 - bx0) / (float)(n - 1) / 3.0f, hy3 = (by1 - by0) / (float)(n - 1) / 3.0f;
+        V2 ga = {0.f, 0.f}, gb = {0.f, 0.f}, gcv = {0.f, 0.f};
+        for (int i = 0; i < n; ++i) {
+            const float px = fem::linspace_at(bx0, bx1, n, i);
+            for (int j = 0; j < n; ++j) {
+                const float py = fem::linspace_at(by0, by1, n, j);
+                const float ind = fem::inside(px, py, a, bb, c);
+                if (ind == 0.0f) continue;
+                const float div = fem::phim_parts(px, py, m, nt_ptr, nt_idx, cells, x, nullptr);
+                const float w = lam * (hx3 * fem::simpson_coef(i, n)) * (hy3 * fem::simpson_coef(j, n)) * fem::forcing(px, py, gpar, g0, g1) / div;
+                fem::aux_grad(px, py, a, bb, c, ind * w, ga, gb, gcv);
+            }
+        }
+        add_rot(g, l, ga, gb, gcv);
+    }
+
+    // evaluation: lattice points in t's bounding box
+    if (g_sol) {
+        const float* gs = g_sol + (int64_t)b * nlat * nlat;
+        int i0, i1, j0, j1;
+        lattice_range(fminf(fminf(p[0].x, p[1].x), p[2].x), fmaxf(fmaxf(p[0].x, p[1].x), p[2].x), lat_x[0], lat_x[nlat - 1], nlat, i0, i1);
+        lattice_range(fminf(fminf(p[0].y, p[1].y), p[2].y), fmaxf(fmaxf(p[0].y, p[1].y), p[2].y), lat_y[0], lat_y[nlat - 1], nlat, j0, j1);
+        for (int i = i0; i <= i1; ++i)
+            for (int j = j0; j <= j1; ++j) {
+                const float px = lat_x[i], py = lat_y[j];
+                const float ind = fem::inside(px, py, p[2], p[1], p[0]);
+                if (ind == 0.0f) continue;
+                const float gp = gs[i * nlat + j];
+                for (int l = 0; l < 3; ++l) {
+                    int va, vb, vc;
+                    fem::rotation(cells, t, l, va, vb, vc);
+                    const float div = fem::phim_parts(px, py, vc, nt_ptr, nt_idx, cells, x, nullptr);
+                    V2 ga = {0.f, 0.f}, gb = {0.f, 0.f}, gcv = {0.f, 0.f};
+                    fem::aux_grad(px, py, ld2(x, va), ld2(x, vb), ld2(x, vc), ind * (gp * coeffs[vc] / div), ga, gb, gcv);
+                    add_rot(g, l, ga, gb, gcv);
+                }
+            }
+    }
+    for (int k = 0; k < 3; ++k) {
+        tgrad[6 * t + 2 * k] = g[k].x;
+        tgrad[6 * t + 2 * k + 1] = g[k].y;
+    }
+}
+
+// gx[v] = sum over v's incidences (t, l) of tgrad[t][l]: a gather in the CSR's fixed order
+__global__ void __launch_bounds__(256) fem_gather_kernel(int n_nodes, const int32_t* __restrict__ nt_ptr, const int32_t* __restrict__ nt_idx,
+                                                         const float* __restrict__ tgrad, float* __restrict__ gx) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n_nodes) return;
+    float sx = 0.0f, sy = 0.0f;
+    for (int e = nt_ptr[v]; e < nt_ptr[v + 1]; ++e) {
+        const int t = nt_idx[e] >> 2, l = nt_idx[e] & 3;
+        sx += tgrad[6 * t + 2 * l];
+        sy += tgrad[6 * t + 2 * l + 1];
+    }
+    gx[2 * v] = sx;
+    gx[2 * v + 1] = sy;
+}
+
+// ---------------------------------------------------------------------------------------------------- C-ABI
+extern "C" int64_t gadapt_fem_factor_lds_bytes(int n_int, int band);
+
+static int check_lat(const float* lat_x, const float* lat_y, int nlat) {
+    if (!lat_x || !lat_y || nlat < 2) return fail(GADAPT_FEM_E_BADARG, "evaluation lattice: need lat_x, lat_y and nlat >= 2");
+    return GADAPT_FEM_OK;
+}
+
+static int check_lds(int max_lds_bytes) {
+    if (max_lds_bytes <= 0 || max_lds_bytes > GADAPT_FEM_LDS_BUDGET)
+        return fail(GADAPT_FEM_E_LDS, "band factor: LDS bytes outside (0, GADAPT_FEM_LDS_BUDGET]");
+    return GADAPT_FEM_OK;
+}
+
+extern "C" int gadapt_fem_forward(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                  const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                                  const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
+                                  int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* sol, void* stream) {
+    if (B <= 0 || N <= 0 || T <= 0 || !meta || !cells || !node_mesh || !int_idx || !int_node || !nt_ptr || !nt_idx || !gptr || !gpar || !x ||
+        !rhs || !coeffs || !lfac || !sol || max_tris <= 0)
+        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_forward: null pointer or bad size");
+    int rc = check_lat(lat_x, lat_y, nlat);
+    if (rc) return rc;
+    if ((rc = check_lds(max_lds_bytes))) return rc;
+    const int64_t eval_lds = gadapt_fem_eval_lds_bytes(max_tris);
+    if (eval_lds > GADAPT_FEM_LDS_BUDGET) return fail(GADAPT_FEM_E_LDS, "evaluation: triangle bin mask exceeds the LDS budget");
+    hipStream_t s = (hipStream_t)stream;
+    fem_rhs_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, cells, node_mesh, int_idx, nt_ptr, nt_idx, gptr, gpar, x, rhs);
+    if ((rc = launched("fem_rhs_kernel"))) return rc;
+    fem_factor_kernel<<<B, FEM_SOLVE_THREADS, max_lds_bytes, s>>>(meta, cells, int_idx, int_node, nt_ptr, nt_idx, x, rhs, coeffs, lfac);
+    if ((rc = launched("fem_factor_kernel"))) return rc;
+    fem_eval_kernel<<<dim3(B, FEM_EVAL_CHUNKS), FEM_EVAL_THREADS, (size_t)eval_lds, s>>>(meta, cells, nt_ptr, nt_idx, x, coeffs, lat_x, lat_y,
+                                                                                         nlat, sol);
+    return launched("fem_eval_kernel");
+}
+
+extern "C" int gadapt_fem_backward(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                   const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                                   const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
+                                   const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs, const float* lfac,
+                                   const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad, float* gx, void* stream) {
+    if (B <= 0 || N <= 0 || T <= 0 || !meta || !cells || !node_mesh || !tri_mesh || !int_idx || !int_node || !nt_ptr || !nt_idx || !gptr ||
+        !gpar || !x || !coeffs || !lfac || !gc || !mu || !tgrad || !gx)
+        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_backward: null pointer or bad size");
+    int rc = check_lat(lat_x, lat_y, nlat);
+    if (rc) return rc;
+    if ((rc = check_lds(max_lds_bytes))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    fem_gc_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, cells, node_mesh, nt_ptr, nt_idx, x, lat_x, lat_y, nlat, g_coeffs, g_sol, gc);
+    if ((rc = launched("fem_gc_kernel"))) return rc;
+    fem_adjoint_kernel<<<B, FEM_SOLVE_THREADS, max_lds_bytes, s>>>(meta, int_idx, int_node, lfac, gc, mu);
+    if ((rc = launched("fem_adjoint_kernel"))) return rc;
+    fem_tri_bwd_kernel<<<(T + 255) / 256, 256, 0, s>>>(T, cells, tri_mesh, int_idx, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y, nlat, coeffs,
+                                                       mu, g_sol, tgrad);
+    if ((rc = launched("fem_tri_bwd_kernel"))) return rc;
+    fem_gather_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, nt_ptr, nt_idx, tgrad, gx);
+    return launched("fem_gather_kernel");
+}

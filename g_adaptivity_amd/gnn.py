@@ -141,6 +141,9 @@ class GNN(nn.Module):
         if opt.get('learn_step'):
             self.steps = nn.ParameterList([nn.Parameter(torch.tensor([opt['time_step']]))
                                            for _ in range(opt['num_layers'])])       # GNN.py:179-180
+        if opt.get('loss_type') == 'pde_loss' and (self.dim != 2 or opt.get('pde_type', 'Poisson') != 'Poisson'):
+            raise NotImplementedError("loss_type='pde_loss' is built for 2-D Poisson only: the 1-D tail (torch_FEM_1D) and "
+                                      "Burgers are out of scope")
         q = torch.linspace(0, 1, opt.get('eval_quad_points', 101))
         self.quad_points = q if self.dim == 1 else list(torch.meshgrid(q, q, indexing='ij'))
         self.end_MLmodel = None
@@ -445,5 +448,7 @@ class GNN(nn.Module):
         self.end_MLmodel = time.time()                                    # GNN.py:301
         if o['loss_type'] in ('mesh_loss', 'modular'):
             return x_phys
-        raise NotImplementedError("loss_type='pde_loss': the differentiable-FEM tail (src/GNN.py:307-342) is outside "
-                                  "the message-passing path (SURVEY.md §2 row 2)")
+        if o['loss_type'] == 'pde_loss':
+            from .fem import gnn_pde_tail                              # (coeffs, x_phys, sol), src/GNN.py:307-342
+            return gnn_pde_tail(self, data, x_phys)
+        raise NotImplementedError(f"loss_type={o['loss_type']!r}")

@@ -258,6 +258,16 @@ class MeshTopology:
         self.coordinates = _Coordinates(np.asarray(cells))
 
 
+def attach_fine_fields(d: MeshData, eval_quad_points: int = 101) -> MeshData:
+    """The target of loss_type='pde_loss' (`src/data.py:234-267`, `run_GNN.py:108-110`): u_true on the evaluation lattice
+    (`GNN.quad_points`, meshgrid(linspace(0,1,n), indexing='ij')), row-major: [n*n] with index i*n + j <-> (x_i, y_j)."""
+    q = torch.linspace(0, 1, eval_quad_points).double()
+    X, Y = torch.meshgrid(q, q, indexing='ij')
+    u, _ = gaussian_fields(torch.stack([X.reshape(-1), Y.reshape(-1)], 1).numpy(), d.pde_params['centers'], d.pde_params['scales'])
+    d.u_true_fine_tensor = torch.tensor(u, dtype=torch.float32)
+    return d
+
+
 class MeshDataset:
     """In-memory list of samples over one shared mesh (`MeshInMemoryDataset` duck type).
 
@@ -265,7 +275,8 @@ class MeshDataset:
     plus `x_comp_shared` and `mesh_dims`.
     """
 
-    def __init__(self, mesh_dims: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2):
+    def __init__(self, mesh_dims: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2, pde_loss_fields: bool = False,
+                 eval_quad_points: int = 101):
         self.mesh_dims = list(mesh_dims)
         self.dim = len(self.mesh_dims)
         if self.dim == 1:
@@ -281,6 +292,8 @@ class MeshDataset:
         self.samples: List[MeshData] = [attach_random_fields(base, rng, num_gauss) for _ in range(num_data)]
         # no Firedrake mesh object here: a stand-in with the one attribute chain the model follows (2-D only)
         self.mesh = MeshTopology(base.cells.numpy()) if self.dim == 2 else None
+        if pde_loss_fields:                                  # loss_type='pde_loss': only when asked, samples are unchanged otherwise
+            _add_pde_loss_fields(self, eval_quad_points)
 
     def __len__(self):
         return len(self.samples)
@@ -298,7 +311,8 @@ class MixedMeshDataset(MeshDataset):
     sample carries its own `mesh` stand-in and `mapping_tensor` (the model reads `data.mesh[i]` / `data.mapping_tensor` for
     this data type, `src/GNN.py:247-248,279`) and its `pde_params`."""
 
-    def __init__(self, mesh_sizes: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2):
+    def __init__(self, mesh_sizes: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2, pde_loss_fields: bool = False,
+                 eval_quad_points: int = 101):
         self.mesh_sizes = list(mesh_sizes)
         self.mesh_dims = [self.mesh_sizes[0], self.mesh_sizes[0]]
         self.dim = 2
@@ -315,6 +329,17 @@ class MixedMeshDataset(MeshDataset):
         self.base = bases[self.mesh_sizes[0]]
         self.x_comp_shared = self.base.x_comp
         self.mesh = MeshTopology(self.base.cells.numpy())
+        if pde_loss_fields:
+            _add_pde_loss_fields(self, eval_quad_points)
+
+
+def _add_pde_loss_fields(ds, eval_quad_points: int):
+    """`mapping_tensor_fine` (identity: the fine lattice is already in lattice order) and per-sample `u_true_fine_tensor`."""
+    if ds.dim != 2:
+        raise NotImplementedError("pde_loss fields: 2-D datasets only")
+    ds.mapping_tensor_fine = torch.arange(eval_quad_points ** 2)
+    for d in ds.samples:
+        attach_fine_fields(d, eval_quad_points)
 
 
 class Mixed_DataLoader:

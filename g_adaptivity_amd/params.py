@@ -41,7 +41,7 @@ def hot_path_opt(**overrides) -> dict:
         'reg_skew': False,                  # params.py:269
         'dropout': 0.0,                     # params.py:287
         # training
-        'loss_type': 'mesh_loss',           # params.py:289 (run_params sets pde_loss; FEM tail is out of scope)
+        'loss_type': 'mesh_loss',           # params.py:289 (run_params sets pde_loss: 2-D Poisson, g_adaptivity_amd/fem.py)
         'loss_fn': 'mse',
         'lr': 0.001, 'decay': 0.0,
         'device': 'cpu',

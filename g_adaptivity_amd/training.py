@@ -57,6 +57,8 @@ class FusedIteration:
             return 'loss is not the native mse_loss / l1_loss'
         if not (model._fusable() and o['share_conv']):
             return 'not a fusable weight-shared block'
+        if o['loss_type'] == 'pde_loss':
+            return 'loss_type pde_loss: the FEM tail trains through the autograd iteration'
         if o.get('learn_step') or o.get('softmax_temp_type') == 'learnable_a' or o['loss_type'] != 'mesh_loss':
             return 'learnable steps / temperature or a loss other than mesh_loss'
         if o.get('gnn_inc_glob_feat_f') or o.get('gnn_inc_glob_feat_uu') or o.get('gnn_normalize'):
