@@ -28,6 +28,12 @@ def _require_gpu(t: torch.Tensor, what: str):
         raise TypeError(f"{what}: fp32 expected, got {t.dtype}")
 
 
+def bucket_cuts(c: int, S: int = 1):
+    """Offsets of [Wq | bq | Wk | bk | end] (S stacked convs each) in a flat parameter or gradient bucket: the layout FlatAdam gives
+    the conv parameters and the weight-gradient ops return."""
+    return [0, S * c * c, S * (c * c + c), S * (2 * c * c + c), S * (2 * c * c + 2 * c)]
+
+
 def composite_coeffs(wq, bq, wk):
     """(A, p0) = (Wk^T Wq, Wk^T bq) on device via the native kernel (no autograd)."""
     c = wq.shape[0]
@@ -148,7 +154,7 @@ class _GrandEulerBlock(torch.autograd.Function):
                                           ptr(d_x0), c, st),
               'gadapt_block_backward')
         scratch = torch.empty(32 * (c * c + c), device=dev, dtype=torch.float32)
-        cuts = [0, S * c * c, S * (c * c + c), S * (2 * c * c + c), S * (2 * c * c + 2 * c)]
+        cuts = bucket_cuts(c, S)
         d_wq, d_wk = flat[cuts[0]:cuts[1]].view(S, c, c), flat[cuts[2]:cuts[3]].view(S, c, c)
         d_bq, d_bk = flat[cuts[1]:cuts[2]].view(S, c), flat[cuts[3]:cuts[4]].view(S, c)
         for s in range(S):                      # slab -> second-level sums + chain rule to the Linear parameters: 2 launches
@@ -405,18 +411,25 @@ def small_backward_fits(graph: MeshGraph, part, c: int) -> bool:
         and lib().gadapt_small_forward_lds_bytes(part[2], part[3], c) > 0 and lib().gadapt_small_backward_lds_bytes(part[2], part[3], c) > 0
 
 
+def _small_args(graph, part, x_comp, dim, f_tensor, uu_tensor, enc_weight, wq, bq, wk, S, layer_params, num_layers, out, out_cols, alpha, x_all):
+    """gadapt_small_forward's argument list up to x_all (gadapt_small_forward_loss continues it with the loss arguments); fields by
+    address (int or None), everything else as tensors."""
+    mesh_ptr, n_meshes, max_nodes, max_edges = part
+    c = wq.shape[-1]
+    return [graph.c_ref, ptr(mesh_ptr[0]), ptr(mesh_ptr[1]), n_meshes, max_nodes, max_edges, x_comp, dim, f_tensor, uu_tensor, ptr(enc_weight),
+            enc_weight.shape[1], ptr(wq), ptr(bq), ptr(wk), c * c if S > 1 else 0, c if S > 1 else 0, ptr(layer_params), num_layers, ptr(out),
+            out_cols, ptr(alpha), ptr(x_all)]
+
+
 def _small_launch(graph, part, x_comp, f_tensor, uu_tensor, enc_weight, wq, bq, wk, layer_params, num_layers, out_cols, want_alpha, keep):
     n, dim = x_comp.shape
     c, S = wq.shape[1], wq.shape[0]
     dev = x_comp.device
-    mesh_ptr, n_meshes, max_nodes, max_edges = part
     out = torch.empty(n, out_cols, device=dev, dtype=torch.float32)
     alpha = torch.empty(num_layers, max(graph.num_edges, 1), device=dev, dtype=torch.float32) if (want_alpha or keep) else None
     x_all = torch.empty(num_layers, n, c, device=dev, dtype=torch.float32) if keep else None
-    check(lib().gadapt_small_forward(graph.c_ref, ptr(mesh_ptr[0]), ptr(mesh_ptr[1]), n_meshes, max_nodes, max_edges, ptr(x_comp), dim,
-                                     ptr(f_tensor), ptr(uu_tensor), ptr(enc_weight), enc_weight.shape[1],
-                                     ptr(wq), ptr(bq), ptr(wk), c * c if S > 1 else 0, c if S > 1 else 0,
-                                     ptr(layer_params), num_layers, ptr(out), out_cols, ptr(alpha), ptr(x_all), c, current_stream(dev)),
+    check(lib().gadapt_small_forward(*_small_args(graph, part, ptr(x_comp), dim, ptr(f_tensor), ptr(uu_tensor), enc_weight, wq, bq, wk, S,
+                                                  layer_params, num_layers, out, out_cols, alpha, x_all), c, current_stream(dev)),
           'gadapt_small_forward')
     return out, alpha, x_all
 
@@ -465,7 +478,7 @@ class _SmallMeshBlock(torch.autograd.Function):
                                           ctx.out_cols, ptr(wq), ptr(bq), ptr(wk), c * c if S > 1 else 0, c if S > 1 else 0, ptr(lp), L,
                                           ptr(slab), c, st), 'gadapt_small_backward')
         flat = torch.empty(S * (2 * c * c + 2 * c), device=dev, dtype=torch.float32)
-        cuts = [0, S * c * c, S * (c * c + c), S * (2 * c * c + c), S * (2 * c * c + 2 * c)]
+        cuts = bucket_cuts(c, S)
         d_wq, d_wk = flat[cuts[0]:cuts[1]].view(S, c, c), flat[cuts[2]:cuts[3]].view(S, c, c)
         d_bq, d_bk = flat[cuts[1]:cuts[2]].view(S, c), flat[cuts[3]:cuts[4]].view(S, c)
         scratch = torch.empty(32 * row, device=dev, dtype=torch.float32)
@@ -543,3 +556,108 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
 def l1_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """`F.l1_loss(out, data.x_phys)` (`src/run_GNN.py:82`) as one launch."""
     return _MeshLoss.apply(pred, target, True)
+
+
+def flat_bucket(wq, bq, wk):
+    """Address of [Wq | bq | Wk] when the three tensors lie back to back in that order (FlatAdam's bucket), else None."""
+    c = wq.shape[0]
+    ok = wq.is_contiguous() and bq.is_contiguous() and wk.is_contiguous() and bq.data_ptr() == wq.data_ptr() + 4 * c * c \
+        and wk.data_ptr() == bq.data_ptr() + 4 * c
+    return wq.data_ptr() if ok else None
+
+
+class _OneCall:
+    """A one-call forward of a weight-shared model: buffers and C-ABI argument list built once; per call only the node-field addresses
+    and the stream are filled in.  The list points into the parameters' storage: `moved()` notices storage that moved (FlatAdam lays
+    its bucket out, `load_state_dict(assign=True)`, `p.data = ...`) and `bind()` rebuilds the list over the same buffers."""
+
+    def moved(self) -> bool:
+        return any(t.data_ptr() != p for t, p in self._live)
+
+    def __call__(self, x_comp, f_tensor, uu_tensor, stream) -> int:
+        """Node fields by address (None: not an input).  Returns the number of loss partials written (0 without a target)."""
+        a, i = self.args, self._at
+        a[i], a[i + 2], a[i + 3], a[-1] = x_comp, f_tensor, uu_tensor, stream
+        rc = self._fn(*a)
+        if rc < 0:
+            check(rc, self._name)
+        return rc
+
+    def _buffers(self, model, graph, target, l1, keep_alpha):
+        o = model.opt
+        self.model, self.graph, self.target, self.l1 = model, graph, target, int(bool(l1))
+        self.n, self.c, self.L, self.d = graph.num_nodes, int(o['hidden_dim']), int(o['num_layers']), int(model.dim)
+        self.f32 = dict(device=torch.device(o['device']), dtype=torch.float32)
+        self.alpha = torch.empty(self.L, max(graph.num_edges, 1), **self.f32) if keep_alpha else None
+        self.seed = torch.empty(self.n, self.d, **self.f32) if target is not None else None
+        self.partials = torch.zeros(lib().gadapt_loss_partials_max(), **self.f32) if target is not None else None
+        self._fn = getattr(lib(), self._name)
+        self._conv = model.conv_layers[0]
+
+
+class BlockForwardCall(_OneCall):
+    """`gadapt_block_forward_loss`: the compact block behind the zero-pad identity encoder (layer 0 reads the node fields, the last
+    layer writes the [N,4] head `out` is a view of).  With `target` it also writes the loss derivative `seed` and the loss partials
+    (`training.FusedIteration`); without, it is the evaluation forward (`inference.GraphedForward`).  `coeffs` (A, p0) are inputs,
+    except where the layer-0 launch computes them from weights laid out back to back (`in_forward`: hidden 64 on wide-forward graphs)."""
+
+    _name, _at = 'gadapt_block_forward_loss', 2
+
+    def __init__(self, model, graph, target=None, l1=False, coeffs=None, store=False):
+        self._buffers(model, graph, target, l1, target is not None or store)
+        n, c, f32 = self.n, self.c, self.f32
+        self.x_all = torch.empty(self.L, n, c, **f32)            # slot l = input of layer l (slot 0: the compact [N,4] rows at its start)
+        self.x_top4 = torch.empty(n, 4, **f32)
+        self.out = self.x_top4[:, :self.d]
+        self.coeffs = coeffs if coeffs is not None else (torch.empty(c, c, **f32), torch.empty(c, **f32))
+        self.lp = model._layer_params(f32['device']).contiguous()
+        self._computes = bool(lib().gadapt_forward_computes_coeffs(graph.c_ref, c))
+        self._fn_coeffs = lib().gadapt_coeffs_forward
+        if store:
+            model._publish_attention(graph, self.alpha)
+        self.bind()
+
+    def bind(self):
+        cv, c = self._conv, self.c
+        wq, bq, wk = self._w = (cv.lin_query.weight, cv.lin_query.bias, cv.lin_key.weight)
+        self._live = [(t, t.data_ptr()) for t in self._w]
+        self.bucket = flat_bucket(wq, bq, wk)
+        self.in_forward = self._computes and self.bucket is not None
+        self.args = [self.graph.c_ref, ptr(self.x_all), None, self.d, None, None, self.L, ptr(self.coeffs[0]), ptr(self.coeffs[1]),
+                     self.bucket if self.in_forward else None, ptr(self.lp), ptr(self.alpha), ptr(self.x_top4), ptr(self.target),
+                     0 if self.target is None else self.d, self.l1, ptr(self.seed), ptr(self.partials), c, None]
+
+    def compute_coeffs(self, stream):
+        """(A, p0) of the weights as they are now: one launch."""
+        wq, bq, wk = self._w
+        rc = self._fn_coeffs(wq.data_ptr(), bq.data_ptr(), wk.data_ptr(), self.args[7], self.args[8], self.c, stream)
+        if rc != 0:
+            check(rc, 'gadapt_coeffs_forward')
+
+
+class SmallForwardCall(_OneCall):
+    """`gadapt_small_forward` (evaluation: `inference.GraphedForward`) or, with `target`, `gadapt_small_forward_loss` (the head of a
+    small-mesh `training.FusedIteration`, keeping x_all / alpha for its backward): encoder, every layer and the head as ONE launch.
+    `route`: the model's route of the batch (`GNN._route`), of form 'small'."""
+
+    _at = 6
+
+    def __init__(self, model, route, target=None, l1=False):
+        self._name = 'gadapt_small_forward' if target is None else 'gadapt_small_forward_loss'
+        self._buffers(model, route.small['graph'], target, l1, target is not None or route.store)
+        self.plan = route.small
+        self.out_cols = self.d if (target is not None or route.ident) else self.c
+        self.out = torch.empty(self.n, self.out_cols, **self.f32)
+        self.x_all = torch.empty(self.L, self.n, self.c, **self.f32) if target is not None else None
+        if route.store:
+            model._publish_attention(self.graph, self.alpha)
+        self.bind()
+
+    def bind(self):
+        w = (self._conv.lin_query.weight, self._conv.lin_query.bias, self._conv.lin_key.weight, self.model.enc.weight)
+        self._live = [(t, t.data_ptr()) for t in w]
+        self.args = _small_args(self.graph, self.plan['part'], None, self.d, None, None, w[3], *w[:3], 1, self.plan['lp'], self.L, self.out,
+                                self.out_cols, self.alpha, self.x_all)
+        if self.target is not None:
+            self.args += [ptr(self.target), self.l1, ptr(self.seed), ptr(self.partials)]
+        self.args += [self.c, None]

@@ -9,7 +9,7 @@ is done once per batch topology (`graph.GraphCache`), and the whole residual loo
 from __future__ import annotations
 
 import time
-from typing import Dict, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -84,6 +84,17 @@ def build_conv_list(opt):
               get_conv(opt, opt['conv_type'], opt['hidden_dim'], opt['hidden_dim'], opt['global_feat_dim'])
               for _ in range(opt['num_layers'])]
     return nn.ModuleList(layers)
+
+
+class Route(NamedTuple):
+    """How `GNN.forward` runs one batch (`GNN._route`), with the facts the one-call consumers decide by."""
+    form: str               # 'small' (one launch per batch) | 'compact' | 'dense' (block op) | 'gat_plus' | 'layers' (layer by layer)
+    small: Optional[dict]   # the one-launch plan of form 'small'
+    shared: bool            # one weight-shared conv, constant steps and temperature
+    plain: bool             # no global features, no gnn_normalize: the node fields go in as they are
+    ident: bool             # dec is Identity
+    store: bool             # the layers keep their attention (stored_ei / stored_alpha)
+    native_in: bool         # fp32 node fields the encoder kernel reads in place
 
 
 class MLP(nn.Module):
@@ -237,19 +248,46 @@ class GNN(nn.Module):
                 and o.get('gat_plus_type') in ('GAT_res_lap', 'GAT_lin') and o['non_lin'] in Fn.NONLIN_CODES
                 and o.get('fused_gat_plus', True) and not (self.training and o.get('dropout', 0.0) > 0))
 
-    # ------------------------------------------------------------------ one-launch forward of small-mesh batches
+    # ------------------------------------------------------------------ the route a forward takes
+    def _route(self, data, graph, x_comp, f, uu) -> 'Route':
+        """The one place that decides how `forward` runs this batch (`Route.form`), together with the facts by which the one-call
+        consumers (`inference.GraphedForward`, `training.FusedIteration.eligible`) choose.  `graph` is read for the small-mesh form
+        only (device tensors): on the CPU every model-side rule applies."""
+        o = self.opt
+        glob = bool(o.get('gnn_inc_glob_feat_f') or o.get('gnn_inc_glob_feat_uu'))
+        ident = isinstance(self.dec, nn.Identity)
+        store = o['conv_type'] == 'GRAND' or isinstance(o.get('show_mesh_evol_plots'), bool)
+        native_in = all(t is None or (t.dtype == torch.float32 and t.dim() == 1) for t in (f, uu)) and x_comp.dtype == torch.float32 \
+            and o['hidden_dim'] in Fn._native.SUPPORTED_HIDDEN         # the encoder kernel's row layouts; other widths: dense GEMM
+        block = self._fusable()
+        small = self._small_plan(data, graph, x_comp, f, uu) if block and not glob else None
+        if small is not None:
+            form = 'small'
+        elif block:
+            enc = self.enc
+            # identity encoder = zero-pad (GNN.py:75-82): layer 0 reads the compact [N,4] features, the padded [N,C] matrix is never
+            # written (nor read back by the layer-0 backward)
+            compact = (not glob and isinstance(enc, nn.Linear) and enc.bias is None and not enc.weight.requires_grad and native_in
+                       and o.get('compact_slots', True) and o['num_layers'] >= 2 and o['hidden_dim'] >= 8 and enc.weight.shape[1] <= 4
+                       and self._enc_is_zero_pad())
+            form = 'compact' if compact else 'dense'
+        else:
+            form = 'gat_plus' if self._gat_plus_fusable() else 'layers'
+        shared = bool(o['share_conv'] and not o.get('learn_step') and o.get('softmax_temp_type') != 'learnable_a')
+        return Route(form, small, shared, not (glob or o.get('gnn_normalize')), ident, store, native_in)
+
     def _small_plan(self, data, graph, x_comp, f, uu):
-        """Everything `functional.small_forward` / `small_block` need besides the node fields, or None when the batch / the model
-        state does not qualify: fusable conv, frozen bias-free Linear encoder on fp32 fields, hidden <= 32, meshes that are
-        contiguous node ranges and fit a workgroup (graph.mesh_partition, functional.small_forward_fits).  With autograd on
-        (training) also: fixed steps and temperature (the one-launch backward returns the conv gradients only)."""
+        """What `functional.small_forward` / `small_block` need besides the node fields and the conv weights, or None when the batch /
+        the model state does not qualify (the caller has checked `_fusable`): frozen bias-free Linear encoder on fp32 fields, hidden <= 32,
+        meshes that are contiguous node ranges and fit a workgroup (graph.mesh_partition, functional.small_forward_fits).  With autograd
+        on (training) also: fixed steps and temperature (the one-launch backward returns the conv gradients only)."""
         o = self.opt
         # training = autograd is on AND some conv parameter wants a gradient: an eval-mode model called outside no_grad with frozen
         # weights is an evaluation (nothing to keep for a backward, the evaluation policy's sizes apply)
         train = torch.is_grad_enabled() and any(p.requires_grad for p in self.conv_layers.parameters())
         if not x_comp.is_cuda:                                             # (the per-layer path raises the no-CPU-fallback error)
             return None
-        if not (Fn.SMALL_MESH_FORWARD and self._fusable() and o['hidden_dim'] <= 32
+        if not (Fn.SMALL_MESH_FORWARD and o['hidden_dim'] <= 32
                 and isinstance(self.enc, nn.Linear) and self.enc.bias is None and not self.enc.weight.requires_grad and x_comp.dtype == torch.float32
                 and all(t is None or (t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous() and not t.requires_grad) for t in (f, uu))
                 and not x_comp.requires_grad and o['loss_type'] in ('mesh_loss', 'modular')):
@@ -259,36 +297,35 @@ class GNN(nn.Module):
         part = graph.mesh_partition(getattr(data, 'batch', None))
         if not (Fn.small_backward_fits if train else Fn.small_forward_fits)(graph, part, o['hidden_dim']):
             return None
-        dev = x_comp.device
-        first = self.conv_layers[0]
-        keep = (lambda t: t) if train else (lambda t: t.detach())
-        if o['share_conv']:
-            wq, bq, wk, bk = (keep(t).unsqueeze(0) for t in (first.lin_query.weight, first.lin_query.bias, first.lin_key.weight, first.lin_key.bias))
-        else:
-            wq = torch.stack([keep(l.lin_query.weight) for l in self.conv_layers])
-            bq = torch.stack([keep(l.lin_query.bias) for l in self.conv_layers])
-            wk = torch.stack([keep(l.lin_key.weight) for l in self.conv_layers])
-            bk = torch.stack([keep(l.lin_key.bias) for l in self.conv_layers])
-        lp = self._layer_params(dev)
+        lp = self._layer_params(x_comp.device)
         if o.get('learn_step'):                                            # _layer_params returned the [L] scales alone
             lp = torch.stack([torch.cat([s_.detach().reshape(1) for s_ in self.steps]), lp.detach()], dim=1)
-        store = o['conv_type'] == 'GRAND' or isinstance(o.get('show_mesh_evol_plots'), bool)
-        ident = isinstance(self.dec, nn.Identity)
-        return {'graph': graph, 'part': part, 'wq': wq.contiguous(), 'bq': bq.contiguous(), 'wk': wk.contiguous(), 'bk': bk, 'lp': lp.detach().contiguous(),
-                'enc_w': self.enc.weight.detach().contiguous(), 'store': store, 'ident': ident, 'out_cols': self.dim if ident else o['hidden_dim'],
-                'train': train}
+        return {'graph': graph, 'part': part, 'lp': lp.detach().contiguous(), 'enc_w': self.enc.weight.detach().contiguous(), 'train': train}
 
-    def _small_run(self, plan, x_comp, f, uu):
+    def _stacked(self, detach=False):
+        """(wq, bq, wk, bk) of the distinct convs as [S,C,C] / [S,C]: S = 1 weight-shared (views of the parameters), else L (stacked)."""
+        names = (('lin_query', 'weight'), ('lin_query', 'bias'), ('lin_key', 'weight'), ('lin_key', 'bias'))
+        get = (lambda l, m, a: getattr(getattr(l, m), a).detach()) if detach else (lambda l, m, a: getattr(getattr(l, m), a))
+        if self.opt['share_conv']:
+            return tuple(get(self.conv_layers[0], m, a).unsqueeze(0) for m, a in names)
+        return tuple(torch.stack([get(l, m, a) for l in self.conv_layers]) for m, a in names)
+
+    def _publish_attention(self, graph, alpha):
+        """stored_ei / stored_alpha of every layer (GRAND_plus.py:253-256, :381, :403-404)."""
+        for l, layer in enumerate(self.conv_layers):
+            layer.stored_ei, layer._stored = graph.edge_index, (graph, alpha[l])
+
+    def _small_run(self, r: Route, x_comp, f, uu):
+        plan, L, out_cols = r.small, self.opt['num_layers'], self.dim if r.ident else self.opt['hidden_dim']
+        wq, bq, wk, bk = self._stacked(detach=not plan['train'])
         if plan['train']:
-            x, alpha = Fn.small_block(plan['graph'], plan['part'], x_comp, f, uu, plan['enc_w'], plan['wq'], plan['bq'], plan['wk'], plan['bk'],
-                                      plan['lp'], self.opt['num_layers'], plan['out_cols'])
+            x, alpha = Fn.small_block(plan['graph'], plan['part'], x_comp, f, uu, plan['enc_w'], wq, bq, wk, bk, plan['lp'], L, out_cols)
         else:
-            x, alpha = Fn.small_forward(plan['graph'], plan['part'], x_comp, f, uu, plan['enc_w'], plan['wq'], plan['bq'], plan['wk'], plan['lp'],
-                                        self.opt['num_layers'], plan['out_cols'], want_alpha=plan['store'])
-        if plan['store']:                                                  # GRAND_plus.py:253-256, :381
-            for l, layer in enumerate(self.conv_layers):
-                layer.stored_ei, layer._stored = plan['graph'].edge_index, (plan['graph'], alpha[l])
-        if not plan['ident']:
+            x, alpha = Fn.small_forward(plan['graph'], plan['part'], x_comp, f, uu, plan['enc_w'], wq, bq, wk, plan['lp'], L, out_cols,
+                                        want_alpha=r.store)
+        if r.store:
+            self._publish_attention(plan['graph'], alpha)
+        if not r.ident:
             x = self.dec(x) if self.dec is not None else x                 # GNN.py:298
             x = x[:, :self.dim]                                            # GNN.py:299
         return x
@@ -337,51 +374,41 @@ class GNN(nn.Module):
         def features():                                                    # the concatenated matrix, only where a caller needs it
             return torch.cat([x_comp] + [t.unsqueeze(-1) for t in (f, uu) if t is not None] + glob, dim=1).float()
 
-        fusable = self._fusable()
-        x_all, sliced, x0_cols = None, False, 0
-        feats, coeffs = None, None
-        first = self.conv_layers[0]
+        r = self._route(data, graph, x_comp, f, uu)
         # ---- small meshes (evaluation, and training at the sizes functional.small_training_policy takes): encoder + all layers + head as
         # ONE launch, one workgroup per mesh (the reference's own
         # sizes: params.py:37,56,107,130-134; utils_eval.py:193-201, utils_eval_Burgers.py:282-300)
-        if fusable and not glob:
-            plan = self._small_plan(data, graph, x_comp, f, uu)
-            if plan is not None:
-                x = self._small_run(plan, x_comp, f, uu)
-                if not self.training and not torch.cuda.is_current_stream_capturing():
-                    torch.cuda.current_stream(dev).synchronize()           # the stamp is read as a latency (utils_eval.py:201)
-                self.end_MLmodel = time.time()                             # GNN.py:301
-                return x
+        if r.form == 'small':
+            x = self._small_run(r, x_comp, f, uu)
+            if not self.training and not torch.cuda.is_current_stream_capturing():
+                torch.cuda.current_stream(dev).synchronize()           # the stamp is read as a latency (utils_eval.py:201)
+            self.end_MLmodel = time.time()                             # GNN.py:301
+            return x
+        block = r.form in ('compact', 'dense')
+        x_all, sliced, x0_cols = None, False, 0
+        feats, coeffs = None, None
+        first = self.conv_layers[0]
         # weight-shared conv (GNN.py:131-140): its composite coefficients ride in the encoder's launch
-        conv_w = (first.lin_query.weight, first.lin_query.bias, first.lin_key.weight) \
-            if (fusable and o['share_conv'] and o['hidden_dim'] in Fn._native.SUPPORTED_HIDDEN) else None
+        conv_w = (first.lin_query.weight, first.lin_query.bias, first.lin_key.weight) if (block and o['share_conv']) else None
         if glob:                                                           # differentiable wrt the CNN parameters
             feats = features()
             x = F.linear(feats, self.enc.weight, self.enc.bias) if isinstance(self.enc, nn.Linear) else self.enc(feats)
         elif isinstance(self.enc, nn.Linear) and not self.enc.weight.requires_grad and self.enc.bias is None:
-            native_in = all(t is None or (t.dtype == torch.float32 and t.dim() == 1) for t in (f, uu)) and x_comp.dtype == torch.float32 \
-                and o['hidden_dim'] in Fn._native.SUPPORTED_HIDDEN         # the encoder kernel's row layouts; other widths: dense GEMM
-            if (fusable or self._gat_plus_fusable()) and not (self.training and o.get('dropout', 0.0) > 0):
+            if r.form != 'layers':
                 # encoder output lands in slot 0 of the block's activation buffer: no copy
                 x_all = torch.empty(o['num_layers'] + 1, n, o['hidden_dim'], device=dev, dtype=torch.float32)
-                out0 = x_all[0]
-            else:
-                out0 = None
-            if (fusable and o.get('compact_slots', True) and native_in and x_all is not None and o['num_layers'] >= 2 and o['hidden_dim'] >= 8
-                    and self.enc.weight.shape[1] <= 4 and self._enc_is_zero_pad()):
-                # identity encoder = zero-pad (GNN.py:75-82): layer 0 reads the compact [N,4] features, the padded
-                # [N,C] matrix is never written (nor read back by the layer-0 backward)
+            if r.form == 'compact':
                 x0_cols = 4
                 x = Fn.encode_features(x_comp, f, uu, self.enc.weight[:4], out=x_all[0].view(-1)[:4 * n].view(n, 4), conv=conv_w)
                 if conv_w is not None:
                     x, coeffs = x
-            elif native_in:                                                # GNN.py:225-239 + :270 in one launch
-                x = Fn.encode_features(x_comp, f, uu, self.enc.weight, out=out0, conv=conv_w if x_all is not None else None)
-                if conv_w is not None and x_all is not None:
+            elif r.native_in:                                              # GNN.py:225-239 + :270 in one launch
+                x = Fn.encode_features(x_comp, f, uu, self.enc.weight, out=None if x_all is None else x_all[0], conv=conv_w)
+                if conv_w is not None:
                     x, coeffs = x
             elif o['hidden_dim'] in Fn._native.SUPPORTED_HIDDEN:
                 feats = features()
-                x = Fn.encode_linear(feats, self.enc.weight, out=out0)
+                x = Fn.encode_linear(feats, self.enc.weight, out=None if x_all is None else x_all[0])
             else:
                 feats = features()
                 x = F.linear(feats, self.enc.weight)
@@ -391,26 +418,14 @@ class GNN(nn.Module):
         if x_all is None:
             x = F.dropout(x, o.get('dropout', 0.0), training=self.training)               # GNN.py:271
 
-        if fusable:
-            if o['share_conv']:
-                wq, bq = first.lin_query.weight.unsqueeze(0), first.lin_query.bias.unsqueeze(0)
-                wk, bk = first.lin_key.weight.unsqueeze(0), first.lin_key.bias.unsqueeze(0)
-            else:
-                wq = torch.stack([l.lin_query.weight for l in self.conv_layers])
-                bq = torch.stack([l.lin_query.bias for l in self.conv_layers])
-                wk = torch.stack([l.lin_key.weight for l in self.conv_layers])
-                bk = torch.stack([l.lin_key.bias for l in self.conv_layers])
-            store = o['conv_type'] == 'GRAND' or isinstance(o.get('show_mesh_evol_plots'), bool)
-            x, alpha = Fn.grand_euler_block(x, wq, bq, wk, bk, self._layer_params(dev), graph,
-                                            o['num_layers'], want_alpha=store, x_all=x_all,
-                                            out_cols=self.dim if (isinstance(self.dec, nn.Identity) and o.get('compact_slots', True)) else None,
-                                            x0_cols=x0_cols, coeffs=coeffs,
+        if block:
+            sliced = r.ident and o.get('compact_slots', True)
+            x, alpha = Fn.grand_euler_block(x, *self._stacked(), self._layer_params(dev), graph, o['num_layers'], want_alpha=r.store,
+                                            x_all=x_all, out_cols=self.dim if sliced else None, x0_cols=x0_cols, coeffs=coeffs,
                                             steps=list(self.steps) if o.get('learn_step') else None)
-            sliced = isinstance(self.dec, nn.Identity) and o.get('compact_slots', True)
-            if store:                                                      # GRAND_plus.py:253-256, :381
-                for l, layer in enumerate(self.conv_layers):
-                    layer.stored_ei, layer._stored = graph.edge_index, (graph, alpha[l])
-        elif self._gat_plus_fusable():
+            if r.store:
+                self._publish_attention(graph, alpha)
+        elif r.form == 'gat_plus':
             # conv_type='GAT_plus' (GNN.py:120-121): the L layers with their update (GNN.py:284-296) as one block op - per layer one
             # fused forward launch, two in backward (csrc/gadapt_gat.inc) - on the self-looped graph GATConv builds
             looped = graph.with_self_loops()
@@ -421,8 +436,7 @@ class GNN(nn.Module):
             x, alpha = Fn.gat_plus_block(x, att_src, att_dst, looped, o['num_layers'], float(o['time_step']), bool(o['residual']),
                                          o['gat_plus_type'] == 'GAT_res_lap', o['non_lin'], out_cols=self.dim if sliced else None,
                                          x_all=x_all if (x_all is not None and x.data_ptr() == x_all.data_ptr()) else None)
-            for l, layer in enumerate(self.conv_layers):                  # GRAND_plus.py:403-404,413-414: stored_ei / stored_alpha
-                layer.stored_ei, layer._stored = looped.edge_index, (looped, alpha[l])
+            self._publish_attention(looped, alpha)
         else:
             mesh = getattr(self.dataset, 'mesh', None)
             if o.get('data_type') == 'randg_mix' and isinstance(getattr(data, 'mesh', None), (list, tuple)) and data.mesh:

@@ -14,9 +14,10 @@ no graph launch (`direct` is True).
 from __future__ import annotations
 
 import time
-from typing import Optional
-
 import torch
+
+from ._native import current_stream
+from .functional import BlockForwardCall, SmallForwardCall, flat_bucket
 
 FIELDS = ('x_comp', 'f_tensor', 'uu_tensor')
 
@@ -26,41 +27,45 @@ class GraphedForward:
         if model.training:
             raise RuntimeError("GraphedForward captures the evaluation forward: call model.eval() first")
         self.model = model
-        dev = torch.device(model.opt['device'])
-        self.device = dev
-        self.direct, self._plan = False, None
-        self.static = data.clone().to(dev)                 # the graph reads these tensors by address
-        o = model.opt
-        if not o.get('gnn_normalize') and not (o.get('gnn_inc_glob_feat_f') or o.get('gnn_inc_glob_feat_uu')):
-            with torch.no_grad():
-                xc = self.static.x_comp if self.static.x_comp.dim() == 2 else self.static.x_comp.unsqueeze(-1)
-                graph = model._graph(self.static, xc.shape[0], dev)
-                f = self.static.f_tensor if o['gnn_inc_feat_f'] else None
-                uu = self.static.uu_tensor if o['gnn_inc_feat_uu'] else None
-                self._plan = model._small_plan(self.static, graph, xc, f, uu)
-        # The direct launch passes raw parameter addresses, taken once: only when every one of them IS live parameter storage - one
-        # shared conv (the plan's weights are views of the parameters) and constant steps / temperature.  Per-layer convs and learnable
-        # steps / temperature are STACKED COPIES in the plan (gnn._small_plan): launched directly they would go stale with the next
-        # optimizer step or load_state_dict, so those models take the captured graph below, which re-stacks from the live parameters on
-        # every replay.
-        if self._plan is not None and not (o['share_conv'] and not o.get('learn_step') and o.get('softmax_temp_type') != 'learnable_a'):
-            self._plan = None
-        self.issued = False
-        if self._plan is not None:                         # one kernel per call: launched directly, nothing to capture
-            self.direct = True
-            self._use_f, self._use_uu = bool(o['gnn_inc_feat_f']), bool(o['gnn_inc_feat_uu'])
-            self._last = {}
-            self._prepare_direct()
-            return
-        self._warmup = warmup
-        if self._issuable():                               # the whole forward as ONE C-ABI call on the caller's tensors (see _prepare_issued)
-            self.issued = True
-            self._use_f, self._use_uu = bool(o['gnn_inc_feat_f']), bool(o['gnn_inc_feat_uu'])
-            self._last = {}
-            self._prepare_issued()
-            return
-        self._capture()
+        self.device = torch.device(model.opt['device'])
+        self.static = data.clone().to(self.device)         # the graph reads these tensors by address
         self._last = {}                                    # field -> (source tensor, its version) of the last copy
+        o = model.opt
+        self._use_f, self._use_uu = bool(o['gnn_inc_feat_f']), bool(o['gnn_inc_feat_uu'])
+        r, graph = self._route()
+        x = self.static.x_comp
+        self._n = x.shape[0]
+        # The one-call forms pass raw parameter addresses, taken once: only when every one of them IS live parameter storage - one
+        # shared conv and constant steps / temperature (per-layer convs and learnable steps / temperature are stacked copies: launched
+        # directly they would go stale with the next optimizer step or load_state_dict, so those models take the captured graph below,
+        # which re-stacks from the live parameters on every replay) - and the node fields go in as they are.
+        one_call = r.shared and r.plain
+        # small meshes: the whole forward is one kernel, launched directly on the caller's field tensors
+        self.direct = one_call and r.form == 'small'
+        # weight-shared blocks behind the identity encoder: the whole forward as ONE C-ABI call on the caller's tensors.  A replay of the
+        # captured forward costs about 8 us of idle GPU before its four launches start (docs/measurements.md K); the same four launches
+        # issued by one call cost the host ~20 us and the GPU nothing extra.  It passes no attention buffer: models that store attention
+        # are captured.
+        self.issued = (one_call and r.form == 'compact' and r.ident and not r.store
+                       and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == model.dim)
+        if self.direct:
+            self._call = SmallForwardCall(model, r)
+            self._dec = not r.ident
+        elif self.issued:
+            self._call = BlockForwardCall(model, graph)
+        else:
+            self._warmup = warmup
+            self._capture()
+            return
+        self.out = self._call.out
+
+    def _route(self):
+        m, o = self.model, self.model.opt
+        with torch.no_grad():
+            xc = self.static.x_comp if self.static.x_comp.dim() == 2 else self.static.x_comp.unsqueeze(-1)
+            graph = m._graph(self.static, xc.shape[0], self.device)
+            return m._route(self.static, graph, xc, self.static.f_tensor if o['gnn_inc_feat_f'] else None,
+                            self.static.uu_tensor if o['gnn_inc_feat_uu'] else None), graph
 
     def _capture(self):
         """Capture `model(self.static)`.  The graph reads the parameters by ADDRESS: in-place updates are followed, parameter storage
@@ -78,112 +83,6 @@ class GraphedForward:
             self.out = model(self.static)
         self._live = [(t, t.data_ptr()) for t in model.parameters()]
 
-    # ------------------------------------------------------------------ weight-shared blocks behind the identity encoder: one C-ABI call
-    def _issuable(self) -> bool:
-        """The model side of `training.FusedIteration.eligible`: the block `gadapt_block_forward_loss` runs with the node fields read by
-        its layer-0 launch - a fusable weight-shared GRAND / GRAND_plus block of >= 2 layers at hidden >= 8, constant steps and temperature,
-        the frozen zero-pad identity encoder, no decoder, no global features or normalisation, compact slots."""
-        import torch.nn as nn
-        m, o = self.model, self.model.opt
-        x = self.static.x_comp
-        return bool(m._fusable() and o['share_conv'] and o.get('compact_slots', True) and o['num_layers'] >= 2 and o['hidden_dim'] >= 8
-                    and not o.get('learn_step') and o.get('softmax_temp_type') != 'learnable_a'
-                    and not (o.get('gnn_inc_glob_feat_f') or o.get('gnn_inc_glob_feat_uu') or o.get('gnn_normalize'))
-                    and isinstance(m.enc, nn.Linear) and m.enc.bias is None and m.enc.weight.shape[1] <= 4 and m._enc_is_zero_pad()
-                    and isinstance(m.dec, nn.Identity) and o['conv_type'] != 'GRAND' and not isinstance(o.get('show_mesh_evol_plots'), bool)
-                    and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == m.dim)
-
-    def _prepare_issued(self):
-        """A replay of the captured forward costs about 8 us of idle GPU before its four launches start (docs/measurements.md K); the same
-        four launches issued by ONE C-ABI call (`gadapt_block_forward_loss` without a target: layer 0 reads the node fields itself, the
-        last layer writes the head rows) cost the host ~20 us and the GPU nothing extra - and they read the caller's field tensors in place,
-        so there are no static buffers to copy into.  The composite coefficients come from the layer-0 launch where it computes them
-        (hidden 64 on graphs the wide forward takes), else from a coefficient launch per call: always those of the weights as they are."""
-        from . import _native
-        from .functional import current_stream
-        m, o, dev = self.model, self.model.opt, self.device
-        xc = self.static.x_comp
-        n, c, L = int(xc.shape[0]), int(o['hidden_dim']), int(o['num_layers'])
-        self._n = n
-        graph = self._graph_obj = m._graph(self.static, n, dev)
-        f32 = dict(device=dev, dtype=torch.float32)
-        self._x_all = torch.empty(L, n, c, **f32)
-        self._x_top4 = torch.empty(n, 4, **f32)
-        self.out = self._x_top4[:, :m.dim]
-        self._coeffs = (torch.empty(c, c, **f32), torch.empty(c, **f32))
-        self._lp = m._layer_params(dev).contiguous()
-        conv = m.conv_layers[0]
-        self._w = (conv.lin_query.weight, conv.lin_query.bias, conv.lin_key.weight)
-        lib = _native.lib()
-        self._in_forward = bool(lib.gadapt_forward_computes_coeffs(graph.c_ref, c)) and self._flat_bucket() is not None
-        self._fn, self._fn_coeffs, self._stream = lib.gadapt_block_forward_loss, lib.gadapt_coeffs_forward, current_stream
-        self._args = [graph.c_ref, self._x_all.data_ptr(), None, m.dim, None, None, L, self._coeffs[0].data_ptr(), self._coeffs[1].data_ptr(), None,
-                      self._lp.data_ptr(), None, self._x_top4.data_ptr(), None, 0, 0, None, None, c, None]
-        self._c = c
-        self._live = [(t, t.data_ptr()) for t in self._w]
-
-    def _flat_bucket(self):
-        """Address of [Wq | bq | Wk] when the three tensors lie back to back in that order (FlatAdam's bucket), else None."""
-        wq, bq, wk = self._w
-        c = wq.shape[0]
-        ok = wq.is_contiguous() and bq.is_contiguous() and wk.is_contiguous() and bq.data_ptr() == wq.data_ptr() + 4 * c * c \
-            and wk.data_ptr() == bq.data_ptr() + 4 * c
-        return wq.data_ptr() if ok else None
-
-    def _issued_call(self, data, fields, sync):
-        if any(t.data_ptr() != ptr_ for t, ptr_ in self._live):     # parameter storage moved (FlatAdam laid its bucket out, ...)
-            self._prepare_issued()
-        a = self._args
-        xc = self._field('x_comp', data, fields, True)
-        f = self._field('f_tensor', data, fields, self._use_f)
-        uu = self._field('uu_tensor', data, fields, self._use_uu)
-        st = self._stream(self.device)
-        a[2], a[4], a[5] = xc.data_ptr(), None if f is None else f.data_ptr(), None if uu is None else uu.data_ptr()
-        if self._in_forward:
-            a[9] = self._flat_bucket()
-        if a[9] is None:                                            # the weights as they are now -> (A, p0): one launch
-            wq, bq, wk = self._w
-            rc = self._fn_coeffs(wq.data_ptr(), bq.data_ptr(), wk.data_ptr(), a[7], a[8], self._c, st)
-            if rc != 0:
-                from . import _native
-                _native.check(rc, 'gadapt_coeffs_forward')
-        a[-1] = st
-        rc = self._fn(*a)
-        if rc != 0:
-            from . import _native
-            _native.check(min(rc, -1), 'gadapt_block_forward_loss')
-        if sync:
-            torch.cuda.current_stream(self.device).synchronize()
-        self.model.end_MLmodel = time.time()               # same stamp the eager forward leaves (GNN.py:301)
-        return self.out
-
-    # ------------------------------------------------------------------ small meshes: one kernel, launched directly
-    def _prepare_direct(self):
-        """The argument list of gadapt_small_forward, built once: per call only the three field pointers and the stream change."""
-        from . import _native
-        from .functional import current_stream
-        pl, m = self._plan, self.model
-        graph, (mesh_ptr, n_meshes, max_nodes, max_edges) = pl['graph'], pl['part']
-        n = graph.num_nodes
-        c, S, L = pl['wq'].shape[1], pl['wq'].shape[0], m.opt['num_layers']
-        self.out = torch.empty(n, pl['out_cols'], device=self.device, dtype=torch.float32)
-        self._alpha = torch.empty(L, max(graph.num_edges, 1), device=self.device, dtype=torch.float32) if pl['store'] else None
-        dim = m.dim
-        n_feat = pl['enc_w'].shape[1]
-        self._fn = _native.lib().gadapt_small_forward
-        self._stream = current_stream
-        self._args = [graph.c_ref, mesh_ptr[0].data_ptr(), mesh_ptr[1].data_ptr(), n_meshes, max_nodes, max_edges, None, dim, None, None, pl['enc_w'].data_ptr(), n_feat,
-                      pl['wq'].data_ptr(), pl['bq'].data_ptr(), pl['wk'].data_ptr(), c * c if S > 1 else 0, c if S > 1 else 0, pl['lp'].data_ptr(), L,
-                      self.out.data_ptr(), pl['out_cols'], None if self._alpha is None else self._alpha.data_ptr(), None, c, None]
-        self._n = n
-        # the parameters whose storage the argument list points into: a re-bound `.data` (FlatAdam lays its bucket out on its first
-        # step, load_state_dict(assign=True), ...) moves them - checked per call (refresh())
-        first = m.conv_layers[0]
-        self._live = [(t, t.data_ptr()) for t in (first.lin_query.weight, first.lin_query.bias, first.lin_key.weight, m.enc.weight)]
-        if pl['store']:                                    # GRAND_plus.py:253-256, :381: the layers show the static attention tensor
-            for l, layer in enumerate(m.conv_layers):
-                layer.stored_ei, layer._stored = graph.edge_index, (graph, self._alpha[l])
-
     def _field(self, name, data, fields, want):
         if not want:
             return None
@@ -197,46 +96,41 @@ class GraphedForward:
             setattr(self.static, name, src)
         if src.numel() != (self._n * self.model.dim if name == 'x_comp' else self._n):
             raise ValueError(f"{name}: {tuple(src.shape)} does not fit the {self._n} nodes this forward was prepared for")
-        return src
+        return src.data_ptr()
 
     def refresh(self):
-        """Rebuild the direct launch's argument list / capture the graph again from the model as it is now (parameter storage that
+        """Rebuild the one call's argument list / capture the graph again from the model as it is now (parameter storage that
         moved)."""
-        if self.issued:
-            self._prepare_issued()
-            return
-        if not self.direct:
+        if not (self.direct or self.issued):
             self._capture()
             return
         if self.direct:
-            with torch.no_grad():
-                xc = self.static.x_comp if self.static.x_comp.dim() == 2 else self.static.x_comp.unsqueeze(-1)
-                o = self.model.opt
-                plan = self.model._small_plan(self.static, self._plan['graph'], xc, self.static.f_tensor if o['gnn_inc_feat_f'] else None,
-                                              self.static.uu_tensor if o['gnn_inc_feat_uu'] else None)
-            if plan is None:
+            r, _ = self._route()
+            if not (r.form == 'small' and r.shared and r.plain):
                 raise RuntimeError("GraphedForward.refresh(): the model no longer qualifies for the one-launch forward; build a new GraphedForward")
-            self._plan = plan
-            self._prepare_direct()
+        self._call.bind()
 
-    def _direct_call(self, data, fields, sync):
-        if any(t.data_ptr() != ptr_ for t, ptr_ in self._live):
+    def _flat_bucket(self):
+        """Address of the conv's [Wq | bq | Wk] when they lie back to back (FlatAdam's bucket), else None."""
+        conv = self.model.conv_layers[0]
+        return flat_bucket(conv.lin_query.weight, conv.lin_query.bias, conv.lin_key.weight)
+
+    def _one_call(self, data, fields, sync):
+        call = self._call
+        if call.moved():                                   # parameter storage moved (FlatAdam laid its bucket out, ...)
             self.refresh()
-        a = self._args
+        st = current_stream(self.device)
         xc = self._field('x_comp', data, fields, True)
         f = self._field('f_tensor', data, fields, self._use_f)
         uu = self._field('uu_tensor', data, fields, self._use_uu)
-        a[6], a[8], a[9] = xc.data_ptr(), None if f is None else f.data_ptr(), None if uu is None else uu.data_ptr()
-        a[24] = self._stream(self.device)
-        rc = self._fn(*a)
-        if rc != 0:
-            from . import _native
-            _native.check(rc, 'gadapt_small_forward')
+        if self.issued and not call.in_forward:            # (A, p0) of the weights as they are now: one launch
+            call.compute_coeffs(st)
+        call(xc, f, uu, st)
         if sync:
             torch.cuda.current_stream(self.device).synchronize()
         self.model.end_MLmodel = time.time()               # same stamp the eager forward leaves (GNN.py:301)
         out = self.out
-        if not self._plan['ident']:
+        if self.direct and self._dec:
             out = self.model.dec(out) if self.model.dec is not None else out   # GNN.py:298
             out = out[:, :self.model.dim]                  # GNN.py:299
         return out
@@ -245,10 +139,8 @@ class GraphedForward:
     def __call__(self, data=None, *, sync: bool = True, **fields) -> torch.Tensor:
         """New node fields either as a batch object (`x_comp`, `f_tensor`, `uu_tensor` are read) or as keywords.
         Returns the static output tensor (overwritten by the next call; clone it to keep it)."""
-        if self.direct:
-            return self._direct_call(data, fields, sync)
-        if self.issued:
-            return self._issued_call(data, fields, sync)
+        if self.direct or self.issued:
+            return self._one_call(data, fields, sync)
         if any(t.data_ptr() != ptr_ for t, ptr_ in self._live):
             self.refresh()
         for name in FIELDS:

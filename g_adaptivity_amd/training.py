@@ -21,16 +21,16 @@ from typing import Callable, Dict, Optional, Tuple
 import torch
 
 from . import graph as _graph_mod
-from .functional import mse_loss, unit_gradient
+from .functional import BlockForwardCall, SmallForwardCall, bucket_cuts, l1_loss, mse_loss, unit_gradient
 from .optim import FlatAdam
-
-import torch.nn as nn
-
-from . import _native
 from ._native import check, current_stream, lib, ptr
 
 INPUT_FIELDS = ('x_comp', 'f_tensor', 'uu_tensor')
 TOPOLOGY_FIELDS = ('edge_index', 'to_boundary_edge_mask', 'to_corner_nodes_mask', 'diff_boundary_edges_mask', 'batch')
+
+
+def _node_fields(model, data):
+    return (data.f_tensor if model.opt['gnn_inc_feat_f'] else None, data.uu_tensor if model.opt['gnn_inc_feat_uu'] else None)
 
 
 class FusedIteration:
@@ -50,22 +50,13 @@ class FusedIteration:
     @staticmethod
     def eligible(model, optimizer, loss_fn, data, target_field: str) -> Optional[str]:
         """None when the fused iteration applies, else the reason it does not."""
-        from .functional import l1_loss
         o = model.opt
-        dev = torch.device(o['device'])
         if loss_fn not in (mse_loss, l1_loss):
             return 'loss is not the native mse_loss / l1_loss'
-        if not (model._fusable() and o['share_conv']):
-            return 'not a fusable weight-shared block'
         if o['loss_type'] == 'pde_loss':
             return 'loss_type pde_loss: the FEM tail trains through the autograd iteration'
-        if o.get('learn_step') or o.get('softmax_temp_type') == 'learnable_a' or o['loss_type'] != 'mesh_loss':
-            return 'learnable steps / temperature or a loss other than mesh_loss'
-        if o.get('gnn_inc_glob_feat_f') or o.get('gnn_inc_glob_feat_uu') or o.get('gnn_normalize'):
-            return 'global features / field normalisation'
-        if not (isinstance(model.enc, nn.Linear) and model.enc.bias is None and not model.enc.weight.requires_grad
-                and model.enc.weight.shape[1] <= 4 and isinstance(model.dec, nn.Identity)):
-            return 'encoder is not a frozen bias-free Linear of at most 4 columns (or the decoder not Identity)'
+        if o['loss_type'] != 'mesh_loss':
+            return 'a loss other than mesh_loss'
         x_comp, tgt = data.x_comp, getattr(data, target_field, None)
         if not (torch.is_tensor(x_comp) and x_comp.is_cuda and x_comp.dtype == torch.float32 and x_comp.dim() == 2 and x_comp.is_contiguous()
                 and x_comp.shape[1] == model.dim and torch.is_tensor(tgt) and tgt.is_cuda and tgt.dtype == torch.float32 and tgt.is_contiguous()
@@ -76,98 +67,69 @@ class FusedIteration:
                 t = getattr(data, name, None)
                 if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.shape == (x_comp.shape[0],) and t.is_contiguous()):
                     return f'{name} is not a dense fp32 [N] device tensor'
+        graph = model._graph(data, x_comp.shape[0], torch.device(o['device']))
+        with torch.enable_grad():
+            r = model._route(data, graph, x_comp, *_node_fields(model, data))
+        if r.form not in ('small', 'compact'):
+            return f"the {r.form} forward: not the one-launch small-mesh form nor the compact block behind the zero-pad identity encoder"
+        if not (r.shared and r.plain and r.ident):
+            return 'not one weight-shared conv with constant steps and temperature, raw node fields and no decoder'
         conv = model.conv_layers[0]
         want = [conv.lin_query.weight, conv.lin_query.bias, conv.lin_key.weight, conv.lin_key.bias]
-        c = o['hidden_dim']
         if not (isinstance(optimizer, FlatAdam) and optimizer.capturable and optimizer.bucket is not None and optimizer._dev_state is not None
                 and optimizer.reduce_op == 'mean' and len(optimizer.active) == 4 and all(a is b for a, b in zip(optimizer.active, want))
-                and list(optimizer.offsets) == [0, c * c, c * c + c, 2 * c * c + c]):
+                and list(optimizer.offsets) == bucket_cuts(o['hidden_dim'])[:4]):
             return 'optimizer is not a laid-out FlatAdam(capturable=True) over exactly [Wq | bq | Wk | bk]'
-        graph = model._graph(data, x_comp.shape[0], dev)
-        with torch.enable_grad():
-            plan = model._small_plan(data, graph, x_comp, getattr(data, 'f_tensor', None) if o['gnn_inc_feat_f'] else None,
-                                     getattr(data, 'uu_tensor', None) if o['gnn_inc_feat_uu'] else None)
-        if plan is not None:                                            # small-mesh batch: the one-launch pair, 4 launches a step
-            if plan['part'][1] * 16 > lib().gadapt_loss_partials_max():
-                return 'small-mesh batch of more meshes than the loss partials (one per wave) allow'
-            return None
-        if not (o.get('compact_slots', True) and o['num_layers'] >= 2 and o['hidden_dim'] >= 8 and model._enc_is_zero_pad()):
-            return 'per-layer kernels: not >= 2 layers at hidden >= 8 with compact slots behind the zero-pad identity encoder'
+        if r.form == 'small' and r.small['part'][1] * 16 > lib().gadapt_loss_partials_max():
+            return 'small-mesh batch of more meshes than the loss partials (one per wave) allow'
         return None
 
     def __init__(self, model, optimizer: FlatAdam, loss_fn, data, target_field: str, coeffs=None):
-        from .functional import l1_loss
         o = model.opt
         self.model, self.optimizer = model, optimizer
         self.l1 = loss_fn is l1_loss
-        dev = self.device = torch.device(o['device'])
-        self.x_comp, self.target = data.x_comp, getattr(data, target_field)
-        self.f = data.f_tensor if o['gnn_inc_feat_f'] else None
-        self.uu = data.uu_tensor if o['gnn_inc_feat_uu'] else None
-        n, c, L = int(self.x_comp.shape[0]), int(o['hidden_dim']), int(o['num_layers'])
-        self.n, self.c, self.L, self.d = n, c, L, int(model.dim)
-        self.graph = model._graph(data, n, dev)
-        e = max(self.graph.num_edges, 1)
-        f32 = dict(device=dev, dtype=torch.float32)
-        self.lp = model._layer_params(dev).contiguous()
-        self._fw = self._bw = self._tl = None                           # argument lists of the C-ABI calls (built on first use: _plans)
-        self._bucket_ptr = None
+        self.device = torch.device(o['device'])
+        x_comp, target = data.x_comp, getattr(data, target_field)
+        f, uu = _node_fields(model, data)
+        self._fields = (x_comp, f, uu)                                  # read by address: kept alive with this object
+        n, c = int(x_comp.shape[0]), int(o['hidden_dim'])
+        self.n, self.c, self.d = n, c, int(model.dim)
+        self.graph = model._graph(data, n, self.device)
         with torch.enable_grad():
-            self.small = model._small_plan(data, self.graph, self.x_comp, self.f, self.uu)
+            r = model._route(data, self.graph, x_comp, f, uu)
+        self.small = r.small
+        self._in = (ptr(x_comp), ptr(f), ptr(uu))
+        f32 = dict(device=self.device, dtype=torch.float32)
         if self.small is not None:
-            self._init_small(optimizer, f32)
-            return
-        # activations: slot l = input of layer l (slot 0: the compact [N,4] rows at its start); the last layer writes the head only
-        self.x_all = torch.empty(L, n, c, **f32)
-        self.alpha = torch.empty(L, e, **f32)
-        self.x_top4 = torch.empty(n, 4, **f32)
-        self.seed = torch.empty(n, self.d, **f32)
-        self.partials = torch.zeros(lib().gadapt_loss_partials_max(), **f32)
-        self.loss = torch.zeros((), **f32)
-        self.g_ws, self.dxd_ws, self.edge_ws = torch.empty(2, n, c, **f32), torch.empty(n, c, **f32), torch.empty(e, 2, **f32)
-        self.slab_rows = lib().gadapt_backward_slab_rows(n, c)
-        self.slab = torch.empty(lib().gadapt_backward_slab_floats(n, c), **f32)
+            # small-mesh batches (csrc/gadapt_smallmesh.inc): the whole forward is ONE launch - encoder, composite coefficients, every
+            # layer, the head, the loss derivative and partial sums - the backward another, then the slab sums and the chain rule + Adam
+            # launch: 4 launches a step (the captured autograd iteration: 7)
+            self.fwd = SmallForwardCall(model, r, target, self.l1)
+            self.slab_rows = self.small['part'][1]
+            self.slab = torch.empty(self.slab_rows * (c * c + c), **f32)
+            self.coeffs, self.coeffs_in_forward = None, True           # the forward launch computes them: nothing to keep or refresh
+        else:
+            self.fwd = BlockForwardCall(model, self.graph, target, self.l1, coeffs, store=r.store)
+            e = max(self.graph.num_edges, 1)
+            self.g_ws, self.dxd_ws, self.edge_ws = torch.empty(2, n, c, **f32), torch.empty(n, c, **f32), torch.empty(e, 2, **f32)
+            self.slab_rows = lib().gadapt_backward_slab_rows(n, c)
+            self.slab = torch.empty(lib().gadapt_backward_slab_floats(n, c), **f32)
+            self.coeffs = self.fwd.coeffs
+            # hidden 64 on a graph the wide forward takes: the layer-0 launch computes (A, p0) from the live weights itself - no
+            # coefficient launch in the step (13 launches), and nothing to refresh when the weights change behind the step's back
+            self.coeffs_in_forward = self.fwd.in_forward
+        self.out, self.loss = self.fwd.out, torch.zeros((), **f32)
         self.scratch = torch.empty(32 * (c * c + c), **f32)
         self.flat = torch.empty(2 * c * c + 2 * c, **f32)                # [dWq | dbq | dWk | dbk]: the parameters' .grad are views of it
-        self.coeffs = coeffs if coeffs is not None else (torch.empty(c, c, **f32), torch.empty(c, **f32))
-        cuts = [0, c * c, c * c + c, 2 * c * c + c, 2 * c * c + 2 * c]
+        cuts = bucket_cuts(c)
         self.grads = [(p, self.flat[cuts[k]:cuts[k + 1]].view_as(p)) for k, p in enumerate(optimizer.active)]
-        self.out = self.x_top4[:, :self.d]
-        # hidden 64 on a graph the wide forward takes: the layer-0 launch computes (A, p0) from the live weights itself - no coefficient
-        # launch in the step (13 launches), and nothing to refresh when the weights change behind the step's back
-        self.coeffs_in_forward = bool(lib().gadapt_forward_computes_coeffs(self.graph.c_ref, c))
-
-    def _init_small(self, optimizer, f32):
-        """Small-mesh batches (csrc/gadapt_smallmesh.inc): the whole forward is ONE launch - encoder, composite coefficients, every
-        layer, the head, and with `gadapt_small_forward_loss` the loss derivative and partial sums - the backward another, then the slab
-        sums and the chain rule + Adam launch: 4 launches a step (the captured autograd iteration: 7)."""
-        n, c, L, pl = self.n, self.c, self.L, self.small
-        e = max(self.graph.num_edges, 1)
-        n_meshes = pl['part'][1]
-        self.x_all, self.alpha = torch.empty(L, n, c, **f32), torch.empty(L, e, **f32)
-        self.out = torch.empty(n, self.d, **f32)
-        self.seed = torch.empty(n, self.d, **f32)
-        self.partials = torch.zeros(lib().gadapt_loss_partials_max(), **f32)
-        self.loss = torch.zeros((), **f32)
-        self.slab_rows, self.slab = n_meshes, torch.empty(n_meshes * (c * c + c), **f32)
-        self.scratch = torch.empty(32 * (c * c + c), **f32)
-        self.flat = torch.empty(2 * c * c + 2 * c, **f32)
-        cuts = [0, c * c, c * c + c, 2 * c * c + c, 2 * c * c + 2 * c]
-        self.grads = [(p, self.flat[cuts[k]:cuts[k + 1]].view_as(p)) for k, p in enumerate(optimizer.active)]
-        self.coeffs, self.coeffs_in_forward = None, True               # the forward launch computes them: nothing to keep or refresh
-        self.enc_w = pl['enc_w']
-        if pl['store']:                                                 # GRAND_plus.py:253-256, :381: the layers show the stored attention
-            for l, layer in enumerate(self.model.conv_layers):
-                layer.stored_ei, layer._stored = self.graph.edge_index, (self.graph, self.alpha[l])
+        self._plans()
 
     def refresh_coeffs(self):
         """(A, p0) of the parameters as they are NOW (one launch): before the first step, and after any change of the weights that did
         not come from `finish()` (an eager optimizer step, `load_state_dict`, a restored snapshot)."""
-        if self.small is not None:
-            return
-        b, c = self.optimizer.bucket, self.c
-        check(lib().gadapt_coeffs_forward(ptr(b), ptr(b[c * c:]), ptr(b[c * c + c:]), ptr(self.coeffs[0]), ptr(self.coeffs[1]), c, current_stream(self.device)),
-              'gadapt_coeffs_forward')
+        if self.small is None:
+            self.fwd.compute_coeffs(current_stream(self.device))
 
     def _world(self) -> int:
         import torch.distributed as dist
@@ -177,32 +139,25 @@ class FusedIteration:
         return 1
 
     def _plans(self):
-        """The argument lists of the step's C-ABI calls, built once: every pointer in them is fixed for the life of this object (its own
-        buffers, the static batch's fields, the optimizer's laid-out bucket and moments) - per call only the stream, the number of loss
-        partials and the optimizer's hyper-parameters are filled in.  (Issued rather than replayed, a step's host cost is what is left of
-        the launch path: 34 us with the lists rebuilt per call, `data_ptr()` by `data_ptr()`.)"""
-        o, c, L, L_ = self.optimizer, self.c, self.L, lib()
+        """The argument lists of the backward and tail calls, built once over the forward's (`self.fwd`): every pointer in them is fixed
+        while the parameters' storage stays where it is (this object's buffers, the static batch's fields, the optimizer's laid-out bucket
+        and moments) - per call only the stream, the number of loss partials and the optimizer's hyper-parameters are filled in.  (Issued
+        rather than replayed, a step's host cost is what is left of the launch path: 34 us with the lists rebuilt per call, `data_ptr()`
+        by `data_ptr()`.)"""
+        o, c, fw, L_ = self.optimizer, self.c, self.fwd, lib()
+        fw.bind()
         b = o.bucket                                                    # [Wq | bq | Wk | bk]: the live parameters
-        self._bucket_ptr = b.data_ptr()
         if self.small is not None:
             mesh_ptr, n_meshes, max_nodes, max_edges = self.small['part']
-            wq, bq, wk = ptr(b), ptr(b[c * c:]), ptr(b[c * c + c:])
-            self._fw = (L_.gadapt_small_forward_loss, [self.graph.c_ref, ptr(mesh_ptr[0]), ptr(mesh_ptr[1]), n_meshes, max_nodes, max_edges,
-                                                       ptr(self.x_comp), self.d, ptr(self.f), ptr(self.uu), ptr(self.enc_w), self.enc_w.shape[1],
-                                                       wq, bq, wk, 0, 0, ptr(self.lp), L, ptr(self.out), self.d, ptr(self.alpha), ptr(self.x_all),
-                                                       ptr(self.target), int(self.l1), ptr(self.seed), ptr(self.partials), c, None], 'gadapt_small_forward_loss')
-            self._bw = (L_.gadapt_small_backward, [self.graph.c_ref, ptr(mesh_ptr[0]), ptr(mesh_ptr[1]), n_meshes, max_nodes, max_edges, ptr(self.x_all),
-                                                   ptr(self.alpha), ptr(self.seed), self.d, wq, bq, wk, 0, 0, ptr(self.lp), L, ptr(self.slab), c, None],
-                        'gadapt_small_backward')
+            cuts = bucket_cuts(c)
+            self._bw = (L_.gadapt_small_backward, [self.graph.c_ref, ptr(mesh_ptr[0]), ptr(mesh_ptr[1]), n_meshes, max_nodes, max_edges, ptr(fw.x_all),
+                                                   ptr(fw.alpha), ptr(fw.seed), self.d, ptr(b), ptr(b[cuts[1]:]), ptr(b[cuts[2]:]), 0, 0,
+                                                   ptr(self.small['lp']), fw.L, ptr(self.slab), c, None], 'gadapt_small_backward')
             a_ptr = p0_ptr = None
         else:
             a, p0 = self.coeffs
-            self._fw = (L_.gadapt_block_forward_loss, [self.graph.c_ref, ptr(self.x_all), ptr(self.x_comp), self.d, ptr(self.f), ptr(self.uu), L, ptr(a), ptr(p0),
-                                                       ptr(b) if self.coeffs_in_forward else None, ptr(self.lp), ptr(self.alpha), ptr(self.x_top4),
-                                                       ptr(self.target), self.d, int(self.l1), ptr(self.seed), ptr(self.partials), c, None],
-                        'gadapt_block_forward_loss')
-            self._bw = (L_.gadapt_block_backward, [self.graph.c_ref, ptr(self.x_all), 4, ptr(self.alpha), ptr(self.seed), self.d, L, ptr(a), 0, ptr(p0), 0,
-                                                   ptr(self.lp), ptr(self.g_ws), ptr(self.dxd_ws), ptr(self.edge_ws), ptr(self.slab), None, 0, None, c, None],
+            self._bw = (L_.gadapt_block_backward, [self.graph.c_ref, ptr(fw.x_all), 4, ptr(fw.alpha), ptr(fw.seed), self.d, fw.L, ptr(a), 0, ptr(p0), 0,
+                                                   ptr(fw.lp), ptr(self.g_ws), ptr(self.dxd_ws), ptr(self.edge_ws), ptr(self.slab), None, 0, None, c, None],
                         'gadapt_block_backward')
             a_ptr, p0_ptr = (None, None) if self.coeffs_in_forward else (ptr(a), ptr(p0))
         # gadapt_step_tail in its three forms: (slab given, moments given) = the whole tail; (slab, no moments) = this rank's gradient;
@@ -210,7 +165,7 @@ class FusedIteration:
         def tail(slab, moments):
             return [ptr(self.slab) if slab else None, self.slab_rows, ptr(self.scratch), ptr(b), ptr(self.flat),
                     ptr(o.exp_avg) if moments else None, ptr(o.exp_avg_sq) if moments else None, 0.0, 0.0, 0.0, 0.0, 0.0, ptr(o._dev_state), 1.0,
-                    a_ptr, p0_ptr, ptr(self.partials) if slab else None, 0, ptr(self.loss), self.n * self.d, c, None]
+                    a_ptr, p0_ptr, ptr(fw.partials) if slab else None, 0, ptr(self.loss), self.n * self.d, c, None]
         self._tl = {(False, False): tail(True, True), (True, False): tail(True, False), (False, True): tail(False, True)}
         self._fn_tail = L_.gadapt_step_tail
 
@@ -218,14 +173,10 @@ class FusedIteration:
         """zero_grad + model(data) + loss + backward: 4 + 7 launches at 4 layers (small-mesh batches: 1 + 1; the gradient of the conv
         parameters is still in the slab: `finish()` sums it).  Data parallel: also the slab sums + chain rule, so that `flat` holds this
         rank's gradient."""
-        if self._fw is None or self._bucket_ptr != self.optimizer.bucket.data_ptr():
+        if self.fwd.moved():
             self._plans()
         st = current_stream(self.device)
-        fn, args, name = self._fw
-        args[-1] = st
-        self.n_part = fn(*args)
-        if self.n_part < 0:
-            check(self.n_part, name)
+        self.n_part = self.fwd(*self._in, st)
         fn, args, name = self._bw
         args[-1] = st
         rc = fn(*args)
@@ -236,7 +187,7 @@ class FusedIteration:
             self._tail(stop_after_gradient=True)
 
     def _tail(self, stop_after_gradient=False, gradient_given=False, scale=1.0):
-        if self._fw is None or self._bucket_ptr != self.optimizer.bucket.data_ptr():
+        if self.fwd.moved():
             self._plans()
         g = self.optimizer.param_groups[0]
         args = self._tl[(stop_after_gradient, gradient_given)]
@@ -316,7 +267,6 @@ class GraphedTrainStep:
         self._hyper_captured: Optional[Tuple] = None
         self._side = torch.cuda.Stream(device=self.device)
         # the native one-launch losses take the preallocated root gradient (functional.unit_gradient): two launches fewer
-        from .functional import l1_loss
         self._root = unit_gradient(self.device) if loss_fn in (mse_loss, l1_loss) else None
         self._pool = None
         # fused=True: topologies whose step qualifies (FusedIteration.eligible) are captured as the 13-launch fused iteration instead of

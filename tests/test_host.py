@@ -469,3 +469,45 @@ def test_device_mesh_loader_fields_and_static_sink_on_cpu():
             seen_static += int(any(b is s for s in sinks.values()))
     assert set(sinks) == {4 * 49, 2 * 49}                           # one static batch per batch size (10 = 4 + 4 + 2)
     assert seen_static == 6 - 2                                     # every batch but the first of each size IS the static object
+
+@pytest.mark.parametrize("overrides,expect", [
+    ({}, dict(form='compact', shared=True, plain=True, ident=True, store=True)),
+    ({'show_mesh_evol_plots': 'False'}, dict(form='compact', store=False)),
+    ({'share_conv': False, 'show_mesh_evol_plots': 'False'}, dict(form='compact', shared=False, store=False)),
+    ({'learn_step': True}, dict(form='compact', shared=False)),
+    ({'softmax_temp_type': 'learnable_a'}, dict(form='compact', shared=False)),
+    ({'gnn_normalize': True}, dict(form='compact', plain=False)),
+    ({'gnn_inc_glob_feat_f': True}, dict(form='dense', plain=False)),
+    ({'conv_type': 'GRAND', 'show_mesh_evol_plots': 'False'}, dict(form='compact', store=True)),
+    ({'conv_type': 'GCN'}, dict(form='layers')),
+    ({'conv_type': 'GAT_plus'}, dict(form='gat_plus')),
+    ({'num_layers': 1}, dict(form='dense')),
+    ({'compact_slots': False}, dict(form='dense')),
+], ids=['default', 'no-plots', 'per-layer-convs', 'learn_step', 'learnable_a', 'gnn_normalize', 'global-features', 'GRAND', 'GCN',
+        'GAT_plus', 'one-layer', 'dense-slots'])
+def test_route_model_side_facts(overrides, expect):
+    """`GNN._route` decides the forward's form and states the facts the one-call consumers (`GraphedForward`, `FusedIteration.eligible`)
+    choose by.  On CPU tensors no small-mesh plan is made; every model-side rule still applies."""
+    opt = hot_path_opt(**{'mesh_dims': [7, 7], 'hidden_dim': 8, 'num_layers': 3, **overrides})
+    ds = MeshDataset([7, 7], 2, seed=0)
+    data = collate(ds.samples)
+    model = GNN(ds, opt)
+    r = model._route(data, None, data.x_comp, data.f_tensor, data.uu_tensor)
+    assert r.small is None
+    for k, v in expect.items():
+        assert getattr(r, k) == v, (k, r)
+
+
+def test_route_follows_the_encoder_and_decoder():
+    """An edited encoder weight is no longer the zero pad (dense slots); a decoder other than Identity is reported."""
+    opt = hot_path_opt(mesh_dims=[7, 7], hidden_dim=8, num_layers=3)
+    ds = MeshDataset([7, 7], 2, seed=0)
+    data = collate(ds.samples)
+    model = GNN(ds, opt)
+    route = lambda: model._route(data, None, data.x_comp, data.f_tensor, data.uu_tensor)
+    assert route().form == 'compact' and route().ident
+    with torch.no_grad():
+        model.enc.weight[0, 1] = 0.5
+    assert route().form == 'dense'
+    model.dec = torch.nn.Linear(8, 2)
+    assert route().form == 'dense' and not route().ident

@@ -17,9 +17,10 @@ for seed in range(3):
     xc = d.x_comp.unsqueeze(-1) if d.x_comp.dim() == 1 else d.x_comp
     graph = model._graph(d, xc.shape[0], dev)
     with torch.enable_grad():
-        plan = model._small_plan(d, graph, xc, d.f_tensor, d.uu_tensor)
+        plan = model._route(d, graph, xc, d.f_tensor, d.uu_tensor).small
     assert plan is not None and plan['train']
-    wq, bq, wk, lp = (plan[k].detach().contiguous() for k in ('wq', 'bq', 'wk', 'lp'))
+    wq, bq, wk, _ = (t.detach().contiguous() for t in model._stacked())
+    lp = plan['lp']
     out, alpha, x_all = Fn._small_launch(graph, plan['part'], xc.contiguous(), d.f_tensor, d.uu_tensor, plan['enc_w'], wq, bq, wk, lp, 1, 1, True, True)
     tgt = d.x_phys.reshape(out.shape)
     g_top = (2.0 * (out - tgt) / out.numel()).contiguous()
