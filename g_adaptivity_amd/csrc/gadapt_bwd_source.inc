@@ -11,6 +11,8 @@ struct BwdSArgs {
     int n_nodes, n_tiles, n_edges;
     unsigned long long* stamps;
     int g_cols;                                                 // GC kernels: g_in is [N,g_cols]
+    int c;                                                      // hidden size (read by grand_bwd_source_narrow_kernel only) ...
+    const int32_t* ell;                                         // ... and the graph's ELL table of out-neighbours (gadapt_graph::ell_s)
 };
 
 // Half of one node's out-edge rows: g_i and x_i of HN targets (two halves cover DM edges)
@@ -446,5 +448,64 @@ __global__ __launch_bounds__(Cfg<C>::NT, (C > 64 ? 2 : GADAPT_WAVES_BWD_S4)) voi
             }
         }
         __syncthreads();                                        // every wave is done with the CSR slice of this tile
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// backward, source pass of the narrow route (every layer input an [N,4] slot: DESIGN.md section 4): grand_bwd_source4_kernel's
+// result, g_out[j][c] = dxd[j][c] + sum_i alpha_ij dt g_i[c] + sum_o A[c][o] y_j[o] + sigma_j p0[c] (c = 0..3), with x_i and y_j
+// four columns wide as well.  ONE NODE PER LANE, grid-stride, no LDS: the out-neighbours and the row bounds in the first memory
+// round trip (ELL), the {alpha dt, ds} pairs, g and x rows (16 bytes each) in the second.  g_in is [N,4], or the compact
+// [N,g_cols] top gradient (g_cols > 0).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void grand_bwd_source_narrow_kernel(BwdSArgs p) {
+    const int C = p.c;
+    float a4[4][4];                                             // A[c][o], c, o < 4
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int o = 0; o < 4; ++o) a4[c][o] = p.A[c * C + o];
+    const float4 p04 = *reinterpret_cast<const float4*>(p.p0);
+    auto ld_g4 = [&](int i) __attribute__((always_inline)) {
+        return p.g_cols ? ld_row4_compact(p.g_in, i, 0, p.g_cols) : *reinterpret_cast<const float4*>(p.g_in + 4 * (size_t)i);
+    };
+    const float2* ew = reinterpret_cast<const float2*>(p.edge_ws);
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < p.n_nodes; j += (int64_t)gridDim.x * 256) {
+        const int e0 = p.rowptr[j], deg = p.rowptr[j + 1] - e0;
+        const int4 el0 = *reinterpret_cast<const int4*>(p.ell + 8 * (size_t)j), el1 = *reinterpret_cast<const int4*>(p.ell + 8 * (size_t)j + 4);
+        const float4 d4 = *reinterpret_cast<const float4*>(p.dxd + 4 * (size_t)j);
+        float4 z4 = f4zero(), y = f4zero();
+        float sig = 0.f;
+        if (deg <= 8 && p.n_edges > 0) {
+            const int last = p.n_edges - 1;
+            const int ej[8] = {el0.x, el0.y, el0.z, el0.w, el1.x, el1.y, el1.z, el1.w};
+            float2 ev[8]; float4 gk[8], xk[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {                        // unconditional, clamped: weight 0 past the row end
+                const int i = max(ej[k], 0);
+                ev[k] = ew[min(e0 + k, last)];
+                gk[k] = ld_g4(i);
+                xk[k] = *reinterpret_cast<const float4*>(p.x_in + 4 * (size_t)i);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float2 e = k < deg ? ev[k] : make_float2(0.f, 0.f);
+                axpy4(z4, e.x, gk[k]); axpy4(y, e.y, xk[k]); sig += e.y;
+            }
+        } else {
+            for (int e = e0; e < e0 + deg; ++e) {
+                const int i = p.col[e];
+                const float2 ev = ew[e];
+                axpy4(z4, ev.x, ld_g4(i)); axpy4(y, ev.y, *reinterpret_cast<const float4*>(p.x_in + 4 * (size_t)i)); sig += ev.y;
+            }
+        }
+        const float yv[4] = {y.x, y.y, y.z, y.w};
+        float t4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) t4[c] = fmaf(yv[o], a4[c][o], t4[c]);
+        *reinterpret_cast<float4*>(p.g_out + 4 * (size_t)j) = make_float4(d4.x + z4.x + t4[0] + sig * p04.x, d4.y + z4.y + t4[1] + sig * p04.y,
+                                                                          d4.z + z4.z + t4[2] + sig * p04.z, d4.w + z4.w + t4[3] + sig * p04.w);
     }
 }

@@ -597,14 +597,27 @@ __global__ __launch_bounds__(Cfg<C>::NT, (C >= GADAPT_ONE_WAVE_C ? 1 : GADAPT_WA
 // ------------------------------------------------------------------------------------------------
 // ELL: the neighbour indices come from the graph's ELL table (gadapt_graph::ell_t: entry k of row i = col[rowptr[i] + k]) with the row
 // bounds, in the FIRST round trip, so the alpha entries and the neighbour rows share the second: two trips per node instead of three.
-template <int SUMS, bool ELL = false>
-__global__ __launch_bounds__(256) void grand_bwd_target_compact_kernel(BwdTArgs p) {
+//
+// NARROW (grand_bwd_target_narrow_kernel): the same pass for a layer above layer 0 on the narrow route, where every layer's input is
+// an [N,4] slot (the zero-pad encoder's columns 4.. stay zero through every GRAND_plus layer: DESIGN.md section 4).  On top of the 20
+// partials it owes the source pass what grand_bwd_target_kernel<64, 0, ., true> (D4) writes: the per-edge pair {alpha dt, ds} in
+// source order (through tpos) and dxd[i][0..3] = (1 - dt) g_i[0..3] + sum_o dP_i[o] A[o][0..3].  g_in is [N,4], or the compact
+// [N,g_cols] top gradient (g_cols > 0).
+template <int SUMS, bool ELL, bool NARROW>
+__device__ __forceinline__ void bwd_target_compact_body(const BwdTArgs& p) {
+    static_assert(!NARROW || (SUMS == 0 && ELL), "narrow route: fixed steps and temperature, ELL graphs");
     __shared__ float red[4][24];
     const int C = p.c;
     const int gs = p.g_stride;                                  // floats between g rows: C, or 4 when the layer above ran the D4 / source4 pair
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float dt = p.lp[0], sc = p.lp[1];
     const float scl = SUMS ? sc * dt : sc;
+    const float w1 = 1.0f - dt;
+    float a4[NARROW ? 4 : 1][4];                                // NARROW: A[o][c], o, c < 4
+#pragma unroll
+    for (int o = 0; o < (NARROW ? 4 : 0); ++o)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) a4[o][c] = p.A[o * C + c];
     float acc[22];                                              // dA[o][c] (16), dp0[o] (4), d dt, d score_scale
 #pragma unroll
     for (int k = 0; k < 22; ++k) acc[k] = 0.f;
@@ -615,7 +628,7 @@ __global__ __launch_bounds__(256) void grand_bwd_target_compact_kernel(BwdTArgs 
     const int e_own = tid < 16 ? (tid >> 2) * C + (tid & 3) : C * C + (min(tid, 19) - 16);
     const float row_old = __builtin_nontemporal_load(row + e_own);
     for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < p.n_nodes; i += (int64_t)gridDim.x * 256) {
-        const float4 g4 = *reinterpret_cast<const float4*>(p.g_in + (size_t)i * gs);
+        const float4 g4 = (NARROW && p.g_cols) ? ld_row4_compact(p.g_in, (int)i, 0, p.g_cols) : *reinterpret_cast<const float4*>(p.g_in + (size_t)i * gs);
         const float4 xi = *reinterpret_cast<const float4*>(p.x_in + 4 * (size_t)i);
         const float4 dm = SUMS ? g4 : make_float4(dt * g4.x, dt * g4.y, dt * g4.z, dt * g4.w);
         const int e0 = p.rowptr[i], e1 = p.rowptr[i + 1], deg = e1 - e0;
@@ -627,13 +640,14 @@ __global__ __launch_bounds__(256) void grand_bwd_target_compact_kernel(BwdTArgs 
             // the usual case, three memory round trips per node: (g row head, x row, row bounds) -> (8 column / alpha pairs,
             // unconditional with clamped indices) -> (8 neighbour rows); a loop over the row would chain them per edge.  (ELL: two.)
             const int last = max(p.n_edges - 1, 0);
-            int cj[8]; float ak[8];
+            int cj[8], tp[8]; float ak[8];
             const int ej[8] = {el0.x, el0.y, el0.z, el0.w, el1.x, el1.y, el1.z, el1.w};
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int e = min(e0 + k, last);
                 if constexpr (ELL) cj[k] = max(ej[k], 0); else cj[k] = p.col[e];
                 ak[k] = p.alpha[e];
+                if constexpr (NARROW) tp[k] = p.tpos[e];
             }
             float4 xk[8];
 #pragma unroll
@@ -654,6 +668,7 @@ __global__ __launch_bounds__(256) void grand_bwd_target_compact_kernel(BwdTArgs 
                 const float ds = ak[k] * (da[k] - D) * scl;
                 dsum += ds;
                 axpy4(dP, ds, xk[k]);
+                if constexpr (NARROW) { if (k < deg) p.edge_ws[tp[k]] = make_float2(ak[k] * dt, ds); }
                 if constexpr (SUMS > 1) { if (ak[k] > 0.f) acc[21] = fmaf(ds, __logf(ak[k]), acc[21]); }
             }
             axpy4(dP, dsum, x0);
@@ -667,11 +682,21 @@ __global__ __launch_bounds__(256) void grand_bwd_target_compact_kernel(BwdTArgs 
                 const float ak = p.alpha[e];
                 const float ds = ak * (dot4(dm, xk) - D) * scl;
                 axpy4(dP, ds, xk);
+                if constexpr (NARROW) p.edge_ws[p.tpos[e]] = make_float2(ak * dt, ds);
                 if constexpr (SUMS > 1) { if (ak > 0.f) acc[21] = fmaf(ds, __logf(ak), acc[21]); }
             }
         }
         if constexpr (SUMS != 0) acc[20] += D - dot4(g4, xi);    // d dt = sum_i <g_i, m_i - x_i>, <g_i, m_i> = D (see the tiled kernel)
         const float dp[4] = {dP.x, dP.y, dP.z, dP.w}, xv[4] = {xi.x, xi.y, xi.z, xi.w};
+        if constexpr (NARROW) {
+            float t4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int o = 0; o < 4; ++o)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) t4[c] = fmaf(dp[o], a4[o][c], t4[c]);
+            *reinterpret_cast<float4*>(p.dxd + 4 * (size_t)i) =
+                make_float4(fmaf(w1, g4.x, t4[0]), fmaf(w1, g4.y, t4[1]), fmaf(w1, g4.z, t4[2]), fmaf(w1, g4.w, t4[3]));
+        }
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
 #pragma unroll
@@ -707,3 +732,6 @@ __global__ __launch_bounds__(256) void grand_bwd_target_compact_kernel(BwdTArgs 
         }
     }
 }
+template <int SUMS, bool ELL = false>
+__global__ __launch_bounds__(256) void grand_bwd_target_compact_kernel(BwdTArgs p) { bwd_target_compact_body<SUMS, ELL, false>(p); }
+__global__ __launch_bounds__(256) void grand_bwd_target_narrow_kernel(BwdTArgs p) { bwd_target_compact_body<0, true, true>(p); }

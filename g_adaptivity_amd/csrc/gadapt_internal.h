@@ -186,6 +186,12 @@ int gadapt_launch_bwd_target_c(int c, const gadapt_graph* g, const float* x_in, 
 // ... and the source pass of the same layer (g_out != NULL)
 int gadapt_launch_bwd_source_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, const float* edge_ws, const float* dxd,
                                const float* a, const float* p0, float* g_out, int g_cols, int out4, hipStream_t st);
+// the narrow route (every layer input an [N,4] slot; hidden 64 on graphs the wide forward takes: gadapt_narrow_takes_c)
+int gadapt_narrow_takes_c(const gadapt_graph* g, int c);
+int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* alpha,
+                                      const float* a, const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, hipStream_t st);
+int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* edge_ws,
+                                      const float* dxd, const float* a, const float* p0, float* g_out, hipStream_t st);
 int gadapt_slab_rows_c(int64_t n_nodes, int c);
 int gadapt_occupancy_fwd_c(int c);
 int gadapt_occupancy_bwd_target_c(int c);

@@ -418,10 +418,12 @@ extern "C" int gadapt_adam_step_dev(float* param, const float* grad, float* exp_
 // ------------------------------------------------------------------------------------------------
 static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers, const float* a, int64_t a_stride,
                          const float* p0, int64_t p0_stride, const float* layer_params, float* alpha_all, float* x_top4,
-                         int c, void* stream, const FwdExtra* extra) {
+                         int c, void* stream, const FwdExtra* extra, bool narrow = false) {
     if (int rc = check_graph(g, c)) return rc;
     if (!x_all || n_layers <= 0 || !a || !p0 || !layer_params) return fail(GADAPT_E_BADARG, "block_forward: bad argument");
     if (x0_cols != 0 && (x0_cols != 4 || n_layers < 2 || c < 8)) return fail(GADAPT_E_BADARG, "block_forward: compact x0 needs 4 columns, >= 2 layers, hidden >= 8");
+    if (narrow && (x0_cols != 4 || !x_top4 || !gadapt_narrow_takes_c(g, c)))
+        return fail(GADAPT_E_BADARG, "block_forward (narrow): compact x0, head rows, hidden 64 on a graph the wide forward takes (gadapt_narrow_route)");
     const size_t nc = (size_t)g->n_nodes * c;
     hipStream_t st = static_cast<hipStream_t>(stream);
     for (int l = 0; l < n_layers; ++l) {
@@ -438,7 +440,10 @@ static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n
             if (last) { ex_l.loss = extra->loss; ex_l.n_partials_out = extra->n_partials_out; }
             ex = &ex_l;
         }
-        if ((l == 0 && x0_cols) || (last && x_top4))             // compact input and/or compact-only output
+        if (narrow)                                              // [N,4] slot in, [N,4] slot out (the last layer: the head rows)
+            rc = gadapt_launch_fwd_c(c, g, x_all + l * nc, nullptr, a + l * a_stride, p0 + l * p0_stride, layer_params + 2 * l, alpha_l, 0, 4,
+                                     last ? x_top4 : x_all + (l + 1) * nc, st, ex);
+        else if ((l == 0 && x0_cols) || (last && x_top4))        // compact input and/or compact-only output
             rc = gadapt_launch_fwd_c(c, g, x_all + l * nc, (last && x_top4) ? nullptr : x_all + (l + 1) * nc, a + l * a_stride, p0 + l * p0_stride,
                                      layer_params + 2 * l, alpha_l, 0, l == 0 ? x0_cols : 0, last ? x_top4 : nullptr, st, ex);
         else
@@ -453,6 +458,12 @@ extern "C" int gadapt_block_forward(const gadapt_graph* g, float* x_all, int x0_
                                     int c, void* stream) {
     return block_forward(g, x_all, x0_cols, n_layers, a, a_stride, p0, p0_stride, layer_params, alpha_all, x_top4, c, stream, nullptr);
 }
+extern "C" int gadapt_narrow_route(const gadapt_graph* g, int c) { return g ? gadapt_narrow_takes_c(g, c) : 0; }
+extern "C" int gadapt_block_forward_narrow(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers, const float* a, int64_t a_stride,
+                                           const float* p0, int64_t p0_stride, const float* layer_params, float* alpha_all, float* x_top4,
+                                           int c, void* stream) {
+    return block_forward(g, x_all, x0_cols, n_layers, a, a_stride, p0, p0_stride, layer_params, alpha_all, x_top4, c, stream, nullptr, true);
+}
 
 // ------------------------------------------------------------------------------------------------
 // fused training step (run_GNN.py:99-131 as 13 launches): forward with the node fields as layer-0 input and the loss in the last
@@ -460,9 +471,9 @@ extern "C" int gadapt_block_forward(const gadapt_graph* g, float* x_all, int x0_
 // ------------------------------------------------------------------------------------------------
 extern "C" int gadapt_loss_partials_max(void) { return GADAPT_LOSS_PARTIALS_MAX; }
 extern "C" int gadapt_forward_computes_coeffs(const gadapt_graph* g, int c) { return g ? gadapt_forward_computes_coeffs_c(g, c) : 0; }
-extern "C" int gadapt_block_forward_loss(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor, const float* uu_tensor,
-                                         int n_layers, float* a, float* p0, const float* param, const float* layer_params, float* alpha_all, float* x_top4,
-                                         const float* target, int d, int l1, float* seed, float* loss_partials, int c, void* stream) {
+static int block_forward_loss(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor, const float* uu_tensor,
+                              int n_layers, float* a, float* p0, const float* param, const float* layer_params, float* alpha_all, float* x_top4,
+                              const float* target, int d, int l1, float* seed, float* loss_partials, int c, void* stream, bool narrow) {
     if (!x_comp || dim < 1 || dim > 4 || dim + (f_tensor ? 1 : 0) + (uu_tensor ? 1 : 0) > 4)
         return fail(GADAPT_E_BADARG, "block_forward_loss: 1..4 coordinates, coordinates + extras <= 4 columns");
     // target == NULL: no loss - the evaluation forward on the node fields (inference.GraphedForward issues it as this one call)
@@ -474,10 +485,23 @@ extern "C" int gadapt_block_forward_loss(const gadapt_graph* g, float* x_all, co
         return fail(GADAPT_E_BADARG, "block_forward_loss: param given, but this graph / hidden size does not compute the coefficients in its layer-0 launch (gadapt_forward_computes_coeffs)");
     FwdExtra ex{FieldSrc{x_comp, f_tensor, uu_tensor, dim}, x_all,
                 LossArgs{target, seed, loss_partials, d, l1 ? 1 : 0, 1.0f / (float)((int64_t)g->n_nodes * (d > 0 ? d : 1))}, &n_partials, param, a, p0};
-    if (int rc = block_forward(g, x_all, 4, n_layers, a, 0, p0, 0, layer_params, alpha_all, x_top4, c, stream, &ex)) return rc;
+    if (int rc = block_forward(g, x_all, 4, n_layers, a, 0, p0, 0, layer_params, alpha_all, x_top4, c, stream, &ex, narrow)) return rc;
     if (!target) return 0;
     if (n_partials <= 0 || n_partials > GADAPT_LOSS_PARTIALS_MAX) return fail(GADAPT_E_RUNTIME, "block_forward_loss: loss partial count out of range");
     return n_partials;
+}
+extern "C" int gadapt_block_forward_loss(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor, const float* uu_tensor,
+                                         int n_layers, float* a, float* p0, const float* param, const float* layer_params, float* alpha_all, float* x_top4,
+                                         const float* target, int d, int l1, float* seed, float* loss_partials, int c, void* stream) {
+    return block_forward_loss(g, x_all, x_comp, dim, f_tensor, uu_tensor, n_layers, a, p0, param, layer_params, alpha_all, x_top4, target, d, l1,
+                              seed, loss_partials, c, stream, false);
+}
+extern "C" int gadapt_block_forward_loss_narrow(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor,
+                                                const float* uu_tensor, int n_layers, float* a, float* p0, const float* param, const float* layer_params,
+                                                float* alpha_all, float* x_top4, const float* target, int d, int l1, float* seed, float* loss_partials,
+                                                int c, void* stream) {
+    return block_forward_loss(g, x_all, x_comp, dim, f_tensor, uu_tensor, n_layers, a, p0, param, layer_params, alpha_all, x_top4, target, d, l1,
+                              seed, loss_partials, c, stream, true);
 }
 
 extern "C" int gadapt_step_tail(const float* slab, int n_rows, float* scratch, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
@@ -563,6 +587,49 @@ extern "C" int gadapt_block_backward(const gadapt_graph* g, const float* x_all, 
                             edge_ws, inplace ? g_next : dxd_ws, slab_l, accumulate, d_dt, d_sc, g_next, 0, g_cols, x_cols, out4, g_stride, 1, st);
         if (rc) return rc;
         g_cur = g_next;
+    }
+    return GADAPT_OK;
+}
+
+// Backward of the narrow route (gadapt_block_forward_narrow): every slot of x_all holds [N,4] rows at its start, g_top is the compact
+// [N,g_top_cols] top gradient.  Layers L-1 .. 1: narrow target pass (dxd [N,4] in dxd_ws, {alpha dt, ds} in edge_ws), narrow source pass
+// (g_out [N,4], alternating between the two halves of g_ws); layer 0: grand_bwd_target_compact_kernel as on the compact route.
+extern "C" int gadapt_block_backward_narrow(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top,
+                                            int g_top_cols, int n_layers, const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
+                                            const float* layer_params, float* g_ws, float* dxd_ws, float* edge_ws, float* slab, float* d_layer_params,
+                                            int want_d_scale, float* d_x0, int c, void* stream) {
+    (void)want_d_scale;
+    if (int rc = check_graph(g, c)) return rc;
+    if (!x_all || !alpha_all || !g_top || n_layers < 2 || !a || !p0 || !layer_params || !g_ws || !dxd_ws || !edge_ws || !slab)
+        return fail(GADAPT_E_BADARG, "block_backward (narrow): bad argument");
+    if (x0_cols != 4 || g_top_cols < 1 || g_top_cols > 4 || d_x0 || d_layer_params || !gadapt_narrow_takes_c(g, c))
+        return fail(GADAPT_E_BADARG, "block_backward (narrow): compact x0, compact top gradient, no d_x0, fixed steps and temperature, "
+                                     "hidden 64 on a graph the wide forward takes (gadapt_narrow_route)");
+    const size_t nc = (size_t)g->n_nodes * c;
+    const bool shared = (a_stride == 0);
+    const int64_t slab_floats = gadapt_backward_slab_floats(g->n_nodes, c);
+    if (slab_floats < 0) return (int)slab_floats;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const float* g_cur = g_top;
+    int g_cols = g_top_cols;
+    for (int l = n_layers - 1; l >= 0; --l) {
+        float* slab_l = shared ? slab : slab + (size_t)l * slab_floats;
+        const int accumulate = (shared && l != n_layers - 1) ? 1 : 0;
+        const float* alpha_l = alpha_all + (size_t)l * g->n_edges;
+        int rc;
+        if (l == 0) {                                           // g_cur: layer 1's [N,4] result
+            rc = gadapt_launch_bwd_target_c(c, g, x_all, g_cur, alpha_l, a, layer_params, edge_ws, dxd_ws, slab_l, accumulate, nullptr, nullptr, 0, 0,
+                                            0, 4, 0, 4, 1, st);
+        } else {
+            float* g_next = g_ws + ((n_layers - 1 - l) & 1) * nc;
+            rc = gadapt_launch_bwd_target_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, alpha_l, a + l * a_stride, layer_params + 2 * l, edge_ws,
+                                                   dxd_ws, slab_l, accumulate, st);
+            if (!rc) rc = gadapt_launch_bwd_source_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, edge_ws, dxd_ws, a + l * a_stride, p0 + l * p0_stride,
+                                                            g_next, st);
+            g_cur = g_next;
+            g_cols = 0;
+        }
+        if (rc) return rc;
     }
     return GADAPT_OK;
 }

@@ -79,3 +79,16 @@ template <int C> static int occupancy_bwd_source() {
     return n;
 }
 int gadapt_occupancy_bwd_source_c(int c) { GADAPT_DISPATCH_C(c, occupancy_bwd_source<CC>()); }
+
+// narrow route (grand_bwd_source_narrow_kernel): x_in, dxd, g_out [N,4]; g_in [N,4] or the compact [N,g_cols] top gradient
+int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* edge_ws,
+                                      const float* dxd, const float* a, const float* p0, float* g_out, hipStream_t st) {
+    if (c != 64 || !g->ell_s || !g->rowptr_s || !g->col_s || g_cols < 0 || g_cols > 4) return fail(GADAPT_E_BADARG, "narrow source pass: hidden 64, ELL graph, 0..4 g columns");
+    BwdSArgs ps{x_in, g_in, edge_ws, dxd, a, p0, g->rowptr_s, g->col_s, nullptr, g_out, g->n_nodes, 0, g->n_edges, nullptr, g_cols};
+    ps.c = c;
+    ps.ell = g->ell_s;
+    const int grid = (int)std::min<int64_t>(((int64_t)g->n_nodes + 255) / 256, 4096);
+    ProfScope prof(2, st, 8);                                   // out4: [N,4] rows in and out
+    hipLaunchKernelGGL(grand_bwd_source_narrow_kernel, dim3(grid), dim3(256), 0, st, ps);
+    return check_launch("grand_bwd_source_narrow_kernel");
+}

@@ -78,3 +78,19 @@ template <int C> static int occupancy_bwd_target() {
     return n;
 }
 int gadapt_occupancy_bwd_target_c(int c) { GADAPT_DISPATCH_C(c, occupancy_bwd_target<CC>()); }
+
+// narrow route, layers 1..L-1 (grand_bwd_target_narrow_kernel): x_in, dxd [N,4]; g_in [N,4] or the compact [N,g_cols] top gradient.  The
+// slab row layout and grid of every other target-pass launch of the block (hidden c), so the layer-0 launch accumulates onto these rows.
+int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* alpha,
+                                      const float* a, const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, hipStream_t st) {
+    if (c != 64 || !g->ell_t || !g->tpos_s || g_cols < 0 || g_cols > 4) return fail(GADAPT_E_BADARG, "narrow target pass: hidden 64, ELL graph, 0..4 g columns");
+    BwdTArgs pt{x_in, g_in, alpha, a, lp, g->rowptr_t, g->col_t, g->tpos_s, nullptr, reinterpret_cast<float2*>(edge_ws), dxd, slab, nullptr,
+                g->n_nodes, tiles_for<64>(g->n_nodes), accumulate, 0, g->n_edges, nullptr, g_cols};
+    pt.c = c;
+    pt.g_stride = 4;
+    pt.ell = g->ell_t;
+    const dim3 grid(grid_for(pt.n_tiles, resident_blocks_bwd_t<64>(GADAPT_BWD_T_MAX_BLOCKS)));
+    ProfScope prof(1, st, g_cols ? 3 : 2);                     // compact input (and compact upstream gradient at the top layer)
+    hipLaunchKernelGGL(grand_bwd_target_narrow_kernel, grid, dim3(256), 0, st, pt);
+    return check_launch("grand_bwd_target_narrow_kernel");
+}

@@ -38,21 +38,26 @@ static int launch_wide_fwd(const gadapt_graph* g, const float* x_in, float* x_ou
             if (!half) { p.cw = ex->cw; p.a_out = ex->a_out; p.p0_out = ex->p0_out; }
             else if (ex->cw) return fail(GADAPT_E_BADARG, "wide forward on four-wave workgroups: the coefficients are given (gadapt_forward_computes_coeffs)");
         }
-        if (!x_out && !x_cols && ex->loss.target) { p.loss = ex->loss; if (ex->n_partials_out) *ex->n_partials_out = nwv * wide_grid(n_steps); }
+        if (!x_out && ex->loss.target) { p.loss = ex->loss; if (ex->n_partials_out) *ex->n_partials_out = nwv * wide_grid(n_steps); }
     }
     ProfScope prof(0, st, (x_cols ? 2 : 0) | (x_out ? 0 : 4));
     auto go = [&](auto kern, int lds) { allow_lds(kern, lds); hipLaunchKernelGGL(kern, dim3(wide_grid(n_steps)), dim3(64 * nwv), lds, st, p); };
     const bool head = !x_out && !x_cols;                        // head-only output: its own instantiation (aggregates one chunk)
+    // narrow route (compact input AND compact output, gadapt_block_forward_narrow): the last layer's launch also seeds the loss
+    const bool xloss = x_cols && !x_out && p.loss.target;
     if (big) {
-        if (x_cols) go(wide::fwd_kernel<true, true>, wide::fwd_lds_bytes<true>());
+        if (xloss) go(wide::fwd_kernel<true, true, true>, wide::fwd_lds_bytes<true>());
+        else if (x_cols) go(wide::fwd_kernel<true, true>, wide::fwd_lds_bytes<true>());
         else if (head) go(wide::fwd_kernel<false, true, true>, wide::fwd_lds_bytes<true>());
         else go(wide::fwd_kernel<false, true>, wide::fwd_lds_bytes<true>());
     } else if (half) {
-        if (x_cols) go(wide::fwd_kernel<true, false, false, 4>, wide::fwd_lds_bytes<false, 4>());
+        if (xloss) go(wide::fwd_kernel<true, false, true, 4>, wide::fwd_lds_bytes<false, 4>());
+        else if (x_cols) go(wide::fwd_kernel<true, false, false, 4>, wide::fwd_lds_bytes<false, 4>());
         else if (head) go(wide::fwd_kernel<false, false, true, 4>, wide::fwd_lds_bytes<false, 4>());
         else go(wide::fwd_kernel<false, false, false, 4>, wide::fwd_lds_bytes<false, 4>());
     } else {
-        if (x_cols) go(wide::fwd_kernel<true, false>, wide::fwd_lds_bytes<false>());
+        if (xloss) go(wide::fwd_kernel<true, false, true>, wide::fwd_lds_bytes<false>());
+        else if (x_cols) go(wide::fwd_kernel<true, false>, wide::fwd_lds_bytes<false>());
         else if (head) go(wide::fwd_kernel<false, false, true>, wide::fwd_lds_bytes<false>());
         else go(wide::fwd_kernel<false, false>, wide::fwd_lds_bytes<false>());
     }
@@ -65,6 +70,9 @@ static bool wide_takes(const gadapt_graph* g) {
 // 1: the layer-0 launch of a fused training step on this graph at this hidden size is the wide kernel, which computes the composite
 // coefficients itself (FwdExtra::cw); 0: they must be given (a coefficient launch ends the step)
 int gadapt_forward_computes_coeffs_c(const gadapt_graph* g, int c) { return (c == 64 && g && wide_takes(g) && !wide_half(g)) ? 1 : 0; }
+// 1: the narrow route (every layer on [N,4] slots, gadapt_block_forward_narrow) runs on this graph at this hidden size - the graphs whose
+// forward is the wide kernel, which reproduces the dense flow's arithmetic on channels 0..3 bit for bit
+int gadapt_narrow_takes_c(const gadapt_graph* g, int c) { return (c == 64 && g && wide_takes(g)) ? 1 : 0; }
 
 template <int C> static int launch_fwd(const gadapt_graph* g, const float* x_in, float* x_out, const float* a, const float* p0,
                                        const float* lp, float* alpha_out, int residual_only, int x_cols, float* x_top4, hipStream_t st, const FwdExtra* ex) {

@@ -56,7 +56,7 @@ class _GrandEulerBlock(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, wq, bq, wk, bk, layer_params, graph: MeshGraph, num_layers: int, want_alpha: bool, x_all=None,
-                out_cols=None, x0_cols=0, coeffs=None, *steps):
+                out_cols=None, x0_cols=0, coeffs=None, narrow=False, *steps):
         for t, n in ((x0, 'x'), (wq, 'lin_query.weight'), (bq, 'lin_query.bias'), (wk, 'lin_key.weight'),
                      (layer_params, 'layer_params')):
             _require_gpu(t, n)
@@ -90,7 +90,9 @@ class _GrandEulerBlock(torch.autograd.Function):
             for s in range(S):
                 check(lib().gadapt_coeffs_forward(ptr(wq[s]), ptr(bq[s]), ptr(wk[s]), ptr(a[s]), ptr(p0[s]), c, st),
                       'gadapt_coeffs_forward')
-        need_grad = any(ctx.needs_input_grad[:6]) or any(ctx.needs_input_grad[13:])
+        need_grad = any(ctx.needs_input_grad[:6]) or any(ctx.needs_input_grad[14:])
+        # narrow: every slot holds [N,4] rows at its start (x_top4 the last layer's); only with the compact x0 and the [N,4] head
+        narrow = bool(narrow) and bool(x0_cols) and out_cols is not None and out_cols <= 4 and not steps
         if x_all is None:                      # else: caller's [(L+1),N,C] buffer whose slot 0 already holds x0
             x_all = torch.empty(L + 1, n, c, device=dev, dtype=torch.float32)
             x_all[0].copy_(x0)
@@ -101,10 +103,11 @@ class _GrandEulerBlock(torch.autograd.Function):
         alpha = torch.empty(L, max(graph.num_edges, 1), device=dev, dtype=torch.float32) if keep_alpha else None
         # out_cols <= 4: the last layer writes only the [N,4] head of its rows (x_phys = x[:, :dim], GNN.py:299)
         x_top4 = torch.empty(n, 4, device=dev, dtype=torch.float32) if (out_cols is not None and out_cols <= 4) else None
-        check(lib().gadapt_block_forward(graph.c_ref, ptr(x_all), int(x0_cols), L, ptr(a), c * c if S > 1 else 0,
-                                         ptr(p0), c if S > 1 else 0, ptr(layer_params), ptr(alpha), ptr(x_top4), c, st),
-              'gadapt_block_forward')
-        ctx.graph, ctx.L, ctx.S, ctx.c = graph, L, S, c
+        fwd = lib().gadapt_block_forward_narrow if narrow else lib().gadapt_block_forward
+        check(fwd(graph.c_ref, ptr(x_all), int(x0_cols), L, ptr(a), c * c if S > 1 else 0,
+                  ptr(p0), c if S > 1 else 0, ptr(layer_params), ptr(alpha), ptr(x_top4), c, st),
+              'gadapt_block_forward_narrow' if narrow else 'gadapt_block_forward')
+        ctx.graph, ctx.L, ctx.S, ctx.c, ctx.narrow = graph, L, S, c, narrow
         ctx.out_cols, ctx.x0_cols = out_cols, int(x0_cols)
         ctx.save_for_backward(x_all, alpha if need_grad else None, a, p0, wq, bq, wk, layer_params)
         if x_top4 is not None:
@@ -137,7 +140,7 @@ class _GrandEulerBlock(torch.autograd.Function):
         dxd_ws = torch.empty(n, c, device=dev, dtype=torch.float32)
         edge_ws = torch.empty(max(graph.num_edges, 1), 2, device=dev, dtype=torch.float32)
         slab = torch.empty(S, slab_floats, device=dev, dtype=torch.float32)
-        want_lp = ctx.needs_input_grad[5] or any(ctx.needs_input_grad[13:])
+        want_lp = ctx.needs_input_grad[5] or any(ctx.needs_input_grad[14:])
         # one flat tensor [dWq | dbq | dWk | dbk | d dt (L) | d scale (L)]: installed as the parameters' .grad without a copy, it
         # is the gradient bucket of optim.FlatAdam (one Adam launch, one all-reduce); the 2L tail only when a step / scale
         # gradient is wanted (summed from per-workgroup partials by gadapt_layer_params_reduce)
@@ -148,11 +151,12 @@ class _GrandEulerBlock(torch.autograd.Function):
             d_lp = flat[n_w:]                   # [2,L], written whole by gadapt_layer_params_reduce below
             d_ws = torch.empty(2 * L * slab_rows, device=dev, dtype=torch.float32)   # one slot per (kind, layer, workgroup)
         d_x0 = torch.empty(n, c, device=dev, dtype=torch.float32) if need_x0 else None
-        check(lib().gadapt_block_backward(graph.c_ref, ptr(x_all), ctx.x0_cols, ptr(alpha), ptr(g_top), g_cols, L,
-                                          ptr(a), c * c if S > 1 else 0, ptr(p0), c if S > 1 else 0, ptr(layer_params),
-                                          ptr(g_ws), ptr(dxd_ws), ptr(edge_ws), ptr(slab), ptr(d_ws), int(bool(ctx.needs_input_grad[5])),
-                                          ptr(d_x0), c, st),
-              'gadapt_block_backward')
+        bwd = lib().gadapt_block_backward_narrow if ctx.narrow else lib().gadapt_block_backward
+        check(bwd(graph.c_ref, ptr(x_all), ctx.x0_cols, ptr(alpha), ptr(g_top), g_cols, L,
+                  ptr(a), c * c if S > 1 else 0, ptr(p0), c if S > 1 else 0, ptr(layer_params),
+                  ptr(g_ws), ptr(dxd_ws), ptr(edge_ws), ptr(slab), ptr(d_ws), int(bool(ctx.needs_input_grad[5])),
+                  ptr(d_x0), c, st),
+              'gadapt_block_backward_narrow' if ctx.narrow else 'gadapt_block_backward')
         scratch = torch.empty(32 * (c * c + c), device=dev, dtype=torch.float32)
         cuts = bucket_cuts(c, S)
         d_wq, d_wk = flat[cuts[0]:cuts[1]].view(S, c, c), flat[cuts[2]:cuts[3]].view(S, c, c)
@@ -166,10 +170,10 @@ class _GrandEulerBlock(torch.autograd.Function):
                   'gadapt_slab_reduce_coeffs_backward')
         if ctx.n_steps:                         # layer_params was the [L] scale vector; the steps get their slices of the d dt row
             d_scales = d_lp[L:] if ctx.needs_input_grad[5] else None
-            d_steps = tuple(d_lp[l:l + 1].view(ctx.step_shapes[l]) if ctx.needs_input_grad[13 + l] else None for l in range(L))
-            return (d_x0, d_wq, d_bq, d_wk, d_bk, d_scales, None, None, None, None, None, None, None) + d_steps
+            d_steps = tuple(d_lp[l:l + 1].view(ctx.step_shapes[l]) if ctx.needs_input_grad[14 + l] else None for l in range(L))
+            return (d_x0, d_wq, d_bq, d_wk, d_bk, d_scales, None, None, None, None, None, None, None, None) + d_steps
         d_lp2 = d_lp.view(2, L).t() if ctx.needs_input_grad[5] else None     # [L,2] view of the [2,L] rows
-        return d_x0, d_wq, d_bq, d_wk, d_bk, d_lp2, None, None, None, None, None, None, None
+        return d_x0, d_wq, d_bq, d_wk, d_bk, d_lp2, None, None, None, None, None, None, None, None
 
 
 class _GrandResidual(torch.autograd.Function):
@@ -231,7 +235,7 @@ def grand_residual(x, wq, bq, wk, bk, scale: torch.Tensor, graph: MeshGraph, wan
 
 def grand_euler_block(x0: torch.Tensor, wq, bq, wk, bk, layer_params: torch.Tensor, graph: MeshGraph,
                       num_layers: int, want_alpha: bool = False, x_all: Optional[torch.Tensor] = None,
-                      out_cols: Optional[int] = None, x0_cols: int = 0, coeffs=None, steps=None):
+                      out_cols: Optional[int] = None, x0_cols: int = 0, coeffs=None, steps=None, narrow: bool = False):
     """Returns (x_L [N,C], alpha [L,E] in target-CSR order or None).
 
     `x_all` (optional): a contiguous [(L+1),N,C] buffer whose slot 0 IS `x0` (same memory); the
@@ -242,10 +246,11 @@ def grand_euler_block(x0: torch.Tensor, wq, bq, wk, bk, layer_params: torch.Tens
     `coeffs=(a [S,C,C], p0 [S,C])`: the composite coefficients of exactly these weights when the caller has them already
     (`encode_features(..., conv=...)` computes them in the encoder's launch).
     `steps`: the L one-element step parameters (`learn_step`); `layer_params` is then the [L] vector of score scales (see
-    `_GrandEulerBlock`)."""
+    `_GrandEulerBlock`).  `narrow`: the block runs on the four live columns (`GNN._route`'s `narrow`) - only
+    with `x0_cols=4`, `out_cols <= 4`, fixed steps, on a graph where `MeshGraph.narrow_route` holds."""
     return _GrandEulerBlock.apply(x0.contiguous(), wq, bq, wk, bk, layer_params, graph, num_layers, want_alpha,
                                   None if x_all is None else [x_all], out_cols, x0_cols, None if coeffs is None else [coeffs],
-                                  *(steps or ()))
+                                  bool(narrow), *(steps or ()))
 
 
 NONLIN_CODES = {'identity': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'leaky_relu': 4, 'elu': 5, 'selu': 6}   # get_nonlin, src/GNN.py:48-64
@@ -603,7 +608,10 @@ class BlockForwardCall(_OneCall):
 
     _name, _at = 'gadapt_block_forward_loss', 2
 
-    def __init__(self, model, graph, target=None, l1=False, coeffs=None, store=False):
+    def __init__(self, model, graph, target=None, l1=False, coeffs=None, store=False, narrow=False):
+        self.narrow = bool(narrow)                                 # the route's `narrow`: every slot holds [N,4] rows at its start
+        if self.narrow:
+            self._name = 'gadapt_block_forward_loss_narrow'
         self._buffers(model, graph, target, l1, target is not None or store)
         n, c, f32 = self.n, self.c, self.f32
         self.x_all = torch.empty(self.L, n, c, **f32)            # slot l = input of layer l (slot 0: the compact [N,4] rows at its start)

@@ -95,6 +95,7 @@ class Route(NamedTuple):
     ident: bool             # dec is Identity
     store: bool             # the layers keep their attention (stored_ei / stored_alpha)
     native_in: bool         # fp32 node fields the encoder kernel reads in place
+    narrow: bool = False    # form 'compact' on the four live columns: every layer on [N,4] slots
 
 
 class MLP(nn.Module):
@@ -274,7 +275,11 @@ class GNN(nn.Module):
         else:
             form = 'gat_plus' if self._gat_plus_fusable() else 'layers'
         shared = bool(o['share_conv'] and not o.get('learn_step') and o.get('softmax_temp_type') != 'learnable_a')
-        return Route(form, small, shared, not (glob or o.get('gnn_normalize')), ident, store, native_in)
+        # narrow route: GRAND_plus (lin_value = Identity, no root weight) keeps the zero-pad encoder's columns 4.. at zero in every layer,
+        # so the block runs on [N,4] slots - where the wide forward takes the graph (its arithmetic on channels 0..3 is the dense flow's)
+        narrow = bool(form == 'compact' and o['conv_type'] == 'GRAND_plus' and o['hidden_dim'] == 64 and shared and ident
+                      and graph is not None and graph.narrow_route(o['hidden_dim']))
+        return Route(form, small, shared, not (glob or o.get('gnn_normalize')), ident, store, native_in, narrow)
 
     def _small_plan(self, data, graph, x_comp, f, uu):
         """What `functional.small_forward` / `small_block` need besides the node fields and the conv weights, or None when the batch /
@@ -422,7 +427,7 @@ class GNN(nn.Module):
             sliced = r.ident and o.get('compact_slots', True)
             x, alpha = Fn.grand_euler_block(x, *self._stacked(), self._layer_params(dev), graph, o['num_layers'], want_alpha=r.store,
                                             x_all=x_all, out_cols=self.dim if sliced else None, x0_cols=x0_cols, coeffs=coeffs,
-                                            steps=list(self.steps) if o.get('learn_step') else None)
+                                            steps=list(self.steps) if o.get('learn_step') else None, narrow=r.narrow)
             if r.store:
                 self._publish_attention(graph, alpha)
         elif r.form == 'gat_plus':

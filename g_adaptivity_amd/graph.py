@@ -210,6 +210,11 @@ class MeshGraph:
                                     ells['t'].data_ptr(), ells['s'].data_ptr(), wide_deg['t'], wide_deg['s'], self.wide_big_deg, self.wide_half_deg)
         self.c_ref = C.byref(self.c_struct)
 
+    def narrow_route(self, c: int) -> bool:
+        """Whether the block runs on the four live columns at hidden size `c` on this graph (`gadapt_narrow_route`: hidden 64 where the
+        wide forward takes the graph)."""
+        return bool(_native.lib().gadapt_narrow_route(self.c_ref, int(c)))
+
     def mesh_partition(self, batch: Optional[torch.Tensor]):
         """(mesh_ptr int32 [2, B+1] on the device - row 0 the first node, row 1 the first in-edge of each mesh -, n_meshes, max nodes
         per mesh, max in-edges per mesh) when the meshes of the batch are

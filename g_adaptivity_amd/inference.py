@@ -52,7 +52,7 @@ class GraphedForward:
             self._call = SmallForwardCall(model, r)
             self._dec = not r.ident
         elif self.issued:
-            self._call = BlockForwardCall(model, graph)
+            self._call = BlockForwardCall(model, graph, narrow=r.narrow)
         else:
             self._warmup = warmup
             self._capture()

@@ -109,7 +109,7 @@ class FusedIteration:
             self.slab = torch.empty(self.slab_rows * (c * c + c), **f32)
             self.coeffs, self.coeffs_in_forward = None, True           # the forward launch computes them: nothing to keep or refresh
         else:
-            self.fwd = BlockForwardCall(model, self.graph, target, self.l1, coeffs, store=r.store)
+            self.fwd = BlockForwardCall(model, self.graph, target, self.l1, coeffs, store=r.store, narrow=r.narrow)
             e = max(self.graph.num_edges, 1)
             self.g_ws, self.dxd_ws, self.edge_ws = torch.empty(2, n, c, **f32), torch.empty(n, c, **f32), torch.empty(e, 2, **f32)
             self.slab_rows = lib().gadapt_backward_slab_rows(n, c)
@@ -156,9 +156,10 @@ class FusedIteration:
             a_ptr = p0_ptr = None
         else:
             a, p0 = self.coeffs
-            self._bw = (L_.gadapt_block_backward, [self.graph.c_ref, ptr(fw.x_all), 4, ptr(fw.alpha), ptr(fw.seed), self.d, fw.L, ptr(a), 0, ptr(p0), 0,
-                                                   ptr(fw.lp), ptr(self.g_ws), ptr(self.dxd_ws), ptr(self.edge_ws), ptr(self.slab), None, 0, None, c, None],
-                        'gadapt_block_backward')
+            name = 'gadapt_block_backward_narrow' if fw.narrow else 'gadapt_block_backward'
+            self._bw = (getattr(L_, name), [self.graph.c_ref, ptr(fw.x_all), 4, ptr(fw.alpha), ptr(fw.seed), self.d, fw.L, ptr(a), 0, ptr(p0), 0,
+                                            ptr(fw.lp), ptr(self.g_ws), ptr(self.dxd_ws), ptr(self.edge_ws), ptr(self.slab), None, 0, None, c, None],
+                        name)
             a_ptr, p0_ptr = (None, None) if self.coeffs_in_forward else (ptr(a), ptr(p0))
         # gadapt_step_tail in its three forms: (slab given, moments given) = the whole tail; (slab, no moments) = this rank's gradient;
         # (no slab, moments) = the gradient is given (all-reduced)

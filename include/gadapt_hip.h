@@ -238,6 +238,32 @@ int gadapt_block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
                               const float* uu_tensor /*nullable*/, int n_layers, float* a, float* p0, const float* param /*nullable*/,
                               const float* layer_params, float* alpha_all, float* x_top4,
                               const float* target, int d, int l1, float* seed, float* loss_partials, int c, void* stream);
+/* ------------------------------------------------------------------ narrow route (ABI 9; resolved by name: a library without them fails to load)
+ * GRAND_plus behind the zero-pad identity encoder keeps columns 4.. of every layer's x at exactly zero (lin_value = Identity,
+ * root_weight = False: x' = x + dt (sum_j alpha_ij x_j - x) maps zero columns to zero columns), so the whole block can run on the
+ * four live columns.  gadapt_narrow_route(g, c) = 1 where it does: hidden 64 on a graph the wide forward kernel takes (its XC
+ * instantiation reproduces the dense flow's arithmetic on channels 0..3 bit for bit).  The three calls below have the signatures and
+ * buffers of their dense-slot namesakes; what differs:
+ *   - every slot of x_all holds [N,4] rows at its start (slot 0 as with x0_cols = 4; layer l < L-1 writes slot l+1, the last layer
+ *     x_top4): x0_cols must be 4 and x_top4 given;
+ *   - gadapt_block_backward_narrow: g_top compact (1 <= g_top_cols <= 4), d_layer_params and d_x0 NULL (fixed steps and temperature);
+ *     layers L-1 .. 1 run the narrow target and source passes on [N,4] rows (dxd_ws, g_ws used at their start), layer 0 the compact
+ *     target pass.  Weight gradients land in the 4 x 4 corner of dA and entries 0..3 of dp0 of the slab rows; the rest of each row is
+ *     written zero, so the slab reduction and gadapt_step_tail are the dense route's. */
+int gadapt_narrow_route(const gadapt_graph* g, int c);
+int gadapt_block_forward_narrow(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers,
+                                const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
+                                const float* layer_params, float* alpha_all, float* x_top4, int c, void* stream);
+int gadapt_block_forward_loss_narrow(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor /*nullable*/,
+                                     const float* uu_tensor /*nullable*/, int n_layers, float* a, float* p0, const float* param /*nullable*/,
+                                     const float* layer_params, float* alpha_all, float* x_top4,
+                                     const float* target, int d, int l1, float* seed, float* loss_partials, int c, void* stream);
+int gadapt_block_backward_narrow(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all,
+                                 const float* g_top, int g_top_cols, int n_layers,
+                                 const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
+                                 const float* layer_params,
+                                 float* g_ws, float* dxd_ws, float* edge_ws, float* slab,
+                                 float* d_layer_params, int want_d_scale, float* d_x0, int c, void* stream);
 /* Tail of the step.  slab != NULL (one GPU): the first-level slab sums (as gadapt_slab_reduce_coeffs_backward's first launch; one
  * extra workgroup advances the optimizer's device step count and sums the loss partials in a fixed order: loss_out[0] = sum /
  * loss_count); ONE launch that finishes the sums, applies the chain rule to the flat gradient grad = [dWq | dbq | dWk | dbk]
