@@ -1,6 +1,6 @@
 # Builds the C-ABI shared library of the hot path for gfx950 (MI355X), in-tree.
 #   make -j8        -> g_adaptivity_amd/libgadapt_hip.so   (one object per kernel family: csrc/gadapt_internal.h)
-#                      g_adaptivity_amd/libgadapt_fem.so   (the pde_loss FEM tail: fem_csrc/, include/gadapt_fem.h)
+#                      g_adaptivity_amd/libgadapt_fem.so   (the FEM tails: 2-D pde_loss and 1-D Burgers / Poisson; fem_csrc/, include/gadapt_fem.h)
 #   make resources  -> per-kernel VGPR/SGPR/LDS/occupancy report
 #   make DEV_C=64   -> development build: tiled kernels for one hidden size only (never shipped)
 HIPCC      ?= /opt/rocm/bin/hipcc
@@ -10,7 +10,7 @@ OBJDIR     := build/obj
 LIB        := g_adaptivity_amd/libgadapt_hip.so
 FEM_CSRC   := g_adaptivity_amd/fem_csrc
 FEM_LIB    := g_adaptivity_amd/libgadapt_fem.so
-FEM_OBJS   := $(OBJDIR)/fem_kernels.o $(OBJDIR)/fem_topology.o
+FEM_OBJS   := $(OBJDIR)/fem_kernels.o $(OBJDIR)/fem1d_kernels.o $(OBJDIR)/fem_topology.o
 HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-variable -Wno-unused-but-set-variable -Wno-unused-function $(EXTRA)
 ifdef DEV_C
 HIPFLAGS   += -DGADAPT_DEV_C=$(DEV_C)
@@ -27,6 +27,10 @@ $(FEM_LIB): $(FEM_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(FEM_OBJS)
 
 $(OBJDIR)/fem_kernels.o: $(FEM_CSRC)/fem_kernels.hip $(FEM_CSRC)/fem_common.h include/gadapt_fem.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+
+$(OBJDIR)/fem1d_kernels.o: $(FEM_CSRC)/fem1d_kernels.hip $(FEM_CSRC)/fem_common.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 

@@ -1,4 +1,4 @@
-"""ctypes binding of `libgadapt_fem.so`, the FEM tail of loss_type='pde_loss' (C-ABI declared in include/gadapt_fem.h).
+"""ctypes binding of `libgadapt_fem.so`, the FEM tails (2-D pde_loss, 1-D Burgers / Poisson; C-ABI in include/gadapt_fem.h).
 
 There is no CPU fallback: if the library is missing, or a call fails, this raises `NativeError`.
 """
@@ -12,11 +12,11 @@ from ._native import NativeError
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgadapt_fem.so')
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 META = 8                                   # GADAPT_FEM_META
 M_N_INT, M_BAND = 5, 6                     # GADAPT_FEM_M_N_INT, GADAPT_FEM_M_BAND
 
-_P, _I, _L = C.c_void_p, C.c_int, C.c_int64
+_P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); must list every symbol include/gadapt_fem.h declares
 PROTOTYPES = {
@@ -29,6 +29,12 @@ PROTOTYPES = {
     'gadapt_fem_eval_lds_bytes': (_L, [_I]),
     'gadapt_fem_forward': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 5),
     'gadapt_fem_backward': (_I, [_I, _I, _I] + [_P] * 13 + [_I, _I] + [_P] * 9),
+    'gadapt_fem1d_lds_bytes': (_L, [_I, _I]),
+    'gadapt_fem1d_burgers_forward': (_I, [_I, _I] + [_P] * 6 + [_F] * 3 + [_I] * 7 + [_P] * 6),
+    'gadapt_fem1d_burgers_backward': (_I, [_I, _I, _P, _P, _P, _F, _F, _I, _I, _I, _I] + [_P] * 7),
+    'gadapt_fem1d_poisson_forward': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P] * 5),
+    'gadapt_fem1d_poisson_backward': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P] * 6),
+    'gadapt_fem1d_expand': (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P]),
 }
 
 _lib = None

@@ -19,6 +19,9 @@ static int fail(int code, const char* msg) {
     return code;
 }
 
+// the 1-D tail (fem1d_kernels.hip) reports through the same message slot
+int fem_fail(int code, const char* msg) { return fail(code, msg); }
+
 static int launched(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -24,7 +24,7 @@ reproducible - results depend on it only through fp32 reassociation.
 from __future__ import annotations
 
 import copy
-from typing import Iterable, List, Optional, Sequence
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -185,7 +185,7 @@ def gaussian_fields(x: np.ndarray, centers: Sequence[np.ndarray], scales: Sequen
 
 
 def attach_random_fields(mesh: MeshData, rng: np.random.Generator, num_gauss: int = 2,
-                         target_noise: float = 0.01) -> MeshData:
+                         target_noise: float = 0.01, burgers: Optional[Tuple[float, float]] = None) -> MeshData:
     """One dataset sample: the shared mesh + its own Gaussians (`src/data.py:147-158`).
 
     `uu` stands in for the coarse FEM solve (= u_true at the nodes); the target
@@ -196,8 +196,15 @@ def attach_random_fields(mesh: MeshData, rng: np.random.Generator, num_gauss: in
     if x.ndim == 1:
         x = x[:, None]
     dim = x.shape[1]
-    centers = [rng.uniform(0.0, 1.0, dim).astype('f') for _ in range(num_gauss)]
-    scales = [rng.uniform(0.1, 0.5, dim).astype('f') for _ in range(num_gauss)]
+    if burgers is None:
+        centers = [rng.uniform(0.0, 1.0, dim).astype('f') for _ in range(num_gauss)]
+        scales = [rng.uniform(0.1, 0.5, dim).astype('f') for _ in range(num_gauss)]
+    else:                           # Burgers draws (`src/data.py:149-151`): burgers = (scale, burgers_limits), scale then centre
+        sc, lim = burgers
+        centers, scales = [], []
+        for _ in range(num_gauss):
+            scales.append(rng.uniform(sc * 0.5, sc * 2.0, dim).astype('f'))
+            centers.append(rng.uniform(sc * lim, 1 - sc * lim, dim).astype('f'))
     u, f = gaussian_fields(x, centers, scales)
     d.u_true_tensor = torch.tensor(u, dtype=torch.float32)
     d.uu_tensor = torch.tensor(u, dtype=torch.float32)
@@ -276,7 +283,7 @@ class MeshDataset:
     """
 
     def __init__(self, mesh_dims: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2, pde_loss_fields: bool = False,
-                 eval_quad_points: int = 101):
+                 eval_quad_points: int = 101, burgers: bool = False, scale: float = 0.1, burgers_limits: float = 3.0):
         self.mesh_dims = list(mesh_dims)
         self.dim = len(self.mesh_dims)
         if self.dim == 1:
@@ -289,7 +296,8 @@ class MeshDataset:
         self.data = base                                     # `dataset.data.x_comp` (read by the MLP baseline, src/GNN.py:20-22)
         self.x_comp_shared = base.x_comp
         self.num_x_comp_features = self.dim
-        self.samples: List[MeshData] = [attach_random_fields(base, rng, num_gauss) for _ in range(num_data)]
+        draws = (scale, burgers_limits) if burgers else None   # burgers=True: the Burgers centres and scales
+        self.samples: List[MeshData] = [attach_random_fields(base, rng, num_gauss, burgers=draws) for _ in range(num_data)]
         # no Firedrake mesh object here: a stand-in with the one attribute chain the model follows (2-D only)
         self.mesh = MeshTopology(base.cells.numpy()) if self.dim == 2 else None
         if pde_loss_fields:                                  # loss_type='pde_loss': only when asked, samples are unchanged otherwise

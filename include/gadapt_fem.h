@@ -25,6 +25,8 @@
  * Batch layout.  Meshes b = 0..B-1 are concatenated: nodes [node_off[b], node_off[b+1]), triangles
  * [tri_off[b], tri_off[b+1]) with GLOBAL node ids in `cells` [T,3].  `meta` is int32 [B, GADAPT_FEM_META]
  * (fields GADAPT_FEM_M_*), built on the host by gadapt_fem_topology_host and copied to the device.
+ *
+ * The 1-D tails (gadapt_fem1d_*, fem_csrc/fem1d_kernels.hip) are declared at the end of this file.
  */
 #ifndef GADAPT_FEM_H
 #define GADAPT_FEM_H
@@ -35,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GADAPT_FEM_ABI 1
+#define GADAPT_FEM_ABI 2
 
 #define GADAPT_FEM_OK          0
 #define GADAPT_FEM_E_BADARG   -1   /* null pointer, bad size, bad lattice */
@@ -99,6 +101,69 @@ int gadapt_fem_backward(int n_meshes, int n_nodes, int n_tris, const int32_t* me
                         const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
                         const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs, const float* lfac,
                         const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad, float* gx, void* stream);
+
+/* ------------------------------------------------------------------------------------------------ 1-D tails
+ * Differentiable 1-D P1 FEM of the reference's modular loss (firedrake_difFEM/difFEM_1d.py): semi-implicit Burgers steps
+ * (torch_FEM_Burgers_1D, get_Burgers_initial_coeffs) and Poisson (torch_FEM_1D), with the reference's trapezoid inner
+ * products, literal hat functions (inclusive interval test, -1 at the node) and searchsorted point location.
+ *
+ * Meshes b = 0..B-1 are concatenated: nodes [node_off[b], node_off[b+1]), coordinates x [N].  Gaussians of mesh b are
+ * gpar[gptr[b]..gptr[b+1]) as (centre, scale) pairs.  Evaluation points `pts` [P] are shared by all meshes; sol is [B,P].
+ * One workgroup per mesh, the mesh's whole state in LDS, one launch forward and one backward.  The tridiagonal solves run
+ * on one lane (Thomas, no pivoting: the Burgers matrix is strictly and the Poisson matrix weakly diagonally dominant;
+ * the Poisson elimination in fp64).
+ * No float atomics: results are bit-reproducible.
+ *
+ * Node cap.  A workgroup has one lane per node (GADAPT_FEM1D_MAX_NODES = 1024, the largest workgroup).  The Burgers
+ * backward keeps 15 floats per node in LDS and the Poisson launches 64 bytes per node (their solve runs in fp64), 64 KB at
+ * 1024 nodes, within GADAPT_FEM_LDS_BUDGET; gadapt_fem1d_lds_bytes gives the need.
+ *
+ * Non-monotone meshes.  Where a mesh folds, the reference's mass and stiffness matrices stop being tridiagonal; the
+ * tridiagonal part is assembled and flags[b] gets bit GADAPT_FEM1D_F_NOT_INCREASING (some x[i+1] - x[i] < 0).  Point
+ * location follows torch's CPU lower-bound search, so it matches the reference there too.
+ *
+ * Clamping.  fn_expansion's slope at index N-1 is 0 (as in the reference); dxfn_expansion clamps its index to N-2 (the
+ * reference would index past its slope list), and soln (Poisson) uses the same evaluation as fn_expansion. */
+
+#define GADAPT_FEM1D_MAX_NODES 1024
+#define GADAPT_FEM1D_F_NOT_INCREASING 1
+
+/* LDS bytes of the 1-D launches for meshes of up to max_nodes nodes and an n_fine-node fine mesh (0: none). */
+int64_t gadapt_fem1d_lds_bytes(int max_nodes, int n_fine);
+
+/* Burgers forward, one launch.
+ *   u0 [N]: initial coefficients, or NULL to project amp * sum_g exp(-(x-c_g)^2/s_g^2) (mass with k_proj points, load with
+ *           k_load, identity boundary rows with u0(0) and u0(1)); bc [B,2]: RHS boundary values, or NULL for u^n's end values
+ *   n_fine > 1 also runs the same steps on linspace(0, 1, n_fine) (its projection's mass uses k_proj_fine points) -> fine_sol
+ *   taunu = float(tau * nu) as the reference forms it; k_stiff: points of the stiffness trapezoid minus one
+ * out hist [(T+1) N]: mesh b's u^0..u^T at hist[(T+1) node_off[b] + t n_b + i]; sol [B,P] = fn_expansion(u^T, x, pts);
+ *     fine_sol [B,P] (if n_fine > 1); flags [B] */
+int gadapt_fem1d_burgers_forward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const float* u0,
+                                 const float* bc, const int32_t* gptr, const float* gpar, float amp, float tau, float taunu,
+                                 int k_load, int k_stiff, int k_proj, int k_proj_fine, int n_steps, int n_fine, int n_pts,
+                                 const float* pts, float* hist, float* sol, float* fine_sol, int32_t* flags, void* stream);
+
+/* Burgers backward, one launch: gx [N] = d L / d x and, if gu0 != NULL, gu0 [N] = d L / d u^0, from g_sol [B,P] and
+ * g_last [N] (d L / d u^T); either may be NULL (zero).  bc as in the forward (explicit boundary values get no gradient). */
+int gadapt_fem1d_burgers_backward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const float* bc,
+                                  float tau, float taunu, int k_load, int k_stiff, int n_steps, int n_pts, const float* pts,
+                                  const float* hist, const float* g_sol, const float* g_last, float* gx, float* gu0,
+                                  void* stream);
+
+/* Poisson forward (torch_FEM_1D), one launch: coeffs [N] = (BC1, interior solution, BC2) per mesh, BC = u_true at the
+ * end nodes (detached); sol [B,P]; flags [B]. */
+int gadapt_fem1d_poisson_forward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
+                                 const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts, float* coeffs,
+                                 float* sol, int32_t* flags, void* stream);
+
+/* Poisson backward, one launch: gx [N] from g_coeffs [N] and g_sol [B,P] (either may be NULL). */
+int gadapt_fem1d_poisson_backward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
+                                  const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts,
+                                  const float* coeffs, const float* g_coeffs, const float* g_sol, float* gx, void* stream);
+
+/* fn_expansion(c, x, pts) per mesh (no gradient): sol [B,P]. */
+int gadapt_fem1d_expand(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const float* c, int n_pts,
+                        const float* pts, float* sol, void* stream);
 
 #ifdef __cplusplus
 }
