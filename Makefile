@@ -42,7 +42,7 @@ $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
 
 $(OBJDIR)/gadapt_kernels.o: $(CSRC)/gadapt_small.inc
-$(OBJDIR)/gadapt_tu_fwd.o: $(CSRC)/gadapt_fwd.inc $(CSRC)/gadapt_wide.inc
+$(OBJDIR)/gadapt_tu_fwd.o: $(CSRC)/gadapt_fwd.inc $(CSRC)/gadapt_wide.inc $(CSRC)/gadapt_narrow_fwd.inc
 $(OBJDIR)/gadapt_tu_bwd_target.o: $(CSRC)/gadapt_bwd_target.inc
 $(OBJDIR)/gadapt_tu_bwd_source.o: $(CSRC)/gadapt_bwd_source.inc
 $(OBJDIR)/gadapt_tu_smallmesh.o: $(CSRC)/gadapt_smallmesh.inc

@@ -188,6 +188,9 @@ int gadapt_launch_bwd_source_c(int c, const gadapt_graph* g, const float* x_in, 
                                const float* a, const float* p0, float* g_out, int g_cols, int out4, hipStream_t st);
 // the narrow route (every layer input an [N,4] slot; hidden 64 on graphs the wide forward takes: gadapt_narrow_takes_c)
 int gadapt_narrow_takes_c(const gadapt_graph* g, int c);
+// its forward layer: [N,4] slot in, [N,4] rows out in x_top4 (extra: layer-0 fields / coefficients, last-layer loss)
+int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* a, const float* p0, const float* lp, float* alpha_out,
+                               int residual_only, float* x_top4, hipStream_t st, const FwdExtra* extra);
 int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* alpha,
                                       const float* a, const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, hipStream_t st);
 int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* edge_ws,

@@ -416,6 +416,19 @@ extern "C" int gadapt_adam_step_dev(float* param, const float* grad, float* exp_
 // ------------------------------------------------------------------------------------------------
 // L-step Euler block (GNN.py:273-291)
 // ------------------------------------------------------------------------------------------------
+// Narrow-route forward layers: wide::fwd_narrow_kernel (one node per lane, default) or wide::fwd_kernel<XC = true>, bit-identical
+// (tests/test_gpu_narrow_forward.py).  GADAPT_NARROW_FWD=0 / gadapt_debug_set_narrow_forward(0): the wide kernel.
+static std::atomic<int> g_narrow_fwd{-1};
+static bool narrow_fwd_enabled() {
+    int v = g_narrow_fwd.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char* e = getenv("GADAPT_NARROW_FWD");
+        v = (e && e[0] == '0') ? 0 : 1;
+        g_narrow_fwd.store(v, std::memory_order_relaxed);
+    }
+    return v == 1;
+}
+extern "C" int gadapt_debug_set_narrow_forward(int on) { g_narrow_fwd.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
 static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers, const float* a, int64_t a_stride,
                          const float* p0, int64_t p0_stride, const float* layer_params, float* alpha_all, float* x_top4,
                          int c, void* stream, const FwdExtra* extra, bool narrow = false) {
@@ -440,7 +453,10 @@ static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n
             if (last) { ex_l.loss = extra->loss; ex_l.n_partials_out = extra->n_partials_out; }
             ex = &ex_l;
         }
-        if (narrow)                                              // [N,4] slot in, [N,4] slot out (the last layer: the head rows)
+        if (narrow && narrow_fwd_enabled())                      // [N,4] slot in, [N,4] slot out (the last layer: the head rows)
+            rc = gadapt_launch_fwd_narrow_c(c, g, x_all + l * nc, a + l * a_stride, p0 + l * p0_stride, layer_params + 2 * l, alpha_l, 0,
+                                            last ? x_top4 : x_all + (l + 1) * nc, st, ex);
+        else if (narrow)                                         // the same through the wide kernel (gadapt_debug_set_narrow_forward(0))
             rc = gadapt_launch_fwd_c(c, g, x_all + l * nc, nullptr, a + l * a_stride, p0 + l * p0_stride, layer_params + 2 * l, alpha_l, 0, 4,
                                      last ? x_top4 : x_all + (l + 1) * nc, st, ex);
         else if ((l == 0 && x0_cols) || (last && x_top4))        // compact input and/or compact-only output

@@ -4,6 +4,7 @@
 #include "gadapt_internal.h"
 #include "gadapt_fwd.inc"
 #include "gadapt_wide.inc"
+#include "gadapt_narrow_fwd.inc"
 
 // The wide kernels take over for hidden size 64 when the graph qualifies; GADAPT_WIDE=0 in the environment keeps the tiled
 // kernels (A/B runs and the tests of the tiled path).
@@ -73,6 +74,34 @@ int gadapt_forward_computes_coeffs_c(const gadapt_graph* g, int c) { return (c =
 // 1: the narrow route (every layer on [N,4] slots, gadapt_block_forward_narrow) runs on this graph at this hidden size - the graphs whose
 // forward is the wide kernel, which reproduces the dense flow's arithmetic on channels 0..3 bit for bit
 int gadapt_narrow_takes_c(const gadapt_graph* g, int c) { return (c == 64 && g && wide_takes(g)) ? 1 : 0; }
+
+// Narrow route (gadapt_block_forward_narrow): compact [N,4] input, compact [N,4] output in x_top4, hidden 64 on a graph the wide forward
+// takes (gadapt_narrow_takes_c).  wide::fwd_narrow_kernel reproduces wide::fwd_kernel<true, ...> on channels 0..3 bit for bit, with the
+// same kmax (the longest in-row of the geometry the wide launch would pick).  gadapt_debug_set_narrow_forward(0) keeps the wide kernel.
+int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* a, const float* p0, const float* lp, float* alpha_out,
+                               int residual_only, float* x_top4, hipStream_t st, const FwdExtra* ex) {
+    if (c != 64 || !g || !x_top4 || !gadapt_narrow_takes_c(g, c)) return fail(GADAPT_E_BADARG, "narrow forward: hidden 64, head rows, a graph the wide forward takes");
+    const bool big = g->wide_deg_t <= 0, half = !big && wide_half(g);
+    const int n_steps = (g->n_nodes + wide::NRW_NT - 1) / wide::NRW_NT;
+    const int grid = n_steps < GADAPT_LOSS_PARTIALS_MAX / 4 ? n_steps : GADAPT_LOSS_PARTIALS_MAX / 4;   // one loss partial per wave
+    wide::FwdArgs p{x_in, nullptr, a, p0, lp, g->ell_t, g->rowptr_t, alpha_out, g->n_nodes, n_steps, residual_only,
+                    big ? g->wide_big_deg_t : (half ? g->wide_half_deg_t : g->wide_deg_t), nullptr, x_top4};
+    if (ex) {
+        p.fs = ex->fs; p.x0c = ex->x0c;
+        if (ex->cw) {
+            if (!gadapt_forward_computes_coeffs_c(g, c)) return fail(GADAPT_E_BADARG, "narrow forward: the coefficients are given on this graph (gadapt_forward_computes_coeffs)");
+            p.cw = ex->cw; p.a_out = ex->a_out; p.p0_out = ex->p0_out;
+        }
+        if (ex->loss.target) { p.loss = ex->loss; if (ex->n_partials_out) *ex->n_partials_out = 4 * grid; }
+    }
+    if (p.cw && grid < 64) return fail(GADAPT_E_BADARG, "narrow forward: in-kernel coefficients need 64 workgroups (one row of A each)");
+    ProfScope prof(0, st, 6);                                   // compact input, head-only output (the variant of the wide launch it replaces)
+    const bool fld = p.fs.x_comp != nullptr, head = p.loss.target != nullptr;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(wide::NRW_NT), 0, st, p); };
+    if (head) { if (fld) go(wide::fwd_narrow_kernel<true, true>); else go(wide::fwd_narrow_kernel<true, false>); }
+    else { if (fld) go(wide::fwd_narrow_kernel<false, true>); else go(wide::fwd_narrow_kernel<false, false>); }
+    return check_launch("wide::fwd_narrow_kernel");
+}
 
 template <int C> static int launch_fwd(const gadapt_graph* g, const float* x_in, float* x_out, const float* a, const float* p0,
                                        const float* lp, float* alpha_out, int residual_only, int x_cols, float* x_top4, hipStream_t st, const FwdExtra* ex) {

@@ -451,6 +451,10 @@ int gadapt_profile_calibrate(int n, void* stream);
  * same row of g_out - so a layer pair touches two [N,C] work buffers instead of three (dxd_ws then only serves layer 0 and the
  * 4-column pair).  Results are bit-identical either way (tests/test_gpu_ops.py::test_block_backward_inplace_is_bit_identical). */
 int gadapt_debug_set_backward_inplace(int on);
+/* Switch: 1 (the default; GADAPT_NARROW_FWD=0 in the environment starts with 0) runs the forward layers of the narrow route
+ * (gadapt_block_forward_narrow, gadapt_block_forward_loss_narrow) on the one-node-per-lane kernel; 0 on the wide kernel with its
+ * compact input.  Results are bit-identical either way (tests/test_gpu_narrow_forward.py). */
+int gadapt_debug_set_narrow_forward(int on);
 /* Diagnostic: runtime-reported workgroups per CU of {forward, backward target, backward source}. */
 int gadapt_debug_occupancy(int c, int* out3);
 

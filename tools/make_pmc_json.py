@@ -26,7 +26,7 @@ def name(n):
     if 'gat::fwd' in n: return 'forward'                    # fused GAT_plus layer kernels (csrc/gadapt_gat.inc)
     if 'gat::bwd_t' in n: return 'backward_target'
     if 'gat::bwd_s' in n: return 'backward_source'
-    if 'grand_fwd' in n or 'wide::fwd' in n: return 'forward'
+    if 'grand_fwd' in n or 'wide::fwd' in n: return 'forward'      # wide::fwd_kernel<...>, wide::fwd_narrow_kernel<HEAD> (narrow route)
     if "bwd_target" in n: return "backward_target"          # grand_bwd_target_kernel<...>, grand_bwd_target_compact_kernel<SUMS>
     if 'bwd_source' in n: return 'backward_source'          # grand_bwd_source_kernel<...>, grand_bwd_source4_kernel<C, GC>
     return None
@@ -54,6 +54,8 @@ def variant(n):
         return 'compact_g+out4' if len(a) > 1 and a[1] == 'true' else 'out4'
     if 'bwd_source' in n:
         return 'compact_g' if len(a) > 1 and a[1] == 'true' else 'dense'
+    if 'wide::fwd_narrow' in n:                             # <HEAD>: the narrow route's [N,4] input, the launches of wide::fwd<true, ...>
+        return 'compact_x'
     if 'wide::fwd' in n:                                    # <XC, BIG, HEAD>
         a += ['false'] * (3 - len(a))
         return 'compact_x' if a[0] == 'true' else 'head_only_out' if a[2] == 'true' else 'dense'
