@@ -5,11 +5,12 @@ Public surface mirrors the reference modules:
     from g_adaptivity_amd import mse_loss, l1_loss          # the training loop's loss_fn, one launch each
     from g_adaptivity_amd import torch_FEM_2D, fem_poisson   # loss_type='pde_loss': the differentiable P1 FEM tail
     from g_adaptivity_amd import gradient_meshpoints_1D, burgers_1d, fem_poisson_1d   # the 1-D modular loss (Burgers, Poisson)
+    from g_adaptivity_amd import gradient_meshpoints_2D    # the 2-D modular loss (Poisson)
 The arithmetic lives in `libgadapt_hip.so` (csrc/, C-ABI in include/gadapt_hip.h) and, for the FEM tail,
 `libgadapt_fem.so` (fem_csrc/, include/gadapt_fem.h).
 """
 from .conv import GAT_conv, GAT_plus, GCN_conv, GRAND_conv, GRAND_plusConv, TRANS_conv
-from .fem import fem_poisson, torch_FEM_2D
+from .fem import fem_poisson, gradient_meshpoints_2D, torch_FEM_2D
 from .fem1d import (burgers_1d, fem_poisson_1d, fn_expansion, get_Burgers_initial_coeffs, gradient_meshpoints_1D, torch_FEM_1D,
                     torch_FEM_Burgers_1D)
 from .functional import l1_loss, mse_loss, unit_gradient
@@ -25,4 +26,4 @@ __all__ = ['GNN', 'MLP', 'get_conv', 'build_conv_list', 'get_enc', 'get_dec', 'g
            'MeshData', 'MeshDataset', 'MeshLoader', 'DeviceMeshLoader', 'MixedMeshDataset', 'Mixed_DataLoader', 'collate', 'interval_mesh', 'square_mesh',
            'synthetic_batch', 'hot_path_opt', 'GraphedTrainStep', 'mse_loss', 'l1_loss', 'unit_gradient',
            'fem_poisson', 'torch_FEM_2D', 'burgers_1d', 'fem_poisson_1d', 'gradient_meshpoints_1D', 'torch_FEM_Burgers_1D',
-           'get_Burgers_initial_coeffs', 'fn_expansion', 'torch_FEM_1D']
+           'get_Burgers_initial_coeffs', 'fn_expansion', 'torch_FEM_1D', 'gradient_meshpoints_2D']

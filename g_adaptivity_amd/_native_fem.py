@@ -12,9 +12,10 @@ from ._native import NativeError
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgadapt_fem.so')
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 META = 8                                   # GADAPT_FEM_META
 M_N_INT, M_BAND = 5, 6                     # GADAPT_FEM_M_N_INT, GADAPT_FEM_M_BAND
+LOSS_MSE, LOSS_SIMPSON = 0, 1              # GADAPT_FEM_LOSS_MSE, GADAPT_FEM_LOSS_SIMPSON
 
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
@@ -28,6 +29,7 @@ PROTOTYPES = {
     'gadapt_fem_factor_lds_bytes': (_L, [_I, _I]),
     'gadapt_fem_eval_lds_bytes': (_L, [_I]),
     'gadapt_fem_forward': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 5),
+    'gadapt_fem_modular_forward': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I, _I] + [_P] * 7),
     'gadapt_fem_backward': (_I, [_I, _I, _I] + [_P] * 13 + [_I, _I] + [_P] * 9),
     'gadapt_fem1d_lds_bytes': (_L, [_I, _I]),
     'gadapt_fem1d_burgers_forward': (_I, [_I, _I] + [_P] * 6 + [_F] * 3 + [_I] * 7 + [_P] * 6),

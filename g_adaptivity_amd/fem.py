@@ -8,6 +8,8 @@ per-triangle chain rule, per-node gather).
 
     torch_FEM_2D(opt, mesh, mesh_points, quad_points, num_meshpoints, c_list, s_list) -> (coeffs [N,1], mesh_points, sol)
     fem_poisson(x_phys, cells, boundary, node_counts, pde_params, lattice) -> (coeffs [N,1], sol [B*Q])
+    gradient_meshpoints_2D(opt, data, x_phys) -> (loss, x_grads [N,2])     # loss_type='modular' (difFEM_2d.py:374-535)
+    modular_loss_2d(x_phys, cells, boundary, node_counts, pde_params, n_lat, reduction) -> (loss [B], x_grads [N,2])
 
 Limits: 2-D Poisson only; each mesh's banded factor must fit the LDS budget (`gadapt_fem_lds_budget()`, 64 KB: square
 meshes up to 26 x 26 nodes); the evaluation points must be a uniform tensor-product lattice.
@@ -24,7 +26,8 @@ from . import _native_fem as _nf
 from ._native import NativeError, current_stream
 from .graph import content_fingerprint
 
-__all__ = ['FemTopology', 'fem_poisson', 'torch_FEM_2D', 'boundary_from_cells', 'gnn_pde_tail']
+__all__ = ['FemTopology', 'fem_poisson', 'torch_FEM_2D', 'boundary_from_cells', 'gnn_pde_tail', 'gradient_meshpoints_2D',
+           'modular_loss_2d', 'simpson_points_per_dim', 'GRAD_TYPES_2D']
 
 
 def _require_gpu(t: torch.Tensor, what: str):
@@ -179,6 +182,13 @@ class _FemPoisson(torch.autograd.Function):
         return gx, None, None, None, None, None
 
 
+def _tri_counts(cells: torch.Tensor, node_counts: Sequence[int]) -> List[int]:
+    """Triangles per mesh of a batch whose cells are ordered mesh by mesh (as `collate` concatenates them)."""
+    c0 = cells[:, 0].detach().cpu()
+    ends = torch.tensor(np.cumsum(node_counts), dtype=c0.dtype)
+    return np.diff(np.concatenate([[0], torch.searchsorted(c0.contiguous(), ends, right=False).numpy()])).tolist()
+
+
 def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
                 pde_params: Sequence[dict], quad_points, tri_counts: Optional[Sequence[int]] = None):
     """Batched P1 Poisson solve on the meshes of `x_phys` [N,2] (differentiable wrt x_phys).
@@ -191,9 +201,7 @@ def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
         raise NotImplementedError(f"pde_loss FEM tail: 2-D meshes only (x_phys {tuple(x_phys.shape)})")
     dev = x_phys.device
     if tri_counts is None:
-        c0 = cells[:, 0].detach().cpu()
-        ends = torch.tensor(np.cumsum(node_counts), dtype=c0.dtype)
-        tri_counts = np.diff(np.concatenate([[0], torch.searchsorted(c0.contiguous(), ends, right=False).numpy()])).tolist()
+        tri_counts = _tri_counts(cells, node_counts)
     topo = _topology(cells, boundary, node_counts, tri_counts, dev)
     gptr, gpar = pack_gaussians(pde_params, dev)
     lx, ly = lattice_axes(quad_points, dev)
@@ -248,3 +256,145 @@ def gnn_pde_tail(model, data, x_phys: torch.Tensor):
         boundary = torch.from_numpy(boundary_from_cells(cells.cpu().numpy(), sum(node_counts)))
     coeffs, sol = fem_poisson(x_phys, cells, boundary, node_counts, params, model.quad_points, tri_counts=tri_counts)
     return coeffs, x_phys, sol
+
+
+# ------------------------------------------------------------------------------------------------ the 2-D modular loss
+GRAD_TYPES_2D = ('PDE_loss_direct_mse', 'PDE_loss_direct_L2', 'PDE_loss_adjoint_L2')
+_REDUCTIONS = {'mse': _nf.LOSS_MSE, 'simpson': _nf.LOSS_SIMPSON}
+
+
+def simpson_points_per_dim(N: int, dim: int = 2) -> int:
+    """Points per dimension of torchquad's Simpson().integrate(N=N, dim=dim): floor(N^(1/dim)), lowered to an odd count
+    (the composite rule needs one), at least 3.  101 -> 9."""
+    n = int(int(N) ** (1.0 / dim) + 1e-8)
+    if n % 2 == 0:
+        n -= 1
+    return max(n, 3)
+
+
+def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
+                    pde_params: Sequence[dict], n_lat: int, reduction: str, n_load: Optional[int] = None,
+                    tri_counts: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-mesh 2-D modular loss and its gradient: (loss [B], x_grads [N,2]), x_grads on a node being the gradient of its
+    own mesh's loss wrt all of that mesh's node coordinates.
+
+    The P1 Poisson solve of `fem_poisson` on each mesh, evaluated on the lattice linspace(0, 1, n_lat)^2 (meshgrid 'ij'),
+    and e = sol - u_true there: reduction 'mse' is mean e^2 (F.mse_loss), 'simpson' torchquad's composite Simpson rule of
+    e^2 over [0,1]^2 (n_lat odd).  n_load: Simpson points per dimension of the load vector; only the compiled
+    `gadapt_fem_simpson_points()` is built.  Five launches forward and backward, no autograd graph, no host wait."""
+    _require_gpu(x_phys, 'modular loss (2-D)')
+    if x_phys.dim() != 2 or x_phys.shape[1] != 2:
+        raise NotImplementedError(f"modular loss (2-D): x_phys must be [N,2] (got {tuple(x_phys.shape)})")
+    if reduction not in _REDUCTIONS:
+        raise ValueError(f"modular loss (2-D): reduction must be one of {sorted(_REDUCTIONS)} (got {reduction!r})")
+    lib = _nf.lib()
+    n_built = int(lib.gadapt_fem_simpson_points())
+    if n_load is not None and int(n_load) != n_built:
+        raise NotImplementedError(f"modular loss (2-D): the load vector's Simpson rule is built for {n_built} points per "
+                                  f"dimension only (got {int(n_load)})")
+    n_lat = int(n_lat)
+    if n_lat < 2 or (reduction == 'simpson' and (n_lat < 3 or n_lat % 2 == 0)):
+        raise ValueError(f"modular loss (2-D): {n_lat} lattice points per dimension for reduction {reduction!r}")
+    dev = x_phys.device
+    x = x_phys.detach().contiguous()
+    if tri_counts is None:
+        tri_counts = _tri_counts(cells, node_counts)
+    topo = _topology(cells, boundary, node_counts, tri_counts, dev)
+    gptr, gpar = pack_gaussians(pde_params, dev)
+    lat = torch.linspace(0, 1, n_lat).to(dev)              # torch's CPU linspace: the reference's lattice, point for point
+    d, N, T, B = topo.dev, topo.n_nodes, topo.n_tris, topo.n_meshes
+    Q = n_lat * n_lat
+    rhs, coeffs, lfac = torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(topo.band_floats, device=dev)
+    sol, g_sol, loss = torch.empty(B * Q, device=dev), torch.empty(B * Q, device=dev), torch.empty(B, device=dev)
+    stream = current_stream(dev)
+    _nf.check(lib.gadapt_fem_modular_forward(
+        B, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
+        d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(), x.data_ptr(),
+        lat.data_ptr(), lat.data_ptr(), n_lat, topo.lds_bytes, topo.max_tris, _REDUCTIONS[reduction], rhs.data_ptr(),
+        coeffs.data_ptr(), lfac.data_ptr(), sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(), stream), 'gadapt_fem_modular_forward')
+    gc, mu, tgrad, gx = torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(T * 6, device=dev), torch.empty(N, 2, device=dev)
+    _nf.check(lib.gadapt_fem_backward(
+        B, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['tri_mesh'].data_ptr(),
+        d['int_idx'].data_ptr(), d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(),
+        gpar.data_ptr(), x.data_ptr(), lat.data_ptr(), lat.data_ptr(), n_lat, topo.lds_bytes, coeffs.data_ptr(), lfac.data_ptr(),
+        None, g_sol.data_ptr(), gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), stream), 'gadapt_fem_backward')
+    return loss, gx
+
+
+def _modular_quadrature(opt, gt: str) -> Tuple[int, int, str]:
+    """(load-vector Simpson points per dimension, loss lattice points per dimension, reduction) of a grad_type."""
+    ev, ld = int(opt.get('eval_quad_points', 101)), int(opt.get('load_quad_points', 101))
+    if gt == 'PDE_loss_direct_mse':                        # difFEM_2d.py:409, :424-435
+        return simpson_points_per_dim(ev), ev, 'mse'
+    n = simpson_points_per_dim(ev if gt == 'PDE_loss_direct_L2' else ld)   # :462/:476, adjoint :505/:523
+    return n, n, 'simpson'
+
+
+def _modular_batch(opt, data, n_nodes: int):
+    """(cells, boundary, node_counts, tri_counts, pde_params) of a batch, as gnn_pde_tail reads them."""
+    batch = getattr(data, 'batch', None)
+    B = int(data.num_graphs) if hasattr(data, 'num_graphs') else (1 if batch is None else int(batch.max()) + 1)
+    node_counts = [n_nodes] if batch is None else torch.bincount(batch.detach().cpu(), minlength=B).tolist()
+    if opt.get('data_type') == 'randg_mix' and hasattr(data, 'batch_dict'):
+        params = [data.batch_dict[i]['pde_params'] for i in range(B)]
+    else:
+        from .fem1d import _split_params
+        params = _split_params(data.pde_params, B)
+    cells, tri_counts = getattr(data, 'cells', None), None
+    if cells is None:                                    # per-mesh topology objects, else the reference's UnitSquareMesh
+        mesh = getattr(data, 'mesh', None)
+        if isinstance(mesh, (list, tuple)):
+            tops = [np.asarray(m.coordinates.cell_node_map().values, np.int64) for m in mesh]
+        elif mesh is not None:
+            tops = [np.asarray(mesh.coordinates.cell_node_map().values, np.int64)] * B
+        else:
+            from .mesh_graph import square_mesh
+            tops = [square_mesh(int(opt['mesh_dims'][0])).cells.numpy()] * B
+        parts, off = [], 0
+        for t, n in zip(tops, node_counts):
+            parts.append(torch.as_tensor(t) + off)
+            off += n
+        cells, tri_counts = torch.cat(parts, 0), [p.shape[0] for p in parts]
+    boundary = getattr(data, 'boundary_nodes', None)
+    if boundary is None:
+        boundary = torch.from_numpy(boundary_from_cells(cells.cpu().numpy(), sum(node_counts)))
+    return cells, boundary, node_counts, tri_counts, params
+
+
+def gradient_meshpoints_2D(opt, data, x_phys):
+    """The reference's 2-D modular loss (`difFEM_2d.py:374-535`, from `src/run_GNN.py:113-118`) for a batch:
+    (loss, x_grads [N,2]); training back-propagates sum(x_phys * x_grads).
+
+    Per mesh, as the reference at batch 1: x_grads on a node is the gradient of its own mesh's loss wrt all of that mesh's
+    node coordinates, boundary nodes included; loss is the mean of the per-mesh losses, a 0-dim tensor on the device
+    (the reference returns it on the CPU).  Nothing waits for the device.
+
+    grad_type (opt['grad_type']):
+      PDE_loss_direct_mse   mean over linspace(0, 1, eval_quad_points)^2 of (sol - u_true)^2; load vector with
+                            eval_quad_points
+      PDE_loss_direct_L2    torchquad's Simpson rule of (sol - u_true)^2 over [0,1]^2; load vector and loss with
+                            eval_quad_points
+      PDE_loss_adjoint_L2   the same loss with load_quad_points for both.  The reference solves without differentiating
+                            and adds grad1 + grad2 from lambda = -A^-T dL/dc; in exact arithmetic that is the direct
+                            gradient, and the backward here already is an adjoint solve on the kept factor, so the two
+                            _L2 types share one path and differ only in the count they read.
+    Quadrature counts N become torchquad's points per dimension (`simpson_points_per_dim`: 101 -> 9); the load vector is
+    built for `gadapt_fem_simpson_points()` only (NotImplementedError otherwise), the loss lattice takes any count.
+    Topology: data.cells (as collate offsets them), else data.mesh / data.mesh[i], else square_mesh(mesh_dims[0]).
+    Limits as the pde_loss tail: 2-D Poisson, square meshes up to 26 x 26 nodes (the LDS budget of the banded factor).
+    The reference's build_mass_matrix is called with three of its four arguments there (a TypeError as shipped); this
+    builds the evident intent, the stiffness of torch_FEM_2D."""
+    if 'grad_type' not in opt:
+        raise ValueError("Error: opt['grad_type'] not specified")
+    gt = opt['grad_type']
+    if gt not in GRAD_TYPES_2D:
+        raise ValueError("Error: opt['grad_type'] incorrectly specified")
+    if x_phys.dim() != 2 or x_phys.shape[1] != 2:
+        raise NotImplementedError(f"gradient_meshpoints_2D: x_phys must be [N,2] (got {tuple(x_phys.shape)}); "
+                                  "1-D meshes take gradient_meshpoints_1D")
+    _require_gpu(x_phys.detach().float(), 'gradient_meshpoints_2D')
+    n_load, n_lat, reduction = _modular_quadrature(opt, gt)
+    cells, boundary, node_counts, tri_counts, params = _modular_batch(opt, data, x_phys.shape[0])
+    loss, x_grads = modular_loss_2d(x_phys.detach().float(), cells, boundary, node_counts, params, n_lat, reduction,
+                                    n_load=n_load, tri_counts=tri_counts)
+    return loss.mean(), x_grads

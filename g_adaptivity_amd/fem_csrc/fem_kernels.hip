@@ -1,6 +1,7 @@
 // fem_kernels.hip - differentiable P1 FEM tail of loss_type='pde_loss' for gfx950 (include/gadapt_fem.h).
 //
-// Forward (three launches): load vector, banded Cholesky solve (one wave per mesh, band in LDS), evaluation on the lattice.
+// Forward (three launches): load vector, banded Cholesky solve (one wave per mesh, band in LDS), evaluation on the lattice;
+// the modular loss adds a fourth, the per-mesh lattice loss and its derivative.
 // Backward (four launches): d L / d c from the evaluation, adjoint solve on the kept factor, per-triangle chain rule
 // (stiffness, load vector, evaluation), per-node gather.  Every sum runs in a fixed order: results are bit-reproducible.
 #include <stdio.h>
@@ -287,6 +288,59 @@ __global__ void __launch_bounds__(FEM_EVAL_THREADS) fem_eval_kernel(const int32_
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- lattice loss
+// The modular loss of mesh b on its lattice, e = sol - u_true (difFEM_2d.py:421-435, :472-476): MSE = mean e^2 (F.mse_loss),
+// or torchquad's composite Simpson rule of e^2, nested as it applies it: the y rule along each x row, then the x rule over
+// the row sums.  One workgroup per mesh, one lane per lattice row (its sum in column order), lane 0 sums the rows in order.
+// g_sol = d loss[b] / d sol for gadapt_fem_backward.
+#define FEM_LOSS_THREADS 256
+
+__global__ void __launch_bounds__(FEM_LOSS_THREADS) fem_loss_kernel(const int32_t* __restrict__ gptr, const float* __restrict__ gpar,
+                                                                    const float* __restrict__ lat_x, const float* __restrict__ lat_y,
+                                                                    int nlat, int reduction, const float* __restrict__ sol,
+                                                                    float* __restrict__ loss, float* __restrict__ g_sol) {
+    extern __shared__ float rows[];
+    const int b = blockIdx.x;
+    const int g0 = gptr[b], g1 = gptr[b + 1];
+    const int64_t base = (int64_t)b * nlat * nlat;
+    const bool simp = reduction == GADAPT_FEM_LOSS_SIMPSON;
+    const float hx3 = (lat_x[nlat - 1] - lat_x[0]) / (float)(nlat - 1) / 3.0f;
+    const float hy3 = (lat_y[nlat - 1] - lat_y[0]) / (float)(nlat - 1) / 3.0f;
+    const float two_over_q = 2.0f / ((float)nlat * (float)nlat);
+    for (int i = threadIdx.x; i < nlat; i += FEM_LOSS_THREADS) {
+        const float px = lat_x[i];
+        const float* s_row = sol + base + (int64_t)i * nlat;
+        float* g_row = g_sol + base + (int64_t)i * nlat;
+        const float wx = hx3 * fem::simpson_coef(i, nlat);
+        float s = 0.0f, f0 = 0.0f, f1 = 0.0f;                  // f0, f1: e^2 at j-2, j-1
+        for (int j = 0; j < nlat; ++j) {
+            const float e = s_row[j] - fem::u_true(px, lat_y[j], gpar, g0, g1);
+            const float f = e * e;
+            if (simp) {
+                g_row[j] = 2.0f * e * (wx * (hy3 * fem::simpson_coef(j, nlat)));
+                if (j > 0 && !(j & 1)) s = s + hy3 * (f0 + 4.0f * f1 + f);
+                f0 = f1;
+                f1 = f;
+            } else {
+                g_row[j] = e * two_over_q;
+                s = s + f;
+            }
+        }
+        rows[i] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float tot = 0.0f;
+        if (simp) {
+            for (int k = 0; k + 2 < nlat; k += 2) tot = tot + hx3 * (rows[k] + 4.0f * rows[k + 1] + rows[k + 2]);
+        } else {
+            for (int i = 0; i < nlat; ++i) tot = tot + rows[i];
+            tot = tot / ((float)nlat * (float)nlat);
+        }
+        loss[b] = tot;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- backward
 // gc[v] = g_coeffs[v] + sum_p g_sol[p] phim(p, v): v's incident triangles, the lattice points of each one's bounding box
 __global__ void __launch_bounds__(256) fem_gc_kernel(int n_nodes, const int32_t* __restrict__ cells, const int32_t* __restrict__ node_mesh,
@@ -477,6 +531,26 @@ extern "C" int gadapt_fem_forward(int B, int N, int T, const int32_t* meta, cons
     fem_eval_kernel<<<dim3(B, FEM_EVAL_CHUNKS), FEM_EVAL_THREADS, (size_t)eval_lds, s>>>(meta, cells, nt_ptr, nt_idx, x, coeffs, lat_x, lat_y,
                                                                                          nlat, sol);
     return launched("fem_eval_kernel");
+}
+
+extern "C" int gadapt_fem_modular_forward(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                          const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                                          const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y,
+                                          int nlat, int max_lds_bytes, int max_tris, int reduction, float* rhs, float* coeffs, float* lfac,
+                                          float* sol, float* loss, float* g_sol, void* stream) {
+    if (B <= 0 || !loss || !g_sol || (reduction != GADAPT_FEM_LOSS_MSE && reduction != GADAPT_FEM_LOSS_SIMPSON))
+        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_modular_forward: null output or unknown reduction");
+    if (reduction == GADAPT_FEM_LOSS_SIMPSON && (nlat < 3 || !(nlat & 1)))
+        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_modular_forward: the Simpson rule needs an odd nlat >= 3");
+    if (nlat > 0 && (int64_t)nlat * 4 > GADAPT_FEM_LDS_BUDGET)
+        return fail(GADAPT_FEM_E_LDS, "gadapt_fem_modular_forward: the lattice's row sums exceed the LDS budget");
+    // gadapt_fem_forward checks the rest of its arguments before it launches anything
+    int rc = gadapt_fem_forward(B, N, T, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y, nlat,
+                                max_lds_bytes, max_tris, rhs, coeffs, lfac, sol, stream);
+    if (rc) return rc;
+    fem_loss_kernel<<<B, FEM_LOSS_THREADS, (size_t)nlat * 4, (hipStream_t)stream>>>(gptr, gpar, lat_x, lat_y, nlat, reduction, sol, loss,
+                                                                                    g_sol);
+    return launched("fem_loss_kernel");
 }
 
 extern "C" int gadapt_fem_backward(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GADAPT_FEM_ABI 2
+#define GADAPT_FEM_ABI 3
 
 #define GADAPT_FEM_OK          0
 #define GADAPT_FEM_E_BADARG   -1   /* null pointer, bad size, bad lattice */
@@ -93,6 +93,21 @@ int gadapt_fem_forward(int n_meshes, int n_nodes, int n_tris, const int32_t* met
                        const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
                        const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
                        int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* sol, void* stream);
+
+/* Lattice-loss reductions of gadapt_fem_modular_forward. */
+#define GADAPT_FEM_LOSS_MSE     0   /* mean over the nlat x nlat lattice of e^2 (F.mse_loss) */
+#define GADAPT_FEM_LOSS_SIMPSON 1   /* torchquad's composite Simpson rule of e^2, y rule per x row, then x (nlat odd, >= 3) */
+
+/* The 2-D modular loss (gradient_meshpoints_2D, difFEM_2d.py:374-535), forward, four launches: the three of
+ * gadapt_fem_forward, then per mesh b the loss of e = sol - u_true on its lattice (u_true from b's own Gaussians):
+ * loss [B] and g_sol [B*nlat*nlat] = d loss[b] / d sol.  One workgroup per mesh, sums in a fixed order.  The gradient
+ * d loss[b] / d x is gadapt_fem_backward with g_coeffs = NULL and this g_sol.  Arguments otherwise as gadapt_fem_forward;
+ * everything is checked before the first launch. */
+int gadapt_fem_modular_forward(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells,
+                               const int32_t* node_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                               const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
+                               const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int reduction, float* rhs,
+                               float* coeffs, float* lfac, float* sol, float* loss, float* g_sol, void* stream);
 
 /* Backward, four launches: d L / d x [N,2] from g_coeffs [N] and g_sol [B*nlat*nlat] (either may be NULL: zero).
  * Work buffers (caller-owned, no initialisation needed): gc [N], mu [N], tgrad [T,3,2]. */
