@@ -1,6 +1,7 @@
 # Builds the C-ABI shared library of the hot path for gfx950 (MI355X), in-tree.
 #   make -j8        -> g_adaptivity_amd/libgadapt_hip.so   (one object per kernel family: csrc/gadapt_internal.h)
 #                      g_adaptivity_amd/libgadapt_fem.so   (the FEM tails: 2-D pde_loss and 1-D Burgers / Poisson; fem_csrc/, include/gadapt_fem.h)
+#                      g_adaptivity_amd/libgadapt_mesh.so  (batched MMPDE5 target meshes; mesh_csrc/, include/gadapt_mesh.h)
 #   make resources  -> per-kernel VGPR/SGPR/LDS/occupancy report
 #   make DEV_C=64   -> development build: tiled kernels for one hidden size only (never shipped)
 HIPCC      ?= /opt/rocm/bin/hipcc
@@ -11,6 +12,8 @@ LIB        := g_adaptivity_amd/libgadapt_hip.so
 FEM_CSRC   := g_adaptivity_amd/fem_csrc
 FEM_LIB    := g_adaptivity_amd/libgadapt_fem.so
 FEM_OBJS   := $(OBJDIR)/fem_kernels.o $(OBJDIR)/fem1d_kernels.o $(OBJDIR)/fem_topology.o
+MESH_CSRC  := g_adaptivity_amd/mesh_csrc
+MESH_LIB   := g_adaptivity_amd/libgadapt_mesh.so
 HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-variable -Wno-unused-but-set-variable -Wno-unused-function $(EXTRA)
 ifdef DEV_C
 HIPFLAGS   += -DGADAPT_DEV_C=$(DEV_C)
@@ -19,7 +22,7 @@ UNITS      := gadapt_kernels gadapt_tu_fwd gadapt_tu_bwd_target gadapt_tu_bwd_so
 OBJS       := $(UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/csr_build.o
 SHARED     := $(CSRC)/gadapt_internal.h $(CSRC)/gadapt_common.inc include/gadapt_hip.h
 
-all: $(LIB) $(FEM_LIB)
+all: $(LIB) $(FEM_LIB) $(MESH_LIB)
 
 # the differentiable P1 FEM tail of loss_type='pde_loss' (include/gadapt_fem.h): its own library, built without FMA contraction
 # (fem_csrc/fem_common.h: the reference's edge tests compare rounded sums)
@@ -35,6 +38,15 @@ $(OBJDIR)/fem1d_kernels.o: $(FEM_CSRC)/fem1d_kernels.hip $(FEM_CSRC)/fem_common.
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
 $(OBJDIR)/fem_topology.o: $(FEM_CSRC)/fem_topology.cpp include/gadapt_fem.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+
+# the MMPDE5 target-mesh generator (include/gadapt_mesh.h): its own library, without FMA contraction like the FEM tails
+# (the stopping step of the fp32 iteration follows the rounding of its increments)
+$(MESH_LIB): $(OBJDIR)/mmpde5_kernels.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $<
+
+$(OBJDIR)/mmpde5_kernels.o: $(MESH_CSRC)/mmpde5_kernels.hip include/gadapt_mesh.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
@@ -62,6 +74,6 @@ resources:
 	python3 tools/resources.py
 
 clean:
-	rm -rf $(OBJDIR) $(LIB) $(FEM_LIB)
+	rm -rf $(OBJDIR) $(LIB) $(FEM_LIB) $(MESH_LIB)
 
 .PHONY: all resources clean

@@ -86,11 +86,13 @@ if __name__ == '__main__':
     ap.add_argument('--cpu_loader', action='store_true', help='collate on the host every step, as the reference does')
     ap.add_argument('--torch_loss', action='store_true')
     ap.add_argument('--eager', action='store_true', help='eager launches instead of the captured training step')
+    ap.add_argument('--target', choices=('noise', 'mmpde5'), default='noise',
+                    help="x_phys of the samples: the noise stand-in, or the reference's MMPDE5 meshes (one batched GPU call; --mesh <= 32)")
     a = ap.parse_args()
     opt = hot_path_opt(mesh_dims=[a.mesh, a.mesh], hidden_dim=a.hidden_dim, num_layers=a.num_layers, batch_size=a.batch_size,
                        epochs=a.epochs, device='cuda:0', loss_fn='mse', lr=1e-3, show_mesh_evol_plots='False',
                        device_loader=not a.cpu_loader, native_loss=not a.torch_loss, graphed=not a.eager)
-    ds = MeshDataset(opt['mesh_dims'], a.num_train, seed=0)
+    ds = MeshDataset(opt['mesh_dims'], a.num_train, seed=0, target=a.target)
     t0 = time.time()
     model, losses, rate = main(opt, ds)
     torch.cuda.synchronize()

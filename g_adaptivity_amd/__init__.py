@@ -6,8 +6,9 @@ Public surface mirrors the reference modules:
     from g_adaptivity_amd import torch_FEM_2D, fem_poisson   # loss_type='pde_loss': the differentiable P1 FEM tail
     from g_adaptivity_amd import gradient_meshpoints_1D, burgers_1d, fem_poisson_1d   # the 1-D modular loss (Burgers, Poisson)
     from g_adaptivity_amd import gradient_meshpoints_2D    # the 2-D modular loss (Poisson)
+    from g_adaptivity_amd import MMPDE5_1d, MMPDE5_2d, mmpde5_batch   # the classical MMPDE5 target meshes, batched
 The arithmetic lives in `libgadapt_hip.so` (csrc/, C-ABI in include/gadapt_hip.h) and, for the FEM tail,
-`libgadapt_fem.so` (fem_csrc/, include/gadapt_fem.h).
+`libgadapt_fem.so` (fem_csrc/, include/gadapt_fem.h); the MMPDE5 generator in `libgadapt_mesh.so` (mesh_csrc/, include/gadapt_mesh.h).
 """
 from .conv import GAT_conv, GAT_plus, GCN_conv, GRAND_conv, GRAND_plusConv, TRANS_conv
 from .fem import fem_poisson, gradient_meshpoints_2D, torch_FEM_2D
@@ -18,6 +19,8 @@ from .gnn import GNN, MLP, build_conv_list, get_conv, get_dec, get_enc, get_mlp,
 from .graph import GraphCache, MeshGraph, prepare_edge_index
 from .mesh_graph import (DeviceMeshLoader, MeshData, MeshDataset, MeshLoader, Mixed_DataLoader, MixedMeshDataset, collate, interval_mesh,
                          square_mesh, synthetic_batch)
+from .mmpde5 import (MMPDE5_1d, MMPDE5_1d_burgers, MMPDE5_2d, deform_mesh_mmpde1d, deform_mesh_mmpde2d, mmpde5_batch, monitor_1d,
+                     monitor_2d)
 from .params import hot_path_opt
 from .training import GraphedTrainStep
 
@@ -26,4 +29,6 @@ __all__ = ['GNN', 'MLP', 'get_conv', 'build_conv_list', 'get_enc', 'get_dec', 'g
            'MeshData', 'MeshDataset', 'MeshLoader', 'DeviceMeshLoader', 'MixedMeshDataset', 'Mixed_DataLoader', 'collate', 'interval_mesh', 'square_mesh',
            'synthetic_batch', 'hot_path_opt', 'GraphedTrainStep', 'mse_loss', 'l1_loss', 'unit_gradient',
            'fem_poisson', 'torch_FEM_2D', 'burgers_1d', 'fem_poisson_1d', 'gradient_meshpoints_1D', 'torch_FEM_Burgers_1D',
-           'get_Burgers_initial_coeffs', 'fn_expansion', 'torch_FEM_1D', 'gradient_meshpoints_2D']
+           'get_Burgers_initial_coeffs', 'fn_expansion', 'torch_FEM_1D', 'gradient_meshpoints_2D',
+           'mmpde5_batch', 'monitor_1d', 'monitor_2d', 'MMPDE5_1d', 'MMPDE5_2d', 'MMPDE5_1d_burgers', 'deform_mesh_mmpde1d',
+           'deform_mesh_mmpde2d']

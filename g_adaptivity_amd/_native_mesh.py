@@ -1,0 +1,58 @@
+"""ctypes binding of `libgadapt_mesh.so`, the batched MMPDE5 target-mesh generator (C-ABI in include/gadapt_mesh.h).
+
+There is no CPU fallback: if the library is missing, or a call fails, this raises `NativeError`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+from ._native import NativeError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, 'libgadapt_mesh.so')
+
+ABI_VERSION = 1
+MAX_NODES = 1024                                       # GADAPT_MMPDE5_MAX_NODES
+MAX_STEPS = 10000000                                   # GADAPT_MMPDE5_MAX_STEPS
+DESC = 4                                               # GADAPT_MMPDE5_DESC: dim, N, node offset, cell offset
+E_SIZE = -3                                            # GADAPT_MESH_E_SIZE
+CONVERGED, CAP, STIFF = 0, 1, 2                        # GADAPT_MMPDE5_CONVERGED / _CAP / _STIFF
+
+_P, _I, _L, _D = C.c_void_p, C.c_int, C.c_int64, C.c_double
+
+# name -> (restype, argtypes); must list every symbol include/gadapt_mesh.h declares
+PROTOTYPES = {
+    'gadapt_mesh_abi_version': (_I, []),
+    'gadapt_mesh_last_error': (C.c_char_p, []),
+    'gadapt_mmpde5_max_nodes': (_I, []),
+    'gadapt_mmpde5_max_steps': (_I, []),
+    'gadapt_mmpde5_threads': (_I, [_I]),
+    'gadapt_mmpde5_lds_bytes': (_L, [_I]),
+    'gadapt_mmpde5_batch': (_I, [_I] + [_P] * 7 + [_D, _D, _I] + [_P] * 6),
+}
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise NativeError(f"{LIB_PATH} not found: build it with `make` (hipcc --offload-arch=gfx950); "
+                              "there is no CPU fallback for the MMPDE5 generator")
+        handle = C.CDLL(LIB_PATH)
+        for name, (res, args) in PROTOTYPES.items():
+            fn = getattr(handle, name)
+            fn.restype, fn.argtypes = res, args
+        if handle.gadapt_mesh_abi_version() != ABI_VERSION:
+            raise NativeError(f"{LIB_PATH}: ABI {handle.gadapt_mesh_abi_version()}, expected {ABI_VERSION}")
+        _lib = handle
+    return _lib
+
+
+def check(rc: int, what: str):
+    """Size errors are the caller's (`ValueError`), everything else a native failure."""
+    if rc < 0:
+        msg = lib().gadapt_mesh_last_error().decode() or f"error {rc}"
+        raise (ValueError if rc == E_SIZE else NativeError)(f"{what}: {msg} (code {rc})")

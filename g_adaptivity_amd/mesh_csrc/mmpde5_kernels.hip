@@ -1,0 +1,283 @@
+// mmpde5_kernels.hip - batched MMPDE5 target-mesh generation (include/gadapt_mesh.h).
+//
+// One workgroup per mesh, the whole pseudo-time loop inside the launch.  The monitor does not move with the mesh, so every
+// node's stencil is four constant coefficients; they stay in registers with the node's coordinates, and the stage values go
+// through two LDS images that alternate, so that a stage needs one barrier: a stage writes image s & 1 and reads its
+// neighbours there, and the image it overwrites was last read two barriers ago.  The wave sums of the update measure ride
+// on the barrier of the next step's first stage (two slots, by step parity), every lane adds them in the same order and
+// takes the same exit.
+//
+// One lane per node, as many waves as the mesh needs (up to 16).  One wave per mesh with several nodes per lane and no
+// workgroup barrier was built and measured too: slower on a single mesh (4.35 against 1.16 ms for 1000 steps at 23 x 23,
+// 0.87 against 0.72 at 11 x 11) and on full batches (4.49 against 2.94 ms for 1024 meshes of 23 x 23), so it was deleted
+// (docs/measurements.md).  A mesh's thread count follows from its own node count, so its arithmetic and the order of its
+// reduction do not depend on the batch it is launched in; waves beyond a mesh's own only keep the barriers company.
+//
+// Built without FMA contraction (Makefile and the pragma below): the stopping step of the fp32 iteration depends on the
+// rounding of increments near half an ulp, and the parity bars are stated against uncontracted fp32 arithmetic.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "gadapt_mesh.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+thread_local char g_err[256] = "";
+
+int mesh_fail(int code, const char* msg) {
+    snprintf(g_err, sizeof g_err, "%s", msg);
+    return code;
+}
+
+constexpr int MAX_NODES = GADAPT_MMPDE5_MAX_NODES;
+constexpr int MAX_WAVES = MAX_NODES / 64;
+
+// Threads of a mesh: one lane per node, whole waves.
+__host__ __device__ inline int mmpde5_threads(int nodes) { return (nodes + 63) & ~63; }
+
+// red[2][MAX_WAVES] in front, then the two images of (X, Y), each MAX of the batch's nodes long
+__host__ __device__ inline int64_t mmpde5_lds_floats(int nodes) { return 2 * MAX_WAVES + 4 * (int64_t)nodes; }
+
+template <int CTRL>
+__device__ inline float dpp_move(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
+}
+
+// Sum over the 64 lanes, the same bits in every lane: a butterfly inside each row of 16 (quad_perm [1,0,3,2], [2,3,0,1],
+// row_half_mirror, row_mirror: each lane adds its partner's value, and a + b == b + a), then the four rows in a fixed order.
+__device__ inline float wave_sum(float v) {
+    v = v + dpp_move<0xB1>(v);
+    v = v + dpp_move<0x4E>(v);
+    v = v + dpp_move<0x141>(v);
+    v = v + dpp_move<0x140>(v);
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
+    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
+    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+    return (r0 + r1) + (r2 + r3);
+}
+
+struct Params {
+    float h, h6, tol, stiff;
+    int tol_zero, max_steps;
+    double tau;
+};
+
+// The right-hand side of one coordinate at one node: `u` is the node's own stage value, the neighbours come from the image.
+template <int DIM>
+__device__ inline float rhs(const float* __restrict__ img, float u, int c, int oi, int oj, float aE, float aW, float aS, float cf) {
+    const float a1 = aE * (img[c + oi] - u) - aW * (u - img[c - oi]);
+    if (DIM == 1) return a1 * cf;
+    const float a2 = aE * (img[c + oj] - u) - aS * (u - img[c - oj]);
+    return (a1 + a2) * cf;
+}
+
+template <int DIM>
+__device__ void mmpde5_run(const int32_t* __restrict__ d, const float* __restrict__ x0, const float* __restrict__ y0,
+                           const float* __restrict__ ms, const float* __restrict__ m2, const Params p, float* __restrict__ xo,
+                           float* __restrict__ yo, int32_t* __restrict__ steps, float* __restrict__ measure,
+                           int32_t* __restrict__ status, float* lds) {
+    const int N = d[GADAPT_MMPDE5_D_N], noff = d[GADAPT_MMPDE5_D_NODE_OFF], coff = d[GADAPT_MMPDE5_D_CELL_OFF];
+    const int nodes = DIM == 2 ? N * N : N;
+    const int T = mmpde5_threads(nodes), nw = T >> 6;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    float* red = lds;
+    float* imgX[2] = {lds + 2 * MAX_WAVES, lds + 2 * MAX_WAVES + 2 * nodes};
+    float* imgY[2] = {imgX[0] + nodes, imgX[1] + nodes};
+
+    float x, y, aE, aW, aS, cf;
+    int c, oi, oj;
+    bool own;
+    const double dxi = 1.0 / (double)(N - 1);
+    {
+        own = tid < nodes;
+        c = own ? tid : 0;
+        bool inner;
+        int cell, cellW, cellS = 0;
+        if (DIM == 2) {
+            const int i = c / N, j = c - i * N;
+            inner = own && i > 0 && i < N - 1 && j > 0 && j < N - 1;
+            cell = i * (N - 1) + j, cellW = cell - (N - 1), cellS = cell - 1;
+            oi = inner ? N : 0, oj = inner ? 1 : 0;
+        } else {
+            inner = own && c > 0 && c < N - 1;
+            cell = c, cellW = cell - 1;
+            oi = inner ? 1 : 0, oj = 0;
+        }
+        aE = inner ? ms[coff + cell] : 0.0f;
+        aW = inner ? ms[coff + cellW] : 0.0f;
+        aS = (DIM == 2 && inner) ? ms[coff + cellS] : 0.0f;
+        cf = inner ? (float)(1.0 / (dxi * dxi * p.tau * (double)m2[noff + c])) : 0.0f;
+        x = own ? x0[noff + c] : 0.0f;
+        y = (DIM == 2 && own) ? y0[noff + c] : 0.0f;
+        if (own) {
+            imgX[0][c] = x;
+            if (DIM == 2) imgY[0][c] = y;
+        }
+    }
+
+    int j = 0;
+    float meas = 1.0f;                                   // the reference's starting value: tol >= 1 takes no step
+    for (;;) {
+        __syncthreads();                                 // image 0 holds the coordinates, red[j & 1] the wave sums of step j
+        if (j > 0) {
+            meas = red[(j & 1) * MAX_WAVES];
+            for (int w = 1; w < nw; ++w) meas = meas + red[(j & 1) * MAX_WAVES + w];
+        }
+        // written so that a NaN measure ends the loop; with tol == 0 only the step count does
+        if (!(j < p.max_steps && (p.tol_zero || meas > p.tol) && !(meas > p.stiff))) break;
+        ++j;
+
+        float sx, sy = 0.0f, kx, ky = 0.0f, ax, ay = 0.0f;
+        ax = rhs<DIM>(imgX[0], x, c, oi, oj, aE, aW, aS, cf);          // k1 at the coordinates
+        sx = x + (p.h * ax) * 0.5f;
+        if (DIM == 2) {
+            ay = rhs<DIM>(imgY[0], y, c, oi, oj, aE, aW, aS, cf);
+            sy = y + (p.h * ay) * 0.5f;
+        }
+        if (own) {
+            imgX[1][c] = sx;
+            if (DIM == 2) imgY[1][c] = sy;
+        }
+        __syncthreads();
+        kx = rhs<DIM>(imgX[1], sx, c, oi, oj, aE, aW, aS, cf);         // k2
+        if (DIM == 2) ky = rhs<DIM>(imgY[1], sy, c, oi, oj, aE, aW, aS, cf);
+        ax = ax + 2.0f * kx;
+        sx = x + (p.h * kx) * 0.5f;
+        if (DIM == 2) {
+            ay = ay + 2.0f * ky;
+            sy = y + (p.h * ky) * 0.5f;
+        }
+        if (own) {
+            imgX[0][c] = sx;
+            if (DIM == 2) imgY[0][c] = sy;
+        }
+        __syncthreads();
+        kx = rhs<DIM>(imgX[0], sx, c, oi, oj, aE, aW, aS, cf);         // k3
+        if (DIM == 2) ky = rhs<DIM>(imgY[0], sy, c, oi, oj, aE, aW, aS, cf);
+        ax = ax + 2.0f * kx;
+        sx = x + p.h * kx;
+        if (DIM == 2) {
+            ay = ay + 2.0f * ky;
+            sy = y + p.h * ky;
+        }
+        if (own) {
+            imgX[1][c] = sx;
+            if (DIM == 2) imgY[1][c] = sy;
+        }
+        __syncthreads();
+        kx = rhs<DIM>(imgX[1], sx, c, oi, oj, aE, aW, aS, cf);         // k4, the new coordinates, this lane's share of the measure
+        if (DIM == 2) ky = rhs<DIM>(imgY[1], sy, c, oi, oj, aE, aW, aS, cf);
+        const float xn = x + p.h6 * (ax + kx);
+        float part = fabsf(xn - x);
+        x = xn;
+        if (DIM == 2) {
+            const float yn = y + p.h6 * (ay + ky);
+            part = part + fabsf(yn - y);
+            y = yn;
+        }
+        if (own) {                                       // image 0 was last read before the barrier above
+            imgX[0][c] = x;
+            if (DIM == 2) imgY[0][c] = y;
+        }
+        const float wsum = wave_sum(part);
+        if (lane == 0 && wave < nw) red[(j & 1) * MAX_WAVES + wave] = wsum;
+    }
+
+    if (own) {
+        xo[noff + c] = x;
+        if (DIM == 2) yo[noff + c] = y;
+    }
+    if (tid == 0) {
+        *steps = j;
+        *measure = meas;
+        const bool finite = meas - meas == 0.0f;
+        *status = (!finite || meas > p.stiff) ? GADAPT_MMPDE5_STIFF
+                  : ((p.tol_zero || meas > p.tol) ? GADAPT_MMPDE5_CAP : GADAPT_MMPDE5_CONVERGED);
+    }
+}
+
+__global__ __launch_bounds__(MAX_NODES) void mmpde5_kernel(const int32_t* __restrict__ desc, const float* __restrict__ x0,
+                                                          const float* __restrict__ y0, const float* __restrict__ ms,
+                                                          const float* __restrict__ m2, const double* __restrict__ step,
+                                                          double tau, float tol, float stiff, int tol_zero, int max_steps,
+                                                          float* __restrict__ xo, float* __restrict__ yo,
+                                                          int32_t* __restrict__ steps, float* __restrict__ measure,
+                                                          int32_t* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int b = blockIdx.x;
+    const int32_t* d = desc + GADAPT_MMPDE5_DESC * b;
+    const double h = step[b];
+    // the reference multiplies fp32 tensors by the Python floats h and h / 6: each rounded to fp32 once
+    const Params p{(float)h, (float)(h / 6.0), tol, stiff, tol_zero, max_steps, tau};
+    if (d[GADAPT_MMPDE5_D_DIM] == 2)
+        mmpde5_run<2>(d, x0, y0, ms, m2, p, xo, yo, steps + b, measure + b, status + b, lds);
+    else
+        mmpde5_run<1>(d, x0, y0, ms, m2, p, xo, yo, steps + b, measure + b, status + b, lds);
+}
+
+}  // namespace
+
+extern "C" int gadapt_mesh_abi_version(void) { return GADAPT_MESH_ABI; }
+extern "C" const char* gadapt_mesh_last_error(void) { return g_err; }
+extern "C" int gadapt_mmpde5_max_nodes(void) { return MAX_NODES; }
+extern "C" int gadapt_mmpde5_max_steps(void) { return GADAPT_MMPDE5_MAX_STEPS; }
+
+extern "C" int gadapt_mmpde5_threads(int nodes) {
+    if (nodes < 3) return mesh_fail(GADAPT_MESH_E_BADARG, "gadapt_mmpde5_threads: a mesh has at least 3 nodes");
+    if (nodes > MAX_NODES) return mesh_fail(GADAPT_MESH_E_SIZE, "gadapt_mmpde5_threads: more nodes than one workgroup holds");
+    return mmpde5_threads(nodes);
+}
+
+extern "C" int64_t gadapt_mmpde5_lds_bytes(int nodes) {
+    if (nodes < 3 || nodes > MAX_NODES) return mesh_fail(GADAPT_MESH_E_SIZE, "gadapt_mmpde5_lds_bytes: 3..1024 nodes");
+    return 4 * mmpde5_lds_floats(nodes);
+}
+
+extern "C" int gadapt_mmpde5_batch(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* x0, const float* y0,
+                                   const float* ms, const float* m2, const double* step, double tau, double tol, int max_steps,
+                                   float* x, float* y, int32_t* steps, float* measure, int32_t* status, void* stream) {
+    char msg[200];
+    if (n_mesh < 1 || !desc_host || !desc || !x0 || !ms || !m2 || !step || !x || !steps || !measure || !status)
+        return mesh_fail(GADAPT_MESH_E_BADARG, "gadapt_mmpde5_batch: empty batch or null pointer");
+    if (!(tau > 0.0) || !(tol >= 0.0) || !isfinite(tau) || !isfinite(tol))
+        return mesh_fail(GADAPT_MESH_E_BADARG, "gadapt_mmpde5_batch: need tau > 0 and tol >= 0, both finite");
+    if (max_steps < 0 || max_steps > GADAPT_MMPDE5_MAX_STEPS) {
+        snprintf(msg, sizeof msg, "gadapt_mmpde5_batch: max_steps %d; 0..%d supported (the loop must end)", max_steps,
+                 GADAPT_MMPDE5_MAX_STEPS);
+        return mesh_fail(GADAPT_MESH_E_SIZE, msg);
+    }
+    int threads = 64, most = 0;
+    for (int b = 0; b < n_mesh; ++b) {
+        const int32_t* d = desc_host + GADAPT_MMPDE5_DESC * b;
+        const int dim = d[GADAPT_MMPDE5_D_DIM], N = d[GADAPT_MMPDE5_D_N];
+        if ((dim != 1 && dim != 2) || N < 3 || d[GADAPT_MMPDE5_D_NODE_OFF] < 0 || d[GADAPT_MMPDE5_D_CELL_OFF] < 0) {
+            snprintf(msg, sizeof msg, "gadapt_mmpde5_batch: mesh %d: dimension %d, N %d, offsets %d / %d", b, dim, N,
+                     d[GADAPT_MMPDE5_D_NODE_OFF], d[GADAPT_MMPDE5_D_CELL_OFF]);
+            return mesh_fail(GADAPT_MESH_E_BADARG, msg);
+        }
+        if (N > MAX_NODES || (dim == 2 && N * N > MAX_NODES)) {
+            snprintf(msg, sizeof msg, "gadapt_mmpde5_batch: mesh %d: N = %d in %d-D; at most %d nodes per mesh (1-D N <= 1024, 2-D N <= 32)",
+                     b, N, dim, MAX_NODES);
+            return mesh_fail(GADAPT_MESH_E_SIZE, msg);
+        }
+        if (dim == 2 && !(y0 && y)) return mesh_fail(GADAPT_MESH_E_BADARG, "gadapt_mmpde5_batch: a 2-D mesh needs y0 and y");
+        const int nodes = dim == 2 ? N * N : N;
+        const int t = mmpde5_threads(nodes);
+        threads = t > threads ? t : threads;
+        most = nodes > most ? nodes : most;
+    }
+    const float tol_f = (float)tol;
+    const int tol_zero = tol_f == 0.0f;
+    const float stiff = tol_zero ? INFINITY : (float)(1.0 / tol);
+    mmpde5_kernel<<<n_mesh, threads, (size_t)(4 * mmpde5_lds_floats(most)), (hipStream_t)stream>>>(
+        desc, x0, y0, ms, m2, step, tau, tol_f, stiff, tol_zero, max_steps, x, y, steps, measure, status);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mesh_fail(GADAPT_MESH_E_LAUNCH, hipGetErrorString(e));
+    return GADAPT_MESH_OK;
+}

@@ -283,7 +283,12 @@ class MeshDataset:
     """
 
     def __init__(self, mesh_dims: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2, pde_loss_fields: bool = False,
-                 eval_quad_points: int = 101, burgers: bool = False, scale: float = 0.1, burgers_limits: float = 3.0):
+                 eval_quad_points: int = 101, burgers: bool = False, scale: float = 0.1, burgers_limits: float = 3.0,
+                 target: str = 'noise', target_params: Optional[dict] = None):
+        """`target`: what `x_phys` of a sample is.  'noise' (default): x_comp + small interior noise, a stand-in.  'mmpde5': the
+        reference's classical target (`src/data.py:206-212`), the MMPDE5 mesh of the sample's own Gaussians, all samples in one
+        batched GPU call at construction (`mmpde5.attach_mmpde5_targets`; `ma_its` per sample).  `target_params`: `mon_power` /
+        `mon_reg` of the monitor and keyword arguments of `mmpde5_batch` under the key 'solver'."""
         self.mesh_dims = list(mesh_dims)
         self.dim = len(self.mesh_dims)
         if self.dim == 1:
@@ -302,6 +307,7 @@ class MeshDataset:
         self.mesh = MeshTopology(base.cells.numpy()) if self.dim == 2 else None
         if pde_loss_fields:                                  # loss_type='pde_loss': only when asked, samples are unchanged otherwise
             _add_pde_loss_fields(self, eval_quad_points)
+        _set_targets(self, target, target_params)
 
     def __len__(self):
         return len(self.samples)
@@ -320,7 +326,7 @@ class MixedMeshDataset(MeshDataset):
     this data type, `src/GNN.py:247-248,279`) and its `pde_params`."""
 
     def __init__(self, mesh_sizes: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2, pde_loss_fields: bool = False,
-                 eval_quad_points: int = 101):
+                 eval_quad_points: int = 101, target: str = 'noise', target_params: Optional[dict] = None):
         self.mesh_sizes = list(mesh_sizes)
         self.mesh_dims = [self.mesh_sizes[0], self.mesh_sizes[0]]
         self.dim = 2
@@ -339,6 +345,19 @@ class MixedMeshDataset(MeshDataset):
         self.mesh = MeshTopology(self.base.cells.numpy())
         if pde_loss_fields:
             _add_pde_loss_fields(self, eval_quad_points)
+        _set_targets(self, target, target_params)
+
+
+def _set_targets(ds, target: str, target_params: Optional[dict]):
+    """`target='mmpde5'`: every sample's `x_phys` from one batched MMPDE5 call (mixed mesh sizes share the launch)."""
+    if target == 'noise':
+        return
+    if target != 'mmpde5':
+        raise ValueError(f"target = {target!r}; 'noise' or 'mmpde5'")
+    from .mmpde5 import attach_mmpde5_targets
+    params = dict(target_params or {})
+    solver = params.pop('solver', {})
+    ds.target_result = attach_mmpde5_targets(ds.samples, params, **solver)
 
 
 def _add_pde_loss_fields(ds, eval_quad_points: int):

@@ -1,0 +1,89 @@
+/*
+ * gadapt_mesh.h - C-ABI of the classical target-mesh generator: batched MMPDE5 (libgadapt_mesh.so).
+ *
+ * The reference builds the target mesh `x_phys` of loss_type='mesh_loss' with the moving-mesh PDE "MMPDE5"
+ * (classical_meshing/ma_mesh_1d.py:7-134, ma_mesh_2d.py:11-103, called from src/data.py:394-416): classical RK4 in
+ * pseudo-time on
+ *
+ *   dX/dt = div(m grad X) / (tau m)          on the fixed computational grid xi, boundary nodes held,
+ *
+ * until the l1 size of one step's update falls to a tolerance.  The monitor m is evaluated on the computational grid,
+ * never on the moving coordinates, so it is a constant of the iteration: the caller passes it as two arrays and the
+ * kernel keeps coordinates, stage values and coefficients in registers and LDS for the whole loop.  One launch advances
+ * a batch of meshes of mixed sizes and dimensions, each to its own stopping step.
+ *
+ * Per mesh b (`desc` is int32 [B, GADAPT_MMPDE5_DESC], fields GADAPT_MMPDE5_D_*):
+ *   dim 1: N nodes; coordinates x [N]; ms [N-1] = m at the cell centres; m2 [N] = m at the nodes
+ *   dim 2: N x N nodes, node = i * N + j (meshgrid(..., indexing='ij')); x, y [N*N]; ms [(N-1)*(N-1)], cell = i * (N-1) + j; m2 [N*N]
+ *   right-hand side at an interior node, per index direction and per coordinate U:
+ *       ms[here] * (U[next] - U[here]) - ms[previous cell] * (U[here] - U[previous])
+ *   summed over the directions and multiplied by 1 / (dxi^2 tau m2[here]), dxi = 1 / (N - 1) (hoisted out of the loop;
+ *   the reference divides three times at every evaluation).  fp32, no FMA contraction.
+ *   loop:  while (steps < max_steps && measure > tol) { ++steps; RK4 step of size step[b];
+ *                                                        measure = sum |new - old| of the stored fp32 coordinates;
+ *                                                        if (measure > 1 / tol) break; }
+ *   tol == 0 switches the stopping test off: exactly max_steps steps.  A NaN measure ends the loop.
+ * All meshes are concatenated: nodes of mesh b start at desc[b].NODE_OFF in x0, y0, m2, x, y (y0 / y are not touched for
+ * dim 1), cells at desc[b].CELL_OFF in ms.  The arithmetic of a mesh, the order of its reduction included, depends on its
+ * own size only: a mesh gives the same bits alone and in any batch.
+ *
+ * Conventions as in gadapt_hip.h: plain pointers, `stream` is a hipStream_t passed as void*.  Entry points return 0 or a
+ * negative GADAPT_MESH_E_* code and never abort; gadapt_mesh_last_error() gives the message.  The launch function neither
+ * allocates nor synchronises, and checks every size on the host copy of `desc` before anything is launched.
+ */
+#ifndef GADAPT_MESH_H
+#define GADAPT_MESH_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define GADAPT_MESH_ABI 1
+
+#define GADAPT_MESH_OK         0
+#define GADAPT_MESH_E_BADARG  -1   /* null pointer, bad dimension, offset or parameter */
+#define GADAPT_MESH_E_LAUNCH  -2   /* hipGetLastError() after the launch */
+#define GADAPT_MESH_E_SIZE    -3   /* a mesh has more nodes than one workgroup holds, or max_steps is beyond the cap */
+
+/* Nodes per mesh: 1-D N <= 1024, 2-D N <= 32 a side. */
+#define GADAPT_MMPDE5_MAX_NODES 1024
+/* The loop always ends: max_steps is bounded on the host. */
+#define GADAPT_MMPDE5_MAX_STEPS 10000000
+
+/* desc fields, per mesh */
+#define GADAPT_MMPDE5_D_DIM      0
+#define GADAPT_MMPDE5_D_N        1
+#define GADAPT_MMPDE5_D_NODE_OFF 2
+#define GADAPT_MMPDE5_D_CELL_OFF 3
+#define GADAPT_MMPDE5_DESC       4
+
+/* status, per mesh */
+#define GADAPT_MMPDE5_CONVERGED 0   /* measure <= tol */
+#define GADAPT_MMPDE5_CAP       1   /* max_steps reached with measure > tol (always, when tol == 0) */
+#define GADAPT_MMPDE5_STIFF     2   /* measure > 1 / tol, or not finite: the step is too large for this monitor */
+
+int gadapt_mesh_abi_version(void);
+const char* gadapt_mesh_last_error(void);
+int gadapt_mmpde5_max_nodes(void);
+int gadapt_mmpde5_max_steps(void);
+
+/* Threads one mesh of `nodes` nodes works with (a multiple of 64; a launch uses the largest of its batch), or a negative code. */
+int gadapt_mmpde5_threads(int nodes);
+/* Dynamic LDS of a launch whose largest mesh has `nodes` nodes. */
+int64_t gadapt_mmpde5_lds_bytes(int nodes);
+
+/* One launch, one workgroup per mesh.
+ *   in   desc_host / desc [B, 4] (the same values on the host and on the device), x0, y0, ms, m2 (device, fp32),
+ *        step [B] (device, fp64: the RK4 step of each mesh, the reference's CFL / N^3), tau, tol, max_steps
+ *   out  x, y (device, fp32; buffers of their own), steps [B] int32, measure [B] fp32, status [B] int32 */
+int gadapt_mmpde5_batch(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* x0, const float* y0,
+                        const float* ms, const float* m2, const double* step, double tau, double tol, int max_steps,
+                        float* x, float* y, int32_t* steps, float* measure, int32_t* status, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif
