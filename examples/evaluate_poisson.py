@@ -1,0 +1,70 @@
+#!/usr/bin/env python
+"""The reference's headline tables (`src/utils_eval.py:106-267`, evaluate_model_fine) on the MI355X, without Firedrake: per test
+sample the FEM error on the uniform grid, on the classical MMPDE5 target mesh and on the model's mesh, and the percentage
+error reduction of the last two, with the model's time per sample.
+
+    python examples/evaluate_poisson.py                         # 2-D, 11 x 11, trains briefly first
+    python examples/evaluate_poisson.py --dim 1 --mesh 21
+    python examples/evaluate_poisson.py --state model.pt         # a saved state_dict instead of the brief training
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from g_adaptivity_amd import GNN, MeshDataset, MeshLoader, eval_grid_MMPDE_MA, evaluate_model_fine, hot_path_opt   # noqa: E402
+
+
+def describe(table) -> str:
+    """`DataFrame.describe()`, or the same summary rows from a dict of numpy arrays where pandas is not installed."""
+    if hasattr(table, 'describe'):
+        return str(table.describe())
+    names = list(table)
+    stats = [('count', lambda v: float(np.isfinite(v).sum())), ('mean', np.nanmean), ('std', lambda v: np.nanstd(v, ddof=1)),
+             ('min', np.nanmin), ('50%', np.nanmedian), ('max', np.nanmax)]
+    lines = [' ' * 6 + ''.join(f"{n:>22}" for n in names)]
+    for label, fn in stats:
+        lines.append(f"{label:<6}" + ''.join(f"{fn(np.asarray(table[n], dtype=float)):>22.6e}" for n in names))
+    return '\n'.join(lines)
+
+
+def train_briefly(model, dataset, opt, epochs):
+    model.train()
+    optim = torch.optim.Adam(model.parameters(), lr=opt['lr'])
+    for _ in range(epochs):
+        for data in MeshLoader(dataset, batch_size=opt['batch_size'], shuffle=False):
+            data = data.to(opt['device'])
+            optim.zero_grad()
+            F.mse_loss(model(data).view_as(data.x_phys), data.x_phys).backward()
+            optim.step()
+    return model.eval()
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--dim', type=int, choices=(1, 2), default=2)
+    ap.add_argument('--mesh', type=int, default=11, help='nodes per dimension (2-D: at most 26)')
+    ap.add_argument('--num_train', type=int, default=32)
+    ap.add_argument('--num_test', type=int, default=16)
+    ap.add_argument('--epochs', type=int, default=20)
+    ap.add_argument('--batch_size', type=int, default=1, help='model batch of the evaluation (1: the latency the reference times)')
+    ap.add_argument('--state', default=None, help='state_dict to load instead of training')
+    a = ap.parse_args()
+    dims = [a.mesh] * a.dim
+    opt = hot_path_opt(mesh_dims=dims, hidden_dim=8, num_layers=4, batch_size=8, device='cuda:0', lr=1e-2, loss_type='mesh_loss',
+                       solver='torch_FEM', evaler='analytical', eval_quad_points=101, load_quad_points=101)
+    test = MeshDataset(dims, a.num_test, seed=1, target='mmpde5')
+    torch.manual_seed(0)
+    model = GNN(test, opt).to(opt['device'])
+    if a.state:
+        model.load_state_dict(torch.load(a.state, map_location=opt['device']))
+    else:
+        train_briefly(model, MeshDataset(dims, a.num_train, seed=0, target='mmpde5'), opt, a.epochs)
+    eval_grid_MMPDE_MA(test, opt)                  # grid and target errors once; further checkpoints reuse them
+    df, df_time = evaluate_model_fine(model, test, opt, batch_size=a.batch_size)
+    print(describe(df))
+    print(describe(df_time))

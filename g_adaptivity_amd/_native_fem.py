@@ -12,7 +12,7 @@ from ._native import NativeError
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgadapt_fem.so')
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 META = 8                                   # GADAPT_FEM_META
 M_N_INT, M_BAND = 5, 6                     # GADAPT_FEM_M_N_INT, GADAPT_FEM_M_BAND
 LOSS_MSE, LOSS_SIMPSON = 0, 1              # GADAPT_FEM_LOSS_MSE, GADAPT_FEM_LOSS_SIMPSON
@@ -29,12 +29,15 @@ PROTOTYPES = {
     'gadapt_fem_factor_lds_bytes': (_L, [_I, _I]),
     'gadapt_fem_eval_lds_bytes': (_L, [_I]),
     'gadapt_fem_forward': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 5),
+    'gadapt_fem_eval_partials_floats': (_I, [_I]),
+    'gadapt_fem_eval_errors': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 6),
     'gadapt_fem_modular_forward': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I, _I] + [_P] * 7),
     'gadapt_fem_backward': (_I, [_I, _I, _I] + [_P] * 13 + [_I, _I] + [_P] * 9),
     'gadapt_fem1d_lds_bytes': (_L, [_I, _I]),
     'gadapt_fem1d_burgers_forward': (_I, [_I, _I] + [_P] * 6 + [_F] * 3 + [_I] * 7 + [_P] * 6),
     'gadapt_fem1d_burgers_backward': (_I, [_I, _I, _P, _P, _P, _F, _F, _I, _I, _I, _I] + [_P] * 7),
     'gadapt_fem1d_poisson_forward': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P] * 5),
+    'gadapt_fem1d_poisson_eval_errors': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P] * 4),
     'gadapt_fem1d_poisson_backward': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P] * 6),
     'gadapt_fem1d_expand': (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P]),
 }

@@ -642,39 +642,141 @@ __device__ inline void poisson_matrix(const W1& w, float& al, float& ad, float& 
     __syncthreads();
 }
 
+// The stiffness trapezoids of stiff_rows per interval in fp64: off (A[i][i+1]), dl and dr (the interval's shares of the
+// diagonals of its left and right node).
+__device__ inline void stiff_intervals64(const float* m, int n, int k, double* off, double* dl, double* dr) {
+    const int t = threadIdx.x;
+    if (t < n - 1) {
+        const double a = m[t], d = (double)m[t + 1] - (double)m[t];
+        const double L = 1.0 / d, R = -L, lr = L * R, ll = L * L, rr = R * R;
+        double o = 0, l = 0, r = 0, xp = a;
+        for (int j = 1; j <= k; ++j) {
+            const double x = a + ((double)j * d) / (double)k, dx = x - xp;
+            o += dx * (lr + lr); l += dx * (ll + ll); r += dx * (rr + rr);
+            xp = x;
+        }
+        off[t] = o / 2.0; dl[t] = l / 2.0; dr[t] = r / 2.0;
+    }
+    __syncthreads();
+}
+
+// Thomas in fp64 on rows 1..n-2 of -A assembled from stiff_intervals64 (l_i = -off[i-1], d_i = -(dl[i-1] + dr[i]),
+// u_i = -off[i]), right-hand side r[i] plus the boundary terms bc1 off[0] (row 1) and off[n-2] bc2 (row n-2); r[1..n-2] gets
+// the solution.  By one lane.
+__device__ inline void thomas64_poisson(const double* off, const double* dl, const double* dr, float* r, double bc1, double bc2,
+                                        double* cp, double* rr, int n) {
+    const int lo = 1, hi = n - 1;
+    for (int i = lo; i < hi; ++i) rr[i] = r[i];
+    rr[lo] += bc1 * off[0];
+    rr[hi - 1] += off[n - 2] * bc2;
+    double den = -(dl[lo - 1] + dr[lo]);
+    cp[lo] = (lo + 1 < hi ? -off[lo] : 0.0) / den;
+    rr[lo] = rr[lo] / den;
+    for (int i = lo + 1; i < hi; ++i) {
+        const double li = -off[i - 1];
+        den = -(dl[i - 1] + dr[i]) - li * cp[i - 1];
+        cp[i] = (i + 1 < hi ? -off[i] : 0.0) / den;
+        rr[i] = (rr[i] - li * rr[i - 1]) / den;
+    }
+    r[hi - 1] = (float)rr[hi - 1];
+    for (int i = hi - 2; i >= lo; --i) {
+        rr[i] = rr[i] - cp[i] * rr[i + 1];
+        r[i] = (float)rr[i];
+    }
+}
+
+// torch_FEM_1D's solve of mesh b by its workgroup: the working set on the launch's LDS, coefficients (BC1, interior, BC2) in w.r.
+// STIFF64 = false is the forward of fem_poisson_1d: the stiffness matrix in fp32 as the reference assembles it.  Its diagonal
+// fl(dl + dr) leaves row sums of an ulp of 2/h, and the solve answers them with coefficient errors of a few 1e-6 of either
+// sign (the reference's own fp32 solve has them as well, elsewhere): up to 3e-4 of an error norm, where e = sol - u_true is
+// ~1e-3 of sol.  An evaluation reports that norm, so STIFF64 = true assembles the same trapezoids in fp64 (coefficients within
+// 1e-7 of an fp64 solve); the load vector, boundary values and expansion stay in fp32.
+template <bool STIFF64>
+__device__ inline W1 poisson_solve(float* L, int b, const int32_t* __restrict__ node_off, const float* __restrict__ x,
+                                   const int32_t* __restrict__ gptr, const float* __restrict__ gpar, int k_load, int k_stiff, int nmax,
+                                   int32_t* __restrict__ flags) {
+    const int t = threadIdx.x;
+    const int off = node_off[b], n = node_off[b + 1] - off, g0 = gptr[b], g1 = gptr[b + 1];
+    W1 w{L, L + nmax, L + 2 * nmax, L + 3 * nmax, L + 4 * nmax, L + 5 * nmax, L + 6 * nmax, L + 7 * nmax, L + 8 * nmax,
+         L + 9 * nmax, L + 10 * nmax, n};
+    load_mesh(w, x, off, 0);
+    const int bad = not_increasing(w);
+    if (t == 0) flags[b] = bad ? GADAPT_FEM1D_F_NOT_INCREASING : 0;
+    double* d64 = reinterpret_cast<double*>(L + 12 * nmax);
+    if constexpr (STIFF64) {
+        const float rhs = load_row(w, k_load, [&](float xq) { return forcing(xq, gpar, g0, g1, nullptr); });   // uses t0, t1
+        const float bc1 = gauss(w.m[0], gpar, g0, g1), bc2 = gauss(w.m[n - 1], gpar, g0, g1);
+        if (t < n) w.r[t] = rhs;
+        // three fp64 rows over the six fp32 rows Sl..t2 (byte offsets 16, 24, 32 nmax: 8-aligned for any nmax)
+        double *o64 = reinterpret_cast<double*>(L + 4 * nmax), *l64 = o64 + nmax, *r64 = o64 + 2 * nmax;
+        stiff_intervals64(w.m, n, k_stiff, o64, l64, r64);
+        if (t == 0) {
+            thomas64_poisson(o64, l64, r64, w.r, bc1, bc2, d64, d64 + nmax, n);
+            w.r[0] = bc1;
+            w.r[n - 1] = bc2;
+        }
+    } else {
+        float al, ad, au;
+        stiff_rows(w, k_stiff, al, ad, au);
+        const float off0 = w.t0[0], offl = w.t0[n - 2];   // A[0][1], A[n-1][n-2]
+        __syncthreads();
+        poisson_matrix(w, al, ad, au);
+        const float rhs = load_row(w, k_load, [&](float xq) { return forcing(xq, gpar, g0, g1, nullptr); });
+        const float bc1 = gauss(w.m[0], gpar, g0, g1), bc2 = gauss(w.m[n - 1], gpar, g0, g1);
+        if (t < n) w.r[t] = rhs;
+        __syncthreads();
+        if (t == 0) {
+            w.r[1] = w.r[1] + bc1 * off0;
+            w.r[n - 2] = w.r[n - 2] + offl * bc2;
+            thomas64(w.Sl, w.Sd, w.Su, w.r, d64, d64 + nmax, 1, n - 1, false);
+            w.r[0] = bc1;
+            w.r[n - 1] = bc2;
+        }
+    }
+    __syncthreads();
+    return w;
+}
+
 __global__ void __launch_bounds__(F1_THREADS) poisson_fwd_kernel(
     const int32_t* __restrict__ node_off, const float* __restrict__ x, const int32_t* __restrict__ gptr, const float* __restrict__ gpar,
     int k_load, int k_stiff, int nmax, int P, const float* __restrict__ pts, float* __restrict__ coeffs, float* __restrict__ sol,
     int32_t* __restrict__ flags) {
     extern __shared__ float lds[];
     const int b = blockIdx.x, t = threadIdx.x;
-    const int off = node_off[b], n = node_off[b + 1] - off, g0 = gptr[b], g1 = gptr[b + 1];
-    float* L = lds;
-    W1 w{L, L + nmax, L + 2 * nmax, L + 3 * nmax, L + 4 * nmax, L + 5 * nmax, L + 6 * nmax, L + 7 * nmax, L + 8 * nmax,
-         L + 9 * nmax, L + 10 * nmax, n};
-    load_mesh(w, x, off, 0);
-    const int bad = not_increasing(w);
-    if (t == 0) flags[b] = bad ? GADAPT_FEM1D_F_NOT_INCREASING : 0;
-    float al, ad, au;
-    stiff_rows(w, k_stiff, al, ad, au);
-    const float off0 = w.t0[0], offl = w.t0[n - 2];   // A[0][1], A[n-1][n-2]
-    __syncthreads();
-    poisson_matrix(w, al, ad, au);
-    const float rhs = load_row(w, k_load, [&](float xq) { return forcing(xq, gpar, g0, g1, nullptr); });
-    const float bc1 = gauss(w.m[0], gpar, g0, g1), bc2 = gauss(w.m[n - 1], gpar, g0, g1);
-    if (t < n) w.r[t] = rhs;
-    __syncthreads();
-    if (t == 0) {
-        w.r[1] = w.r[1] + bc1 * off0;
-        w.r[n - 2] = w.r[n - 2] + offl * bc2;
-        double* d64 = reinterpret_cast<double*>(L + 12 * nmax);
-        thomas64(w.Sl, w.Sd, w.Su, w.r, d64, d64 + nmax, 1, n - 1, false);
-        w.r[0] = bc1;
-        w.r[n - 1] = bc2;
-    }
-    __syncthreads();
-    if (t < n) coeffs[off + t] = w.r[t];
+    const W1 w = poisson_solve<false>(lds, b, node_off, x, gptr, gpar, k_load, k_stiff, nmax, flags);
+    if (t < w.n) coeffs[node_off[b] + t] = w.r[t];
     evaluate(w, w.r, P, pts, sol + (size_t)b * P);
+}
+
+// The Poisson forward (stiffness in fp64: poisson_solve) with the reference's trapezium norms of e = sol - u_true over pts
+// (evaluate_error_np) reduced in the same launch: L1 = sum_j (|e_j| + |e_j+1|) (p_j+1 - p_j) / 2, L2 = sqrt of the same sum of squares.  The first wave
+// reduces: lane l takes intervals l, l + 64, ... in order and the lanes are added in a fixed butterfly, so the order does not
+// depend on the workgroup's size (which follows the largest mesh of the batch).
+__global__ void __launch_bounds__(F1_THREADS) poisson_err_kernel(
+    const int32_t* __restrict__ node_off, const float* __restrict__ x, const int32_t* __restrict__ gptr, const float* __restrict__ gpar,
+    int k_load, int k_stiff, int nmax, int P, const float* __restrict__ pts, float* __restrict__ err, int32_t* __restrict__ flags) {
+    extern __shared__ float lds[];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const W1 w = poisson_solve<true>(lds, b, node_off, x, gptr, gpar, k_load, k_stiff, nmax, flags);
+    const int g0 = gptr[b], g1 = gptr[b + 1];
+    if (t >= 64) return;                              // no barrier below: the first wave reduces, whatever the workgroup's size
+    float s1 = 0.0f, s2 = 0.0f;
+    for (int j = t; j + 1 < P; j += 64) {
+        const float p0 = pts[j], p1 = pts[j + 1];
+        const float e0 = expand(w.m, w.r, w.n, p0, locate(w.m, w.n, p0)) - gauss(p0, gpar, g0, g1);
+        const float e1 = expand(w.m, w.r, w.n, p1, locate(w.m, w.n, p1)) - gauss(p1, gpar, g0, g1);
+        const float dx = p1 - p0;
+        s1 = s1 + (fabsf(e1) + fabsf(e0)) * dx;
+        s2 = s2 + (e1 * e1 + e0 * e0) * dx;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 = s1 + __shfl_xor(s1, o, 64);
+        s2 = s2 + __shfl_xor(s2, o, 64);
+    }
+    if (t == 0) {
+        err[2 * b] = s1 / 2.0f;
+        err[2 * b + 1] = sqrtf(s2 / 2.0f);
+    }
 }
 
 __global__ void __launch_bounds__(F1_THREADS) poisson_bwd_kernel(
@@ -846,6 +948,22 @@ extern "C" int gadapt_fem1d_poisson_forward(int B, int nmax, const int32_t* node
     if ((rc = check_lds(lds, "gadapt_fem1d_poisson_forward"))) return rc;
     poisson_fwd_kernel<<<B, threads_for(nmax), (size_t)lds, (hipStream_t)stream>>>(node_off, x, gptr, gpar, k_load, k_stiff, nmax, P, pts,
                                                                                    coeffs, sol, flags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
+    return GADAPT_FEM_OK;
+}
+
+extern "C" int gadapt_fem1d_poisson_eval_errors(int B, int nmax, const int32_t* node_off, const float* x, const int32_t* gptr,
+                                                const float* gpar, int k_load, int k_stiff, int P, const float* pts, float* err,
+                                                int32_t* flags, void* stream) {
+    int rc = check_common(B, nmax, 3, node_off, x, P, pts, k_load, k_stiff, "gadapt_fem1d_poisson_eval_errors");
+    if (rc) return rc;
+    if (!gptr || !gpar || !err || !flags || P < 2)
+        return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_poisson_eval_errors: null pointer or fewer than 2 evaluation points");
+    const int64_t lds = poisson_lds_bytes(nmax);
+    if ((rc = check_lds(lds, "gadapt_fem1d_poisson_eval_errors"))) return rc;
+    poisson_err_kernel<<<B, threads_for(nmax), (size_t)lds, (hipStream_t)stream>>>(node_off, x, gptr, gpar, k_load, k_stiff, nmax, P, pts,
+                                                                                   err, flags);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
     return GADAPT_FEM_OK;

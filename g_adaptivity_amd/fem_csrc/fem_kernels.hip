@@ -1,7 +1,8 @@
 // fem_kernels.hip - differentiable P1 FEM tail of loss_type='pde_loss' for gfx950 (include/gadapt_fem.h).
 //
 // Forward (three launches): load vector, banded Cholesky solve (one wave per mesh, band in LDS), evaluation on the lattice;
-// the modular loss adds a fourth, the per-mesh lattice loss and its derivative.
+// the modular loss adds a fourth, the per-mesh lattice loss and its derivative.  The error norms of an evaluation
+// (gadapt_fem_eval_errors) fuse the lattice evaluation with their reduction: sol is never written.
 // Backward (four launches): d L / d c from the evaluation, adjoint solve on the kept factor, per-triangle chain rule
 // (stiffness, load vector, evaluation), per-node gather.  Every sum runs in a fixed order: results are bit-reproducible.
 #include <stdio.h>
@@ -209,6 +210,7 @@ __global__ void __launch_bounds__(FEM_SOLVE_THREADS) fem_factor_kernel(const int
     band_factor(A, pairs, n, w);
     band_solve(A, bv, n, w);
     for (int r = lane; r < n; r += FEM_SOLVE_THREADS) coeffs[int_node[io + r]] = bv[r];
+    if (!lfac) return;                                             // an evaluation keeps no factor: nothing differentiates through it
     float* out = lfac + mt[GADAPT_FEM_M_BAND_OFF];
     for (int i = lane; i < n * ld; i += FEM_SOLVE_THREADS) out[i] = A[i];
 }
@@ -237,7 +239,61 @@ __global__ void __launch_bounds__(FEM_SOLVE_THREADS) fem_adjoint_kernel(const in
 #define FEM_EVAL_THREADS 256
 #define FEM_EVAL_CHUNKS 8
 
+// the lattice's square and the scale from a coordinate to its bin
+struct EvalFrame {
+    float lox, hix, loy, hiy, scx, scy;
+};
+
+__device__ inline EvalFrame eval_frame(const float* __restrict__ lat_x, const float* __restrict__ lat_y, int nlat) {
+    EvalFrame f{lat_x[0], lat_x[nlat - 1], lat_y[0], lat_y[nlat - 1], 0.0f, 0.0f};
+    f.scx = (float)FEM_NB / (f.hix - f.lox);
+    f.scy = (float)FEM_NB / (f.hiy - f.loy);
+    return f;
+}
+
+// the bin mask of mesh triangles [t0, t0 + nt) in LDS (W words per bin), by the whole workgroup; ends with a barrier
+__device__ inline void build_bin_mask(uint32_t* mask, int W, int t0, int nt, const EvalFrame& f, const int32_t* __restrict__ cells,
+                                      const float* __restrict__ x) {
+    for (int i = threadIdx.x; i < FEM_NB * FEM_NB * W; i += blockDim.x) mask[i] = 0u;
+    __syncthreads();
+    for (int t = threadIdx.x; t < nt; t += blockDim.x) {
+        const V2 p0 = ld2(x, cells[3 * (t0 + t)]), p1 = ld2(x, cells[3 * (t0 + t) + 1]), p2 = ld2(x, cells[3 * (t0 + t) + 2]);
+        const int bx0 = max(bin_of(fminf(fminf(p0.x, p1.x), p2.x), f.lox, f.scx) - 1, 0);
+        const int bx1 = min(bin_of(fmaxf(fmaxf(p0.x, p1.x), p2.x), f.lox, f.scx) + 1, FEM_NB - 1);
+        const int by0 = max(bin_of(fminf(fminf(p0.y, p1.y), p2.y), f.loy, f.scy) - 1, 0);
+        const int by1 = min(bin_of(fmaxf(fmaxf(p0.y, p1.y), p2.y), f.loy, f.scy) + 1, FEM_NB - 1);
+        for (int bx = bx0; bx <= bx1; ++bx)
+            for (int by = by0; by <= by1; ++by) atomicOr(&mask[(bx * FEM_NB + by) * W + (t >> 5)], 1u << (t & 31));
+    }
+    __syncthreads();
+}
+
 // sol(p) = sum over triangles T containing p, over their vertices v: c_v aux_T(p; v) / repeat(p, v)  (difFEM_2d.py:312-318)
+__device__ inline float eval_point(float px, float py, const uint32_t* mask, int W, int t0, const EvalFrame& f,
+                                   const int32_t* __restrict__ cells, const int32_t* __restrict__ nt_ptr,
+                                   const int32_t* __restrict__ nt_idx, const float* __restrict__ x, const float* __restrict__ coeffs) {
+    const uint32_t* bm = mask + (bin_of(px, f.lox, f.scx) * FEM_NB + bin_of(py, f.loy, f.scy)) * W;
+    float acc = 0.0f;
+    for (int wd = 0; wd < W; ++wd) {
+        uint32_t bits = bm[wd];
+        while (bits) {
+            const int t = t0 + wd * 32 + __builtin_ctz(bits);
+            bits &= bits - 1;
+            const float ind = fem::inside(px, py, ld2(x, cells[3 * t + 2]), ld2(x, cells[3 * t + 1]), ld2(x, cells[3 * t]));
+            if (ind == 0.0f) continue;
+            for (int l = 0; l < 3; ++l) {
+                int va, vb, vc;
+                fem::rotation(cells, t, l, va, vb, vc);
+                const float inc = fem::aux_value(px, py, ld2(x, va), ld2(x, vb), ld2(x, vc), ind);
+                if (inc == 0.0f) continue;
+                const float div = fem::phim_parts(px, py, vc, nt_ptr, nt_idx, cells, x, nullptr);
+                acc += coeffs[vc] * (inc / div);
+            }
+        }
+    }
+    return acc;
+}
+
 __global__ void __launch_bounds__(FEM_EVAL_THREADS) fem_eval_kernel(const int32_t* __restrict__ meta, const int32_t* __restrict__ cells,
                                                                     const int32_t* __restrict__ nt_ptr, const int32_t* __restrict__ nt_idx,
                                                                     const float* __restrict__ x, const float* __restrict__ coeffs,
@@ -247,45 +303,82 @@ __global__ void __launch_bounds__(FEM_EVAL_THREADS) fem_eval_kernel(const int32_
     const int32_t* mt = meta + blockIdx.x * GADAPT_FEM_META;
     const int t0 = mt[GADAPT_FEM_M_TRI_OFF], nt = mt[GADAPT_FEM_M_N_TRIS];
     const int W = (int)eval_words(nt);
-    const float lox = lat_x[0], hix = lat_x[nlat - 1], loy = lat_y[0], hiy = lat_y[nlat - 1];
-    const float scx = (float)FEM_NB / (hix - lox), scy = (float)FEM_NB / (hiy - loy);
-    for (int i = threadIdx.x; i < FEM_NB * FEM_NB * W; i += FEM_EVAL_THREADS) mask[i] = 0u;
-    __syncthreads();
-    for (int t = threadIdx.x; t < nt; t += FEM_EVAL_THREADS) {
-        const V2 p0 = ld2(x, cells[3 * (t0 + t)]), p1 = ld2(x, cells[3 * (t0 + t) + 1]), p2 = ld2(x, cells[3 * (t0 + t) + 2]);
-        const int bx0 = max(bin_of(fminf(fminf(p0.x, p1.x), p2.x), lox, scx) - 1, 0);
-        const int bx1 = min(bin_of(fmaxf(fmaxf(p0.x, p1.x), p2.x), lox, scx) + 1, FEM_NB - 1);
-        const int by0 = max(bin_of(fminf(fminf(p0.y, p1.y), p2.y), loy, scy) - 1, 0);
-        const int by1 = min(bin_of(fmaxf(fmaxf(p0.y, p1.y), p2.y), loy, scy) + 1, FEM_NB - 1);
-        for (int bx = bx0; bx <= bx1; ++bx)
-            for (int by = by0; by <= by1; ++by) atomicOr(&mask[(bx * FEM_NB + by) * W + (t >> 5)], 1u << (t & 31));
-    }
-    __syncthreads();
+    const EvalFrame f = eval_frame(lat_x, lat_y, nlat);
+    build_bin_mask(mask, W, t0, nt, f, cells, x);
     const int Q = nlat * nlat;
     const int q0 = (int)((int64_t)Q * blockIdx.y / gridDim.y), q1 = (int)((int64_t)Q * (blockIdx.y + 1) / gridDim.y);
+    for (int q = q0 + threadIdx.x; q < q1; q += FEM_EVAL_THREADS)
+        sol[(int64_t)blockIdx.x * Q + q] = eval_point(lat_x[q / nlat], lat_y[q % nlat], mask, W, t0, f, cells, nt_ptr, nt_idx, x, coeffs);
+}
+
+// ---------------------------------------------------------------------------------------------------- error norms
+// The evaluation fused with the trapezium L1 / L2 norms of e = sol - u_true on the lattice (the reference's
+// evaluate_error_np_2d: every cell gives dx dy / 4 to each of its corners, so a lattice point weighs h_x h_y times 1, 1/2 or
+// 1/4 inside, on an edge, at a corner).  sol never reaches memory.  Each lane sums its points in increasing index, a wave
+// adds its lanes in a fixed butterfly, lane 0 adds the waves in order through LDS and writes the chunk's pair of partial
+// sums; fem_err_finish_kernel adds a mesh's chunks in order.  No float atomics: a mesh's result is the same in any batch.
+__device__ inline float wave_sum(float v) {
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(FEM_EVAL_THREADS) fem_eval_err_kernel(const int32_t* __restrict__ meta, const int32_t* __restrict__ cells,
+                                                                        const int32_t* __restrict__ nt_ptr, const int32_t* __restrict__ nt_idx,
+                                                                        const int32_t* __restrict__ gptr, const float* __restrict__ gpar,
+                                                                        const float* __restrict__ x, const float* __restrict__ coeffs,
+                                                                        const float* __restrict__ lat_x, const float* __restrict__ lat_y,
+                                                                        int nlat, float* __restrict__ partials) {
+    extern __shared__ uint32_t mask[];
+    const int b = blockIdx.x;
+    const int32_t* mt = meta + b * GADAPT_FEM_META;
+    const int t0 = mt[GADAPT_FEM_M_TRI_OFF], nt = mt[GADAPT_FEM_M_N_TRIS];
+    const int W = (int)eval_words(nt);
+    const int g0 = gptr[b], g1 = gptr[b + 1];
+    const EvalFrame f = eval_frame(lat_x, lat_y, nlat);
+    build_bin_mask(mask, W, t0, nt, f, cells, x);
+    const int Q = nlat * nlat;
+    const int q0 = (int)((int64_t)Q * blockIdx.y / gridDim.y), q1 = (int)((int64_t)Q * (blockIdx.y + 1) / gridDim.y);
+    float s1 = 0.0f, s2 = 0.0f;
     for (int q = q0 + threadIdx.x; q < q1; q += FEM_EVAL_THREADS) {
-        const float px = lat_x[q / nlat], py = lat_y[q % nlat];
-        const uint32_t* bm = mask + (bin_of(px, lox, scx) * FEM_NB + bin_of(py, loy, scy)) * W;
-        float acc = 0.0f;
-        for (int wd = 0; wd < W; ++wd) {
-            uint32_t bits = bm[wd];
-            while (bits) {
-                const int t = t0 + wd * 32 + __builtin_ctz(bits);
-                bits &= bits - 1;
-                const float ind = fem::inside(px, py, ld2(x, cells[3 * t + 2]), ld2(x, cells[3 * t + 1]), ld2(x, cells[3 * t]));
-                if (ind == 0.0f) continue;
-                for (int l = 0; l < 3; ++l) {
-                    int va, vb, vc;
-                    fem::rotation(cells, t, l, va, vb, vc);
-                    const float inc = fem::aux_value(px, py, ld2(x, va), ld2(x, vb), ld2(x, vc), ind);
-                    if (inc == 0.0f) continue;
-                    const float div = fem::phim_parts(px, py, vc, nt_ptr, nt_idx, cells, x, nullptr);
-                    acc += coeffs[vc] * (inc / div);
-                }
-            }
-        }
-        sol[(int64_t)blockIdx.x * Q + q] = acc;
+        const int i = q / nlat, j = q % nlat;
+        const float px = lat_x[i], py = lat_y[j];
+        const float e = eval_point(px, py, mask, W, t0, f, cells, nt_ptr, nt_idx, x, coeffs) - fem::u_true(px, py, gpar, g0, g1);
+        const float w = ((i == 0 || i == nlat - 1) ? 0.5f : 1.0f) * ((j == 0 || j == nlat - 1) ? 0.5f : 1.0f);
+        s1 = s1 + w * fabsf(e);
+        s2 = s2 + w * (e * e);
     }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    __syncthreads();                                               // every lane is done with the mask: its first words carry the wave sums
+    float* red = reinterpret_cast<float*>(mask);
+    constexpr int waves = FEM_EVAL_THREADS / 64;
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = s1;
+        red[waves + (threadIdx.x >> 6)] = s2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float a1 = red[0], a2 = red[waves];
+        for (int k = 1; k < waves; ++k) { a1 = a1 + red[k]; a2 = a2 + red[waves + k]; }
+        float* out = partials + ((int64_t)b * gridDim.y + blockIdx.y) * 2;
+        out[0] = a1;
+        out[1] = a2;
+    }
+}
+
+__global__ void __launch_bounds__(256) fem_err_finish_kernel(int n_meshes, int chunks, const float* __restrict__ lat_x,
+                                                             const float* __restrict__ lat_y, int nlat, const float* __restrict__ partials,
+                                                             float* __restrict__ err) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= n_meshes) return;
+    const float hx = (lat_x[nlat - 1] - lat_x[0]) / (float)(nlat - 1), hy = (lat_y[nlat - 1] - lat_y[0]) / (float)(nlat - 1);
+    float a1 = 0.0f, a2 = 0.0f;
+    for (int k = 0; k < chunks; ++k) {
+        a1 = a1 + partials[((int64_t)b * chunks + k) * 2];
+        a2 = a2 + partials[((int64_t)b * chunks + k) * 2 + 1];
+    }
+    err[2 * b] = (hx * hy) * a1;
+    err[2 * b + 1] = sqrtf((hx * hy) * a2);
 }
 
 // ---------------------------------------------------------------------------------------------------- lattice loss
@@ -511,26 +604,74 @@ static int check_lds(int max_lds_bytes) {
     return GADAPT_FEM_OK;
 }
 
+// everything gadapt_fem_forward and gadapt_fem_eval_errors check alike, before anything is launched
+static int check_solve_args(const char* who, int B, int N, int T, const void* meta, const void* cells, const void* node_mesh, const void* int_idx,
+                            const void* int_node, const void* nt_ptr, const void* nt_idx, const void* gptr, const void* gpar, const void* x,
+                            const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris, const void* rhs,
+                            const void* coeffs, int64_t* eval_lds) {
+    if (B <= 0 || N <= 0 || T <= 0 || !meta || !cells || !node_mesh || !int_idx || !int_node || !nt_ptr || !nt_idx || !gptr || !gpar || !x ||
+        !rhs || !coeffs || max_tris <= 0) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "%s: null pointer or bad size", who);
+        return fail(GADAPT_FEM_E_BADARG, msg);
+    }
+    int rc = check_lat(lat_x, lat_y, nlat);
+    if (rc) return rc;
+    if ((rc = check_lds(max_lds_bytes))) return rc;
+    *eval_lds = gadapt_fem_eval_lds_bytes(max_tris);
+    if (*eval_lds > GADAPT_FEM_LDS_BUDGET) return fail(GADAPT_FEM_E_LDS, "evaluation: triangle bin mask exceeds the LDS budget");
+    return GADAPT_FEM_OK;
+}
+
+// load vector and banded Cholesky solve -> coeffs (lfac may be NULL: the factor is not kept)
+static int launch_solve(int B, int N, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh, const int32_t* int_idx,
+                        const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx, const int32_t* gptr, const float* gpar,
+                        const float* x, int max_lds_bytes, float* rhs, float* coeffs, float* lfac, hipStream_t s) {
+    fem_rhs_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, cells, node_mesh, int_idx, nt_ptr, nt_idx, gptr, gpar, x, rhs);
+    int rc = launched("fem_rhs_kernel");
+    if (rc) return rc;
+    fem_factor_kernel<<<B, FEM_SOLVE_THREADS, max_lds_bytes, s>>>(meta, cells, int_idx, int_node, nt_ptr, nt_idx, x, rhs, coeffs, lfac);
+    return launched("fem_factor_kernel");
+}
+
 extern "C" int gadapt_fem_forward(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
                                   const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
                                   const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
                                   int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* sol, void* stream) {
-    if (B <= 0 || N <= 0 || T <= 0 || !meta || !cells || !node_mesh || !int_idx || !int_node || !nt_ptr || !nt_idx || !gptr || !gpar || !x ||
-        !rhs || !coeffs || !lfac || !sol || max_tris <= 0)
-        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_forward: null pointer or bad size");
-    int rc = check_lat(lat_x, lat_y, nlat);
+    int64_t eval_lds = 0;
+    int rc = check_solve_args("gadapt_fem_forward", B, N, T, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x,
+                              lat_y, nlat, max_lds_bytes, max_tris, rhs, coeffs, &eval_lds);
     if (rc) return rc;
-    if ((rc = check_lds(max_lds_bytes))) return rc;
-    const int64_t eval_lds = gadapt_fem_eval_lds_bytes(max_tris);
-    if (eval_lds > GADAPT_FEM_LDS_BUDGET) return fail(GADAPT_FEM_E_LDS, "evaluation: triangle bin mask exceeds the LDS budget");
+    if (!lfac || !sol) return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_forward: null pointer or bad size");
     hipStream_t s = (hipStream_t)stream;
-    fem_rhs_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, cells, node_mesh, int_idx, nt_ptr, nt_idx, gptr, gpar, x, rhs);
-    if ((rc = launched("fem_rhs_kernel"))) return rc;
-    fem_factor_kernel<<<B, FEM_SOLVE_THREADS, max_lds_bytes, s>>>(meta, cells, int_idx, int_node, nt_ptr, nt_idx, x, rhs, coeffs, lfac);
-    if ((rc = launched("fem_factor_kernel"))) return rc;
+    if ((rc = launch_solve(B, N, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, max_lds_bytes, rhs, coeffs, lfac, s)))
+        return rc;
     fem_eval_kernel<<<dim3(B, FEM_EVAL_CHUNKS), FEM_EVAL_THREADS, (size_t)eval_lds, s>>>(meta, cells, nt_ptr, nt_idx, x, coeffs, lat_x, lat_y,
                                                                                          nlat, sol);
     return launched("fem_eval_kernel");
+}
+
+extern "C" int gadapt_fem_eval_partials_floats(int n_meshes) { return n_meshes > 0 ? n_meshes * FEM_EVAL_CHUNKS * 2 : 0; }
+
+extern "C" int gadapt_fem_eval_errors(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                      const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                                      const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
+                                      int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* partials, float* err,
+                                      void* stream) {
+    int64_t eval_lds = 0;
+    int rc = check_solve_args("gadapt_fem_eval_errors", B, N, T, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x,
+                              lat_y, nlat, max_lds_bytes, max_tris, rhs, coeffs, &eval_lds);
+    if (rc) return rc;
+    if (!partials || !err) return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_eval_errors: null pointer or bad size");
+    if (nlat > 46340) return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_eval_errors: nlat * nlat exceeds the int range");
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = launch_solve(B, N, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, max_lds_bytes, rhs, coeffs, lfac, s)))
+        return rc;
+    fem_eval_err_kernel<<<dim3(B, FEM_EVAL_CHUNKS), FEM_EVAL_THREADS, (size_t)eval_lds, s>>>(meta, cells, nt_ptr, nt_idx, gptr, gpar, x, coeffs,
+                                                                                             lat_x, lat_y, nlat, partials);
+    if ((rc = launched("fem_eval_err_kernel"))) return rc;
+    fem_err_finish_kernel<<<(B + 255) / 256, 256, 0, s>>>(B, FEM_EVAL_CHUNKS, lat_x, lat_y, nlat, partials, err);
+    return launched("fem_err_finish_kernel");
 }
 
 extern "C" int gadapt_fem_modular_forward(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,

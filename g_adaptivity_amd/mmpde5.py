@@ -273,7 +273,8 @@ def attach_mmpde5_targets(samples, monitor_params: Optional[dict] = None, **solv
     dataset builder stores it (`src/data.py:206-212`: the step count in 1-D, the count plus one in 2-D).
 
     The monitor of a sample is `monitor_1d` / `monitor_2d` of its own `pde_params` (centres and scales), with
-    `monitor_params` (`mon_power`, `mon_reg`) added.  The samples' meshes must be in grid order (`interval_mesh`,
+    `monitor_params` (`mon_power`, `mon_reg`) added.  `build_time` per sample (the reference's `data.build_time`, read by
+    `evaluate_model_fine` as MA_time) is the wall time of the batched call divided by the sample count.  The samples' meshes must be in grid order (`interval_mesh`,
     `square_mesh`): the start mesh is `x_comp`.  `solver`: keyword arguments of `mmpde5_batch`."""
     coords, monitors = [], []
     for d in samples:
@@ -288,11 +289,15 @@ def attach_mmpde5_targets(samples, monitor_params: Optional[dict] = None, **solv
                 raise ValueError(f"{d.x_comp.shape[0]} nodes: not a square grid")
             coords.append(d.x_comp.t().reshape(2, n, n))
             monitors.append(monitor_arrays_2d(lambda a, b: monitor_2d(a, b, params), n))
+    t0 = time.time()
     res = mmpde5_batch(coords, monitors, **solver)
+    steps = res.steps.tolist()                            # waits for the device: the batched call is done
+    build_time = (time.time() - t0) / max(len(samples), 1)
     warn_unconverged(res.status, 'MMPDE5 (dataset targets)')
-    for d, xy, j in zip(samples, res.coords, res.steps.tolist()):
+    for d, xy, j in zip(samples, res.coords, steps):
         if xy.dim() == 1:
             d.x_phys, d.ma_its = xy.contiguous(), j
         else:
             d.x_phys, d.ma_its = xy.reshape(2, -1).t().contiguous(), j + 1
+        d.build_time = build_time                         # seconds, the batched call's wall time shared out evenly
     return res

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define GADAPT_FEM_ABI 3
+#define GADAPT_FEM_ABI 4
 
 #define GADAPT_FEM_OK          0
 #define GADAPT_FEM_E_BADARG   -1   /* null pointer, bad size, bad lattice */
@@ -93,6 +93,22 @@ int gadapt_fem_forward(int n_meshes, int n_nodes, int n_tris, const int32_t* met
                        const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
                        const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
                        int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* sol, void* stream);
+
+/* Error norms of an evaluation (the reference's evaluate_model_fine, src/utils_eval.py:46-65), forward only, four launches:
+ * the load vector and banded Cholesky solve of gadapt_fem_forward, then the lattice evaluation fused with the trapezium
+ * norms of e = sol - u_true (u_true from each mesh's own Gaussians), then the sum of each mesh's chunk partials:
+ *   err [B,2] = (L1, L2):  L1 = sum_p w_p |e_p|,  L2 = sqrt(sum_p w_p e_p^2),
+ *   w_p = h_x h_y times 1, 1/2 or 1/4 for interior, edge and corner points (every lattice cell gives dx dy / 4 to each corner).
+ * sol is never written.  Arguments as gadapt_fem_forward without sol; lfac may be NULL (the factor is not kept).
+ * partials: caller-owned work buffer of gadapt_fem_eval_partials_floats floats, no initialisation needed.  Every sum runs in a
+ * fixed order without atomics: a mesh's pair does not depend on the rest of the batch.  Everything is checked before the first
+ * launch. */
+int gadapt_fem_eval_partials_floats(int n_meshes);
+int gadapt_fem_eval_errors(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                           const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                           const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
+                           int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* partials, float* err,
+                           void* stream);
 
 /* Lattice-loss reductions of gadapt_fem_modular_forward. */
 #define GADAPT_FEM_LOSS_MSE     0   /* mean over the nlat x nlat lattice of e^2 (F.mse_loss) */
@@ -170,6 +186,14 @@ int gadapt_fem1d_burgers_backward(int n_meshes, int max_nodes, const int32_t* no
 int gadapt_fem1d_poisson_forward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
                                  const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts, float* coeffs,
                                  float* sol, int32_t* flags, void* stream);
+
+/* Poisson forward with the reference's 1-D trapezium norms (evaluate_error_np, src/utils_eval.py:32-44) of e = sol - u_true over
+ * pts [P >= 2] reduced in the same launch: err [B,2] = (L1, L2), L1 = sum_j (|e_j| + |e_j+1|) (pts_j+1 - pts_j) / 2 and L2 the
+ * square root of the same sum over e^2; flags [B] as the forward sets them.  Neither coeffs nor sol is written.  The stiffness
+ * matrix is assembled in fp64 here (in fp32 its rounded row sums move the norms by up to 3e-4); the rest is the forward's fp32. */
+int gadapt_fem1d_poisson_eval_errors(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
+                                     const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts, float* err,
+                                     int32_t* flags, void* stream);
 
 /* Poisson backward, one launch: gx [N] from g_coeffs [N] and g_sol [B,P] (either may be NULL). */
 int gadapt_fem1d_poisson_backward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
