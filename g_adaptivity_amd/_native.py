@@ -91,6 +91,7 @@ PROTOTYPES = {
     'gadapt_profile_calibrate': (_I, [_I, _P]),
     'gadapt_debug_set_backward_inplace': (_I, [_I]),
     'gadapt_debug_set_narrow_forward': (_I, [_I]),
+    'gadapt_debug_set_narrow_backward_fused': (_I, [_I]),
     'gadapt_debug_occupancy': (_I, [_I, C.POINTER(C.c_int)]),
 }
 

@@ -603,9 +603,16 @@ __global__ __launch_bounds__(Cfg<C>::NT, (C >= GADAPT_ONE_WAVE_C ? 1 : GADAPT_WA
 // partials it owes the source pass what grand_bwd_target_kernel<64, 0, ., true> (D4) writes: the per-edge pair {alpha dt, ds} in
 // source order (through tpos) and dxd[i][0..3] = (1 - dt) g_i[0..3] + sum_o dP_i[o] A[o][0..3].  g_in is [N,4], or the compact
 // [N,g_cols] top gradient (g_cols > 0).
-template <int SUMS, bool ELL, bool NARROW>
-__device__ __forceinline__ void bwd_target_compact_body(const BwdTArgs& p) {
+//
+// SRC (gadapt_narrow_bwd.inc: the fused narrow backward): where g_i comes from.  NoFusedSource: from p.g_in.  A fused source computes it
+// in this lane - the source pass of the layer ABOVE on the same node - and its loads ride in this pass's two round trips: issue1() goes
+// out with the row bounds, the ELL row and x_i, issue2() with the alpha entries and the neighbour rows (both unconditional here, ahead
+// of the degree branch), finish() returns g_i before the first use.
+struct NoFusedSource { static constexpr bool FUSED = false; struct Regs {}; };
+template <int SUMS, bool ELL, bool NARROW, class SRC = NoFusedSource>
+__device__ __forceinline__ void bwd_target_compact_body(const BwdTArgs& p, const SRC& src = SRC()) {
     static_assert(!NARROW || (SUMS == 0 && ELL), "narrow route: fixed steps and temperature, ELL graphs");
+    static_assert(!SRC::FUSED || (SUMS == 0 && ELL), "fused source pass: the narrow route");
     __shared__ float red[4][24];
     const int C = p.c;
     const int gs = p.g_stride;                                  // floats between g rows: C, or 4 when the layer above ran the D4 / source4 pair
@@ -628,19 +635,23 @@ __device__ __forceinline__ void bwd_target_compact_body(const BwdTArgs& p) {
     const int e_own = tid < 16 ? (tid >> 2) * C + (tid & 3) : C * C + (min(tid, 19) - 16);
     const float row_old = __builtin_nontemporal_load(row + e_own);
     for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < p.n_nodes; i += (int64_t)gridDim.x * 256) {
-        const float4 g4 = (NARROW && p.g_cols) ? ld_row4_compact(p.g_in, (int)i, 0, p.g_cols) : *reinterpret_cast<const float4*>(p.g_in + (size_t)i * gs);
+        float4 g4 = f4zero();
+        if constexpr (!SRC::FUSED)
+            g4 = (NARROW && p.g_cols) ? ld_row4_compact(p.g_in, (int)i, 0, p.g_cols) : *reinterpret_cast<const float4*>(p.g_in + (size_t)i * gs);
         const float4 xi = *reinterpret_cast<const float4*>(p.x_in + 4 * (size_t)i);
-        const float4 dm = SUMS ? g4 : make_float4(dt * g4.x, dt * g4.y, dt * g4.z, dt * g4.w);
         const int e0 = p.rowptr[i], e1 = p.rowptr[i + 1], deg = e1 - e0;
         int4 el0 = make_int4(0, 0, 0, 0), el1 = el0;
         if constexpr (ELL) { el0 = *reinterpret_cast<const int4*>(p.ell + 8 * (size_t)i); el1 = *reinterpret_cast<const int4*>(p.ell + 8 * (size_t)i + 4); }
-        float D = 0.f;
-        float4 dP = f4zero();
-        if (deg <= 8 && p.n_edges > 0) {                          // (an edgeless graph has no col / alpha entry to clamp to)
-            // the usual case, three memory round trips per node: (g row head, x row, row bounds) -> (8 column / alpha pairs,
-            // unconditional with clamped indices) -> (8 neighbour rows); a loop over the row would chain them per edge.  (ELL: two.)
+        [[maybe_unused]] typename SRC::Regs sr;
+        if constexpr (SRC::FUSED) {
+            src.issue1(sr, i);
+            __builtin_amdgcn_sched_barrier(0);                    // every load of the first trip is out before anything waits for one
+        }
+        int cj[8], tp[8]; float ak[8];
+        float4 xk[8];
+        // second round trip: 8 column / alpha pairs (and the neighbour rows: ELL), unconditional with clamped indices
+        auto issue2 = [&]() __attribute__((always_inline)) {
             const int last = max(p.n_edges - 1, 0);
-            int cj[8], tp[8]; float ak[8];
             const int ej[8] = {el0.x, el0.y, el0.z, el0.w, el1.x, el1.y, el1.z, el1.w};
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -649,9 +660,24 @@ __device__ __forceinline__ void bwd_target_compact_body(const BwdTArgs& p) {
                 ak[k] = p.alpha[e];
                 if constexpr (NARROW) tp[k] = p.tpos[e];
             }
-            float4 xk[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) xk[k] = *reinterpret_cast<const float4*>(p.x_in + 4 * (size_t)cj[k]);
+        };
+        if constexpr (SRC::FUSED) {
+            if (p.n_edges > 0) {                                 // for every degree: the loads of both halves go out together
+                issue2();
+                src.issue2(sr);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            g4 = src.finish(sr, i);
+        }
+        const float4 dm = SUMS ? g4 : make_float4(dt * g4.x, dt * g4.y, dt * g4.z, dt * g4.w);
+        float D = 0.f;
+        float4 dP = f4zero();
+        if (deg <= 8 && p.n_edges > 0) {                          // (an edgeless graph has no col / alpha entry to clamp to)
+            // the usual case, three memory round trips per node: (g row head, x row, row bounds) -> (8 column / alpha pairs,
+            // unconditional with clamped indices) -> (8 neighbour rows); a loop over the row would chain them per edge.  (ELL: two.)
+            if constexpr (!SRC::FUSED) issue2();
             float da[8];
             // difference form (see consume() of the tiled kernel; SUMS: plain form, D doubles as <g_i, m_i>)
             const float4 x0 = SUMS == 0 ? xi : f4zero();

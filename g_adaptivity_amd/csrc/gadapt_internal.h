@@ -6,7 +6,8 @@
 // 2 min 20 s on one core):
 //   gadapt_kernels.hip         C-ABI of layers / blocks / small per-step kernels, error + profiling state
 //   gadapt_tu_fwd.hip          grand_fwd_kernel<C> (gadapt_fwd.inc), wide::fwd_kernel (gadapt_wide.inc)
-//   gadapt_tu_bwd_target.hip   grand_bwd_target_kernel<C,...>, grand_bwd_target_compact_kernel (gadapt_bwd_target.inc)
+//   gadapt_tu_bwd_target.hip   grand_bwd_target_kernel<C,...>, grand_bwd_target_compact_kernel (gadapt_bwd_target.inc),
+//                              grand_bwd_target_fused_narrow_kernel (gadapt_narrow_bwd.inc)
 //   gadapt_tu_bwd_source.hip   grand_bwd_source_kernel<C,...>, grand_bwd_source4_kernel (gadapt_bwd_source.inc)
 //   gadapt_tu_smallmesh.hip    one-launch small-mesh pair (gadapt_smallmesh.inc)
 //   gadapt_tu_sparse.hip       generic CSR primitives (gadapt_sparse.inc)
@@ -195,6 +196,10 @@ int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const float*
                                       const float* a, const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, hipStream_t st);
 int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* edge_ws,
                                       const float* dxd, const float* a, const float* p0, float* g_out, hipStream_t st);
+// source pass of one layer and target pass of the layer below in one launch (gadapt_narrow_bwd.inc; gadapt_debug_set_narrow_backward_fused)
+int gadapt_launch_bwd_fused_narrow_c(int c, const gadapt_graph* g, const float* x_src, const float* g_in, int g_cols, const float* edge_in,
+                                     const float* a_src, const float* p0_src, float* g_out, const float* x_tgt, const float* alpha, const float* a_tgt, const float* lp_tgt,
+                                     float* edge_out, float* dxd, float* slab, int accumulate, int layer0, hipStream_t st);
 int gadapt_slab_rows_c(int64_t n_nodes, int c);
 int gadapt_occupancy_fwd_c(int c);
 int gadapt_occupancy_bwd_target_c(int c);

@@ -429,6 +429,20 @@ static bool narrow_fwd_enabled() {
     return v == 1;
 }
 extern "C" int gadapt_debug_set_narrow_forward(int on) { g_narrow_fwd.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
+// Narrow-route backward: each source pass inside the next layer's target pass (grand_bwd_target_fused_narrow_kernel, default), or the
+// pair of launches per layer, bit-identical (tests/test_gpu_narrow_backward.py).  GADAPT_NARROW_BWD_FUSED=0 /
+// gadapt_debug_set_narrow_backward_fused(0): the pairs.
+static std::atomic<int> g_narrow_bwd_fused{-1};
+static bool narrow_bwd_fused_enabled() {
+    int v = g_narrow_bwd_fused.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char* e = getenv("GADAPT_NARROW_BWD_FUSED");
+        v = (e && e[0] == '0') ? 0 : 1;
+        g_narrow_bwd_fused.store(v, std::memory_order_relaxed);
+    }
+    return v == 1;
+}
+extern "C" int gadapt_debug_set_narrow_backward_fused(int on) { g_narrow_bwd_fused.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
 static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers, const float* a, int64_t a_stride,
                          const float* p0, int64_t p0_stride, const float* layer_params, float* alpha_all, float* x_top4,
                          int c, void* stream, const FwdExtra* extra, bool narrow = false) {
@@ -610,6 +624,11 @@ extern "C" int gadapt_block_backward(const gadapt_graph* g, const float* x_all, 
 // Backward of the narrow route (gadapt_block_forward_narrow): every slot of x_all holds [N,4] rows at its start, g_top is the compact
 // [N,g_top_cols] top gradient.  Layers L-1 .. 1: narrow target pass (dxd [N,4] in dxd_ws, {alpha dt, ds} in edge_ws), narrow source pass
 // (g_out [N,4], alternating between the two halves of g_ws); layer 0: grand_bwd_target_compact_kernel as on the compact route.
+// By default (gadapt_debug_set_narrow_backward_fused) the source pass of layer l runs inside the target pass of layer l-1
+// (gadapt_launch_bwd_fused_narrow_c): T_{L-1}, [S_{L-1}+T_{L-2}], ..., [S_1+T_0] - L launches instead of 2L - 1, bit-identical.  Lanes
+// of a fused launch read one layer's {alpha dt, ds} pairs while others scatter the next layer's, so the launches alternate between
+// edge_ws and a second buffer of 2E floats carved out of dxd_ws (the caller's N c floats, of which this route uses the first 4N) at
+// float offset 4N; where that does not fit (2E > (c - 4) N) or the graph has no ELL table of out-neighbours, the pairs run.
 extern "C" int gadapt_block_backward_narrow(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top,
                                             int g_top_cols, int n_layers, const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
                                             const float* layer_params, float* g_ws, float* dxd_ws, float* edge_ws, float* slab, float* d_layer_params,
@@ -628,6 +647,22 @@ extern "C" int gadapt_block_backward_narrow(const gadapt_graph* g, const float* 
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const float* g_cur = g_top;
     int g_cols = g_top_cols;
+    if (narrow_bwd_fused_enabled() && g->ell_s && g->rowptr_s && g->col_s && 2 * (int64_t)g->n_edges <= (int64_t)(c - 4) * g->n_nodes) {
+        float* edge_buf[2] = {edge_ws, dxd_ws + 4 * (size_t)g->n_nodes};
+        int l = n_layers - 1, eb = 0;
+        int rc = gadapt_launch_bwd_target_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, alpha_all + (size_t)l * g->n_edges, a + l * a_stride,
+                                                   layer_params + 2 * l, edge_buf[eb], dxd_ws, shared ? slab : slab + (size_t)l * slab_floats, 0, st);
+        for (; !rc && l >= 1; --l, eb ^= 1) {                   // source pass of layer l + target pass of layer l-1
+            float* g_next = g_ws + ((n_layers - 1 - l) & 1) * nc;
+            rc = gadapt_launch_bwd_fused_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, edge_buf[eb], a + l * a_stride, p0 + l * p0_stride, g_next,
+                                                  x_all + (l - 1) * nc, alpha_all + (size_t)(l - 1) * g->n_edges, a + (l - 1) * a_stride,
+                                                  layer_params + 2 * (l - 1), edge_buf[eb ^ 1], dxd_ws,
+                                                  shared ? slab : slab + (size_t)(l - 1) * slab_floats, shared ? 1 : 0, l == 1 ? 1 : 0, st);
+            g_cur = g_next;
+            g_cols = 0;
+        }
+        return rc;
+    }
     for (int l = n_layers - 1; l >= 0; --l) {
         float* slab_l = shared ? slab : slab + (size_t)l * slab_floats;
         const int accumulate = (shared && l != n_layers - 1) ? 1 : 0;

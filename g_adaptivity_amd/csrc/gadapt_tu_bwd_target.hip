@@ -3,6 +3,7 @@
 // unit of libgadapt_hip.so (see gadapt_internal.h).
 #include "gadapt_internal.h"
 #include "gadapt_bwd_target.inc"
+#include "gadapt_narrow_bwd.inc"
 
 // out4: only columns 0..3 of g_out are wanted (dxd is [N,4]: D4 target pass, then grand_bwd_source4_kernel).
 // g_stride: row pitch of g_in in floats for the compact-input launch (0 = C).
@@ -93,4 +94,31 @@ int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const float*
     ProfScope prof(1, st, g_cols ? 3 : 2);                     // compact input (and compact upstream gradient at the top layer)
     hipLaunchKernelGGL(grand_bwd_target_narrow_kernel, grid, dim3(256), 0, st, pt);
     return check_launch("grand_bwd_target_narrow_kernel");
+}
+
+// narrow route, fused launch (grand_bwd_target_fused_narrow_kernel, gadapt_narrow_bwd.inc): the source pass of layer l (x_src, g_in [N,4]
+// or - g_cols > 0 - the compact [N,g_cols] top gradient, the pairs in edge_in, a_src / p0_src; its dxd row is read from dxd) and, in the same lane, the target pass of layer l-1 (x_tgt, alpha,
+// a_tgt, lp_tgt) on the result.  layer0 = 0: g_out [N,4], dxd and the pairs of layer l-1 (edge_out, NOT edge_in: lanes of one launch
+// read one and scatter into the other) are written; layer0 = 1 (l-1 = 0): slab partials only.  Grid and slab rows of every target launch.
+int gadapt_launch_bwd_fused_narrow_c(int c, const gadapt_graph* g, const float* x_src, const float* g_in, int g_cols, const float* edge_in,
+                                     const float* a_src, const float* p0_src, float* g_out, const float* x_tgt, const float* alpha, const float* a_tgt, const float* lp_tgt,
+                                     float* edge_out, float* dxd, float* slab, int accumulate, int layer0, hipStream_t st) {
+    if (c != 64 || !g->ell_t || !g->tpos_s || !g->ell_s || !g->rowptr_s || !g->col_s || g_cols < 0 || g_cols > 4)
+        return fail(GADAPT_E_BADARG, "fused narrow backward: hidden 64, ELL graph, 0..4 g columns");
+    if (!layer0 && (!g_out || !edge_out || edge_out == edge_in)) return fail(GADAPT_E_BADARG, "fused narrow backward: a second edge buffer and g_out above layer 0");
+    BwdFusedNarrowArgs pf{};
+    pf.t = BwdTArgs{x_tgt, nullptr, alpha, a_tgt, lp_tgt, g->rowptr_t, g->col_t, g->tpos_s, nullptr, reinterpret_cast<float2*>(edge_out), dxd, slab, nullptr,
+                    g->n_nodes, tiles_for<64>(g->n_nodes), accumulate, 0, g->n_edges, nullptr, 0};
+    pf.t.c = c;
+    pf.t.g_stride = 4;
+    pf.t.ell = g->ell_t;
+    pf.x_src = x_src; pf.g_in = g_in; pf.edge_in = edge_in; pf.A_src = a_src; pf.p0_src = p0_src;
+    pf.rowptr_s = g->rowptr_s; pf.col_s = g->col_s; pf.ell_s = g->ell_s;
+    pf.g_out = g_out; pf.g_cols = g_cols;
+    const dim3 grid(grid_for(pf.t.n_tiles, resident_blocks_bwd_t<64>(GADAPT_BWD_T_MAX_BLOCKS)));
+    ProfScope prof(1, st, 2);                                   // a target-pass launch on compact input (the source pass rides in it)
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, pf); };
+    if (layer0) { if (g_cols) go(grand_bwd_target_fused_narrow_kernel<true, true>); else go(grand_bwd_target_fused_narrow_kernel<true, false>); }
+    else { if (g_cols) go(grand_bwd_target_fused_narrow_kernel<false, true>); else go(grand_bwd_target_fused_narrow_kernel<false, false>); }
+    return check_launch("grand_bwd_target_fused_narrow_kernel");
 }

@@ -171,7 +171,8 @@ class FusedIteration:
         self._fn_tail = L_.gadapt_step_tail
 
     def forward_backward(self):
-        """zero_grad + model(data) + loss + backward: 4 + 7 launches at 4 layers (small-mesh batches: 1 + 1; the gradient of the conv
+        """zero_grad + model(data) + loss + backward: 4 + 7 launches at 4 layers (narrow route: 4 + 4, each source pass inside the next
+        target pass; small-mesh batches: 1 + 1; the gradient of the conv
         parameters is still in the slab: `finish()` sums it).  Data parallel: also the slab sums + chain rule, so that `flat` holds this
         rank's gradient."""
         if self.fwd.moved():

@@ -248,7 +248,8 @@ int gadapt_block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
  *     x_top4): x0_cols must be 4 and x_top4 given;
  *   - gadapt_block_backward_narrow: g_top compact (1 <= g_top_cols <= 4), d_layer_params and d_x0 NULL (fixed steps and temperature);
  *     layers L-1 .. 1 run the narrow target and source passes on [N,4] rows (dxd_ws, g_ws used at their start), layer 0 the compact
- *     target pass.  Weight gradients land in the 4 x 4 corner of dA and entries 0..3 of dp0 of the slab rows; the rest of each row is
+ *     target pass - by default with each source pass inside the next target pass (gadapt_debug_set_narrow_backward_fused), which
+ *     uses floats 4N .. 4N + 2E of dxd_ws (N c floats, as for gadapt_block_backward) as a second edge buffer.  Weight gradients land in the 4 x 4 corner of dA and entries 0..3 of dp0 of the slab rows; the rest of each row is
  *     written zero, so the slab reduction and gadapt_step_tail are the dense route's. */
 int gadapt_narrow_route(const gadapt_graph* g, int c);
 int gadapt_block_forward_narrow(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers,
@@ -455,6 +456,11 @@ int gadapt_debug_set_backward_inplace(int on);
  * (gadapt_block_forward_narrow, gadapt_block_forward_loss_narrow) on the one-node-per-lane kernel; 0 on the wide kernel with its
  * compact input.  Results are bit-identical either way (tests/test_gpu_narrow_forward.py). */
 int gadapt_debug_set_narrow_forward(int on);
+/* Switch: 1 (the default; GADAPT_NARROW_BWD_FUSED=0 in the environment starts with 0) lets gadapt_block_backward_narrow run the source
+ * pass of each layer inside the target pass of the layer below (L launches instead of 2L - 1; the second edge buffer the fused launches
+ * alternate with lives in the unused tail of dxd_ws); 0 runs the pair of launches per layer.  Results are bit-identical either way
+ * (tests/test_gpu_narrow_backward.py). */
+int gadapt_debug_set_narrow_backward_fused(int on);
 /* Diagnostic: runtime-reported workgroups per CU of {forward, backward target, backward source}. */
 int gadapt_debug_occupancy(int c, int* out3);
 

@@ -27,7 +27,7 @@ def name(n):
     if 'gat::bwd_t' in n: return 'backward_target'
     if 'gat::bwd_s' in n: return 'backward_source'
     if 'grand_fwd' in n or 'wide::fwd' in n: return 'forward'      # wide::fwd_kernel<...>, wide::fwd_narrow_kernel<HEAD> (narrow route)
-    if "bwd_target" in n: return "backward_target"          # grand_bwd_target_kernel<...>, grand_bwd_target_compact_kernel<SUMS>
+    if "bwd_target" in n: return "backward_target"          # grand_bwd_target_kernel<...>, grand_bwd_target_compact_kernel<SUMS>, grand_bwd_target_fused_narrow_kernel<L0, GC>
     if 'bwd_source' in n: return 'backward_source'          # grand_bwd_source_kernel<...>, grand_bwd_source4_kernel<C, GC>
     return None
 
@@ -39,7 +39,7 @@ def variant(n):
         a = n[n.index('<') + 1:n.index('>')].replace(' ', '').split(',')
     except ValueError:
         return None
-    if 'bwd_target_compact' in n:
+    if 'bwd_target_compact' in n or 'bwd_target_fused_narrow' in n:   # fused narrow backward <L0, GC>: a target launch on [N,4] rows
         return 'compact_x'
     if 'bwd_target' in n and len(a) <= 4:                   # round 6 on: <C, SUMS, GC, D4>
         a += ['false'] * (4 - len(a))
