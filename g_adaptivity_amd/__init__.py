@@ -8,12 +8,15 @@ Public surface mirrors the reference modules:
     from g_adaptivity_amd import gradient_meshpoints_2D    # the 2-D modular loss (Poisson)
     from g_adaptivity_amd import MMPDE5_1d, MMPDE5_2d, mmpde5_batch   # the classical MMPDE5 target meshes, batched
     from g_adaptivity_amd import evaluate_model_fine, eval_grid_MMPDE_MA, poisson_eval_errors   # the Poisson error-reduction tables
+    from g_adaptivity_amd import evaluate_model_fine_burgers, evaluate_model_fine_burgers_time_step   # the Burgers one-step and rollout tables
+    from g_adaptivity_amd import cubic_spline_1d            # batched not-a-knot cubic splines (scipy's UnivariateSpline(s=0))
 The arithmetic lives in `libgadapt_hip.so` (csrc/, C-ABI in include/gadapt_hip.h) and, for the FEM tail,
 `libgadapt_fem.so` (fem_csrc/, include/gadapt_fem.h); the MMPDE5 generator in `libgadapt_mesh.so` (mesh_csrc/, include/gadapt_mesh.h).
 """
 from .conv import GAT_conv, GAT_plus, GCN_conv, GRAND_conv, GRAND_plusConv, TRANS_conv
 from .evaluation import (calculate_error_reduction, eval_grid_MMPDE_MA, evaluate_error_np, evaluate_error_np_2d, evaluate_model_fine,
                          poisson_eval_errors)
+from .evaluation_burgers import burgers_project, evaluate_model_fine_burgers, evaluate_model_fine_burgers_time_step
 from .fem import fem_poisson, gradient_meshpoints_2D, torch_FEM_2D
 from .fem1d import (burgers_1d, fem_poisson_1d, fn_expansion, get_Burgers_initial_coeffs, gradient_meshpoints_1D, torch_FEM_1D,
                     torch_FEM_Burgers_1D)
@@ -25,6 +28,7 @@ from .mesh_graph import (DeviceMeshLoader, MeshData, MeshDataset, MeshLoader, Mi
 from .mmpde5 import (MMPDE5_1d, MMPDE5_1d_burgers, MMPDE5_2d, deform_mesh_mmpde1d, deform_mesh_mmpde2d, mmpde5_batch, monitor_1d,
                      monitor_2d)
 from .params import hot_path_opt
+from .spline import cubic_spline_1d
 from .training import GraphedTrainStep
 
 __all__ = ['GNN', 'MLP', 'get_conv', 'build_conv_list', 'get_enc', 'get_dec', 'get_mlp', 'get_nonlin',
@@ -35,4 +39,5 @@ __all__ = ['GNN', 'MLP', 'get_conv', 'build_conv_list', 'get_enc', 'get_dec', 'g
            'get_Burgers_initial_coeffs', 'fn_expansion', 'torch_FEM_1D', 'gradient_meshpoints_2D',
            'mmpde5_batch', 'monitor_1d', 'monitor_2d', 'MMPDE5_1d', 'MMPDE5_2d', 'MMPDE5_1d_burgers', 'deform_mesh_mmpde1d',
            'deform_mesh_mmpde2d', 'poisson_eval_errors', 'eval_grid_MMPDE_MA', 'evaluate_model_fine', 'evaluate_error_np',
-           'evaluate_error_np_2d', 'calculate_error_reduction']
+           'evaluate_error_np_2d', 'calculate_error_reduction', 'cubic_spline_1d', 'evaluate_model_fine_burgers',
+           'evaluate_model_fine_burgers_time_step', 'burgers_project']

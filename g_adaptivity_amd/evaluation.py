@@ -23,6 +23,7 @@ tail's mesh sizes (2-D: square meshes up to 26 x 26 nodes, the load vector's bui
 """
 from __future__ import annotations
 
+import contextlib
 import time
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -239,6 +240,45 @@ def _as_float(v) -> float:
     return float(v.item()) if torch.is_tensor(v) else float(v)
 
 
+def _picked(dataset, opt):
+    """(indices, samples) to evaluate: all, or those opt['overfit_num'] lists."""
+    picked = [i for i in range(len(dataset)) if not opt.get('overfit_num') or i in opt['overfit_num']]
+    return picked, [dataset[i] for i in picked]
+
+
+def _eval_loader(dataset, picked, opt, batch_size: int):
+    """The evaluation's loader over the picked samples, in order: `Mixed_DataLoader` for data_type 'randg_mix', else `MeshLoader`."""
+    sub = dataset[picked]
+    if opt.get('data_type') == 'randg_mix':
+        exclude = ['boundary_nodes_dict', 'mapping_dict', 'node_boundary_map', 'eval_errors', 'pde_params']
+        return Mixed_DataLoader(sub, batch_size=batch_size, shuffle=False, exclude_keys=exclude, follow_batch=[])
+    return MeshLoader(sub, batch_size=batch_size, shuffle=False)
+
+
+@contextlib.contextmanager
+def _eval_mode(model):
+    """The module that stamps `end_MLmodel` (a GraphedForward stamps its model), in eval mode for the block."""
+    stamp = getattr(model, 'model', model)
+    was_training = bool(getattr(stamp, 'training', False))
+    if hasattr(stamp, 'eval'):
+        stamp.eval()
+    try:
+        yield stamp
+    finally:
+        if was_training:
+            stamp.train()
+
+
+def _tables(rows, trow, columns, time_columns):
+    """(df, df_time): pandas DataFrames where pandas imports, else dicts of numpy arrays (None -> NaN), same keys and order."""
+    try:
+        import pandas as pd
+    except ImportError:
+        as_arr = lambda v: np.asarray([np.nan if a is None else a for a in v], dtype=np.float64)
+        return {k: as_arr(v) for k, v in rows.items()}, {k: as_arr(v) for k, v in trow.items()}
+    return pd.DataFrame(rows, columns=columns), pd.DataFrame(trow, columns=time_columns)
+
+
 def evaluate_model_fine(model, dataset, opt, fine_eval: bool = True, batch_size: int = 1):
     """The reference's `evaluate_model_fine` (`src/utils_eval.py:106-267`) on the GPU: (df, df_time), one row per evaluated
     sample, columns ERROR_COLUMNS and TIME_COLUMNS.  pandas DataFrames when pandas imports, else dicts of numpy arrays with
@@ -269,38 +309,24 @@ def evaluate_model_fine(model, dataset, opt, fine_eval: bool = True, batch_size:
     if batch_size < 1:
         raise ValueError("evaluate_model_fine: batch_size >= 1")
     dev = torch.device(opt.get('device', 'cuda'))
-    picked = [i for i in range(len(dataset)) if not opt.get('overfit_num') or i in opt['overfit_num']]
-    samples = [dataset[i] for i in picked]
+    picked, samples = _picked(dataset, opt)
     missing = [s for s in samples if not isinstance(getattr(s, 'eval_errors', None), dict)]
     if missing:
         print("Pre process eval data doesn't exists, calculating...")
         eval_grid_MMPDE_MA(missing, opt)
 
-    sub = dataset[picked]
-    if opt.get('data_type') == 'randg_mix':
-        exclude = ['boundary_nodes_dict', 'mapping_dict', 'node_boundary_map', 'eval_errors', 'pde_params']
-        loader = Mixed_DataLoader(sub, batch_size=batch_size, shuffle=False, exclude_keys=exclude, follow_batch=[])
-    else:
-        loader = MeshLoader(sub, batch_size=batch_size, shuffle=False)
-    stamp = getattr(model, 'model', model)                        # a GraphedForward stamps its model
-    was_training = bool(getattr(stamp, 'training', False))
-    if hasattr(stamp, 'eval'):
-        stamp.eval()
+    loader = _eval_loader(dataset, picked, opt, batch_size)
     coords, times = [], []
-    try:
-        with torch.no_grad():
-            for data in loader:
-                nb = data.num_graphs
-                counts = torch.bincount(data.batch, minlength=nb).tolist()
-                data = data.to(dev)
-                start = time.time()
-                out = model(data)
-                x = out[1] if loss_type == 'pde_loss' else out
-                times += [(stamp.end_MLmodel - start) / nb] * nb
-                coords += list(torch.split(x.detach(), counts))
-    finally:
-        if was_training:
-            stamp.train()
+    with _eval_mode(model) as stamp, torch.no_grad():
+        for data in loader:
+            nb = data.num_graphs
+            counts = torch.bincount(data.batch, minlength=nb).tolist()
+            data = data.to(dev)
+            start = time.time()
+            out = model(data)
+            x = out[1] if loss_type == 'pde_loss' else out
+            times += [(stamp.end_MLmodel - start) / nb] * nb
+            coords += list(torch.split(x.detach(), counts))
     ml = _errors_of(coords, samples, n_eval, opt, dev).cpu().double().numpy() if samples else np.zeros((0, 2))
 
     rows = {k: [] for k in ERROR_COLUMNS}
@@ -316,9 +342,4 @@ def evaluate_model_fine(model, dataset, opt, fine_eval: bool = True, batch_size:
         bt = getattr(s, 'build_time', None)
         trow['MA_time'].append(float('nan') if bt is None else _as_float(bt))
         trow['MLmodel_time'].append(times[k])
-    try:
-        import pandas as pd
-    except ImportError:
-        as_arr = lambda v: np.asarray([np.nan if a is None else a for a in v], dtype=np.float64)
-        return {k: as_arr(v) for k, v in rows.items()}, {k: as_arr(v) for k, v in trow.items()}
-    return pd.DataFrame(rows, columns=ERROR_COLUMNS), pd.DataFrame(trow, columns=TIME_COLUMNS)
+    return _tables(rows, trow, ERROR_COLUMNS, TIME_COLUMNS)

@@ -37,6 +37,8 @@
 extern "C" {
 #endif
 
+/* 4: also with gadapt_fem1d_spline, an addition that changes no existing signature (a library without it fails when the
+ * caller resolves its table of prototypes). */
 #define GADAPT_FEM_ABI 4
 
 #define GADAPT_FEM_OK          0
@@ -203,6 +205,23 @@ int gadapt_fem1d_poisson_backward(int n_meshes, int max_nodes, const int32_t* no
 /* fn_expansion(c, x, pts) per mesh (no gradient): sol [B,P]. */
 int gadapt_fem1d_expand(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const float* c, int n_pts,
                         const float* pts, float* sol, void* stream);
+
+/* Batched not-a-knot interpolating cubic splines (fem_csrc/spline_kernels.hip), one launch: scipy's
+ * UnivariateSpline(x, y, s=0) / CubicSpline(bc_type='not-a-knot') of the Burgers rollout (src/utils_eval_Burgers.py:215-239),
+ * the C2 piecewise cubic through all points whose third derivative is continuous at x[1] and x[n-2]; n = 4 is the cubic
+ * through four points.
+ *   sets b = 0..B-1 concatenated: points [set_off[b], set_off[b+1]) of x (strictly increasing) and y, 4 <= n_b <= max_nodes
+ *   queries: q_off == NULL: q [Q] shared by all sets, out [B,Q];  else q [q_off[B]] per set, out laid out like q
+ *   deriv 0, 1, 2: the value, first or second derivative; queries outside [x[0], x[n-1]] use the end pieces
+ * One workgroup per set; x, y and the second derivatives in LDS as fp64 (32 bytes per point), elimination (one lane's Thomas
+ * sweep) and evaluation in fp64, fp32 in and out.  status [B]: GADAPT_SPLINE_S_*; a flagged set writes NaN to its own
+ * outputs and touches nothing else.  A set's output does not depend on the rest of the batch. */
+#define GADAPT_SPLINE_S_OK             0
+#define GADAPT_SPLINE_S_NOT_INCREASING 1   /* some x[i+1] <= x[i] */
+#define GADAPT_SPLINE_S_NOT_FINITE     2   /* a NaN or infinity in x or y */
+#define GADAPT_SPLINE_S_BAD_COUNT      3   /* n_b outside 4..max_nodes */
+int gadapt_fem1d_spline(int n_sets, int max_nodes, const int32_t* set_off, const float* x, const float* y, int n_queries,
+                        const float* q, const int32_t* q_off, int deriv, float* out, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
