@@ -686,12 +686,11 @@ __device__ inline void thomas64_poisson(const double* off, const double* dl, con
 }
 
 // torch_FEM_1D's solve of mesh b by its workgroup: the working set on the launch's LDS, coefficients (BC1, interior, BC2) in w.r.
-// STIFF64 = false is the forward of fem_poisson_1d: the stiffness matrix in fp32 as the reference assembles it.  Its diagonal
-// fl(dl + dr) leaves row sums of an ulp of 2/h, and the solve answers them with coefficient errors of a few 1e-6 of either
-// sign (the reference's own fp32 solve has them as well, elsewhere): up to 3e-4 of an error norm, where e = sol - u_true is
-// ~1e-3 of sol.  An evaluation reports that norm, so STIFF64 = true assembles the same trapezoids in fp64 (coefficients within
-// 1e-7 of an fp64 solve); the load vector, boundary values and expansion stay in fp32.
-template <bool STIFF64>
+// The stiffness trapezoids are assembled in fp64.  The reference assembles them in fp32, where the diagonal fl(dl + dr) leaves
+// row sums of an ulp of 2/h and the solve answers them with coefficient errors that grow as N^2: a few 1e-6 at 21 nodes (up
+// to 3e-4 of an error norm, where e = sol - u_true is ~1e-3 of sol) and 1.4e-4 to 3e-4 of the coefficients at 1023 nodes,
+// twice what the reference's own fp32 solve shows there.  In fp64 the coefficients are within 1e-7 of an fp64 solve; the load
+// vector, boundary values and expansion stay in fp32.  The forward and the evaluation's error norms share this solve.
 __device__ inline W1 poisson_solve(float* L, int b, const int32_t* __restrict__ node_off, const float* __restrict__ x,
                                    const int32_t* __restrict__ gptr, const float* __restrict__ gpar, int k_load, int k_stiff, int nmax,
                                    int32_t* __restrict__ flags) {
@@ -703,35 +702,16 @@ __device__ inline W1 poisson_solve(float* L, int b, const int32_t* __restrict__ 
     const int bad = not_increasing(w);
     if (t == 0) flags[b] = bad ? GADAPT_FEM1D_F_NOT_INCREASING : 0;
     double* d64 = reinterpret_cast<double*>(L + 12 * nmax);
-    if constexpr (STIFF64) {
-        const float rhs = load_row(w, k_load, [&](float xq) { return forcing(xq, gpar, g0, g1, nullptr); });   // uses t0, t1
-        const float bc1 = gauss(w.m[0], gpar, g0, g1), bc2 = gauss(w.m[n - 1], gpar, g0, g1);
-        if (t < n) w.r[t] = rhs;
-        // three fp64 rows over the six fp32 rows Sl..t2 (byte offsets 16, 24, 32 nmax: 8-aligned for any nmax)
-        double *o64 = reinterpret_cast<double*>(L + 4 * nmax), *l64 = o64 + nmax, *r64 = o64 + 2 * nmax;
-        stiff_intervals64(w.m, n, k_stiff, o64, l64, r64);
-        if (t == 0) {
-            thomas64_poisson(o64, l64, r64, w.r, bc1, bc2, d64, d64 + nmax, n);
-            w.r[0] = bc1;
-            w.r[n - 1] = bc2;
-        }
-    } else {
-        float al, ad, au;
-        stiff_rows(w, k_stiff, al, ad, au);
-        const float off0 = w.t0[0], offl = w.t0[n - 2];   // A[0][1], A[n-1][n-2]
-        __syncthreads();
-        poisson_matrix(w, al, ad, au);
-        const float rhs = load_row(w, k_load, [&](float xq) { return forcing(xq, gpar, g0, g1, nullptr); });
-        const float bc1 = gauss(w.m[0], gpar, g0, g1), bc2 = gauss(w.m[n - 1], gpar, g0, g1);
-        if (t < n) w.r[t] = rhs;
-        __syncthreads();
-        if (t == 0) {
-            w.r[1] = w.r[1] + bc1 * off0;
-            w.r[n - 2] = w.r[n - 2] + offl * bc2;
-            thomas64(w.Sl, w.Sd, w.Su, w.r, d64, d64 + nmax, 1, n - 1, false);
-            w.r[0] = bc1;
-            w.r[n - 1] = bc2;
-        }
+    const float rhs = load_row(w, k_load, [&](float xq) { return forcing(xq, gpar, g0, g1, nullptr); });   // uses t0, t1
+    const float bc1 = gauss(w.m[0], gpar, g0, g1), bc2 = gauss(w.m[n - 1], gpar, g0, g1);
+    if (t < n) w.r[t] = rhs;
+    // three fp64 rows over the six fp32 rows Sl..t2 (byte offsets 16, 24, 32 nmax: 8-aligned for any nmax)
+    double *o64 = reinterpret_cast<double*>(L + 4 * nmax), *l64 = o64 + nmax, *r64 = o64 + 2 * nmax;
+    stiff_intervals64(w.m, n, k_stiff, o64, l64, r64);
+    if (t == 0) {
+        thomas64_poisson(o64, l64, r64, w.r, bc1, bc2, d64, d64 + nmax, n);
+        w.r[0] = bc1;
+        w.r[n - 1] = bc2;
     }
     __syncthreads();
     return w;
@@ -743,12 +723,12 @@ __global__ void __launch_bounds__(F1_THREADS) poisson_fwd_kernel(
     int32_t* __restrict__ flags) {
     extern __shared__ float lds[];
     const int b = blockIdx.x, t = threadIdx.x;
-    const W1 w = poisson_solve<false>(lds, b, node_off, x, gptr, gpar, k_load, k_stiff, nmax, flags);
+    const W1 w = poisson_solve(lds, b, node_off, x, gptr, gpar, k_load, k_stiff, nmax, flags);
     if (t < w.n) coeffs[node_off[b] + t] = w.r[t];
     evaluate(w, w.r, P, pts, sol + (size_t)b * P);
 }
 
-// The Poisson forward (stiffness in fp64: poisson_solve) with the reference's trapezium norms of e = sol - u_true over pts
+// The Poisson forward (poisson_solve) with the reference's trapezium norms of e = sol - u_true over pts
 // (evaluate_error_np) reduced in the same launch: L1 = sum_j (|e_j| + |e_j+1|) (p_j+1 - p_j) / 2, L2 = sqrt of the same sum of squares.  The first wave
 // reduces: lane l takes intervals l, l + 64, ... in order and the lanes are added in a fixed butterfly, so the order does not
 // depend on the workgroup's size (which follows the largest mesh of the batch).
@@ -757,7 +737,7 @@ __global__ void __launch_bounds__(F1_THREADS) poisson_err_kernel(
     int k_load, int k_stiff, int nmax, int P, const float* __restrict__ pts, float* __restrict__ err, int32_t* __restrict__ flags) {
     extern __shared__ float lds[];
     const int b = blockIdx.x, t = threadIdx.x;
-    const W1 w = poisson_solve<true>(lds, b, node_off, x, gptr, gpar, k_load, k_stiff, nmax, flags);
+    const W1 w = poisson_solve(lds, b, node_off, x, gptr, gpar, k_load, k_stiff, nmax, flags);
     const int g0 = gptr[b], g1 = gptr[b + 1];
     if (t >= 64) return;                              // no barrier below: the first wave reduces, whatever the workgroup's size
     float s1 = 0.0f, s2 = 0.0f;

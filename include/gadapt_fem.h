@@ -144,7 +144,7 @@ int gadapt_fem_backward(int n_meshes, int n_nodes, int n_tris, const int32_t* me
  * gpar[gptr[b]..gptr[b+1]) as (centre, scale) pairs.  Evaluation points `pts` [P] are shared by all meshes; sol is [B,P].
  * One workgroup per mesh, the mesh's whole state in LDS, one launch forward and one backward.  The tridiagonal solves run
  * on one lane (Thomas, no pivoting: the Burgers matrix is strictly and the Poisson matrix weakly diagonally dominant;
- * the Poisson elimination in fp64).
+ * the Poisson stiffness trapezoids and elimination in fp64: the system's condition grows as N^2).
  * No float atomics: results are bit-reproducible.
  *
  * Node cap.  A workgroup has one lane per node (GADAPT_FEM1D_MAX_NODES = 1024, the largest workgroup).  The Burgers
@@ -191,8 +191,8 @@ int gadapt_fem1d_poisson_forward(int n_meshes, int max_nodes, const int32_t* nod
 
 /* Poisson forward with the reference's 1-D trapezium norms (evaluate_error_np, src/utils_eval.py:32-44) of e = sol - u_true over
  * pts [P >= 2] reduced in the same launch: err [B,2] = (L1, L2), L1 = sum_j (|e_j| + |e_j+1|) (pts_j+1 - pts_j) / 2 and L2 the
- * square root of the same sum over e^2; flags [B] as the forward sets them.  Neither coeffs nor sol is written.  The stiffness
- * matrix is assembled in fp64 here (in fp32 its rounded row sums move the norms by up to 3e-4); the rest is the forward's fp32. */
+ * square root of the same sum over e^2; flags [B] as the forward sets them.  Neither coeffs nor sol is written.  The solve is the
+ * forward's (stiffness in fp64: in fp32 its rounded row sums move the norms by up to 3e-4; load, boundary values, expansion in fp32). */
 int gadapt_fem1d_poisson_eval_errors(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
                                      const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts, float* err,
                                      int32_t* flags, void* stream);

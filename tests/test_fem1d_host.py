@@ -134,3 +134,54 @@ def test_dataset_defaults_unchanged_and_burgers_draws():
     for s in b.samples:
         c, sc = float(s.pde_params['centers'][0][0]), float(s.pde_params['scales'][0][0])
         assert 0.3 <= c <= 0.7 and 0.05 <= sc <= 0.2
+
+
+# ------------------------------------------------------------------------ the banded restatement against the dense one
+BANDED_N = (2, 3, 4, 21, 65)
+
+
+def _pin_meshes(dtype):
+    for n in BANDED_N:
+        yield f"n={n} uniform", _mesh(n, dtype=dtype)
+        yield f"n={n} jittered", _mesh(n, jitter=0.3, seed=n, dtype=dtype)
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.float64])
+@pytest.mark.parametrize('k', [2, 11, 101])
+def test_banded_mass_is_the_tridiagonal_part_of_the_dense_one(k, dtype):
+    for label, x in _pin_meshes(dtype):
+        M = R.mass_matrix(x, k)
+        lo, di, up = R.mass_bands(x, k)
+        assert di.dtype == dtype
+        assert torch.equal(di, torch.diagonal(M)), (label, k)
+        assert torch.equal(lo, torch.diagonal(M, -1)) and torch.equal(up, torch.diagonal(M, 1)), (label, k)
+        assert torch.equal(R.mass_matrix(x, k, banded=True), torch.tril(torch.triu(M, -1), 1)), (label, k)
+
+
+@pytest.mark.parametrize('k', [2, 11, 101])
+def test_dense_mass_beyond_the_three_diagonals_is_rounding_level(k):
+    """The 'rounding-level terms' the kernel header says mass_rows drops: at most 1e-12 of the largest entry in fp64."""
+    for label, x in _pin_meshes(torch.float64):
+        M = R.mass_matrix(x, k)
+        far = (M - torch.tril(torch.triu(M, -1), 1)).abs().max().item()
+        assert far <= 1e-12 * M.abs().max().item(), (label, k, far, M.abs().max().item())
+
+
+@pytest.mark.parametrize('k', [2, 11, 101])
+def test_banded_burgers_and_its_mesh_gradient_equal_the_dense_run(k):
+    """fp64 rounding: 1e-11 of the largest value (the banded run differs by the dropped terms, 1e-12 of M, through two
+    solves whose condition is of order 10; a missing or misplaced band would be an O(1) difference)."""
+    opt = dict(OPT, load_quad_points=k, eval_quad_points=k)
+    pts = torch.linspace(0.013, 0.987, 17, dtype=torch.float64)
+    for label, x in _pin_meshes(torch.float64):
+        out = {}
+        for banded in (False, True):
+            xx = x.clone().requires_grad_(True)
+            u, sol, fsol = R.burgers(xx, C, S, opt, 2, pts, banded=banded)
+            (sol ** 2).sum().backward()
+            out[banded] = (u.detach(), sol.detach(), fsol, xx.grad)
+        for name, a, b in zip(('u', 'sol', 'fine_sol', 'x.grad'), out[True], out[False]):
+            assert (a - b).abs().max().item() <= 1e-11 * max(b.abs().max().item(), 1e-3), (label, k, name)
+    xx = _mesh(21, jitter=0.3, seed=2).requires_grad_(True)
+    o = dict(opt, grad_type='burgers_timestep_loss_direct_mse', num_time_steps=2)
+    assert abs(R.modular_loss(xx, C, S, o, pts, banded=True).item() - R.modular_loss(xx, C, S, o, pts).item()) <= 1e-14

@@ -13,7 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mmpde5_restatement as R  # noqa: E402
-from test_mmpde5_host import CASES, load  # noqa: E402
+from test_mmpde5_host import CASES, EDGE_1D, EDGE_2D, EDGE_STEPS, edge_case, edge_restated, load  # noqa: E402
 
 from g_adaptivity_amd import (MMPDE5_1d, MMPDE5_1d_burgers, MMPDE5_2d, DeviceMeshLoader, MeshDataset, MixedMeshDataset,  # noqa: E402
                               deform_mesh_mmpde1d, deform_mesh_mmpde2d, mmpde5_batch, square_mesh)
@@ -82,6 +82,46 @@ def test_alone_and_in_a_mixed_batch_bit_identical(gpu_device):
     assert both.status.tolist() == [CAP, CONVERGED, CONVERGED] and both.steps[0].item() == 2000
     assert both.steps[1].item() == solo.steps.item() and torch.equal(both.coords[1], solo.coords[0])
     assert torch.equal(both.coords[1], both.coords[2])
+
+
+EDGES = [(1, n) for n in EDGE_1D] + [(2, n) for n in EDGE_2D]
+
+
+def _measure_bar(m32, m64):
+    """4x the fp32 restatement's own measure error; 4 ulp of the measure should that error be exactly zero (it is not at any
+    size of EDGES: the smallest, 8e-7 of the measure, is at 9 x 9)."""
+    own = abs(m32 - m64)
+    return 4 * own if own > 0 else 4 * float(torch.nextafter(torch.tensor(m64, dtype=torch.float32), torch.tensor(float('inf'))) - m64)
+
+
+@pytest.mark.parametrize('dim,N', EDGES)
+def test_wave_and_workgroup_edges_against_fp64(gpu_device, dim, N):
+    """50 steps with tol = 0 at the sizes where the wave count changes and where the last wave is nearly empty: coordinates
+    under the bar of test_fixed_step_count_against_fp64, and the last step's measure (the only value that goes through the
+    cross-wave sum) under the same 4x bar against the fp64 restatement's measure."""
+    z0, mon = edge_case(dim, N)
+    res = mmpde5_batch([z0.to(gpu_device)], [mon], tol=0.0, max_steps=EDGE_STEPS)
+    (z64, m64), (z32, m32) = edge_restated(dim, N, torch.float64), edge_restated(dim, N, torch.float32)
+    err = (res.coords[0].cpu().double() - z64).abs().max().item()
+    bar = 4 * (z32.double() - z64).abs().max().item()
+    merr, mbar = abs(res.measure.item() - m64), _measure_bar(m32, m64)
+    print(f"mmpde5 {dim}d N={N}: coords err {err:.3e} bar {bar:.3e}; measure {res.measure.item():.9e} fp64 {m64:.9e} "
+          f"err {merr:.3e} bar {mbar:.3e}")
+    assert res.steps.tolist() == [EDGE_STEPS] and res.status.tolist() == [CAP]
+    assert res.coords[0].shape == z0.shape
+    assert err <= bar
+    assert merr <= mbar
+
+
+def test_wave_and_workgroup_edges_in_one_launch_equal_solo_runs(gpu_device):
+    cases = [edge_case(dim, N) for dim, N in EDGES]
+    coords, mons = [c[0].to(gpu_device) for c in cases], [c[1] for c in cases]
+    mixed = mmpde5_batch(coords, mons, tol=0.0, max_steps=EDGE_STEPS)
+    assert mixed.steps.tolist() == [EDGE_STEPS] * len(EDGES) and mixed.status.tolist() == [CAP] * len(EDGES)
+    for b, (xy, mon) in enumerate(zip(coords, mons)):
+        alone = mmpde5_batch([xy], [mon], tol=0.0, max_steps=EDGE_STEPS)
+        assert torch.equal(alone.coords[0], mixed.coords[b]), EDGES[b]
+        assert alone.measure.item() == mixed.measure[b].item() and alone.steps.item() == EDGE_STEPS, EDGES[b]
 
 
 def test_reference_signatures(gpu_device):

@@ -167,3 +167,42 @@ def test_noise_targets_are_unchanged(kind):
     assert _digest(make()) == RECORDED[kind]                 # the default is today's data, bit for bit
     assert _digest(make(target='noise')) == RECORDED[kind]
     assert not hasattr(make().samples[0], 'ma_its')
+
+
+# ---------------------------------------------------------------- the wave and workgroup edges of test_gpu_mmpde5.py
+EDGE_1D = (3, 4, 63, 64, 65, 128, 129, 1023, 1024)        # 1 wave, 1 / 2 / 3 waves with the last nearly empty, 16 waves
+EDGE_2D = (3, 7, 8, 9, 16, 17, 31, 32)                    # 9, 49, 64, 81, 256, 289, 961, 1024 nodes
+EDGE_STEPS = 50
+
+
+def edge_case(dim, N):
+    """Uniform start and a random constant monitor (1 + rand at the cells, constant at the nodes), as
+    test_alone_and_in_a_mixed_batch_bit_identical builds them.  The RK4 step is the default cfl / N^3 at every size."""
+    g = torch.Generator().manual_seed(10 * N + dim)
+    lin = torch.linspace(0, 1, N)
+    if dim == 1:
+        return lin, (1 + torch.rand(N - 1, generator=g), torch.ones(N))
+    return torch.stack(torch.meshgrid(lin, lin, indexing='ij')), (1 + torch.rand(N - 1, N - 1, generator=g), torch.ones(N, N) * 1.5)
+
+
+_edge = {}
+
+
+def edge_restated(dim, N, dtype):
+    """(Z, measure) of the restatement after EDGE_STEPS steps with tol = 0, computed once per session."""
+    if (dim, N, dtype) not in _edge:
+        z0, (ms, m2) = edge_case(dim, N)
+        z, j, measure = R.mmpde5(z0, ms, m2, dtype=dtype, tol=0, max_steps=EDGE_STEPS)
+        assert j == EDGE_STEPS
+        _edge[(dim, N, dtype)] = (z, measure)
+    return _edge[(dim, N, dtype)]
+
+
+@pytest.mark.parametrize('dim,N', [(1, n) for n in EDGE_1D] + [(2, n) for n in EDGE_2D])
+def test_edge_cases_move_in_fifty_default_steps(dim, N):
+    """A comparison after 50 steps means something only if the nodes have moved by more than rounding: the fp64 restatement
+    moves some node by at least 100 spacings of fp32 at 1.0 (measured: 184 at N = 1024 in 1-D, the least; 5e4 at 32 x 32)."""
+    z0, _ = edge_case(dim, N)
+    z, measure = edge_restated(dim, N, torch.float64)
+    assert bool(torch.isfinite(z).all()) and measure > 0
+    assert (z - z0.double()).abs().max().item() >= 100 * 2.0 ** -23
