@@ -11,7 +11,7 @@ OBJDIR     := build/obj
 LIB        := g_adaptivity_amd/libgadapt_hip.so
 FEM_CSRC   := g_adaptivity_amd/fem_csrc
 FEM_LIB    := g_adaptivity_amd/libgadapt_fem.so
-FEM_OBJS   := $(OBJDIR)/fem_kernels.o $(OBJDIR)/fem1d_kernels.o $(OBJDIR)/spline_kernels.o $(OBJDIR)/fem_topology.o
+FEM_OBJS   := $(OBJDIR)/fem_kernels.o $(OBJDIR)/fem1d_kernels.o $(OBJDIR)/spline_kernels.o $(OBJDIR)/descent_kernels.o $(OBJDIR)/fem_topology.o
 MESH_CSRC  := g_adaptivity_amd/mesh_csrc
 MESH_LIB   := g_adaptivity_amd/libgadapt_mesh.so
 HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-variable -Wno-unused-but-set-variable -Wno-unused-function $(EXTRA)
@@ -38,6 +38,10 @@ $(OBJDIR)/fem1d_kernels.o: $(FEM_CSRC)/fem1d_kernels.hip $(FEM_CSRC)/fem_common.
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
 $(OBJDIR)/spline_kernels.o: $(FEM_CSRC)/spline_kernels.hip include/gadapt_fem.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+
+$(OBJDIR)/descent_kernels.o: $(FEM_CSRC)/descent_kernels.hip $(FEM_CSRC)/fem_common.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 

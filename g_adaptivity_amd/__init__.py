@@ -10,10 +10,14 @@ Public surface mirrors the reference modules:
     from g_adaptivity_amd import evaluate_model_fine, eval_grid_MMPDE_MA, poisson_eval_errors   # the Poisson error-reduction tables
     from g_adaptivity_amd import evaluate_model_fine_burgers, evaluate_model_fine_burgers_time_step   # the Burgers one-step and rollout tables
     from g_adaptivity_amd import cubic_spline_1d            # batched not-a-knot cubic splines (scipy's UnivariateSpline(s=0))
+    from g_adaptivity_amd import backFEM_2D, backFEM_1D, Fixed_Mesh_2D, Fixed_Mesh_1D, get_model   # the network-free baselines
+    from g_adaptivity_amd import mesh_descent_2d, mesh_descent_1d   # their loop: SGD of the mesh nodes on the FEM error, one call
 The arithmetic lives in `libgadapt_hip.so` (csrc/, C-ABI in include/gadapt_hip.h) and, for the FEM tail,
 `libgadapt_fem.so` (fem_csrc/, include/gadapt_fem.h); the MMPDE5 generator in `libgadapt_mesh.so` (mesh_csrc/, include/gadapt_mesh.h).
 """
+from .baselines import Fixed_Mesh_1D, Fixed_Mesh_2D, backFEM_1D, backFEM_2D, get_model
 from .conv import GAT_conv, GAT_plus, GCN_conv, GRAND_conv, GRAND_plusConv, TRANS_conv
+from .descent import DescentResult, mesh_descent_1d, mesh_descent_2d
 from .evaluation import (calculate_error_reduction, eval_grid_MMPDE_MA, evaluate_error_np, evaluate_error_np_2d, evaluate_model_fine,
                          poisson_eval_errors)
 from .evaluation_burgers import burgers_project, evaluate_model_fine_burgers, evaluate_model_fine_burgers_time_step
@@ -27,7 +31,7 @@ from .mesh_graph import (DeviceMeshLoader, MeshData, MeshDataset, MeshLoader, Mi
                          square_mesh, synthetic_batch)
 from .mmpde5 import (MMPDE5_1d, MMPDE5_1d_burgers, MMPDE5_2d, deform_mesh_mmpde1d, deform_mesh_mmpde2d, mmpde5_batch, monitor_1d,
                      monitor_2d)
-from .params import hot_path_opt
+from .params import hot_path_opt, model_defaults
 from .spline import cubic_spline_1d
 from .training import GraphedTrainStep
 
@@ -40,4 +44,5 @@ __all__ = ['GNN', 'MLP', 'get_conv', 'build_conv_list', 'get_enc', 'get_dec', 'g
            'mmpde5_batch', 'monitor_1d', 'monitor_2d', 'MMPDE5_1d', 'MMPDE5_2d', 'MMPDE5_1d_burgers', 'deform_mesh_mmpde1d',
            'deform_mesh_mmpde2d', 'poisson_eval_errors', 'eval_grid_MMPDE_MA', 'evaluate_model_fine', 'evaluate_error_np',
            'evaluate_error_np_2d', 'calculate_error_reduction', 'cubic_spline_1d', 'evaluate_model_fine_burgers',
-           'evaluate_model_fine_burgers_time_step', 'burgers_project']
+           'evaluate_model_fine_burgers_time_step', 'burgers_project', 'backFEM_2D', 'backFEM_1D', 'Fixed_Mesh_2D', 'Fixed_Mesh_1D',
+           'get_model', 'mesh_descent_2d', 'mesh_descent_1d', 'DescentResult', 'model_defaults']

@@ -41,7 +41,10 @@ PROTOTYPES = {
     'gadapt_fem1d_poisson_backward': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P] * 6),
     'gadapt_fem1d_expand': (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P]),
     'gadapt_fem1d_spline': (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
+    'gadapt_fem_descend': (_I, [_I, _I, _I] + [_P] * 14 + [_I, _I, _I, _I, _F] + [_P] * 16),
+    'gadapt_fem1d_descend': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P, _I, _F, _I, _I] + [_P] * 11),
 }
+DESCEND_INTERNAL, DESCEND_ALL = 0, 1       # GADAPT_FEM1D_DESCEND_*
 SPLINE_OK, SPLINE_NOT_INCREASING, SPLINE_NOT_FINITE, SPLINE_BAD_COUNT = 0, 1, 2, 3   # GADAPT_SPLINE_S_*
 
 _lib = None

@@ -9,6 +9,26 @@ reference's argparse front end.
 """
 from __future__ import annotations
 
+BASELINE_MODEL_NAMES = ('fixed_mesh_1D', 'fixed_mesh_2D', 'backFEM_1D', 'backFEM_2D')
+
+
+def model_defaults(model: str, mesh_dims=None) -> dict:
+    """The reference's per-model settings for the network-free baselines (`src/params.py:73-104`); {} for any other model."""
+    if model == 'fixed_mesh_1D':                 # params.py:73-76 (its loss_type line is a comparison: nothing is set)
+        return {'solver': 'firedrake', 'evaler': 'analytical'}
+    if model == 'fixed_mesh_2D':                 # params.py:78-81
+        return {'solver': 'firedrake', 'evaler': 'analytical', 'loss_type': 'mesh_loss'}
+    if model == 'backFEM_1D':                    # params.py:83-96: the more nodes, the smaller lr must be to stop crossing
+        out = {'loss_type': 'pde_loss', 'solver': 'torch_FEM', 'evaler': 'analytical', 'mesh_params': 'internal', 'epochs': 10}
+        lr = {11: 0.05, 21: 0.01, 51: 0.001}.get(int(mesh_dims[0])) if mesh_dims else None
+        if lr is not None:
+            out['lr'] = lr
+        return out
+    if model == 'backFEM_2D':                    # params.py:98-104
+        return {'loss_type': 'pde_loss', 'evaler': 'analytical', 'solver': 'torch_FEM', 'epochs': 200, 'lr': 0.2,
+                'load_quad_points': 101}
+    return {}
+
 
 def hot_path_opt(**overrides) -> dict:
     opt = {
@@ -53,5 +73,8 @@ def hot_path_opt(**overrides) -> dict:
         # top gradient (the literal GNN.py:270,299 data flow) instead of their compact forms
         'compact_slots': True,
     }
+    if overrides.get('model') in BASELINE_MODEL_NAMES:     # read only when a baseline is named; explicit overrides still win
+        opt.update(stiff_quad_points=3, load_quad_points=101)                            # params.py:69-70
+        opt.update(model_defaults(overrides['model'], overrides.get('mesh_dims', opt['mesh_dims'])))
     opt.update(overrides)
     return opt

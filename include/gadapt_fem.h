@@ -223,6 +223,49 @@ int gadapt_fem1d_expand(int n_meshes, int max_nodes, const int32_t* node_off, co
 int gadapt_fem1d_spline(int n_sets, int max_nodes, const int32_t* set_off, const float* x, const float* y, int n_queries,
                         const float* q, const int32_t* q_off, int deriv, float* out, int32_t* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ mesh descent
+ * The reference's backFEM baselines (train_step_adjoint, difFEM_2d.py:593-685; train_step_vec, difFEM_1d.py:241-292): gradient
+ * descent of the node coordinates themselves on the FEM error, plain SGD, no network (fem_csrc/descent_kernels.hip).  One call
+ * enqueues every epoch on the caller's stream: it neither synchronises nor allocates, and the host waits for nothing.  These
+ * entry points were added without changing GADAPT_FEM_ABI (no existing signature changed).
+ *
+ * 2-D.  Arguments as gadapt_fem_modular_forward and gadapt_fem_backward (all their outputs and work buffers are the caller's,
+ * with their sizes), and
+ *   x [N,2]            in: the starting coordinates; out: the coordinates after `epochs` steps
+ *   x_ref [N,2]        the mesh whose triangle orientations count as untangled; NULL: the starting coordinates
+ *   epochs, lr         epoch j: the four launches of gadapt_fem_modular_forward (reduction GADAPT_FEM_LOSS_SIMPSON), the four of
+ *                      gadapt_fem_backward (g_coeffs = NULL), then one step launch, a workgroup per mesh: x -= lr * gx on
+ *                      interior nodes (the product rounded before the subtraction, as torch.optim.SGD); boundary nodes are not
+ *                      touched.  epochs == 0 launches only the orientation pass.
+ *   loss_hist [E,B]    loss of epoch j, i.e. on the mesh before that epoch's step (may be NULL when epochs == 0)
+ *   mesh_hist [E,N,2]  coordinates after each step, or NULL
+ *   first_tangled [B]  the first epoch after whose step min_t D_t(x) sign(D_t(x_ref)) <= 0 or NaN, D twice the signed triangle
+ *                      area as the stiffness computes it; -1 if none.  The descent goes on regardless (as the reference, whose
+ *                      FEM uses |D|).
+ *   min_area [B]       that minimum after the latest step, kept from the first tangled epoch on; +inf before any step
+ *   sign [T]           int8 scratch: the orientations on x_ref, written by a launch before epoch 0
+ * coeffs, sol, loss, gx, ... are left as the last epoch's launches wrote them: coeffs is the solve on the mesh BEFORE the last
+ * step (the reference returns that one too). */
+int gadapt_fem_descend(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                       const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                       const int32_t* nt_idx, const int32_t* gptr, const float* gpar, float* x, const float* x_ref, const float* lat_x,
+                       const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int epochs, float lr, float* rhs, float* coeffs,
+                       float* lfac, float* sol, float* loss, float* g_sol, float* gc, float* mu, float* tgrad, float* gx,
+                       float* loss_hist, float* mesh_hist, int32_t* first_tangled, float* min_area, int8_t* sign, void* stream);
+
+/* 1-D.  Epoch j: gadapt_fem1d_poisson_forward, the seed launch (loss [B] = torch.trapezoid((sol - u_true)^2, pts), the loss of
+ * gradient_meshpoints_1D's PDE_loss_direct_L2, and g_sol [B,P] = d loss / d sol), gadapt_fem1d_poisson_backward, the step.
+ *   mesh_params  INTERNAL: nodes 1..n-2 move.  ALL: every node moves, then the mesh is rescaled to (x - min) / (max - min) and
+ *                its ends are set to 0 and 1 (difFEM_1d.py:273-279; it is not sorted).
+ *   n_nodes      N, the node total (the row length of mesh_hist [E,N])
+ *   first_tangled / min_area watch min_i x[i+1] - x[i]; P >= 2; the rest as in 2-D and in the Poisson entry points. */
+#define GADAPT_FEM1D_DESCEND_INTERNAL 0
+#define GADAPT_FEM1D_DESCEND_ALL      1
+int gadapt_fem1d_descend(int n_meshes, int max_nodes, const int32_t* node_off, float* x, const int32_t* gptr, const float* gpar,
+                         int k_load, int k_stiff, int n_pts, const float* pts, int epochs, float lr, int mesh_params, int n_nodes,
+                         float* coeffs, float* sol, int32_t* flags, float* loss, float* g_sol, float* gx, float* loss_hist,
+                         float* mesh_hist, int32_t* first_tangled, float* min_area, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
