@@ -15,7 +15,11 @@ model's output coordinates), loss.npy, grad.npy (the flat gradient the optimizer
 parameter bucket after the update), all float32.  The batch and the initial weights are seeded and the step count before the dump
 is fixed by the arguments, so two builds run with the same arguments can be compared array for array.
 
-Extra objects on the JSON line:
+A plain run does only that: set-up, warm-up, the K timed steps, the dump if asked for, the result line.  Everything else this file
+measures or checks - the objects below - runs after the headline, and only with `--full`; without it their keys are null / empty
+(`full: false` on the line says so).  The `--no-...` switches pick among the `--full` measurements.
+
+Extra objects on the JSON line (`--full`):
   roofline     - dominant hot kernel: algorithmic bytes per launch / its measured
                  duration (HIP events on the launch stream, second instrumented pass of K steps).
   cpu_baseline - the CPU oracle (PyG-equivalent op sequence in plain torch) on the host cores, rank 0, N=1.
@@ -152,6 +156,11 @@ def main():
                          "short A/B in set-up finds faster on one GPU / issued under data parallelism (nothing to capture around the all-reduce)")
     ap.add_argument('--no-fused-step', action='store_true',
                     help='the captured autograd iteration (16 launches) instead of the fused 13-launch iteration (training.FusedIteration)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run every secondary measurement: the other slot flow, GAT_plus, the other BASELINE.json '
+                         'workloads, the instrumented per-kernel / roofline pass, the training loop on changing batches, the CPU baseline and '
+                         '(N > 1) the all-reduce timing.  Off by default: a plain run times the headline only; the --no-... switches below '
+                         'pick among the --full measurements')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--dense-slots', action='store_true',
                     help='materialise the zero-padded encoder output, the full last-layer output and the padded top gradient '
@@ -454,7 +463,7 @@ def main():
     # the step issues (FlatAdam.all_reduce on the flat gradient bucket), alone on the stream, event pair around it (RCCL) or host
     # clock around call + synchronisation (other backends); median of 30
     allreduce_us = None
-    if world > 1 and optim.grad_bucket is not None:
+    if args.full and world > 1 and optim.grad_bucket is not None:
         samples = []
         for _ in range(35):
             barrier(); torch.cuda.synchronize()
@@ -474,7 +483,7 @@ def main():
     # the other slot flow in the same run: the headline's compact slots follow the identity encoder's
     # zero-pad contract; the dense flow is the literal one SURVEY.md 8(d)'s bytes describe.  Fused GRAND kernels only.
     companion = None
-    if not args.no_companion and w['conv'] in ('GRAND', 'GRAND_plus'):
+    if args.full and not args.no_companion and w['conv'] in ('GRAND', 'GRAND_plus'):
         other = build_runner(not args.dense_slots)
         c_el, c_win = summarise(timed_windows(other['step']))
         companion = {'slots': 'compact' if args.dense_slots else 'dense', 'value': round(meshes / c_el, 1),
@@ -486,7 +495,7 @@ def main():
     # the same mesh batch through the other trainable conv of the operator factory (GNN.py:120-121: conv_type='GAT_plus', the fused block
     # of csrc/gadapt_gat.inc), same step, same timing protocol, fewer windows: on the default line so the driver's record carries it
     gat_plus = None
-    if rank == 0 and world == 1 and not args.no_gat_plus and args.workload == 'poisson2d_64x64_b32_L4_C64' and not args.dense_slots:
+    if args.full and rank == 0 and world == 1 and not args.no_gat_plus and args.workload == 'poisson2d_64x64_b32_L4_C64' and not args.dense_slots:
         wg = WORKLOADS['poisson2d_64x64_b32_L4_C64_GAT_plus']
         other = build_runner(False, wg)
         g_el, g_win = summarise(timed_windows(other['step'], min(args.windows, 3)))
@@ -581,13 +590,13 @@ def main():
         return kernels, roofline
 
     roofline, kernels = None, {}
-    if rank == 0:
+    if args.full and rank == 0:
         kernels, roofline = instrument(main_run, w, args.workload)
 
     # ---- the other single-GPU BASELINE.json configurations on the same line: same step, same timing protocol, two
     # windows, their own instrumented pass; no second slot flow, no CPU leg.  Default workload, one GPU only.
     other_workloads = None
-    if rank == 0 and world == 1 and not args.no_other_workloads and args.workload == 'poisson2d_64x64_b32_L4_C64' and not args.dense_slots:
+    if args.full and rank == 0 and world == 1 and not args.no_other_workloads and args.workload == 'poisson2d_64x64_b32_L4_C64' and not args.dense_slots:
         other_workloads = {}
         for name in OTHER_BASELINE_WORKLOADS:
             wo = WORKLOADS[name]
@@ -641,7 +650,7 @@ def main():
     # (training.GraphedTrainStep), the loader gathering the next batch into the captured buffers.  Reported beside the headline,
     # which replays ONE static batch: the difference is the batch assembly (one launch) and the Python loop.
     train_loop = None
-    if rank == 0 and world == 1 and not args.no_train_loop and not args.no_graph and w['conv'] in ('GRAND', 'GRAND_plus', 'GAT_plus'):
+    if args.full and rank == 0 and world == 1 and not args.no_train_loop and not args.no_graph and w['conv'] in ('GRAND', 'GRAND_plus', 'GAT_plus'):
         from g_adaptivity_amd import DeviceMeshLoader, GraphedTrainStep
         n_batches = 8
         tds = MeshDataset([w['n'], w['n']], n_batches * w['batch'], seed=1)
@@ -683,7 +692,7 @@ def main():
     # cost is linear in the meshes), a short sweep over thread counts (index_add_ / scatter ops stop scaling early), then
     # >= 10 timed steps at the best count.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.pyg_restatement import OracleGNN
         sub = max(1, w['batch'] // 4)
         cdata = collate(ds.samples[:sub])
@@ -744,7 +753,7 @@ def main():
             'metric': 'meshes/sec fwd+bwd, 2D Poisson 64x64 mesh graph, batch 32, 1/2/4/8 GPU',
             'value': round(value, 1), 'unit': 'meshes/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': round(1e3 * elapsed / args.steps, 4), 'windows': windows, 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'full': args.full,
             'config': {'workload': args.workload, 'mesh': f"{w['n']}x{w['n']}", 'meshes_per_gpu': w['batch'],
                        'global_batch': w['batch'] * world, 'mp_layers': w['layers'], 'hidden': w['hidden'],
                        'conv_type': w['conv'], 'parallelism': f'dp{world}',

@@ -190,7 +190,7 @@ def test_two_rank_step_equals_full_batch_step(gpu_device, graphed):
 @pytest.mark.gpu
 @pytest.mark.parametrize("capture_allreduce", [False, True], ids=['eager-collective', 'capture-allreduce-requested'])
 def test_bench_two_ranks_rehearsal(gpu_device, capture_allreduce):
-    """`bench.py --gpus 2` exactly as the driver launches it (torch.distributed.run, one process per rank), rehearsed on the ONE
+    """`bench.py --gpus 2 --full` exactly as the driver launches it (torch.distributed.run, one process per rank), rehearsed on the ONE
     GPU of the test box: GADAPT_BENCH_SHARE_GPU=1 maps both ranks onto it and GADAPT_BENCH_BACKEND=gloo carries the collectives
     (RCCL needs a GPU per rank).  The N > 1 launch mode runs: the fused iteration issued as its C-ABI calls - forward + loss + backward,
     chain rule, the all-reduce of the flat gradient, device-stepped Adam.  With GADAPT_BENCH_CAPTURE_ALLREDUCE=1 the collective would be
@@ -203,7 +203,7 @@ def test_bench_two_ranks_rehearsal(gpu_device, capture_allreduce):
     if capture_allreduce:
         env['GADAPT_BENCH_CAPTURE_ALLREDUCE'] = '1'
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
-                        '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2'],
+                        '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', '--full'],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     if r.returncode != 0:                                   # the ranks' tracebacks, where a truncated assertion message cannot hide them
         os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
@@ -229,13 +229,13 @@ def test_bench_two_ranks_rehearsal(gpu_device, capture_allreduce):
 @pytest.mark.one_dispatch
 @pytest.mark.gpu
 def test_bench_gpus_2_starts_its_own_ranks(gpu_device):
-    """Plain `python bench.py --gpus 2` - how the driver invokes `--gpus 1` - must start the two ranks itself (a child
+    """`python bench.py --gpus 2` without a launcher - how the driver invokes `--gpus 1` - must start the two ranks itself (a child
     torch.distributed.run before anything touches a GPU) and relay ONE JSON line with n_gpus 2, the all-reduce time per step and
     the collective's description.  Rehearsed on the one GPU of the test box (shared GPU, gloo collectives), as above."""
     import math
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(GADAPT_BENCH_SHARE_GPU='1', GADAPT_BENCH_BACKEND='gloo')
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', '--windows', '2', '--no-companion'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', '--full', '--windows', '2', '--no-companion'],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]

@@ -196,11 +196,11 @@ def test_compact_encoder_output_equals_dense(gpu_device):
 @pytest.mark.one_dispatch
 @pytest.mark.gpu
 def test_bench_line_contract(gpu_device):
-    """bench.py prints ONE JSON line with the driver's keys, the roofline object of the dominant kernel group and a
+    """`bench.py --full` prints ONE JSON line with the driver's keys, the roofline object of the dominant kernel group and a
     bounded CPU baseline (run as the driver runs it: a child process, small K / W)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2', '--cpu-seconds', '2'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2', '--full', '--cpu-seconds', '2'],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -211,6 +211,7 @@ def test_bench_line_contract(gpu_device):
         assert k in d, k
     assert d['n_gpus'] == 1 and d['steps'] == 4 and d['warmup'] == 2 and d['unit'] == 'meshes/s' and d['scaling'] == 'weak'
     assert d['vs_baseline'] is None and d['dtype'] == 'f32' and d['data'] == 'synthetic' and 'workload' in d['config']
+    assert d['full'] is True
     rf, cb = d['roofline'], d['cpu_baseline']
     assert rf['bound'] == 'hbm' and rf['peak'] == 8000.0 and abs(rf['frac'] - rf['achieved'] / rf['peak']) < 1e-3 and rf['unit'] == 'GB/s'
     assert cb['kind'] == 'port' and cb['cores'] >= 1 and cb['value'] > 0 and 'sample' in cb
@@ -242,6 +243,39 @@ def test_bench_line_contract(gpu_device):
         for k in ('kernel', 'variant', 'frac', 'avg_launch_us', 'alg_bytes_per_launch', 'profile'):
             assert k in orf, (name, k)
         assert abs(orf['frac'] - orf['alg_bytes_per_launch'] / (orf['avg_launch_us'] * 1e-6) / 8e12) < 2e-3, (name, orf)
+
+
+@pytest.mark.one_dispatch
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean(gpu_device):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` does what its headline needs and nothing else: one JSON line with the headline's
+    keys meaning what they mean under `--full`, every secondary measurement absent (null / empty, `full` false), and at most 30 s of
+    the whole run - a new process, from start to exit - outside its K + W steps."""
+    import json, os, subprocess, sys, time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 4, 2
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup)],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d['metric'] == 'meshes/sec fwd+bwd, 2D Poisson 64x64 mesh graph, batch 32, 1/2/4/8 GPU' and d['unit'] == 'meshes/s'
+    assert d['higher_is_better'] is True and d['dtype'] == 'f32' and d['n_gpus'] == 1 and d['steps'] == steps and d['warmup'] == warmup
+    assert d['value'] > 0 and abs(d['value'] - 32 * 1000.0 / d['ms_per_step']) / d['value'] < 0.01
+    wd = d['windows']
+    assert wd['n'] == 1 and wd['steps_per_window'] == steps and abs(wd['window_ms'] / steps - d['ms_per_step']) < 1e-3
+    assert d['config']['workload'] == 'poisson2d_64x64_b32_L4_C64' and d['config']['slots'] == 'compact' and d['config']['fused_step'] is True
+    assert d['full'] is False
+    for k in ('roofline', 'roofline_mfma', 'cpu_baseline', 'train_loop', 'gat_plus', 'other_workloads'):
+        assert d[k] is None, k
+    assert d['kernels'] == {}
+    assert not [k for k in d if k.endswith('_dense_slots') or k.endswith('_compact_slots')]
+    outside = wall - (steps + warmup) * 1e-3 * d['ms_per_step']
+    print(f"plain bench run: {wall:.2f} s in all, {outside:.2f} s outside its {steps + warmup} steps")
+    assert outside <= 30.0, (wall, d['ms_per_step'])
 
 
 @pytest.mark.one_dispatch

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 for lib in build/variants/*.so; do
   out=gpurun_out/ab_small_$(basename $lib .so)
-  GADAPT_LIB=$PWD/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
+  GADAPT_LIB=$PWD/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > /dev/null 2>&1
   echo "== $lib"; python3 - "$out" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + '/**/*kernel_stats.csv', recursive=True)[0]

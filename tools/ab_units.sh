@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-.}
 WL=$1; shift
 for V in base "$@"; do
   LIBV=""; [ "$V" != base ] && LIBV="variants/$V.so"
-  GADAPT_LIB=$LIBV timeout -k 10 200 python bench.py --workload $WL --steps 30 --warmup 5 --no-cpu-baseline --no-companion --no-train-loop --no-other-workloads --no-gat-plus \
+  GADAPT_LIB=$LIBV timeout -k 10 200 python bench.py --workload $WL --steps 30 --warmup 5 --full --no-cpu-baseline --no-companion --no-train-loop --no-other-workloads --no-gat-plus \
       > gpurun_out/ab_$V.json 2> gpurun_out/ab_$V.err
   python - "$V" <<'PY'
 import json, sys

@@ -4,7 +4,7 @@ WL=${WL:-"poisson2d_64x64_b32_L4_C64 burgers2d_64x64_b32_L6_C128 euler20_128x128
 for rep in 1 2; do
 for w in $WL; do
   for lib in build/variants/*.so; do
-    GADAPT_LIB=$PWD/$lib timeout -k 10 200 python bench.py --workload $w --steps ${STEPS:-100} --warmup 10 --no-cpu-baseline 2>/dev/null | python -c "
+    GADAPT_LIB=$PWD/$lib timeout -k 10 200 python bench.py --workload $w --steps ${STEPS:-100} --warmup 10 --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); k=d.get('kernels',{})
 print('$w', '$lib', 'ms/step', d['ms_per_step'], 'meshes/s', d['value'], {n:k[n]['avg_us'] for n in k})"
