@@ -31,6 +31,9 @@ PROTOTYPES = {
     'gadapt_fem_forward': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 5),
     'gadapt_fem_eval_partials_floats': (_I, [_I]),
     'gadapt_fem_eval_errors': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 6),
+    'gadapt_fem_window_lds_bytes': (_L, [_I, _I]),
+    'gadapt_fem_window_workspace_floats': (_L, [_I, _P]),
+    'gadapt_fem_eval_errors_window': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 3 + [_I] + [_P] * 3),
     'gadapt_fem_modular_forward': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I, _I] + [_P] * 7),
     'gadapt_fem_backward': (_I, [_I, _I, _I] + [_P] * 13 + [_I, _I] + [_P] * 9),
     'gadapt_fem1d_lds_bytes': (_L, [_I, _I]),

@@ -19,7 +19,8 @@ device.  A mesh's pair of norms does not depend on what else is in the batch.  T
 in fp64 (the fp32 matrix of `fem_poisson_1d` moves these norms by up to 3e-4: docs/measurements.md), the rest is that forward.
 
 Limits: `solver='torch_FEM'` with `evaler='analytical'` only (the others need Firedrake); `fine_eval=True` only; the FEM
-tail's mesh sizes (2-D: square meshes up to 26 x 26 nodes, the load vector's built Simpson rule; 1-D: 1024 nodes).
+tail's mesh sizes (2-D: square meshes up to 26 x 26 nodes, or up to 81 x 81 with opt['fem_band'] = 'window', the windowed
+band solve of `poisson_eval_errors(band='window')`; the load vector's built Simpson rule; 1-D: 1024 nodes).
 """
 from __future__ import annotations
 
@@ -32,7 +33,7 @@ import torch
 
 from . import _native_fem as _nf
 from ._native import NativeError, current_stream
-from .fem import _topology, _tri_counts, pack_gaussians, simpson_points_per_dim
+from .fem import BAND_ROUTES, _topology, _tri_counts, pack_gaussians, simpson_points_per_dim
 from .fem1d import _Batch, _split_params, _watch_flags
 from .mesh_graph import MeshData, MeshLoader, Mixed_DataLoader
 
@@ -83,18 +84,31 @@ def eval_lattice(n_eval: int) -> torch.Tensor:
 
 def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params: Sequence[dict], n_eval: int, *,
                         cells: Optional[torch.Tensor] = None, boundary: Optional[torch.Tensor] = None,
-                        tri_counts: Optional[Sequence[int]] = None, opt: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                        tri_counts: Optional[Sequence[int]] = None, opt: Optional[dict] = None, band: str = 'lds',
+                        tri_slab: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """(L1 [B], L2 [B]) on the device: per mesh, the P1 Poisson solve with its own Gaussians, expanded on the lattice
     linspace(0, 1, n_eval) per dimension, and the trapezium norms of sol - u_true there.
 
     x [N,2]: 2-D meshes, concatenated; cells [T,3] (global node ids, mesh by mesh), boundary [N] and tri_counts as
     `fem_poisson` takes them, its topology cache reused.  x [N] or [N,1]: 1-D meshes; opt supplies load_quad_points /
     stiff_quad_points as `fem_poisson_1d` reads them.  In 2-D opt['load_quad_points'], when given, must map to the built
-    Simpson rule.  GPU tensors only; no gradient."""
+    Simpson rule.  GPU tensors only; no gradient.
+
+    band (2-D only; 1-D input ignores it): 'lds' keeps each mesh's banded factor resident in LDS (square meshes up to
+    26 x 26 nodes); 'window' streams it through a ring of band rows and a global workspace allocated here (fp64, about
+    2 MB per 64 x 64 mesh), and takes the triangles in slabs of `tri_slab` ids (a multiple of 32; 0: the largest slab the
+    LDS budget leaves): square meshes up to 81 x 81 nodes.  The windowed route factors and substitutes in fp64 and evaluates
+    the load vector's forcing in fp64 (fp32 missed the evaluation's accuracy rule from 27 x 27 on), so where both routes take
+    a mesh their norms agree to the fp32 rounding of those, not bitwise; the result does not depend on `tri_slab`, bit for bit."""
     if not torch.is_tensor(x) or not x.is_cuda:
         raise NativeError(f"poisson_eval_errors: the FEM tail runs on the MI355X only (got a "
                           f"{x.device if torch.is_tensor(x) else type(x).__name__} tensor); there is no CPU fallback")
     opt = opt or {}
+    if band not in BAND_ROUTES:
+        raise ValueError(f"poisson_eval_errors: band must be one of {BAND_ROUTES} (got {band!r})")
+    tri_slab = int(tri_slab)
+    if tri_slab < 0 or tri_slab % 32:
+        raise ValueError(f"poisson_eval_errors: tri_slab must be 0 or a positive multiple of 32 (got {tri_slab})")
     n_eval = int(n_eval)
     if n_eval < 2:
         raise ValueError(f"poisson_eval_errors: {n_eval} lattice points per dimension; at least 2")
@@ -115,18 +129,28 @@ def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params:
         x = x.contiguous()
         if tri_counts is None:
             tri_counts = _tri_counts(cells, node_counts)
-        topo = _topology(cells, boundary, node_counts, tri_counts, dev)       # refuses meshes beyond the LDS budget (26 x 26)
+        topo = _topology(cells, boundary, node_counts, tri_counts, dev, band)  # refuses meshes beyond the route's LDS budget
         if topo.n_nodes != x.shape[0]:
             raise ValueError(f"poisson_eval_errors: {x.shape[0]} coordinates for {topo.n_nodes} nodes")
         gptr, gpar = pack_gaussians(pde_params, dev)
         d, N = topo.dev, topo.n_nodes
         rhs, coeffs = torch.empty(N, device=dev), torch.empty(N, device=dev)
         partials = torch.empty(int(lib.gadapt_fem_eval_partials_floats(B)), device=dev)
-        _nf.check(lib.gadapt_fem_eval_errors(
-            B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
-            d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(), x.data_ptr(),
-            lat.data_ptr(), lat.data_ptr(), n_eval, topo.lds_bytes, topo.max_tris, rhs.data_ptr(), coeffs.data_ptr(), None,
-            partials.data_ptr(), err.data_ptr(), stream), 'gadapt_fem_eval_errors')
+        if band == 'window':
+            meta = topo.host['meta']
+            work = torch.empty(max(int(lib.gadapt_fem_window_workspace_floats(B, meta.ctypes.data)), 1), device=dev)
+            _nf.check(lib.gadapt_fem_eval_errors_window(
+                B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
+                d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(),
+                x.data_ptr(), lat.data_ptr(), lat.data_ptr(), n_eval, topo.lds_bytes, topo.max_tris, rhs.data_ptr(),
+                coeffs.data_ptr(), work.data_ptr(), tri_slab, partials.data_ptr(), err.data_ptr(), stream),
+                'gadapt_fem_eval_errors_window')
+        else:
+            _nf.check(lib.gadapt_fem_eval_errors(
+                B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
+                d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(),
+                x.data_ptr(), lat.data_ptr(), lat.data_ptr(), n_eval, topo.lds_bytes, topo.max_tris, rhs.data_ptr(),
+                coeffs.data_ptr(), None, partials.data_ptr(), err.data_ptr(), stream), 'gadapt_fem_eval_errors')
     elif x.dim() == 1 or (x.dim() == 2 and x.shape[1] == 1):
         x = x.reshape(-1).contiguous()
         if sum(int(n) for n in node_counts) != x.shape[0]:
@@ -203,6 +227,7 @@ def _errors_of(coords: Sequence[torch.Tensor], samples: Sequence[MeshData], n_ev
     counts = [int(c.shape[0]) for c in coords]
     x = torch.cat([c.detach().to(dev, non_blocking=True).float().reshape(c.shape[0], -1) for c in coords], 0)
     params = [s.pde_params for s in samples]
+    band = opt.get('fem_band', 'lds')
     if x.shape[1] == 1:
         l1, l2 = poisson_eval_errors(x, counts, params, n_eval, opt=opt)
     else:
@@ -210,7 +235,7 @@ def _errors_of(coords: Sequence[torch.Tensor], samples: Sequence[MeshData], n_ev
         cells = torch.cat([s.cells.cpu() + int(o) for s, o in zip(samples, off[:-1])], 0)
         boundary = torch.cat([s.boundary_nodes.cpu() for s in samples], 0)
         l1, l2 = poisson_eval_errors(x, counts, params, n_eval, cells=cells, boundary=boundary,
-                                     tri_counts=[int(s.cells.shape[0]) for s in samples], opt=opt)
+                                     tri_counts=[int(s.cells.shape[0]) for s in samples], opt=opt, band=band)
     return torch.stack([l1, l2], 1)
 
 
@@ -289,7 +314,8 @@ def evaluate_model_fine(model, dataset, opt, fine_eval: bool = True, batch_size:
     `poisson_eval_errors` call after the model loop) and the four reductions `calculate_error_reduction(e_grid, e)`.
 
     The model runs in eval mode without gradients through `MeshLoader`, or `Mixed_DataLoader` for
-    `opt['data_type'] == 'randg_mix'`; `loss_type` 'mesh_loss' and 'modular' return the coordinates, 'pde_loss' the triple
+    `opt['data_type'] == 'randg_mix'`; `opt.get('fem_band', 'lds')` picks the FEM route of every `poisson_eval_errors` call
+    here and in `eval_grid_MMPDE_MA` ('window': meshes beyond 26 x 26 nodes); `loss_type` 'mesh_loss' and 'modular' return the coordinates, 'pde_loss' the triple
     whose second entry they are.  `opt['overfit_num']`, when set, lists the sample indices to evaluate.  With `batch_size=1`
     the model is called once per sample and `MLmodel_time` is `model.end_MLmodel - start` as in the reference (the forward
     waits for the device before it stamps); with a larger `batch_size` it is the batch's time divided by the batch's size.

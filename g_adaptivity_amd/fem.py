@@ -30,6 +30,12 @@ __all__ = ['FemTopology', 'fem_poisson', 'torch_FEM_2D', 'boundary_from_cells', 
            'modular_loss_2d', 'simpson_points_per_dim', 'GRAD_TYPES_2D']
 
 
+BAND_ROUTES = ('lds', 'window')
+# appended to the refusals of the resident-band route
+WINDOW_HINT = ("; the evaluation (poisson_eval_errors, evaluate_model_fine) takes larger meshes with band='window' "
+               "(opt['fem_band'] = 'window')")
+
+
 def _require_gpu(t: torch.Tensor, what: str):
     if not t.is_cuda:
         raise NativeError(f"{what}: the FEM tail runs on the MI355X only (got a {t.device} tensor); there is no CPU fallback")
@@ -51,7 +57,13 @@ def boundary_from_cells(cells: np.ndarray, n_nodes: int) -> np.ndarray:
 class FemTopology:
     """Interior numbering, band and node -> triangle CSR of a batch (gadapt_fem_topology_host), on the device."""
 
-    def __init__(self, cells: np.ndarray, boundary: np.ndarray, node_counts: Sequence[int], tri_counts: Sequence[int], device):
+    def __init__(self, cells: np.ndarray, boundary: np.ndarray, node_counts: Sequence[int], tri_counts: Sequence[int], device,
+                 band: str = 'lds'):
+        """band='lds': each mesh's banded factor and the evaluation's bin mask must fit the LDS budget (every FEM tail).
+        band='window': the ring of the windowed solve must (the evaluation-only route of `poisson_eval_errors`: square meshes
+        up to 81 x 81 nodes); `lds_bytes` is then the ring's."""
+        if band not in BAND_ROUTES:
+            raise ValueError(f"FEM topology: band must be one of {BAND_ROUTES} (got {band!r})")
         lib = _nf.lib()
         B = len(node_counts)
         cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
@@ -73,18 +85,27 @@ class FemTopology:
         self.n_meshes, self.n_nodes, self.n_tris = B, N, T
         self.n_int = meta[:, _nf.M_N_INT].copy()
         self.band = meta[:, _nf.M_BAND].copy()
+        self.route = band
         budget = int(lib.gadapt_fem_lds_budget())
-        need = [int(lib.gadapt_fem_factor_lds_bytes(int(n), int(w))) for n, w in zip(self.n_int, self.band)]
-        if max(need) > budget:
-            b = int(np.argmax(need))
-            raise NotImplementedError(f"pde_loss FEM tail: mesh {b} ({int(node_counts[b])} nodes, {int(self.n_int[b])} interior, "
-                                      f"half-bandwidth {int(self.band[b])}) needs {need[b]} B of LDS for its banded factor; the "
-                                      f"limit is {budget} B (square meshes up to 26 x 26 nodes)")
         self.max_tris = int(max(tri_counts))
-        eval_need = int(lib.gadapt_fem_eval_lds_bytes(self.max_tris))
-        if eval_need > budget:
-            raise NotImplementedError(f"pde_loss FEM tail: {self.max_tris} triangles per mesh need {eval_need} B of LDS for the "
-                                      f"evaluation's bin mask; the limit is {budget} B")
+        if band == 'window':
+            need = [int(lib.gadapt_fem_window_lds_bytes(int(n), int(w))) for n, w in zip(self.n_int, self.band)]
+            if max(need) > budget:
+                b = int(np.argmax(need))
+                raise NotImplementedError(f"windowed FEM solve: mesh {b} ({int(node_counts[b])} nodes, {int(self.n_int[b])} interior, "
+                                          f"half-bandwidth {int(self.band[b])}) needs {need[b]} B of LDS for its ring of band rows; "
+                                          f"the limit is {budget} B (square meshes up to 81 x 81 nodes)")
+        else:
+            need = [int(lib.gadapt_fem_factor_lds_bytes(int(n), int(w))) for n, w in zip(self.n_int, self.band)]
+            if max(need) > budget:
+                b = int(np.argmax(need))
+                raise NotImplementedError(f"pde_loss FEM tail: mesh {b} ({int(node_counts[b])} nodes, {int(self.n_int[b])} interior, "
+                                          f"half-bandwidth {int(self.band[b])}) needs {need[b]} B of LDS for its banded factor; the "
+                                          f"limit is {budget} B (square meshes up to 26 x 26 nodes)" + WINDOW_HINT)
+            eval_need = int(lib.gadapt_fem_eval_lds_bytes(self.max_tris))
+            if eval_need > budget:
+                raise NotImplementedError(f"pde_loss FEM tail: {self.max_tris} triangles per mesh need {eval_need} B of LDS for the "
+                                          f"evaluation's bin mask; the limit is {budget} B" + WINDOW_HINT)
         self.lds_bytes = max(need)
         self.host = dict(meta=meta, cells=cells, node_mesh=node_mesh, tri_mesh=tri_mesh, int_idx=int_idx, int_node=int_node,
                          nt_ptr=nt_ptr, nt_idx=nt_idx, boundary=bnd.astype(bool))
@@ -95,12 +116,12 @@ class FemTopology:
 _topo_cache: Dict[Tuple, FemTopology] = {}
 
 
-def _topology(cells: torch.Tensor, boundary: torch.Tensor, node_counts, tri_counts, device) -> FemTopology:
+def _topology(cells: torch.Tensor, boundary: torch.Tensor, node_counts, tri_counts, device, band: str = 'lds') -> FemTopology:
     key = (tuple(int(n) for n in node_counts), tuple(int(t) for t in tri_counts), str(device),
-           content_fingerprint([cells, boundary]))
+           content_fingerprint([cells, boundary]), band)
     topo = _topo_cache.get(key)
     if topo is None:
-        topo = FemTopology(cells.detach().cpu().numpy(), boundary.detach().cpu().numpy(), node_counts, tri_counts, device)
+        topo = FemTopology(cells.detach().cpu().numpy(), boundary.detach().cpu().numpy(), node_counts, tri_counts, device, band)
         if len(_topo_cache) >= 32:
             _topo_cache.pop(next(iter(_topo_cache)))
         _topo_cache[key] = topo

@@ -716,3 +716,6 @@ extern "C" int gadapt_fem_backward(int B, int N, int T, const int32_t* meta, con
     fem_gather_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, nt_ptr, nt_idx, tgrad, gx);
     return launched("fem_gather_kernel");
 }
+
+// the windowed band solve and slabbed evaluation of band='window' (gadapt_fem_eval_errors_window): same translation unit, new code only
+#include "fem_window_kernels.hip"

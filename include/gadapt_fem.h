@@ -112,6 +112,41 @@ int gadapt_fem_eval_errors(int n_meshes, int n_nodes, int n_tris, const int32_t*
                            int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* partials, float* err,
                            void* stream);
 
+/* The same error norms for meshes whose band does not stay resident (fem_csrc/fem_window_kernels.hip), forward only, four
+ * launches; these entry points were added without changing GADAPT_FEM_ABI (no existing signature changed).
+ *   load        gadapt_fem_forward's load vector with the forcing and the two Simpson sums in fp64 (points, hat function and
+ *               boundary values as there, stored in fp32): the fp32 forcing cancels and alone costs 1.2e-3 of the 64 x 64
+ *               error norm (L1), beyond the evaluation's rule
+ *   solve       one 256-lane workgroup per mesh; a ring of band rows in LDS (the w + 1 rows a column touches, plus as many
+ *               slack rows, at most 64, as the launch's LDS leaves: rows enter the window in groups, one lane assembling each);
+ *               row k of L goes to `work` once column k is eliminated, the forward substitution rides along, the back
+ *               substitution reads the factor back in reverse.  The element terms are the fp32 expressions of
+ *               gadapt_fem_forward's assembly; they are summed into an fp64 ring, and the factor, the stored rows and both
+ *               substitutions are fp64 (an fp32 ring, bit-identical to gadapt_fem_forward's solve, was 2.6e-4 from the fp64
+ *               yardstick in L1 at 27 x 27, beyond the evaluation's 2e-4 rule): coeffs differ from gadapt_fem_forward's in
+ *               the last digits.
+ *   evaluation  the triangles of a mesh in slabs of tri_slab ids (a multiple of 32; 0: the largest slab the budget leaves
+ *               beside the chunk's running sums, 1888 triangles at nlat = 101); the bin mask is rebuilt per slab and a
+ *               lattice point's sum runs on over the slabs, so in increasing triangle id as in gadapt_fem_eval_errors: err
+ *               does not depend on tri_slab, bit for bit.  partials and the last launch are those of gadapt_fem_eval_errors.
+ *   gadapt_fem_window_lds_bytes(n_int, band)   the ring's least LDS: pair table, max(band + 1, 2) fp64 rows (padded to an
+ *               even length) and their right-hand side.  Within GADAPT_FEM_LDS_BUDGET up to band 79: square meshes up to
+ *               81 x 81 nodes (64 x 64, band 62: 40 572 B).  128 x 128 (band 126, 159 KB) is refused: GADAPT_FEM_E_LDS.
+ *   gadapt_fem_window_workspace_floats(B, meta)   host, from the HOST copy of meta: the floats of `work` (caller-owned, 8-byte
+ *               aligned, no initialisation needed): 2 sum_b n_int[b] * (band[b] + 2), i.e. per mesh n_int fp64 rows of
+ *               band + 1 and the fp64 intermediate y [n_int]; mesh b's part starts at double meta[b, BAND_OFF] + meta[b, INT_OFF].
+ *               1.97 MB per 64 x 64 mesh.
+ *   max_lds_bytes  the largest gadapt_fem_window_lds_bytes of the batch; the launch asks for up to the budget on top of it
+ *   tri_slab < 0 or not a multiple of 32: GADAPT_FEM_E_BADARG; a slab whose mask exceeds the budget: GADAPT_FEM_E_LDS.
+ * The other arguments as gadapt_fem_eval_errors.  Everything is checked before the first launch. */
+int64_t gadapt_fem_window_lds_bytes(int n_int, int band);
+int64_t gadapt_fem_window_workspace_floats(int n_meshes, const int32_t* meta);
+int gadapt_fem_eval_errors_window(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells,
+                                  const int32_t* node_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                                  const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
+                                  const float* lat_y, int nlat, int max_lds_bytes, int max_tris, float* rhs, float* coeffs,
+                                  float* work, int tri_slab, float* partials, float* err, void* stream);
+
 /* Lattice-loss reductions of gadapt_fem_modular_forward. */
 #define GADAPT_FEM_LOSS_MSE     0   /* mean over the nlat x nlat lattice of e^2 (F.mse_loss) */
 #define GADAPT_FEM_LOSS_SIMPSON 1   /* torchquad's composite Simpson rule of e^2, y rule per x row, then x (nlat odd, >= 3) */
