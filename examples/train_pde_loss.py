@@ -5,6 +5,7 @@ training meshes 15 and 20).  Prints the loss per epoch and ms per step, split in
 forward / backward.
 
     python examples/train_pde_loss.py --epochs 3 --num_train 32 --batch_size 8
+    python examples/train_pde_loss.py --mesh 64 --band window --num_train 4 --batch_size 2   # beyond 26 x 26: the windowed route
 """
 import argparse
 import os
@@ -23,12 +24,16 @@ def main():
     ap.add_argument('--num_train', type=int, default=32)
     ap.add_argument('--batch_size', type=int, default=8)
     ap.add_argument('--mesh_dims_train', type=int, nargs='+', default=[15, 20])
+    ap.add_argument('--mesh', type=int, default=None, help="one training mesh size instead of --mesh_dims_train")
+    ap.add_argument('--band', choices=['lds', 'window'], default='lds',
+                    help="FEM route (opt['fem_band']): 'lds' keeps the banded factor in LDS (meshes up to 26 x 26), 'window' streams "
+                         "it through a workspace (up to 81 x 81)")
     ap.add_argument('--lr', type=float, default=1e-3)
     a = ap.parse_args()
     dev = torch.device('cuda:0')
-    for n in a.mesh_dims_train:
+    for n in ([a.mesh] if a.mesh else a.mesh_dims_train):
         opt = hot_path_opt(mesh_dims=[n, n], hidden_dim=8, num_layers=4, time_step=0.1, loss_type='pde_loss', loss_fn='l1',
-                           device=str(dev))
+                           device=str(dev), fem_band=a.band)
         ds = MeshDataset([n, n], a.num_train, seed=n, pde_loss_fields=True)
         torch.manual_seed(0)
         model = GNN(ds, opt).to(dev).train()
@@ -48,7 +53,7 @@ def main():
                 e[1].record()
                 xd = x_phys.detach().requires_grad_(True)
                 counts = torch.bincount(dd.batch.cpu()).tolist()
-                coeffs, sol = fem_poisson(xd, dd.cells, dd.boundary_nodes, counts, dd.pde_params, model.quad_points)
+                coeffs, sol = fem_poisson(xd, dd.cells, dd.boundary_nodes, counts, dd.pde_params, model.quad_points, band=a.band)
                 loss = l1_loss(sol.view(-1, 1), dd.u_true_fine_tensor.view(-1, 1))
                 e[2].record()
                 loss.backward()

@@ -13,6 +13,11 @@ per-triangle chain rule, per-node gather).
 
 Limits: 2-D Poisson only; each mesh's banded factor must fit the LDS budget (`gadapt_fem_lds_budget()`, 64 KB: square
 meshes up to 26 x 26 nodes); the evaluation points must be a uniform tensor-product lattice.
+
+band='window' (`fem_poisson`, `modular_loss_2d`; opt['fem_band'] = 'window' for `torch_FEM_2D`, `gnn_pde_tail` and
+`gradient_meshpoints_2D`) takes square meshes up to 81 x 81 nodes: the solve keeps a ring of band rows in LDS and streams the
+fp64 factor through a global workspace, which the autograd node keeps for its adjoint solve in lfac's place
+(gadapt_fem_forward_window, gadapt_fem_modular_forward_window, gadapt_fem_backward_window).  The default stays 'lds'.
 """
 from __future__ import annotations
 
@@ -60,8 +65,8 @@ class FemTopology:
     def __init__(self, cells: np.ndarray, boundary: np.ndarray, node_counts: Sequence[int], tri_counts: Sequence[int], device,
                  band: str = 'lds'):
         """band='lds': each mesh's banded factor and the evaluation's bin mask must fit the LDS budget (every FEM tail).
-        band='window': the ring of the windowed solve must (the evaluation-only route of `poisson_eval_errors`: square meshes
-        up to 81 x 81 nodes); `lds_bytes` is then the ring's."""
+        band='window': the ring of the windowed solve must (`poisson_eval_errors`, `fem_poisson` and `modular_loss_2d` with
+        band='window': square meshes up to 81 x 81 nodes); `lds_bytes` is then the ring's."""
         if band not in BAND_ROUTES:
             raise ValueError(f"FEM topology: band must be one of {BAND_ROUTES} (got {band!r})")
         lib = _nf.lib()
@@ -128,6 +133,22 @@ def _topology(cells: torch.Tensor, boundary: torch.Tensor, node_counts, tri_coun
     return topo
 
 
+def _check_route(what: str, band, tri_slab) -> int:
+    """The route arguments of a FEM tail, before anything is launched: (band, tri_slab) -> tri_slab as an int."""
+    if band not in BAND_ROUTES:
+        raise ValueError(f"{what}: band must be one of {BAND_ROUTES} (got {band!r})")
+    tri_slab = int(tri_slab)
+    if tri_slab < 0 or tri_slab % 32:
+        raise ValueError(f"{what}: tri_slab must be 0 or a positive multiple of 32 (got {tri_slab})")
+    return tri_slab
+
+
+def _workspace(topo: FemTopology, device) -> torch.Tensor:
+    """The windowed solve's workspace (fp64 factor rows and y of every mesh), as the fp32 buffer the C-ABI takes."""
+    floats = int(_nf.lib().gadapt_fem_window_workspace_floats(topo.n_meshes, topo.host['meta'].ctypes.data))
+    return torch.empty(max(floats, 1), device=device)
+
+
 def pack_gaussians(pde_params: Sequence[dict], device) -> Tuple[torch.Tensor, torch.Tensor]:
     """gptr [B+1] int32 and gpar [G,4] fp32 = (c0, c1, s0, s1): per mesh its own number of Gaussians."""
     counts, rows = [0], []
@@ -164,7 +185,7 @@ def lattice_axes(quad_points, device) -> Tuple[torch.Tensor, torch.Tensor]:
 
 class _FemPoisson(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, topo: FemTopology, gptr, gpar, lat_x, lat_y):
+    def forward(ctx, x, topo: FemTopology, gptr, gpar, lat_x, lat_y, tri_slab=0):
         _require_gpu(x, 'FEM node coordinates')
         x = x.contiguous()
         d, dev = topo.dev, x.device
@@ -172,13 +193,21 @@ class _FemPoisson(torch.autograd.Function):
         N, B = topo.n_nodes, topo.n_meshes
         rhs = torch.empty(N, device=dev)
         coeffs = torch.empty(N, device=dev)
-        lfac = torch.empty(topo.band_floats, device=dev)
         sol = torch.empty(B * nlat * nlat, device=dev)
-        _nf.check(_nf.lib().gadapt_fem_forward(
-            B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
-            d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(), x.data_ptr(),
-            lat_x.data_ptr(), lat_y.data_ptr(), nlat, topo.lds_bytes, topo.max_tris, rhs.data_ptr(), coeffs.data_ptr(),
-            lfac.data_ptr(), sol.data_ptr(), current_stream(dev)), 'gadapt_fem_forward')
+        if topo.route == 'window':                               # lfac: the fp64 workspace, kept for the adjoint solve
+            lfac = _workspace(topo, dev)
+            _nf.check(_nf.lib().gadapt_fem_forward_window(
+                B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
+                d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(),
+                x.data_ptr(), lat_x.data_ptr(), lat_y.data_ptr(), nlat, topo.lds_bytes, topo.max_tris, rhs.data_ptr(),
+                coeffs.data_ptr(), lfac.data_ptr(), tri_slab, sol.data_ptr(), current_stream(dev)), 'gadapt_fem_forward_window')
+        else:
+            lfac = torch.empty(topo.band_floats, device=dev)
+            _nf.check(_nf.lib().gadapt_fem_forward(
+                B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
+                d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(),
+                x.data_ptr(), lat_x.data_ptr(), lat_y.data_ptr(), nlat, topo.lds_bytes, topo.max_tris, rhs.data_ptr(),
+                coeffs.data_ptr(), lfac.data_ptr(), sol.data_ptr(), current_stream(dev)), 'gadapt_fem_forward')
         ctx.topo, ctx.nlat = topo, nlat
         ctx.save_for_backward(x, coeffs, lfac, gptr, gpar, lat_x, lat_y)
         return coeffs, sol
@@ -194,13 +223,14 @@ class _FemPoisson(torch.autograd.Function):
         gx = torch.empty(N, 2, device=dev)
         g_coeffs = None if g_coeffs is None else g_coeffs.contiguous().float()
         g_sol = None if g_sol is None else g_sol.contiguous().float()
-        _nf.check(_nf.lib().gadapt_fem_backward(
+        name = 'gadapt_fem_backward_window' if topo.route == 'window' else 'gadapt_fem_backward'
+        _nf.check(getattr(_nf.lib(), name)(
             topo.n_meshes, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['tri_mesh'].data_ptr(),
             d['int_idx'].data_ptr(), d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(),
             gpar.data_ptr(), x.data_ptr(), lat_x.data_ptr(), lat_y.data_ptr(), ctx.nlat, topo.lds_bytes, coeffs.data_ptr(),
             lfac.data_ptr(), None if g_coeffs is None else g_coeffs.data_ptr(), None if g_sol is None else g_sol.data_ptr(),
-            gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), current_stream(dev)), 'gadapt_fem_backward')
-        return gx, None, None, None, None, None
+            gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), current_stream(dev)), name)
+        return gx, None, None, None, None, None, None
 
 
 def _tri_counts(cells: torch.Tensor, node_counts: Sequence[int]) -> List[int]:
@@ -211,28 +241,39 @@ def _tri_counts(cells: torch.Tensor, node_counts: Sequence[int]) -> List[int]:
 
 
 def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
-                pde_params: Sequence[dict], quad_points, tri_counts: Optional[Sequence[int]] = None):
+                pde_params: Sequence[dict], quad_points, tri_counts: Optional[Sequence[int]] = None, band: str = 'lds',
+                tri_slab: int = 0):
     """Batched P1 Poisson solve on the meshes of `x_phys` [N,2] (differentiable wrt x_phys).
 
     cells [T,3] global node ids, mesh by mesh; boundary [N] bool; node_counts per mesh; pde_params per mesh
     ({'centers': [...], 'scales': [...]}, any number of Gaussians); quad_points the evaluation lattice (GNN.quad_points).
-    Returns coeffs [N,1] and sol [B*nlat*nlat] (mesh by mesh, lattice row-major)."""
+    Returns coeffs [N,1] and sol [B*nlat*nlat] (mesh by mesh, lattice row-major).
+
+    band: 'lds' keeps each mesh's banded factor resident in LDS (square meshes up to 26 x 26 nodes); 'window' is the
+    windowed solve of `poisson_eval_errors(band='window')` (fp64 ring, factor and substitutions, fp64 forcing in the load
+    vector; square meshes up to 81 x 81 nodes) with its workspace kept for an fp64 adjoint solve in the backward, and the
+    lattice evaluated over slabs of `tri_slab` triangle ids (a multiple of 32; 0: the largest slab the LDS budget leaves).
+    Where both routes take a mesh their results agree to the rounding of an fp32 solve, not bitwise; the windowed result
+    does not depend on `tri_slab`, bit for bit."""
+    tri_slab = _check_route('pde_loss FEM tail', band, tri_slab)
     _require_gpu(x_phys, 'pde_loss FEM tail')
     if x_phys.dim() != 2 or x_phys.shape[1] != 2:
         raise NotImplementedError(f"pde_loss FEM tail: 2-D meshes only (x_phys {tuple(x_phys.shape)})")
     dev = x_phys.device
     if tri_counts is None:
         tri_counts = _tri_counts(cells, node_counts)
-    topo = _topology(cells, boundary, node_counts, tri_counts, dev)
+    topo = _topology(cells, boundary, node_counts, tri_counts, dev, band)
     gptr, gpar = pack_gaussians(pde_params, dev)
     lx, ly = lattice_axes(quad_points, dev)
-    coeffs, sol = _FemPoisson.apply(x_phys, topo, gptr, gpar, lx, ly)
+    coeffs, sol = _FemPoisson.apply(x_phys, topo, gptr, gpar, lx, ly, tri_slab)
     return coeffs.unsqueeze(1), sol
 
 
 def torch_FEM_2D(opt, mesh, mesh_points, quad_points, num_meshpoints, c_list, s_list):
     """The reference's entry point (`difFEM_2d.py:320-372`) on one mesh: (coeffs [N,1], mesh_points, sol shaped as
-    quad_points[0])."""
+    quad_points[0]).  opt['fem_band'] = 'window' takes meshes beyond 26 x 26 nodes, up to 81 x 81 (`fem_poisson`)."""
+    band = opt.get('fem_band', 'lds')
+    _check_route('torch_FEM_2D', band, 0)
     cells_np = np.asarray(mesh.coordinates.cell_node_map().values, dtype=np.int64)
     n = mesh_points.shape[0]
     if n != num_meshpoints ** 2:
@@ -241,14 +282,17 @@ def torch_FEM_2D(opt, mesh, mesh_points, quad_points, num_meshpoints, c_list, s_
     boundary = torch.from_numpy(boundary_from_cells(cells_np, n))
     params = [{'centers': [np.asarray(c.detach().cpu() if torch.is_tensor(c) else c, np.float32) for c in c_list],
                'scales': [np.asarray(s.detach().cpu() if torch.is_tensor(s) else s, np.float32) for s in s_list]}]
-    coeffs, sol = fem_poisson(mesh_points, cells, boundary, [n], params, quad_points, tri_counts=[cells_np.shape[0]])
+    coeffs, sol = fem_poisson(mesh_points, cells, boundary, [n], params, quad_points, tri_counts=[cells_np.shape[0]], band=band)
     shape = quad_points[0].shape if quad_points[0].dim() == 2 else (quad_points[0].numel(), quad_points[1].numel())
     return coeffs, mesh_points, sol.view(shape)
 
 
 def gnn_pde_tail(model, data, x_phys: torch.Tensor):
-    """`GNN.forward`'s pde_loss branch (`src/GNN.py:307-342`) for a batch: (coeffs [N,1], x_phys, sol [B*Q])."""
+    """`GNN.forward`'s pde_loss branch (`src/GNN.py:307-342`) for a batch: (coeffs [N,1], x_phys, sol [B*Q]).
+    opt['fem_band'] = 'window' takes meshes beyond 26 x 26 nodes, up to 81 x 81 (`fem_poisson`)."""
     o = model.opt
+    band = o.get('fem_band', 'lds')
+    _check_route("loss_type='pde_loss'", band, 0)
     if model.dim != 2:
         raise NotImplementedError("loss_type='pde_loss' is built for 2-D Poisson only; the 1-D tail (torch_FEM_1D) is out of scope")
     if o.get('pde_type', 'Poisson') != 'Poisson':
@@ -275,7 +319,7 @@ def gnn_pde_tail(model, data, x_phys: torch.Tensor):
     boundary = getattr(data, 'boundary_nodes', None)
     if boundary is None:
         boundary = torch.from_numpy(boundary_from_cells(cells.cpu().numpy(), sum(node_counts)))
-    coeffs, sol = fem_poisson(x_phys, cells, boundary, node_counts, params, model.quad_points, tri_counts=tri_counts)
+    coeffs, sol = fem_poisson(x_phys, cells, boundary, node_counts, params, model.quad_points, tri_counts=tri_counts, band=band)
     return coeffs, x_phys, sol
 
 
@@ -295,14 +339,17 @@ def simpson_points_per_dim(N: int, dim: int = 2) -> int:
 
 def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
                     pde_params: Sequence[dict], n_lat: int, reduction: str, n_load: Optional[int] = None,
-                    tri_counts: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                    tri_counts: Optional[Sequence[int]] = None, band: str = 'lds',
+                    tri_slab: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-mesh 2-D modular loss and its gradient: (loss [B], x_grads [N,2]), x_grads on a node being the gradient of its
     own mesh's loss wrt all of that mesh's node coordinates.
 
     The P1 Poisson solve of `fem_poisson` on each mesh, evaluated on the lattice linspace(0, 1, n_lat)^2 (meshgrid 'ij'),
     and e = sol - u_true there: reduction 'mse' is mean e^2 (F.mse_loss), 'simpson' torchquad's composite Simpson rule of
     e^2 over [0,1]^2 (n_lat odd).  n_load: Simpson points per dimension of the load vector; only the compiled
-    `gadapt_fem_simpson_points()` is built.  Five launches forward and backward, no autograd graph, no host wait."""
+    `gadapt_fem_simpson_points()` is built.  Five launches forward and backward, no autograd graph, no host wait.
+    band, tri_slab: as `fem_poisson` ('window': square meshes up to 81 x 81 nodes)."""
+    tri_slab = _check_route('modular loss (2-D)', band, tri_slab)
     _require_gpu(x_phys, 'modular loss (2-D)')
     if x_phys.dim() != 2 or x_phys.shape[1] != 2:
         raise NotImplementedError(f"modular loss (2-D): x_phys must be [N,2] (got {tuple(x_phys.shape)})")
@@ -320,25 +367,32 @@ def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.T
     x = x_phys.detach().contiguous()
     if tri_counts is None:
         tri_counts = _tri_counts(cells, node_counts)
-    topo = _topology(cells, boundary, node_counts, tri_counts, dev)
+    topo = _topology(cells, boundary, node_counts, tri_counts, dev, band)
     gptr, gpar = pack_gaussians(pde_params, dev)
     lat = torch.linspace(0, 1, n_lat).to(dev)              # torch's CPU linspace: the reference's lattice, point for point
     d, N, T, B = topo.dev, topo.n_nodes, topo.n_tris, topo.n_meshes
     Q = n_lat * n_lat
-    rhs, coeffs, lfac = torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(topo.band_floats, device=dev)
+    window = topo.route == 'window'
+    rhs, coeffs = torch.empty(N, device=dev), torch.empty(N, device=dev)
+    lfac = _workspace(topo, dev) if window else torch.empty(topo.band_floats, device=dev)
     sol, g_sol, loss = torch.empty(B * Q, device=dev), torch.empty(B * Q, device=dev), torch.empty(B, device=dev)
     stream = current_stream(dev)
-    _nf.check(lib.gadapt_fem_modular_forward(
-        B, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
-        d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(), x.data_ptr(),
-        lat.data_ptr(), lat.data_ptr(), n_lat, topo.lds_bytes, topo.max_tris, _REDUCTIONS[reduction], rhs.data_ptr(),
-        coeffs.data_ptr(), lfac.data_ptr(), sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(), stream), 'gadapt_fem_modular_forward')
+    head = (B, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
+            d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(), x.data_ptr(),
+            lat.data_ptr(), lat.data_ptr(), n_lat, topo.lds_bytes, topo.max_tris, _REDUCTIONS[reduction], rhs.data_ptr(),
+            coeffs.data_ptr(), lfac.data_ptr())
+    tail = (sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(), stream)
+    if window:
+        _nf.check(lib.gadapt_fem_modular_forward_window(*head, tri_slab, *tail), 'gadapt_fem_modular_forward_window')
+    else:
+        _nf.check(lib.gadapt_fem_modular_forward(*head, *tail), 'gadapt_fem_modular_forward')
     gc, mu, tgrad, gx = torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(T * 6, device=dev), torch.empty(N, 2, device=dev)
-    _nf.check(lib.gadapt_fem_backward(
+    name = 'gadapt_fem_backward_window' if window else 'gadapt_fem_backward'
+    _nf.check(getattr(lib, name)(
         B, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['tri_mesh'].data_ptr(),
         d['int_idx'].data_ptr(), d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(),
         gpar.data_ptr(), x.data_ptr(), lat.data_ptr(), lat.data_ptr(), n_lat, topo.lds_bytes, coeffs.data_ptr(), lfac.data_ptr(),
-        None, g_sol.data_ptr(), gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), stream), 'gadapt_fem_backward')
+        None, g_sol.data_ptr(), gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), stream), name)
     return loss, gx
 
 
@@ -402,7 +456,8 @@ def gradient_meshpoints_2D(opt, data, x_phys):
     Quadrature counts N become torchquad's points per dimension (`simpson_points_per_dim`: 101 -> 9); the load vector is
     built for `gadapt_fem_simpson_points()` only (NotImplementedError otherwise), the loss lattice takes any count.
     Topology: data.cells (as collate offsets them), else data.mesh / data.mesh[i], else square_mesh(mesh_dims[0]).
-    Limits as the pde_loss tail: 2-D Poisson, square meshes up to 26 x 26 nodes (the LDS budget of the banded factor).
+    Limits as the pde_loss tail: 2-D Poisson, square meshes up to 26 x 26 nodes (the LDS budget of the banded factor), or
+    up to 81 x 81 with opt['fem_band'] = 'window' (`modular_loss_2d(band='window')`).
     The reference's build_mass_matrix is called with three of its four arguments there (a TypeError as shipped); this
     builds the evident intent, the stiffness of torch_FEM_2D."""
     if 'grad_type' not in opt:
@@ -413,9 +468,11 @@ def gradient_meshpoints_2D(opt, data, x_phys):
     if x_phys.dim() != 2 or x_phys.shape[1] != 2:
         raise NotImplementedError(f"gradient_meshpoints_2D: x_phys must be [N,2] (got {tuple(x_phys.shape)}); "
                                   "1-D meshes take gradient_meshpoints_1D")
+    band = opt.get('fem_band', 'lds')
+    _check_route('gradient_meshpoints_2D', band, 0)
     _require_gpu(x_phys.detach().float(), 'gradient_meshpoints_2D')
     n_load, n_lat, reduction = _modular_quadrature(opt, gt)
     cells, boundary, node_counts, tri_counts, params = _modular_batch(opt, data, x_phys.shape[0])
     loss, x_grads = modular_loss_2d(x_phys.detach().float(), cells, boundary, node_counts, params, n_lat, reduction,
-                                    n_load=n_load, tri_counts=tri_counts)
+                                    n_load=n_load, tri_counts=tri_counts, band=band)
     return loss.mean(), x_grads

@@ -719,3 +719,7 @@ extern "C" int gadapt_fem_backward(int B, int N, int T, const int32_t* meta, con
 
 // the windowed band solve and slabbed evaluation of band='window' (gadapt_fem_eval_errors_window): same translation unit, new code only
 #include "fem_window_kernels.hip"
+
+// the differentiable tail of the windowed route (gadapt_fem_forward_window, gadapt_fem_modular_forward_window,
+// gadapt_fem_backward_window): same translation unit, new code only
+#include "fem_window_grad_kernels.hip"

@@ -37,8 +37,9 @@ def hot_path_opt(**overrides) -> dict:
         'data_type': 'randg',               # params.py:30
         'fix_boundary': True,               # params.py:67
         'eval_quad_points': 101,            # params.py:68
-        # not a reference key: the FEM route of the evaluation (evaluate_model_fine, eval_grid_MMPDE_MA).  'lds': the banded factor
-        # resident in LDS, 2-D meshes up to 26 x 26; 'window': the windowed band solve, up to 81 x 81
+        # not a reference key: the FEM route of the evaluation (evaluate_model_fine, eval_grid_MMPDE_MA) and of the differentiable
+        # tails (pde_loss, the 2-D modular loss, torch_FEM_2D).  'lds': the banded factor resident in LDS, 2-D meshes up to
+        # 26 x 26; 'window': the windowed band solve, up to 81 x 81
         'fem_band': 'lds',
         # features
         'gnn_inc_feat_f': True,             # params.py:114

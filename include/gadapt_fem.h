@@ -170,6 +170,43 @@ int gadapt_fem_backward(int n_meshes, int n_nodes, int n_tris, const int32_t* me
                         const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs, const float* lfac,
                         const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad, float* gx, void* stream);
 
+/* The differentiable tail on the windowed route (fem_csrc/fem_window_grad_kernels.hip): forward, modular forward and backward
+ * for meshes whose band does not stay resident, square meshes up to 81 x 81 nodes; these entry points were added without
+ * changing GADAPT_FEM_ABI (no existing signature changed).
+ *   gadapt_fem_forward_window          gadapt_fem_forward's arguments with the fp64 workspace `work` (sized by
+ *               gadapt_fem_window_workspace_floats, 8-byte aligned, no initialisation needed) in lfac's place and tri_slab
+ *               after it.  Three launches: the load vector and the windowed solve of gadapt_fem_eval_errors_window, then
+ *               its slab walk with each lattice point's sum stored to sol (one chain of fp32 additions over the triangles
+ *               in increasing id: sol does not depend on tri_slab, bit for bit).  The workspace keeps the factor for the
+ *               backward.
+ *   gadapt_fem_modular_forward_window  the same, then gadapt_fem_modular_forward's loss launch as it is (loss, g_sol).
+ *   gadapt_fem_backward_window         gadapt_fem_backward's arguments with the workspace in lfac's place.  Four launches:
+ *               gadapt_fem_backward's first, third and fourth as they are; the second solves P_II mu = gc_I on the kept
+ *               workspace, one 256-lane workgroup per mesh with the solve's ring: both substitutions in fp64, mu stored in
+ *               fp32, 0 on boundary nodes.  The forward substitution's intermediate overwrites the mesh's y slot in the
+ *               workspace and is rewritten on every call; the factor is only read, so a second backward on one forward gives
+ *               the same bits.  Each row's sum runs over its columns in increasing index whatever the ring's slack or the
+ *               batch.
+ *   max_lds_bytes, tri_slab as gadapt_fem_eval_errors_window; the ring's and the slab's LDS are sized by the same code.
+ * Everything is checked before the first launch: null pointers, the workspace's alignment, tri_slab < 0 or not a multiple
+ * of 32 (GADAPT_FEM_E_BADARG), LDS beyond the budget (GADAPT_FEM_E_LDS). */
+int gadapt_fem_forward_window(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells,
+                              const int32_t* node_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                              const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
+                              const float* lat_y, int nlat, int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* work,
+                              int tri_slab, float* sol, void* stream);
+int gadapt_fem_modular_forward_window(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells,
+                                      const int32_t* node_mesh, const int32_t* int_idx, const int32_t* int_node,
+                                      const int32_t* nt_ptr, const int32_t* nt_idx, const int32_t* gptr, const float* gpar,
+                                      const float* x, const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes,
+                                      int max_tris, int reduction, float* rhs, float* coeffs, float* work, int tri_slab, float* sol,
+                                      float* loss, float* g_sol, void* stream);
+int gadapt_fem_backward_window(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells,
+                               const int32_t* node_mesh, const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node,
+                               const int32_t* nt_ptr, const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x,
+                               const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs, float* work,
+                               const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad, float* gx, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ 1-D tails
  * Differentiable 1-D P1 FEM of the reference's modular loss (firedrake_difFEM/difFEM_1d.py): semi-implicit Burgers steps
  * (torch_FEM_Burgers_1D, get_Burgers_initial_coeffs) and Poisson (torch_FEM_1D), with the reference's trapezoid inner
