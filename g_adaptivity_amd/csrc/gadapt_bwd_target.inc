@@ -16,6 +16,7 @@ struct BwdTArgs {
     int g_stride;                                               // ... and the row pitch of its g_in, in floats
     int sums_partials;                                          // 1: sums_out / sums_sc_out are per-workgroup arrays [gridDim.x] (written, not added to)
     const int32_t* ell;                                         // grand_bwd_target_compact_kernel<., true>: gadapt_graph::ell_t ([N_pad][8] in-neighbours, -1 = unused)
+    int slab_packed;                                            // bwd_target_compact_body: 1 = rows of GADAPT_NARROW_SLAB_ROW floats (its 20 partials side by side), 0 = rows of C*C + C
 };
 
 template <int NROWS, int NV> struct TBuf {
@@ -631,8 +632,11 @@ __device__ __forceinline__ void bwd_target_compact_body(const BwdTArgs& p, const
     // this workgroup's slab row (layout of the tiled kernel: dA [C][C], then dp0 [C]).  The entry this thread adds to at the end of an
     // accumulating launch is requested HERE, with the first node's rows (unconditionally): read where it is added, it was one more
     // memory round trip at the very end of the launch
-    float* row = p.slab + (size_t)blockIdx.x * (C * C + C);
-    const int e_own = tid < 16 ? (tid >> 2) * C + (tid & 3) : C * C + (min(tid, 19) - 16);
+    // Packed rows (p.slab_packed; gadapt_block_backward_narrow_packed): GADAPT_NARROW_SLAB_ROW = 32 floats, one 128-byte line per
+    // workgroup - entry 4 o + c = dA[o][c], entry 16 + o = dp0[o], entries 20..31 zero.
+    float* row = p.slab + (size_t)blockIdx.x * (p.slab_packed ? GADAPT_NARROW_SLAB_ROW : C * C + C);
+    const int e_own = p.slab_packed ? min(tid, GADAPT_NARROW_SLAB_ROW - 1)
+                                    : (tid < 16 ? (tid >> 2) * C + (tid & 3) : C * C + (min(tid, 19) - 16));
     const float row_old = __builtin_nontemporal_load(row + e_own);
     for (int64_t i = (int64_t)blockIdx.x * 256 + tid; i < p.n_nodes; i += (int64_t)gridDim.x * 256) {
         float4 g4 = f4zero();
@@ -738,7 +742,9 @@ __device__ __forceinline__ void bwd_target_compact_body(const BwdTArgs& p, const
         if (lane == 0) red[wave][k] = acc[k];
     }
     __syncthreads();
-    if (!p.accumulate) {                                        // accumulate = 0: the row is written whole
+    if (!p.accumulate && p.slab_packed) {                       // accumulate = 0: the row is written whole - packed: its 12 spare entries
+        if (tid >= 20 && tid < GADAPT_NARROW_SLAB_ROW) row[e_own] = 0.f;
+    } else if (!p.accumulate) {
         for (int e = tid; e < C * C + C; e += 256) {
             const int o = e / C, c = e % C;
             const bool live = (e < C * C) ? (o < 4 && c < 4) : (e - C * C < 4);

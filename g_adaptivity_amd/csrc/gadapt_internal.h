@@ -53,6 +53,9 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define GADAPT_SLAB_CHUNKS 8    // second-level partials of the slab reduction (<= 32: the scratch the callers allocate).
                                 // 32 / 16 / 8 chunks: first level 5.1 / 5.5 / 5.0 us, second level + chain rule 12.1 / 8.8 / 6.6 us
 #endif
+// Packed slab row of the narrow route (gadapt_block_backward_narrow_packed): the 20 weight-gradient partials of a target-pass workgroup
+// (dA[o][c] at 4 o + c, dp0[o] at 16 + o; o, c < 4) and 12 zeros - one 128-byte line per workgroup, so no two workgroups share a line.
+#define GADAPT_NARROW_SLAB_ROW 32
 // Softmax arithmetic: expf / IEEE division (<= 1 ulp each).  The approximate forms (v_exp_f32 of a rounded product, v_rcp_f32)
 // leave alpha with ~4x the rounding error of the reference's exp / true division; harmless for the coordinates (2e-7 either way)
 // but visible in parameter gradients that are the small remainder of large cancelling sums (64x64, 6 layers, hidden 128: 3.4e-4
@@ -183,7 +186,8 @@ int gadapt_launch_fwd_c(int c, const gadapt_graph* g, const float* x_in, float* 
 int gadapt_launch_bwd_target_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, const float* alpha, const float* a,
                                const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, float* sums_out, float* sums_sc_out,
                                int want_source, int residual_only, int g_cols, int x_cols, int out4, int g_stride, int sums_partials,
-                               hipStream_t st);
+                               hipStream_t st, int slab_packed = 0);
+// (slab_packed, here and below: GADAPT_NARROW_SLAB_ROW-float slab rows - the compact layer-0 launch and the narrow route's launches only)
 // ... and the source pass of the same layer (g_out != NULL)
 int gadapt_launch_bwd_source_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, const float* edge_ws, const float* dxd,
                                const float* a, const float* p0, float* g_out, int g_cols, int out4, hipStream_t st);
@@ -193,13 +197,14 @@ int gadapt_narrow_takes_c(const gadapt_graph* g, int c);
 int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* a, const float* p0, const float* lp, float* alpha_out,
                                int residual_only, float* x_top4, hipStream_t st, const FwdExtra* extra);
 int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* alpha,
-                                      const float* a, const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, hipStream_t st);
+                                      const float* a, const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, hipStream_t st,
+                                      int slab_packed = 0);
 int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* edge_ws,
                                       const float* dxd, const float* a, const float* p0, float* g_out, hipStream_t st);
 // source pass of one layer and target pass of the layer below in one launch (gadapt_narrow_bwd.inc; gadapt_debug_set_narrow_backward_fused)
 int gadapt_launch_bwd_fused_narrow_c(int c, const gadapt_graph* g, const float* x_src, const float* g_in, int g_cols, const float* edge_in,
                                      const float* a_src, const float* p0_src, float* g_out, const float* x_tgt, const float* alpha, const float* a_tgt, const float* lp_tgt,
-                                     float* edge_out, float* dxd, float* slab, int accumulate, int layer0, hipStream_t st);
+                                     float* edge_out, float* dxd, float* slab, int accumulate, int layer0, hipStream_t st, int slab_packed = 0);
 int gadapt_slab_rows_c(int64_t n_nodes, int c);
 int gadapt_occupancy_fwd_c(int c);
 int gadapt_occupancy_bwd_target_c(int c);

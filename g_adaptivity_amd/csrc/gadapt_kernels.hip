@@ -578,6 +578,30 @@ extern "C" int gadapt_step_tail(const float* slab, int n_rows, float* scratch, f
     return gadapt_coeffs_forward(param, param + c2, param + c2 + c, a_out, p0_out, c, stream);
 }
 
+// The narrow route's tail over the PACKED slab (gadapt_block_backward_narrow_packed) as ONE launch, hidden 64: step_tail_narrow_kernel.
+// The forms of gadapt_step_tail that read a slab - the whole tail, and (no moments) the flat gradient only; bit-identical to them on
+// the equivalent full-width slab (tests/test_gpu_narrow_tail.py).  The gradient-given form has no slab: gadapt_step_tail.
+extern "C" int gadapt_step_tail_narrow(const float* slab, int n_rows, float* scratch, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, int32_t* state, float grad_scale,
+                                       float* a_out, float* p0_out, const float* loss_partials, int n_loss_partials, float* loss_out,
+                                       int64_t loss_count, int c, void* stream) {
+    const bool gradient_only = !exp_avg && !exp_avg_sq;             // data parallel, first half: stop at the flat gradient
+    if (c != 64) return fail(GADAPT_E_BADARG, "step_tail_narrow: hidden 64 only (gadapt_narrow_route)");
+    if (!slab || n_rows <= 0 || !scratch) return fail(GADAPT_E_BADARG, "step_tail_narrow: the packed slab, its row count and the scratch");
+    if (!param || !grad || (!gradient_only && (!state || !exp_avg || !exp_avg_sq || (!a_out != !p0_out))))
+        return fail(GADAPT_E_BADARG, "step_tail_narrow: bad argument");
+    if (loss_partials && (n_loss_partials <= 0 || !loss_out || loss_count <= 0))
+        return fail(GADAPT_E_BADARG, "step_tail_narrow: loss partials need a count and a destination");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    TailNarrowArgs p{slab, n_rows, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, grad_scale, gradient_only ? nullptr : state,
+                     loss_partials, n_loss_partials, loss_partials ? 1.0f / (float)loss_count : 0.f, loss_out};
+    hipLaunchKernelGGL(step_tail_narrow_kernel, dim3(loss_partials ? 2 : 1), dim3(1024), 0, st, p);
+    if (int rc = check_launch("step_tail_narrow")) return rc;
+    if (gradient_only || !a_out) return GADAPT_OK;
+    const int c2 = c * c;
+    return gadapt_coeffs_forward(param, param + c2, param + c2 + c, a_out, p0_out, c, stream);
+}
+
 extern "C" int gadapt_block_backward(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top, int g_top_cols, int n_layers,
                                      const float* a, int64_t a_stride, const float* p0, int64_t p0_stride, const float* layer_params,
                                      float* g_ws, float* dxd_ws, float* edge_ws, float* slab, float* d_layer_params, int want_d_scale, float* d_x0,
@@ -629,17 +653,21 @@ extern "C" int gadapt_block_backward(const gadapt_graph* g, const float* x_all, 
 // of a fused launch read one layer's {alpha dt, ds} pairs while others scatter the next layer's, so the launches alternate between
 // edge_ws and a second buffer of 2E floats carved out of dxd_ws (the caller's N c floats, of which this route uses the first 4N) at
 // float offset 4N; where that does not fit (2E > (c - 4) N) or the graph has no ELL table of out-neighbours, the pairs run.
-extern "C" int gadapt_block_backward_narrow(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top,
-                                            int g_top_cols, int n_layers, const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
-                                            const float* layer_params, float* g_ws, float* dxd_ws, float* edge_ws, float* slab, float* d_layer_params,
-                                            int want_d_scale, float* d_x0, int c, void* stream) {
-    (void)want_d_scale;
+//
+// packed (gadapt_block_backward_narrow_packed): the slab rows are GADAPT_NARROW_SLAB_ROW = 32 floats - the 20 partials a workgroup owes
+// and 12 zeros, one 128-byte line - instead of C*C + C of which 4140 are written zero: every launcher of the route passes the layout on,
+// the sums and their order are the same.  One shared conv only (one slab).
+static int block_backward_narrow(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top,
+                                 int g_top_cols, int n_layers, const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
+                                 const float* layer_params, float* g_ws, float* dxd_ws, float* edge_ws, float* slab, float* d_layer_params,
+                                 float* d_x0, int c, void* stream, int packed) {
     if (int rc = check_graph(g, c)) return rc;
     if (!x_all || !alpha_all || !g_top || n_layers < 2 || !a || !p0 || !layer_params || !g_ws || !dxd_ws || !edge_ws || !slab)
         return fail(GADAPT_E_BADARG, "block_backward (narrow): bad argument");
     if (x0_cols != 4 || g_top_cols < 1 || g_top_cols > 4 || d_x0 || d_layer_params || !gadapt_narrow_takes_c(g, c))
         return fail(GADAPT_E_BADARG, "block_backward (narrow): compact x0, compact top gradient, no d_x0, fixed steps and temperature, "
                                      "hidden 64 on a graph the wide forward takes (gadapt_narrow_route)");
+    if (packed && (a_stride != 0 || p0_stride != 0)) return fail(GADAPT_E_BADARG, "block_backward (narrow, packed slab): one shared conv (a_stride = p0_stride = 0)");
     const size_t nc = (size_t)g->n_nodes * c;
     const bool shared = (a_stride == 0);
     const int64_t slab_floats = gadapt_backward_slab_floats(g->n_nodes, c);
@@ -651,13 +679,13 @@ extern "C" int gadapt_block_backward_narrow(const gadapt_graph* g, const float* 
         float* edge_buf[2] = {edge_ws, dxd_ws + 4 * (size_t)g->n_nodes};
         int l = n_layers - 1, eb = 0;
         int rc = gadapt_launch_bwd_target_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, alpha_all + (size_t)l * g->n_edges, a + l * a_stride,
-                                                   layer_params + 2 * l, edge_buf[eb], dxd_ws, shared ? slab : slab + (size_t)l * slab_floats, 0, st);
+                                                   layer_params + 2 * l, edge_buf[eb], dxd_ws, shared ? slab : slab + (size_t)l * slab_floats, 0, st, packed);
         for (; !rc && l >= 1; --l, eb ^= 1) {                   // source pass of layer l + target pass of layer l-1
             float* g_next = g_ws + ((n_layers - 1 - l) & 1) * nc;
             rc = gadapt_launch_bwd_fused_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, edge_buf[eb], a + l * a_stride, p0 + l * p0_stride, g_next,
                                                   x_all + (l - 1) * nc, alpha_all + (size_t)(l - 1) * g->n_edges, a + (l - 1) * a_stride,
                                                   layer_params + 2 * (l - 1), edge_buf[eb ^ 1], dxd_ws,
-                                                  shared ? slab : slab + (size_t)(l - 1) * slab_floats, shared ? 1 : 0, l == 1 ? 1 : 0, st);
+                                                  shared ? slab : slab + (size_t)(l - 1) * slab_floats, shared ? 1 : 0, l == 1 ? 1 : 0, st, packed);
             g_cur = g_next;
             g_cols = 0;
         }
@@ -670,11 +698,11 @@ extern "C" int gadapt_block_backward_narrow(const gadapt_graph* g, const float* 
         int rc;
         if (l == 0) {                                           // g_cur: layer 1's [N,4] result
             rc = gadapt_launch_bwd_target_c(c, g, x_all, g_cur, alpha_l, a, layer_params, edge_ws, dxd_ws, slab_l, accumulate, nullptr, nullptr, 0, 0,
-                                            0, 4, 0, 4, 1, st);
+                                            0, 4, 0, 4, 1, st, packed);
         } else {
             float* g_next = g_ws + ((n_layers - 1 - l) & 1) * nc;
             rc = gadapt_launch_bwd_target_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, alpha_l, a + l * a_stride, layer_params + 2 * l, edge_ws,
-                                                   dxd_ws, slab_l, accumulate, st);
+                                                   dxd_ws, slab_l, accumulate, st, packed);
             if (!rc) rc = gadapt_launch_bwd_source_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, edge_ws, dxd_ws, a + l * a_stride, p0 + l * p0_stride,
                                                             g_next, st);
             g_cur = g_next;
@@ -683,4 +711,24 @@ extern "C" int gadapt_block_backward_narrow(const gadapt_graph* g, const float* 
         if (rc) return rc;
     }
     return GADAPT_OK;
+}
+extern "C" int gadapt_block_backward_narrow(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top,
+                                            int g_top_cols, int n_layers, const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
+                                            const float* layer_params, float* g_ws, float* dxd_ws, float* edge_ws, float* slab, float* d_layer_params,
+                                            int want_d_scale, float* d_x0, int c, void* stream) {
+    (void)want_d_scale;
+    return block_backward_narrow(g, x_all, x0_cols, alpha_all, g_top, g_top_cols, n_layers, a, a_stride, p0, p0_stride, layer_params, g_ws, dxd_ws,
+                                 edge_ws, slab, d_layer_params, d_x0, c, stream, 0);
+}
+extern "C" int64_t gadapt_narrow_slab_floats(int64_t n_nodes) {
+    const int rows = gadapt_backward_slab_rows(n_nodes, 64);
+    return rows < 0 ? rows : (int64_t)rows * GADAPT_NARROW_SLAB_ROW;
+}
+extern "C" int gadapt_block_backward_narrow_packed(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top,
+                                                   int g_top_cols, int n_layers, const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
+                                                   const float* layer_params, float* g_ws, float* dxd_ws, float* edge_ws, float* slab,
+                                                   float* d_layer_params, int want_d_scale, float* d_x0, int c, void* stream) {
+    (void)want_d_scale;
+    return block_backward_narrow(g, x_all, x0_cols, alpha_all, g_top, g_top_cols, n_layers, a, a_stride, p0, p0_stride, layer_params, g_ws, dxd_ws,
+                                 edge_ws, slab, d_layer_params, d_x0, c, stream, 1);
 }

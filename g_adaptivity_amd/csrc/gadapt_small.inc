@@ -424,6 +424,150 @@ __global__ __launch_bounds__(1024) void step_tail_kernel(TailArgs p) {
 }
 __global__ void step_count_kernel(int* state) { if (blockIdx.x == 0 && threadIdx.x == 0) state[0] += 1; }
 
+// Tail of a fused training step on the NARROW route (hidden 64; gadapt_step_tail_narrow): what slab_reduce1_kernel + step_tail_kernel<64>
+// (or reduce2_coeffs_bwd_kernel<64>: p.m == nullptr, the flat gradient only) compute from a full-width slab whose rows are zero outside
+// the 4 x 4 corner of dA and dp0[0..3], from the PACKED slab [n_rows][GADAPT_NARROW_SLAB_ROW] - the same bits (up to the sign of a zero) in one launch:
+//   workgroup 0 (1024 threads): both levels of the slab sums in the two-launch tail's order, the chain-rule terms whose dA / dp0 factor
+//     can be non-zero (a dropped term is fmaf(w, 0, v) = v for finite w), Adam on all 2 C^2 + 2 C entries (NE = 9 per thread) and the
+//     step count - read, and advanced by thread 0, inside this one workgroup;
+//   workgroup 1 (only with loss partials): the loss sum of slab_reduce1_kernel's extra workgroup on its first 256 threads.
+// The two share nothing, so the launch has no exchange between workgroups.
+// First level: thread (j, q, e) owns interleaved sum v_j of entry e over chunk q's groups of 32 rows (rows j, j+4, .. of each group in
+// order; leftover rows one by one into v_0), the four meet in LDS as (v0 + v1) + (v2 + v3); second level: the chunks in ascending order.
+struct TailNarrowArgs {
+    const float* slab; int n_rows;
+    float* param; float* grad; float* m; float* v;
+    float lr, b1, b2, eps, wd, gscale;
+    int* state;
+    const float* loss_partials; int n_loss; float loss_scale; float* loss_out;
+};
+__global__ __launch_bounds__(1024) void step_tail_narrow_kernel(TailNarrowArgs p) {
+    constexpr int C = 64, c2 = C * C, NPAR = 2 * c2 + 2 * C, NE = (NPAR + 1023) / 1024, RW = GADAPT_NARROW_SLAB_ROW, Q = GADAPT_SLAB_CHUNKS;
+    static_assert(Q * RW * 4 == 1024, "one thread per (interleaved sum, chunk, entry)");
+    __shared__ float part[4][Q * RW];                           // v_j of (chunk, entry)
+    __shared__ float sums[RW];                                  // dA[o][c] at 4 o + c, dp0[o] at 16 + o
+    __shared__ float wq4[C][4], wk4[C][4], bqs[C];              // old Wq[r][0..3], Wk[r][0..3], bq[r]
+    __shared__ float lred[4];
+    const int tid = threadIdx.x;
+    if (blockIdx.x == 1) {                                      // the loss value: slab_reduce1_kernel's order (256 threads)
+        float v = 0.f;
+        if (tid < 256) {
+            float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+            for (int r = tid; r < p.n_loss; r += 1024) {
+                v0 += p.loss_partials[r];
+                if (r + 256 < p.n_loss) v1 += p.loss_partials[r + 256];
+                if (r + 512 < p.n_loss) v2 += p.loss_partials[r + 512];
+                if (r + 768 < p.n_loss) v3 += p.loss_partials[r + 768];
+            }
+            v = (v0 + v1) + (v2 + v3);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            if ((tid & 63) == 0) lred[tid >> 6] = v;
+        }
+        __syncthreads();
+        if (tid == 0) p.loss_out[0] = ((lred[0] + lred[1]) + (lred[2] + lred[3])) * p.loss_scale;
+        return;
+    }
+    const bool adam = p.m != nullptr;
+    // Every request of the launch goes out before the first wait (see step_tail_kernel): the step count, this thread's NE entries of
+    // param / m / v and the first group of slab rows; the two powf run behind them
+    const int step_now = adam ? p.state[0] + 1 : 1;            // steps taken INCLUDING this one
+    float pv[NE], mm[NE], vv[NE];
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const int e = min(tid + 1024 * i, NPAR - 1);
+        pv[i] = p.param[e];
+        mm[i] = adam ? p.m[e] : 0.f;
+        vv[i] = adam ? p.v[e] : 0.f;
+    }
+    const int j = tid >> 8, q = (tid >> 5) & (Q - 1), en = tid & (RW - 1);
+    const int per = (p.n_rows + Q - 1) / Q;
+    const int r0 = q * per, r1 = min(p.n_rows, r0 + per);
+    const float* src = p.slab + en;
+    float t[8];
+    int r = r0;
+    const bool first = r + 32 <= r1;
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t[k] = src[(size_t)(r + 4 * k + j) * RW];
+    }
+    float bc1 = 0.f, bc2_sqrt = 0.f;
+    if (adam) {
+        const float stepf = (float)step_now;
+        bc1 = 1.0f - powf(p.b1, stepf); bc2_sqrt = sqrtf(1.0f - powf(p.b2, stepf));
+        asm volatile("" : "+v"(bc1), "+v"(bc2_sqrt));           // (hipcc otherwise sinks them to their use, behind the sums)
+    }
+    // the rows of the flat bucket the chain rule reads, staged before anyone overwrites them: [Wq | bq | Wk | bk]
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const int e = tid + 1024 * i;
+        if (e < c2) { if ((e & (C - 1)) < 4) wq4[e >> 6][e & 3] = pv[i]; }
+        else if (e < c2 + C) bqs[e - c2] = pv[i];
+        else if (e < 2 * c2 + C) { const int f = e - c2 - C; if ((f & (C - 1)) < 4) wk4[f >> 6][f & 3] = pv[i]; }
+    }
+    float vj = 0.f;
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) vj += t[k];
+        r += 32;
+    }
+    for (; r + 32 <= r1; r += 32) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t[k] = src[(size_t)(r + 4 * k + j) * RW];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) vj += t[k];
+    }
+    if (j == 0) for (; r < r1; ++r) vj += src[(size_t)r * RW];
+    part[j][q * RW + en] = vj;
+    __syncthreads();
+    if (tid < Q * RW) part[0][tid] = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+    __syncthreads();
+    if (tid < RW) {
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < Q; ++k) v += part[0][k * RW + tid];   // same order as slab_reduce2_kernel
+        sums[tid] = v;
+    }
+    __syncthreads();
+    const float* da = sums;                                     // dA[o][cc] = da[4 o + cc]
+    const float* dp = sums + 16;
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+        const int e = tid + 1024 * i;
+        if (e >= NPAR) break;
+        float g = 0.f;
+        if (e < c2) {                           // d_wq[r][cc] = sum_o wk[r][o] dA[o][cc]
+            const int rr = e >> 6, cc = e & (C - 1);
+            if (cc < 4) {
+                float v[4];
+#pragma unroll
+                for (int o = 0; o < 4; ++o) v[o] = fmaf(wk4[rr][o], da[4 * o + cc], 0.f);
+                g = (v[0] + v[1]) + (v[2] + v[3]);
+            }
+        } else if (e < c2 + C) {                // d_bq[r] = sum_o wk[r][o] dp0[o]
+            const int rr = e - c2;
+            float v = 0.f;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) v = fmaf(wk4[rr][o], dp[o], v);
+            g = v;
+        } else if (e < 2 * c2 + C) {            // d_wk[r][o] = sum_cc wq[r][cc] dA[o][cc] + bq[r] dp0[o]
+            const int f = e - c2 - C, rr = f >> 6, o = f & (C - 1);
+            if (o < 4) {
+                float v[4] = {bqs[rr] * dp[o], 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int cc = 0; cc < 4; ++cc) v[cc] = fmaf(wq4[rr][cc], da[4 * o + cc], v[cc]);
+                g = (v[0] + v[1]) + (v[2] + v[3]);
+            }
+        }                                       // d_bk = 0 (softmax shift invariance: d/d lin_key.bias vanishes identically)
+        p.grad[e] = g;
+        if (adam) {
+            const float pn = adam_update(pv[i], g * p.gscale, mm[i], vv[i], p.lr, p.b1, p.b2, p.eps, p.wd, bc1, bc2_sqrt);
+            p.m[e] = mm[i]; p.v[e] = vv[i]; p.param[e] = pn;
+        }
+    }
+    if (adam && tid == 0) p.state[0] = step_now;
+}
+
 __global__ void mesh_loss_seed_kernel(const float* x_top, const float* target, float* x_phys, float* g_top, float* loss_out,
                                       int64_t n_nodes, int d, int c, int l1, float gscale) {
     __shared__ float red[256];

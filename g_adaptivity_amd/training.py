@@ -113,7 +113,9 @@ class FusedIteration:
             e = max(self.graph.num_edges, 1)
             self.g_ws, self.dxd_ws, self.edge_ws = torch.empty(2, n, c, **f32), torch.empty(n, c, **f32), torch.empty(e, 2, **f32)
             self.slab_rows = lib().gadapt_backward_slab_rows(n, c)
-            self.slab = torch.empty(lib().gadapt_backward_slab_floats(n, c), **f32)
+            # narrow route: packed slab rows (32 floats: the 20 partials a target-pass workgroup owes) and the one-launch tail over them
+            slab_floats = lib().gadapt_narrow_slab_floats(n) if r.narrow else lib().gadapt_backward_slab_floats(n, c)
+            self.slab = torch.empty(slab_floats, **f32)
             self.coeffs = self.fwd.coeffs
             # hidden 64 on a graph the wide forward takes: the layer-0 launch computes (A, p0) from the live weights itself - no
             # coefficient launch in the step (13 launches), and nothing to refresh when the weights change behind the step's back
@@ -156,7 +158,7 @@ class FusedIteration:
             a_ptr = p0_ptr = None
         else:
             a, p0 = self.coeffs
-            name = 'gadapt_block_backward_narrow' if fw.narrow else 'gadapt_block_backward'
+            name = 'gadapt_block_backward_narrow_packed' if fw.narrow else 'gadapt_block_backward'
             self._bw = (getattr(L_, name), [self.graph.c_ref, ptr(fw.x_all), 4, ptr(fw.alpha), ptr(fw.seed), self.d, fw.L, ptr(a), 0, ptr(p0), 0,
                                             ptr(fw.lp), ptr(self.g_ws), ptr(self.dxd_ws), ptr(self.edge_ws), ptr(self.slab), None, 0, None, c, None],
                         name)
@@ -168,11 +170,14 @@ class FusedIteration:
                     ptr(o.exp_avg) if moments else None, ptr(o.exp_avg_sq) if moments else None, 0.0, 0.0, 0.0, 0.0, 0.0, ptr(o._dev_state), 1.0,
                     a_ptr, p0_ptr, ptr(fw.partials) if slab else None, 0, ptr(self.loss), self.n * self.d, c, None]
         self._tl = {(False, False): tail(True, True), (True, False): tail(True, False), (False, True): tail(False, True)}
-        self._fn_tail = L_.gadapt_step_tail
+        # (the narrow route's packed slab has its own tail, one launch; a given gradient has no slab: gadapt_step_tail)
+        narrow = self.small is None and fw.narrow
+        self._fn_tail = {k: ('gadapt_step_tail_narrow' if narrow and not k[1] else 'gadapt_step_tail') for k in self._tl}
+        self._fn_tail = {k: (getattr(L_, name), name) for k, name in self._fn_tail.items()}
 
     def forward_backward(self):
         """zero_grad + model(data) + loss + backward: 4 + 7 launches at 4 layers (narrow route: 4 + 4, each source pass inside the next
-        target pass; small-mesh batches: 1 + 1; the gradient of the conv
+        target pass, into packed slab rows; small-mesh batches: 1 + 1; the gradient of the conv
         parameters is still in the slab: `finish()` sums it).  Data parallel: also the slab sums + chain rule, so that `flat` holds this
         rank's gradient."""
         if self.fwd.moved():
@@ -193,14 +198,15 @@ class FusedIteration:
             self._plans()
         g = self.optimizer.param_groups[0]
         args = self._tl[(stop_after_gradient, gradient_given)]
+        fn, name = self._fn_tail[(stop_after_gradient, gradient_given)]
         args[7], (args[8], args[9]), args[10], args[11], args[13], args[17] = g['lr'], g['betas'], g['eps'], g['weight_decay'], scale, self.n_part
         args[-1] = current_stream(self.device)
-        rc = self._fn_tail(*args)
+        rc = fn(*args)
         if rc:
-            check(rc, 'gadapt_step_tail')
+            check(rc, name)
 
     def finish(self):
-        """optimizer.step(): one GPU - slab sums + chain rule + Adam + next coefficients (2 launches); data parallel - all-reduce of
+        """optimizer.step(): one GPU - slab sums + chain rule + Adam + next coefficients (2 launches; narrow route: 1); data parallel - all-reduce of
         the flat gradient, then Adam + next coefficients (1 launch)."""
         world = self._world() if self.optimizer.data_parallel else 1
         if world == 1:

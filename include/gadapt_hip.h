@@ -282,6 +282,28 @@ int gadapt_step_tail(const float* slab /*nullable*/, int n_rows, float* scratch,
                      float grad_scale, float* a_out, float* p0_out,
                      const float* loss_partials /*nullable*/, int n_loss_partials, float* loss_out, int64_t loss_count,
                      int c, void* stream);
+/* Narrow route with PACKED slab rows: a target-pass workgroup of the narrow backward owes 20 numbers, so a row is 32 floats instead of
+ * c*c + c - entry 4*o + k = dA[o][k], entry 16 + o = dp0[o] (o, k < 4), entries 20..31 zero: one 128-byte line per workgroup.
+ * gadapt_narrow_slab_floats = 32 * gadapt_backward_slab_rows at hidden 64.  gadapt_block_backward_narrow_packed: arguments, launches
+ * and sums of gadapt_block_backward_narrow - the 20 live entries of every row carry the same bits - for ONE shared conv
+ * (a_stride = p0_stride = 0); every float of the slab is written.  gadapt_step_tail_narrow: arguments of gadapt_step_tail, hidden 64,
+ * slab = the packed slab (required, like scratch - unused, kept for the common argument list): ONE launch that sums the rows in the
+ * order of gadapt_step_tail's first-level and second-level sums, keeps the chain-rule terms whose dA / dp0 factor can be non-zero,
+ * runs Adam on the whole bucket, advances the step count and sums the loss partials; exp_avg = exp_avg_sq = NULL stops at the flat
+ * gradient (state untouched).  Bit-identical to gadapt_step_tail on the full-width slab with the same live entries
+ * (tests/test_gpu_narrow_tail.py).  The gradient-given form (no slab) stays with gadapt_step_tail. */
+int64_t gadapt_narrow_slab_floats(int64_t n_nodes);
+int gadapt_block_backward_narrow_packed(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all,
+                                        const float* g_top, int g_top_cols, int n_layers,
+                                        const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
+                                        const float* layer_params,
+                                        float* g_ws, float* dxd_ws, float* edge_ws, float* slab,
+                                        float* d_layer_params, int want_d_scale, float* d_x0, int c, void* stream);
+int gadapt_step_tail_narrow(const float* slab, int n_rows, float* scratch, float* param, float* grad, float* exp_avg,
+                            float* exp_avg_sq, float lr, float beta1, float beta2, float eps, float weight_decay, int32_t* state,
+                            float grad_scale, float* a_out, float* p0_out,
+                            const float* loss_partials /*nullable*/, int n_loss_partials, float* loss_out, int64_t loss_count,
+                            int c, void* stream);
 
 /* ------------------------------------------------------------------ small meshes: the whole evaluation forward in ONE launch
  * The reference's own sizes (params.py:37,56,107,130-134: 11x11 ... 23x23 meshes, hidden 8, 4 layers; evaluation one sample per call,

@@ -29,6 +29,7 @@ def name(n):
     if 'grand_fwd' in n or 'wide::fwd' in n: return 'forward'      # wide::fwd_kernel<...>, wide::fwd_narrow_kernel<HEAD> (narrow route)
     if "bwd_target" in n: return "backward_target"          # grand_bwd_target_kernel<...>, grand_bwd_target_compact_kernel<SUMS>, grand_bwd_target_fused_narrow_kernel<L0, GC>
     if 'bwd_source' in n: return 'backward_source'          # grand_bwd_source_kernel<...>, grand_bwd_source4_kernel<C, GC>
+    if 'step_tail' in n: return 'step_tail'                 # step_tail_kernel<C>, step_tail_narrow_kernel (narrow route: the whole tail in one launch)
     return None
 
 
