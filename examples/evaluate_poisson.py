@@ -7,6 +7,8 @@ error reduction of the last two, with the model's time per sample.
     python examples/evaluate_poisson.py --dim 1 --mesh 21
     python examples/evaluate_poisson.py --state model.pt         # a saved state_dict instead of the brief training
     python examples/evaluate_poisson.py --mesh 64 --band window  # beyond 26 x 26: the windowed band solve
+    python examples/evaluate_poisson.py --mesh 64 --band window --mmpde5_route strided --mmpde5_cfl 0.5 --mmpde5_max_steps 40000
+                                                                 # ... with real MMPDE5 targets beyond 32 x 32
 """
 import argparse
 import os
@@ -51,6 +53,10 @@ if __name__ == '__main__':
     ap.add_argument('--mesh', type=int, default=11, help="nodes per dimension (2-D: at most 26, with --band window 81)")
     ap.add_argument('--band', choices=('lds', 'window'), default='lds',
                     help="FEM route of the 2-D evaluation: 'lds' keeps the banded factor in LDS, 'window' streams it (opt['fem_band'])")
+    ap.add_argument('--mmpde5_route', choices=('lane', 'strided'), default='lane',
+                    help="MMPDE5 targets: 'lane' stops at 32 a side in 2-D (beyond it the noise stand-in is used), 'strided' at 81")
+    ap.add_argument('--mmpde5_cfl', type=float, default=None, help='RK4 step of MMPDE5 is cfl / N^3 (default: the reference 0.05)')
+    ap.add_argument('--mmpde5_max_steps', type=int, default=None, help='step cap of MMPDE5 (default: the reference 10000)')
     ap.add_argument('--num_train', type=int, default=32)
     ap.add_argument('--num_test', type=int, default=16)
     ap.add_argument('--epochs', type=int, default=20)
@@ -60,16 +66,20 @@ if __name__ == '__main__':
     dims = [a.mesh] * a.dim
     opt = hot_path_opt(mesh_dims=dims, hidden_dim=8, num_layers=4, batch_size=8, device='cuda:0', lr=1e-2, loss_type='mesh_loss',
                        solver='torch_FEM', evaler='analytical', eval_quad_points=101, load_quad_points=101,
-                       fem_band=a.band)
-    # the batched MMPDE5 generator stops at 32 nodes a side in 2-D: beyond it the "MA" columns are those of the stand-in target
-    target = 'mmpde5' if a.dim == 1 or a.mesh <= 32 else 'noise'
-    test = MeshDataset(dims, a.num_test, seed=1, target=target)
+                       fem_band=a.band, mmpde5_route=a.mmpde5_route)
+    # the default route of the batched MMPDE5 generator stops at 32 nodes a side in 2-D: beyond it the "MA" columns are those of
+    # the stand-in target unless --mmpde5_route strided is given (81 a side)
+    target = 'mmpde5' if a.dim == 1 or a.mesh <= (81 if opt['mmpde5_route'] == 'strided' else 32) else 'noise'
+    solver = {'route': opt['mmpde5_route']}
+    solver.update({k: v for k, v in (('cfl', a.mmpde5_cfl), ('max_steps', a.mmpde5_max_steps)) if v is not None})
+    target_params = {'solver': solver} if target == 'mmpde5' else None
+    test = MeshDataset(dims, a.num_test, seed=1, target=target, target_params=target_params)
     torch.manual_seed(0)
     model = GNN(test, opt).to(opt['device'])
     if a.state:
         model.load_state_dict(torch.load(a.state, map_location=opt['device']))
     else:
-        train_briefly(model, MeshDataset(dims, a.num_train, seed=0, target=target), opt, a.epochs)
+        train_briefly(model, MeshDataset(dims, a.num_train, seed=0, target=target, target_params=target_params), opt, a.epochs)
     eval_grid_MMPDE_MA(test, opt)                  # grid and target errors once; further checkpoints reuse them
     df, df_time = evaluate_model_fine(model, test, opt, batch_size=a.batch_size)
     print(describe(df))

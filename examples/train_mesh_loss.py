@@ -87,12 +87,20 @@ if __name__ == '__main__':
     ap.add_argument('--torch_loss', action='store_true')
     ap.add_argument('--eager', action='store_true', help='eager launches instead of the captured training step')
     ap.add_argument('--target', choices=('noise', 'mmpde5'), default='noise',
-                    help="x_phys of the samples: the noise stand-in, or the reference's MMPDE5 meshes (one batched GPU call; --mesh <= 32)")
+                    help="x_phys of the samples: the noise stand-in, or the reference's MMPDE5 meshes (one batched GPU call; --mesh <= 32, "
+                         "or <= 81 with --mmpde5_route strided)")
+    ap.add_argument('--mmpde5_route', choices=('lane', 'strided'), default='lane', help="route of the MMPDE5 generator (--target mmpde5)")
+    ap.add_argument('--mmpde5_cfl', type=float, default=None, help='RK4 step of MMPDE5 is cfl / N^3 (default: the reference 0.05)')
+    ap.add_argument('--mmpde5_max_steps', type=int, default=None, help='step cap of MMPDE5 (default: the reference 10000)')
     a = ap.parse_args()
     opt = hot_path_opt(mesh_dims=[a.mesh, a.mesh], hidden_dim=a.hidden_dim, num_layers=a.num_layers, batch_size=a.batch_size,
                        epochs=a.epochs, device='cuda:0', loss_fn='mse', lr=1e-3, show_mesh_evol_plots='False',
-                       device_loader=not a.cpu_loader, native_loss=not a.torch_loss, graphed=not a.eager)
-    ds = MeshDataset(opt['mesh_dims'], a.num_train, seed=0, target=a.target)
+                       device_loader=not a.cpu_loader, native_loss=not a.torch_loss, graphed=not a.eager,
+                       mmpde5_route=a.mmpde5_route)
+    solver = {'route': opt['mmpde5_route']}
+    solver.update({k: v for k, v in (('cfl', a.mmpde5_cfl), ('max_steps', a.mmpde5_max_steps)) if v is not None})
+    ds = MeshDataset(opt['mesh_dims'], a.num_train, seed=0, target=a.target,
+                     target_params={'solver': solver} if a.target == 'mmpde5' else None)
     t0 = time.time()
     model, losses, rate = main(opt, ds)
     torch.cuda.synchronize()

@@ -12,8 +12,9 @@ from ._native import NativeError
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'libgadapt_mesh.so')
 
-ABI_VERSION = 1
-MAX_NODES = 1024                                       # GADAPT_MMPDE5_MAX_NODES
+ABI_VERSION = 2
+MAX_NODES = 1024                                       # GADAPT_MMPDE5_MAX_NODES (route='lane'; 1-D on both routes)
+STRIDED_MAX_SIDE = 81                                  # gadapt_mmpde5_strided_max_side(): 2-D, route='strided'
 MAX_STEPS = 10000000                                   # GADAPT_MMPDE5_MAX_STEPS
 DESC = 4                                               # GADAPT_MMPDE5_DESC: dim, N, node offset, cell offset
 E_SIZE = -3                                            # GADAPT_MESH_E_SIZE
@@ -30,6 +31,9 @@ PROTOTYPES = {
     'gadapt_mmpde5_threads': (_I, [_I]),
     'gadapt_mmpde5_lds_bytes': (_L, [_I]),
     'gadapt_mmpde5_batch': (_I, [_I] + [_P] * 7 + [_D, _D, _I] + [_P] * 6),
+    'gadapt_mmpde5_strided_max_side': (_I, []),
+    'gadapt_mmpde5_strided_lds_bytes': (_L, [_I]),
+    'gadapt_mmpde5_batch_strided': (_I, [_I] + [_P] * 7 + [_D, _D, _I] + [_P] * 6),
 }
 
 _lib = None
@@ -42,11 +46,14 @@ def lib():
             raise NativeError(f"{LIB_PATH} not found: build it with `make` (hipcc --offload-arch=gfx950); "
                               "there is no CPU fallback for the MMPDE5 generator")
         handle = C.CDLL(LIB_PATH)
+        handle.gadapt_mesh_abi_version.restype = _I                    # first: a stale library lacks the newer symbols
+        if handle.gadapt_mesh_abi_version() != ABI_VERSION:
+            raise NativeError(f"{LIB_PATH}: ABI {handle.gadapt_mesh_abi_version()}, expected {ABI_VERSION}; rebuild it with `make`")
         for name, (res, args) in PROTOTYPES.items():
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
-        if handle.gadapt_mesh_abi_version() != ABI_VERSION:
-            raise NativeError(f"{LIB_PATH}: ABI {handle.gadapt_mesh_abi_version()}, expected {ABI_VERSION}")
+        if handle.gadapt_mmpde5_strided_max_side() != STRIDED_MAX_SIDE:
+            raise NativeError(f"{LIB_PATH}: strided route up to {handle.gadapt_mmpde5_strided_max_side()} a side, expected {STRIDED_MAX_SIDE}")
         _lib = handle
     return _lib
 

@@ -288,7 +288,8 @@ class MeshDataset:
         """`target`: what `x_phys` of a sample is.  'noise' (default): x_comp + small interior noise, a stand-in.  'mmpde5': the
         reference's classical target (`src/data.py:206-212`), the MMPDE5 mesh of the sample's own Gaussians, all samples in one
         batched GPU call at construction (`mmpde5.attach_mmpde5_targets`; `ma_its` per sample).  `target_params`: `mon_power` /
-        `mon_reg` of the monitor and keyword arguments of `mmpde5_batch` under the key 'solver'."""
+        `mon_reg` of the monitor and keyword arguments of `mmpde5_batch` under the key 'solver'.  2-D meshes of 33..81 a side
+        need `target_params={'solver': {'route': 'strided', ...}}`, and want `cfl` or `max_steps` raised there (`mmpde5.py`)."""
         self.mesh_dims = list(mesh_dims)
         self.dim = len(self.mesh_dims)
         if self.dim == 1:
@@ -323,7 +324,8 @@ class MeshDataset:
 class MixedMeshDataset(MeshDataset):
     """`data_type='randg_mix'`: samples over SEVERAL meshes (`src/data_mixed.py`), so a batch mixes node counts.  Every
     sample carries its own `mesh` stand-in and `mapping_tensor` (the model reads `data.mesh[i]` / `data.mapping_tensor` for
-    this data type, `src/GNN.py:247-248,279`) and its `pde_params`."""
+    this data type, `src/GNN.py:247-248,279`) and its `pde_params`.  `target` / `target_params` as in `MeshDataset`
+    (`{'solver': {'route': 'strided'}}` for sizes of 33..81 a side)."""
 
     def __init__(self, mesh_sizes: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2, pde_loss_fields: bool = False,
                  eval_quad_points: int = 101, target: str = 'noise', target_params: Optional[dict] = None):

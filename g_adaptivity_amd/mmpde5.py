@@ -9,7 +9,18 @@ sense.  The monitor function is evaluated on the fixed computational grid, so it
 `mmpde5_batch` is the batched form; `MMPDE5_1d`, `MMPDE5_2d`, `MMPDE5_1d_burgers`, `deform_mesh_mmpde1d` and
 `deform_mesh_mmpde2d` keep the reference's names, argument lists and return tuples.  Tensors may live on the CPU or the GPU;
 the iteration always runs on the GPU (there is no CPU fallback: `NativeError` without one) and results come back on the
-device of the input.  Sizes beyond one workgroup (1-D N > 1024, 2-D N > 32) raise `ValueError`.
+device of the input.
+
+Two routes run the same arithmetic.  `route='lane'` (the default) holds one node per lane of the workgroup: 1-D N <= 1024,
+2-D N <= 32.  `route='strided'` holds up to 7 nodes per lane and takes 2-D meshes up to 81 x 81, the limit of the windowed
+FEM route (`fem_band='window'`); a mesh of at most 1024 nodes gives the same bits on both.  Sizes beyond a route's limit raise
+`ValueError`; nothing changes its route unasked.
+
+The reference's step is cfl / N^3 with cfl = 0.05, so the diffusion number falls like 1 / N and the step count grows like
+N^3: with two Gaussians and the default monitor the fp32 iteration needs 20 046 steps at 33 x 33 (beyond the reference's cap
+of 10 000, so the default call returns CAP as the reference would) and has a measure of 2.3e-4 left after 50 000 steps at
+64 x 64, where `cfl=0.5` is stable and converges after 15 556.  Large meshes want `max_steps` or `cfl` raised; a STIFF status
+says when `cfl` was too much.  The defaults are the reference's at every size.
 """
 from __future__ import annotations
 
@@ -85,8 +96,11 @@ def monitor_arrays_2d(m: Callable, n: int, device=None):
 # the batched iteration
 # --------------------------------------------------------------------------
 
-def _shape_of(b: int, xy, ms, m2):
-    """(dim, N) of mesh b; ValueError for anything the kernel does not take."""
+ROUTES = ('lane', 'strided')
+
+
+def _shape_of(b: int, xy, ms, m2, route: str = 'lane'):
+    """(dim, N) of mesh b; ValueError for anything the kernel of `route` does not take."""
     if xy.dim() == 1:
         dim, n = 1, xy.shape[0]
         want_ms, want_m2 = (n - 1,), (n,)
@@ -97,19 +111,25 @@ def _shape_of(b: int, xy, ms, m2):
         raise ValueError(f"mesh {b}: coordinates of shape {tuple(xy.shape)}; [N] (1-D) or [2, N, N] (2-D, square) expected")
     if n < 3:
         raise ValueError(f"mesh {b}: N = {n}; at least 3 nodes a side")
-    if n ** dim > _native_mesh.MAX_NODES:
+    if route == 'strided':
+        if n > (_native_mesh.MAX_NODES if dim == 1 else _native_mesh.STRIDED_MAX_SIDE):
+            raise ValueError(f"mesh {b}: N = {n} in {dim}-D; route='strided' takes 1-D N <= {_native_mesh.MAX_NODES} and "
+                             f"2-D N <= {_native_mesh.STRIDED_MAX_SIDE} a side (one workgroup holds a mesh)")
+    elif n ** dim > _native_mesh.MAX_NODES:
         raise ValueError(f"mesh {b}: N = {n} in {dim}-D; at most {_native_mesh.MAX_NODES} nodes per mesh "
-                         "(1-D N <= 1024, 2-D N <= 32: one workgroup holds a mesh)")
+                         "(1-D N <= 1024, 2-D N <= 32: one workgroup holds a mesh; route='strided' takes 2-D up to 81 a side)")
     if tuple(ms.shape) != want_ms or tuple(m2.shape) != want_m2:
         raise ValueError(f"mesh {b}: monitor arrays of shapes {tuple(ms.shape)}, {tuple(m2.shape)}; {want_ms}, {want_m2} expected")
     return dim, n
 
 
 def _prepare(coords: Sequence, monitors: Sequence, *, cfl: float = 0.05, step=None, tol: float = 1e-6,
-             max_steps: int = 10000, tau: float = 0.1, device=None):
+             max_steps: int = 10000, tau: float = 0.1, device=None, route: str = 'lane'):
     """The host side of `mmpde5_batch`: checks, one concatenated copy of the batch on the GPU, the argument list.  Returns
     (launch, collect, keep): `launch()` issues the one kernel (it may be issued again: inputs are not overwritten),
     `collect()` gives the MMPDE5Result."""
+    if route not in ROUTES:
+        raise ValueError(f"route = {route!r}; one of {ROUTES}")
     if len(coords) == 0 or len(coords) != len(monitors):
         raise ValueError(f"{len(coords)} meshes and {len(monitors)} monitor pairs")
     if not (0 <= int(max_steps) <= _native_mesh.MAX_STEPS):
@@ -117,7 +137,7 @@ def _prepare(coords: Sequence, monitors: Sequence, *, cfl: float = 0.05, step=No
     if not (tol >= 0 and tau > 0):
         raise ValueError(f"tol = {tol}, tau = {tau}; tol >= 0 and tau > 0 expected")
     xs = [torch.stack([torch.as_tensor(c[0]), torch.as_tensor(c[1])]) if isinstance(c, (tuple, list)) else c for c in coords]
-    shapes = [_shape_of(b, xy, ms, m2) for b, (xy, (ms, m2)) in enumerate(zip(xs, monitors))]
+    shapes = [_shape_of(b, xy, ms, m2, route) for b, (xy, (ms, m2)) in enumerate(zip(xs, monitors))]
     B = len(xs)
     if step is None:
         steps_in = [cfl / n ** 3 for _, n in shapes]
@@ -159,9 +179,11 @@ def _prepare(coords: Sequence, monitors: Sequence, *, cfl: float = 0.05, step=No
             measure.data_ptr(), status.data_ptr())
     keep = (desc_host, desc_dev, x0, y0, ms, m2, step_dev)               # what the argument list points into
 
+    entry = 'gadapt_mmpde5_batch' if route == 'lane' else 'gadapt_mmpde5_batch_strided'
+
     def launch(_keep=keep):                                              # the closure keeps the inputs alive
         with torch.cuda.device(dev):
-            _native_mesh.check(_native_mesh.lib().gadapt_mmpde5_batch(*args, current_stream(dev)), 'gadapt_mmpde5_batch')
+            _native_mesh.check(getattr(_native_mesh.lib(), entry)(*args, current_stream(dev)), entry)
 
     def collect():
         out, o = [], 0
@@ -176,7 +198,7 @@ def _prepare(coords: Sequence, monitors: Sequence, *, cfl: float = 0.05, step=No
 
 
 def mmpde5_batch(coords: Sequence, monitors: Sequence, *, cfl: float = 0.05, step=None, tol: float = 1e-6,
-                 max_steps: int = 10000, tau: float = 0.1, device=None) -> MMPDE5Result:
+                 max_steps: int = 10000, tau: float = 0.1, device=None, route: str = 'lane') -> MMPDE5Result:
     """MMPDE5 on many meshes of mixed sizes and dimensions, one launch.
 
     coords[b]    start coordinates: a tensor [N] (1-D), or [2, N, N] / a pair (X, Y) of [N, N] (2-D, node (i, j) of
@@ -185,11 +207,14 @@ def mmpde5_batch(coords: Sequence, monitors: Sequence, *, cfl: float = 0.05, ste
     cfl / step   RK4 step: cfl / N^3 per mesh (the reference's, cfl = 0.05), or `step` (a number or one per mesh)
     tol          stop when sum |new - old| <= tol; 0 runs exactly `max_steps` steps
     max_steps    the reference's cap is 10 000;  tau: the reference's 0.1
+    route        'lane' (default): one node per lane, 2-D N <= 32.  'strided': several nodes per lane, 2-D N <= 81; the same
+                 bits as 'lane' for a mesh of at most 1024 nodes.  1-D N <= 1024 on both.
 
     Returns MMPDE5Result(coords, steps, measure, status): the coordinates in the shapes given, and per-mesh tensors of the
     step count (int32), the last measure and CONVERGED / CAP / STIFF.  A mesh's result does not depend on its batch.
     """
-    launch, collect, _ = _prepare(coords, monitors, cfl=cfl, step=step, tol=tol, max_steps=max_steps, tau=tau, device=device)
+    launch, collect, _ = _prepare(coords, monitors, cfl=cfl, step=step, tol=tol, max_steps=max_steps, tau=tau, device=device,
+                                  route=route)
     launch()
     return collect()
 
@@ -204,11 +229,11 @@ def warn_unconverged(status, what: str = 'MMPDE5'):
                       "(step cap reached)", RuntimeWarning, stacklevel=3)
 
 
-def _timed_single(xy, ms, m2):
+def _timed_single(xy, ms, m2, **solver):
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     t0 = time.time()
-    res = mmpde5_batch([xy], [(ms, m2)])
+    res = mmpde5_batch([xy], [(ms, m2)], **solver)
     torch.cuda.synchronize()
     build_time = time.time() - t0
     warn_unconverged(res.status)
@@ -231,10 +256,19 @@ def MMPDE5_1d_burgers(m: Callable, X: torch.Tensor, N: int):
     return _timed_single(X, torch.as_tensor(ms), torch.as_tensor(m2))
 
 
-def MMPDE5_2d(X: torch.Tensor, Y: torch.Tensor, N: int, params):
-    """`MMPDE5_2d(X, Y, N, params)` -> (X, Y, j, build_time) on [N, N] grids (`indexing='ij'`), monitor `monitor_2d`."""
+def _solver_kwargs(solver: dict) -> dict:
+    extra = set(solver) - {'route', 'cfl', 'max_steps', 'tol'}
+    if extra:
+        raise TypeError(f"unexpected keyword arguments {sorted(extra)}; route, cfl, max_steps and tol go to mmpde5_batch")
+    return solver
+
+
+def MMPDE5_2d(X: torch.Tensor, Y: torch.Tensor, N: int, params, **solver):
+    """`MMPDE5_2d(X, Y, N, params)` -> (X, Y, j, build_time) on [N, N] grids (`indexing='ij'`), monitor `monitor_2d`.
+    Keyword-only `route`, `cfl`, `max_steps`, `tol` go to `mmpde5_batch` (N > 32 needs `route='strided'`)."""
+    _solver_kwargs(solver)
     ms, m2 = monitor_arrays_2d(lambda a, b: monitor_2d(a, b, params), N, X.device)
-    xy, j, build_time = _timed_single(torch.stack([X, Y]), ms, m2)
+    xy, j, build_time = _timed_single(torch.stack([X, Y]), ms, m2, **solver)
     return xy[0], xy[1], j, build_time
 
 
@@ -244,18 +278,19 @@ def deform_mesh_mmpde1d(x_comp: torch.Tensor, n: int, opt):
     return MMPDE5_1d(torch.linspace(0, 1, n, device=x_comp.device), n, opt)
 
 
-def deform_mesh_mmpde2d(x_comp: torch.Tensor, n: int, m: int, pde_params):
+def deform_mesh_mmpde2d(x_comp: torch.Tensor, n: int, m: int, pde_params, **solver):
     """`src/data.py:404-416`: the MMPDE5 mesh of the uniform n x m grid written back in the node order of `x_comp` [n*m, 2]
     (each grid point goes to the node nearest to it after scaling to the unit square) -> (x_phys, j + 1, build_time).
 
     The count is the step count plus one "to account for the initial mesh".  (As shipped the reference's write-back loop
     reuses the name `j`, so it returns m whatever the iteration did; the documented intent is built.)  Square grids only:
-    the reference's own mapping does not hold otherwise (`src/utils_data.py:52`)."""
+    the reference's own mapping does not hold otherwise (`src/utils_data.py:52`).  Keyword-only `route`, `cfl`, `max_steps`,
+    `tol` go to `mmpde5_batch`, as in `MMPDE5_2d`."""
     if n != m:
         raise ValueError(f"deform_mesh_mmpde2d: {n} x {m} grid; square grids only")
     lin = torch.linspace(0, 1, n, device=x_comp.device)
     gx, gy = torch.meshgrid(lin, lin, indexing='ij')
-    X, Y, j, build_time = MMPDE5_2d(gx, gy, n, pde_params)
+    X, Y, j, build_time = MMPDE5_2d(gx, gy, n, pde_params, **solver)
     lo, hi = x_comp.min(0).values, x_comp.max(0).values
     scaled = ((x_comp - lo) / (hi - lo)).to(torch.float32)
     node = torch.cdist(torch.stack([gx.reshape(-1), gy.reshape(-1)], 1), scaled).argmin(1)
@@ -275,7 +310,8 @@ def attach_mmpde5_targets(samples, monitor_params: Optional[dict] = None, **solv
     The monitor of a sample is `monitor_1d` / `monitor_2d` of its own `pde_params` (centres and scales), with
     `monitor_params` (`mon_power`, `mon_reg`) added.  `build_time` per sample (the reference's `data.build_time`, read by
     `evaluate_model_fine` as MA_time) is the wall time of the batched call divided by the sample count.  The samples' meshes must be in grid order (`interval_mesh`,
-    `square_mesh`): the start mesh is `x_comp`.  `solver`: keyword arguments of `mmpde5_batch`."""
+    `square_mesh`): the start mesh is `x_comp`.  `solver`: keyword arguments of `mmpde5_batch` (`route='strided'` for 2-D meshes
+    of 33..81 a side, with `cfl` / `max_steps` / `tol`)."""
     coords, monitors = [], []
     for d in samples:
         params = dict(d.pde_params, **(monitor_params or {}))

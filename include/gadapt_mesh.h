@@ -27,6 +27,13 @@
  * dim 1), cells at desc[b].CELL_OFF in ms.  The arithmetic of a mesh, the order of its reduction included, depends on its
  * own size only: a mesh gives the same bits alone and in any batch.
  *
+ * Two routes run this arithmetic.  gadapt_mmpde5_batch holds one node per lane of one workgroup: 1-D N <= 1024, 2-D N <= 32.
+ * gadapt_mmpde5_batch_strided holds K = ceil(nodes / T) nodes per lane, T = min(nodes rounded up to whole waves, 1024):
+ * lane t owns nodes t + k * T, and 2-D meshes go up to 81 a side (K <= 7; 105 104 bytes of LDS at 81 x 81).  There the measure
+ * is summed in a fixed order: a lane adds |dx| + |dy| of its nodes in increasing k, the 64 lanes of a wave are summed as on the
+ * other route, then the waves in increasing order.  For K = 1 the two orders are the same, so a mesh of at most 1024 nodes
+ * gives the same bits on both routes.
+ *
  * Conventions as in gadapt_hip.h: plain pointers, `stream` is a hipStream_t passed as void*.  Entry points return 0 or a
  * negative GADAPT_MESH_E_* code and never abort; gadapt_mesh_last_error() gives the message.  The launch function neither
  * allocates nor synchronises, and checks every size on the host copy of `desc` before anything is launched.
@@ -40,14 +47,14 @@
 extern "C" {
 #endif
 
-#define GADAPT_MESH_ABI 1
+#define GADAPT_MESH_ABI 2
 
 #define GADAPT_MESH_OK         0
 #define GADAPT_MESH_E_BADARG  -1   /* null pointer, bad dimension, offset or parameter */
-#define GADAPT_MESH_E_LAUNCH  -2   /* hipGetLastError() after the launch */
+#define GADAPT_MESH_E_LAUNCH  -2   /* hipGetLastError() after the launch, or the strided route's LDS was refused */
 #define GADAPT_MESH_E_SIZE    -3   /* a mesh has more nodes than one workgroup holds, or max_steps is beyond the cap */
 
-/* Nodes per mesh: 1-D N <= 1024, 2-D N <= 32 a side. */
+/* Nodes per mesh on the one-node-per-lane route: 1-D N <= 1024, 2-D N <= 32 a side (the strided route: 2-D N <= 81). */
 #define GADAPT_MMPDE5_MAX_NODES 1024
 /* The loop always ends: max_steps is bounded on the host. */
 #define GADAPT_MMPDE5_MAX_STEPS 10000000
@@ -81,6 +88,16 @@ int64_t gadapt_mmpde5_lds_bytes(int nodes);
 int gadapt_mmpde5_batch(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* x0, const float* y0,
                         const float* ms, const float* m2, const double* step, double tau, double tol, int max_steps,
                         float* x, float* y, int32_t* steps, float* measure, int32_t* status, void* stream);
+
+/* The strided route: 1-D meshes up to 1024 nodes and 2-D meshes up to gadapt_mmpde5_strided_max_side() (81) a side in one
+ * launch; arguments, outputs and status words as gadapt_mmpde5_batch.  GADAPT_MESH_E_SIZE for a larger mesh,
+ * GADAPT_MESH_E_LAUNCH if the device refuses the launch or its LDS. */
+int gadapt_mmpde5_strided_max_side(void);
+/* Dynamic LDS of a strided launch whose largest mesh has `nodes` nodes (3..6561). */
+int64_t gadapt_mmpde5_strided_lds_bytes(int nodes);
+int gadapt_mmpde5_batch_strided(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* x0, const float* y0,
+                                const float* ms, const float* m2, const double* step, double tau, double tol, int max_steps,
+                                float* x, float* y, int32_t* steps, float* measure, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
