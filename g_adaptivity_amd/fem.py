@@ -18,6 +18,12 @@ band='window' (`fem_poisson`, `modular_loss_2d`; opt['fem_band'] = 'window' for 
 `gradient_meshpoints_2D`) takes square meshes up to 81 x 81 nodes: the solve keeps a ring of band rows in LDS and streams the
 fp64 factor through a global workspace, which the autograd node keeps for its adjoint solve in lfac's place
 (gadapt_fem_forward_window, gadapt_fem_modular_forward_window, gadapt_fem_backward_window).  The default stays 'lds'.
+
+What bounds a route is the half-bandwidth of the interior block in the node numbering the mesh is given in, not its side
+length: `gadapt_fem_factor_lds_bytes(n_int, band)` ('lds') or `gadapt_fem_window_lds_bytes(n_int, band)` ('window') against
+the 64 KB budget.  The sides quoted here are those of `square_mesh`'s row-major numbering (band n - 2).  A band of 79 is the
+windowed maximum for any mesh; a reference-style numbering (`mesh.coordinates.cell_node_map()`) with a wider band than
+row-major may be refused at a smaller size.  The nodes are not reordered here.
 """
 from __future__ import annotations
 
