@@ -513,6 +513,14 @@ static int block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
     // x_all slot 0 starts with the compact [N,4] layer-0 input (written by the layer-0 launch for the layer-0 backward)
     if (param && !gadapt_forward_computes_coeffs_c(g, c))
         return fail(GADAPT_E_BADARG, "block_forward_loss: param given, but this graph / hidden size does not compute the coefficients in its layer-0 launch (gadapt_forward_computes_coeffs)");
+    // narrow route: wide::fwd_narrow_kernel leaves one row of A / p0 per workgroup 0..63 and has one workgroup per 256-node step, so a
+    // batch of fewer than 64 steps gets its coefficients from the coefficient launch first (the same arithmetic: coeffs_fwd_body) and
+    // the layers take them as given
+    if (narrow && param && (g->n_nodes + 255) / 256 < 64) {
+        if (!a || !p0) return fail(GADAPT_E_BADARG, "block_forward_loss (narrow): param given without the coefficient buffers");
+        if (int rc = gadapt_coeffs_forward(param, param + c * c, param + c * c + c, a, p0, c, stream)) return rc;
+        param = nullptr;
+    }
     FwdExtra ex{FieldSrc{x_comp, f_tensor, uu_tensor, dim}, x_all,
                 LossArgs{target, seed, loss_partials, d, l1 ? 1 : 0, 1.0f / (float)((int64_t)g->n_nodes * (d > 0 ? d : 1))}, &n_partials, param, a, p0};
     if (int rc = block_forward(g, x_all, 4, n_layers, a, 0, p0, 0, layer_params, alpha_all, x_top4, c, stream, &ex, narrow)) return rc;

@@ -250,7 +250,10 @@ int gadapt_block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
  *     layers L-1 .. 1 run the narrow target and source passes on [N,4] rows (dxd_ws, g_ws used at their start), layer 0 the compact
  *     target pass - by default with each source pass inside the next target pass (gadapt_debug_set_narrow_backward_fused), which
  *     uses floats 4N .. 4N + 2E of dxd_ws (N c floats, as for gadapt_block_backward) as a second edge buffer.  Weight gradients land in the 4 x 4 corner of dA and entries 0..3 of dp0 of the slab rows; the rest of each row is
- *     written zero, so the slab reduction and gadapt_step_tail are the dense route's. */
+ *     written zero, so the slab reduction and gadapt_step_tail are the dense route's;
+ *   - gadapt_block_forward_loss_narrow with param != NULL: the layer-0 launch spreads the rows of A / p0 over its first 64 workgroups
+ *     (one per 256-node step), so on a graph of fewer than 64 steps the call issues gadapt_coeffs_forward first and the layers take
+ *     (a, p0) as given - the same values, one launch more. */
 int gadapt_narrow_route(const gadapt_graph* g, int c);
 int gadapt_block_forward_narrow(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers,
                                 const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
