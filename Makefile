@@ -29,19 +29,19 @@ all: $(LIB) $(FEM_LIB) $(MESH_LIB)
 $(FEM_LIB): $(FEM_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(FEM_OBJS)
 
-$(OBJDIR)/fem_kernels.o: $(FEM_CSRC)/fem_kernels.hip $(FEM_CSRC)/fem_window_kernels.hip $(FEM_CSRC)/fem_window_grad_kernels.hip $(FEM_CSRC)/fem_common.h include/gadapt_fem.h
+$(OBJDIR)/fem_kernels.o: $(FEM_CSRC)/fem_kernels.hip $(FEM_CSRC)/fem_window_kernels.hip $(FEM_CSRC)/fem_window_grad_kernels.hip $(FEM_CSRC)/fem_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
-$(OBJDIR)/fem1d_kernels.o: $(FEM_CSRC)/fem1d_kernels.hip $(FEM_CSRC)/fem_common.h include/gadapt_fem.h
+$(OBJDIR)/fem1d_kernels.o: $(FEM_CSRC)/fem1d_kernels.hip $(FEM_CSRC)/fem_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
-$(OBJDIR)/spline_kernels.o: $(FEM_CSRC)/spline_kernels.hip include/gadapt_fem.h
+$(OBJDIR)/spline_kernels.o: $(FEM_CSRC)/spline_kernels.hip $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
-$(OBJDIR)/descent_kernels.o: $(FEM_CSRC)/descent_kernels.hip $(FEM_CSRC)/fem_common.h include/gadapt_fem.h
+$(OBJDIR)/descent_kernels.o: $(FEM_CSRC)/descent_kernels.hip $(FEM_CSRC)/fem_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 

@@ -76,3 +76,8 @@ def check(rc: int, what: str):
     if rc < 0:
         msg = lib().gadapt_fem_last_error().decode() or f"error {rc}"
         raise NativeError(f"{what}: {msg} (code {rc})")
+
+
+def call(name: str, *args):
+    """lib().<name>(*args), raising NativeError with the library's message when it returns an error code."""
+    check(getattr(lib(), name)(*args), name)

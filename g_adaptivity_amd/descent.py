@@ -21,7 +21,7 @@ import torch
 
 from . import _native_fem as _nf
 from ._native import NativeError, current_stream
-from .fem import _topology, _tri_counts, pack_gaussians
+from .fem import _ptr, _topology, _tri_counts, pack_gaussians
 from .fem1d import _Batch, _points, _watch_flags
 
 __all__ = ['DescentResult', 'mesh_descent_2d', 'mesh_descent_1d', 'LAUNCHES_PER_EPOCH_2D', 'LAUNCHES_PER_EPOCH_1D']
@@ -60,10 +60,6 @@ def _require_gpu(t, what: str):
                           f"{t.device if torch.is_tensor(t) else type(t).__name__} tensor); there is no CPU fallback")
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
 def mesh_descent_2d(x0: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
                     pde_params: Sequence[dict], epochs: int, lr: float, n_lat: Optional[int] = None, n_load: Optional[int] = None,
                     x_ref: Optional[torch.Tensor] = None, keep_meshes: bool = False,
@@ -96,7 +92,7 @@ def mesh_descent_2d(x0: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
     if tri_counts is None:
         tri_counts = _tri_counts(cells, node_counts)
     topo = _topology(cells, boundary, node_counts, tri_counts, dev)          # refuses meshes beyond the LDS budget
-    d, N, T, B = topo.dev, topo.n_nodes, topo.n_tris, topo.n_meshes
+    N, T, B = topo.n_nodes, topo.n_tris, topo.n_meshes
     if x0.shape[0] != N:
         raise ValueError(f"mesh_descent_2d: {x0.shape[0]} coordinates for {N} nodes")
     if x_ref is not None:
@@ -109,20 +105,18 @@ def mesh_descent_2d(x0: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
     x = x0.detach().clone().contiguous()
     Q = n_lat * n_lat
     f = lambda *shape: torch.empty(*shape, device=dev)
-    rhs, coeffs, lfac, sol, g_sol, loss = f(N), f(N), f(topo.band_floats), f(B * Q), f(B * Q), f(B)
-    gc, mu, tgrad, gx = f(N), f(N), f(T * 6), f(N, 2)
+    rhs, coeffs, lfac, sol, g_sol, loss = f(N), f(N), topo.factor_buffer(dev), f(B * Q), f(B * Q), f(B)
+    gc, mu, tgrad, gx = topo.backward_buffers(dev)
     loss_hist = f(epochs, B)
     mesh_hist = f(epochs, N, 2) if keep_meshes else None
     first_tangled = torch.empty(B, dtype=torch.int32, device=dev)
     min_area = f(B)
     sign = torch.empty(T, dtype=torch.int8, device=dev)
-    _nf.check(lib.gadapt_fem_descend(
-        B, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['tri_mesh'].data_ptr(),
-        d['int_idx'].data_ptr(), d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(),
-        gpar.data_ptr(), x.data_ptr(), _ptr(x_ref), lat.data_ptr(), lat.data_ptr(), n_lat, topo.lds_bytes, topo.max_tris, epochs,
-        float(lr), rhs.data_ptr(), coeffs.data_ptr(), lfac.data_ptr(), sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(),
-        gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), loss_hist.data_ptr() if epochs else None, _ptr(mesh_hist),
-        first_tangled.data_ptr(), min_area.data_ptr(), sign.data_ptr(), current_stream(dev)), 'gadapt_fem_descend')
+    head = topo.head(gptr, gpar, x, lat, lat, n_lat, tri_mesh=True)
+    _nf.call('gadapt_fem_descend', *head[:-5], _ptr(x_ref), *head[-5:],        # x_ref comes after x, before the lattice
+             epochs, float(lr), rhs.data_ptr(), coeffs.data_ptr(), lfac.data_ptr(), sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(),
+             gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), loss_hist.data_ptr() if epochs else None, _ptr(mesh_hist),
+             first_tangled.data_ptr(), min_area.data_ptr(), sign.data_ptr(), current_stream(dev))
     return DescentResult(x=x, coeffs=coeffs if epochs else None, loss_hist=loss_hist, mesh_hist=mesh_hist,
                          first_tangled=first_tangled, min_area=min_area)
 

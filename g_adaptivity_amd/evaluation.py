@@ -33,7 +33,7 @@ import torch
 
 from . import _native_fem as _nf
 from ._native import NativeError, current_stream
-from .fem import BAND_ROUTES, _topology, _tri_counts, pack_gaussians, simpson_points_per_dim
+from .fem import ENTRY_POINTS, _check_route, _solve_tail, _topology, _tri_counts, pack_gaussians, simpson_points_per_dim
 from .fem1d import _Batch, _split_params, _watch_flags
 from .mesh_graph import MeshData, MeshLoader, Mixed_DataLoader
 
@@ -104,11 +104,7 @@ def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params:
         raise NativeError(f"poisson_eval_errors: the FEM tail runs on the MI355X only (got a "
                           f"{x.device if torch.is_tensor(x) else type(x).__name__} tensor); there is no CPU fallback")
     opt = opt or {}
-    if band not in BAND_ROUTES:
-        raise ValueError(f"poisson_eval_errors: band must be one of {BAND_ROUTES} (got {band!r})")
-    tri_slab = int(tri_slab)
-    if tri_slab < 0 or tri_slab % 32:
-        raise ValueError(f"poisson_eval_errors: tri_slab must be 0 or a positive multiple of 32 (got {tri_slab})")
+    tri_slab = _check_route('poisson_eval_errors', band, tri_slab)
     n_eval = int(n_eval)
     if n_eval < 2:
         raise ValueError(f"poisson_eval_errors: {n_eval} lattice points per dimension; at least 2")
@@ -133,24 +129,11 @@ def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params:
         if topo.n_nodes != x.shape[0]:
             raise ValueError(f"poisson_eval_errors: {x.shape[0]} coordinates for {topo.n_nodes} nodes")
         gptr, gpar = pack_gaussians(pde_params, dev)
-        d, N = topo.dev, topo.n_nodes
-        rhs, coeffs = torch.empty(N, device=dev), torch.empty(N, device=dev)
+        rhs, coeffs = torch.empty(topo.n_nodes, device=dev), torch.empty(topo.n_nodes, device=dev)
         partials = torch.empty(int(lib.gadapt_fem_eval_partials_floats(B)), device=dev)
-        if band == 'window':
-            meta = topo.host['meta']
-            work = torch.empty(max(int(lib.gadapt_fem_window_workspace_floats(B, meta.ctypes.data)), 1), device=dev)
-            _nf.check(lib.gadapt_fem_eval_errors_window(
-                B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
-                d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(),
-                x.data_ptr(), lat.data_ptr(), lat.data_ptr(), n_eval, topo.lds_bytes, topo.max_tris, rhs.data_ptr(),
-                coeffs.data_ptr(), work.data_ptr(), tri_slab, partials.data_ptr(), err.data_ptr(), stream),
-                'gadapt_fem_eval_errors_window')
-        else:
-            _nf.check(lib.gadapt_fem_eval_errors(
-                B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
-                d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(),
-                x.data_ptr(), lat.data_ptr(), lat.data_ptr(), n_eval, topo.lds_bytes, topo.max_tris, rhs.data_ptr(),
-                coeffs.data_ptr(), None, partials.data_ptr(), err.data_ptr(), stream), 'gadapt_fem_eval_errors')
+        work = topo.factor_buffer(dev) if band == 'window' else None           # 'lds': the factor is not kept
+        _nf.call(ENTRY_POINTS['eval_errors'][band], *topo.head(gptr, gpar, x, lat, lat, n_eval),
+                 *_solve_tail(topo, rhs, coeffs, work, tri_slab), partials.data_ptr(), err.data_ptr(), stream)
     elif x.dim() == 1 or (x.dim() == 2 and x.shape[1] == 1):
         x = x.reshape(-1).contiguous()
         if sum(int(n) for n in node_counts) != x.shape[0]:

@@ -122,6 +122,28 @@ class FemTopology:
                          nt_ptr=nt_ptr, nt_idx=nt_idx, boundary=bnd.astype(bool))
         dev = torch.device(device)
         self.dev = {k: torch.from_numpy(v).to(dev) for k, v in self.host.items() if k != 'boundary'}
+        names = ('meta', 'cells', 'node_mesh', 'tri_mesh', 'int_idx', 'int_node', 'nt_ptr', 'nt_idx')
+        self._head = {tm: (B, N, T) + tuple(self.dev[k].data_ptr() for k in names if tm or k != 'tri_mesh') for tm in (False, True)}
+
+    def head(self, gptr, gpar, x, lat_x, lat_y, nlat: int, tri_mesh: bool = False, max_tris: bool = True) -> tuple:
+        """The arguments every 2-D entry point of include/gadapt_fem.h starts with, in its order: sizes, topology (with
+        tri_mesh where the entry point differentiates), Gaussians, coordinates, lattice, max_lds_bytes and max_tris."""
+        return (self._head[tri_mesh] + (gptr.data_ptr(), gpar.data_ptr(), x.data_ptr(), lat_x.data_ptr(), lat_y.data_ptr(), nlat,
+                                        self.lds_bytes) + ((self.max_tris,) if max_tris else ()))
+
+    def factor_buffer(self, device) -> torch.Tensor:
+        """What the solve leaves for the adjoint solve: 'lds' the fp32 band factors (lfac); 'window' the workspace (fp64
+        factor rows and y of every mesh), as the fp32 buffer the C-ABI takes."""
+        if self.route == 'window':
+            floats = int(_nf.lib().gadapt_fem_window_workspace_floats(self.n_meshes, self.host['meta'].ctypes.data))
+            return torch.empty(max(floats, 1), device=device)
+        return torch.empty(self.band_floats, device=device)
+
+    def backward_buffers(self, device) -> Tuple[torch.Tensor, ...]:
+        """(gc [N], mu [N], tgrad [T*6], gx [N,2]) of gadapt_fem_backward[_window]; gx is its result."""
+        N, T = self.n_nodes, self.n_tris
+        return (torch.empty(N, device=device), torch.empty(N, device=device), torch.empty(T * 6, device=device),
+                torch.empty(N, 2, device=device))
 
 
 _topo_cache: Dict[Tuple, FemTopology] = {}
@@ -149,10 +171,19 @@ def _check_route(what: str, band, tri_slab) -> int:
     return tri_slab
 
 
-def _workspace(topo: FemTopology, device) -> torch.Tensor:
-    """The windowed solve's workspace (fp64 factor rows and y of every mesh), as the fp32 buffer the C-ABI takes."""
-    floats = int(_nf.lib().gadapt_fem_window_workspace_floats(topo.n_meshes, topo.host['meta'].ctypes.data))
-    return torch.empty(max(floats, 1), device=device)
+# operation -> route -> symbol of include/gadapt_fem.h (tests/test_fem_window_grad_host.py pins the pairing)
+ENTRY_POINTS = {op: {'lds': f'gadapt_fem_{op}', 'window': f'gadapt_fem_{op}_window'}
+                for op in ('forward', 'modular_forward', 'backward', 'eval_errors')}
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _solve_tail(topo: FemTopology, rhs, coeffs, factor, tri_slab: int) -> tuple:
+    """rhs, coeffs and the factor buffer (None: not kept) as the forward and evaluation entry points take them after the
+    head; the windowed ones take tri_slab next."""
+    return (rhs.data_ptr(), coeffs.data_ptr(), _ptr(factor)) + ((tri_slab,) if topo.route == 'window' else ())
 
 
 def pack_gaussians(pde_params: Sequence[dict], device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -194,26 +225,12 @@ class _FemPoisson(torch.autograd.Function):
     def forward(ctx, x, topo: FemTopology, gptr, gpar, lat_x, lat_y, tri_slab=0):
         _require_gpu(x, 'FEM node coordinates')
         x = x.contiguous()
-        d, dev = topo.dev, x.device
-        nlat = int(lat_x.numel())
-        N, B = topo.n_nodes, topo.n_meshes
-        rhs = torch.empty(N, device=dev)
-        coeffs = torch.empty(N, device=dev)
-        sol = torch.empty(B * nlat * nlat, device=dev)
-        if topo.route == 'window':                               # lfac: the fp64 workspace, kept for the adjoint solve
-            lfac = _workspace(topo, dev)
-            _nf.check(_nf.lib().gadapt_fem_forward_window(
-                B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
-                d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(),
-                x.data_ptr(), lat_x.data_ptr(), lat_y.data_ptr(), nlat, topo.lds_bytes, topo.max_tris, rhs.data_ptr(),
-                coeffs.data_ptr(), lfac.data_ptr(), tri_slab, sol.data_ptr(), current_stream(dev)), 'gadapt_fem_forward_window')
-        else:
-            lfac = torch.empty(topo.band_floats, device=dev)
-            _nf.check(_nf.lib().gadapt_fem_forward(
-                B, N, topo.n_tris, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
-                d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(),
-                x.data_ptr(), lat_x.data_ptr(), lat_y.data_ptr(), nlat, topo.lds_bytes, topo.max_tris, rhs.data_ptr(),
-                coeffs.data_ptr(), lfac.data_ptr(), sol.data_ptr(), current_stream(dev)), 'gadapt_fem_forward')
+        dev, nlat = x.device, int(lat_x.numel())
+        rhs, coeffs = torch.empty(topo.n_nodes, device=dev), torch.empty(topo.n_nodes, device=dev)
+        sol = torch.empty(topo.n_meshes * nlat * nlat, device=dev)
+        lfac = topo.factor_buffer(dev)                               # kept for the adjoint solve
+        _nf.call(ENTRY_POINTS['forward'][topo.route], *topo.head(gptr, gpar, x, lat_x, lat_y, nlat),
+                 *_solve_tail(topo, rhs, coeffs, lfac, tri_slab), sol.data_ptr(), current_stream(dev))
         ctx.topo, ctx.nlat = topo, nlat
         ctx.save_for_backward(x, coeffs, lfac, gptr, gpar, lat_x, lat_y)
         return coeffs, sol
@@ -221,22 +238,20 @@ class _FemPoisson(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_coeffs, g_sol):
         x, coeffs, lfac, gptr, gpar, lat_x, lat_y = ctx.saved_tensors
-        topo, d, dev = ctx.topo, ctx.topo.dev, x.device
-        N, T = topo.n_nodes, topo.n_tris
-        gc = torch.empty(N, device=dev)
-        mu = torch.empty(N, device=dev)
-        tgrad = torch.empty(T * 6, device=dev)
-        gx = torch.empty(N, 2, device=dev)
+        topo, dev = ctx.topo, x.device
         g_coeffs = None if g_coeffs is None else g_coeffs.contiguous().float()
         g_sol = None if g_sol is None else g_sol.contiguous().float()
-        name = 'gadapt_fem_backward_window' if topo.route == 'window' else 'gadapt_fem_backward'
-        _nf.check(getattr(_nf.lib(), name)(
-            topo.n_meshes, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['tri_mesh'].data_ptr(),
-            d['int_idx'].data_ptr(), d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(),
-            gpar.data_ptr(), x.data_ptr(), lat_x.data_ptr(), lat_y.data_ptr(), ctx.nlat, topo.lds_bytes, coeffs.data_ptr(),
-            lfac.data_ptr(), None if g_coeffs is None else g_coeffs.data_ptr(), None if g_sol is None else g_sol.data_ptr(),
-            gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), current_stream(dev)), name)
-        return gx, None, None, None, None, None, None
+        return _backward(topo, gptr, gpar, x, lat_x, lat_y, ctx.nlat, coeffs, lfac, g_coeffs, g_sol, current_stream(dev)), \
+            None, None, None, None, None, None
+
+
+def _backward(topo: FemTopology, gptr, gpar, x, lat_x, lat_y, nlat: int, coeffs, factor, g_coeffs, g_sol, stream) -> torch.Tensor:
+    """gadapt_fem_backward[_window] on the kept factor: d / d x [N,2] of what g_coeffs and g_sol (None: nothing) seed."""
+    gc, mu, tgrad, gx = topo.backward_buffers(x.device)
+    _nf.call(ENTRY_POINTS['backward'][topo.route], *topo.head(gptr, gpar, x, lat_x, lat_y, nlat, tri_mesh=True, max_tris=False),
+             coeffs.data_ptr(), factor.data_ptr(), _ptr(g_coeffs), _ptr(g_sol), gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(),
+             gx.data_ptr(), stream)
+    return gx
 
 
 def _tri_counts(cells: torch.Tensor, node_counts: Sequence[int]) -> List[int]:
@@ -376,30 +391,13 @@ def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.T
     topo = _topology(cells, boundary, node_counts, tri_counts, dev, band)
     gptr, gpar = pack_gaussians(pde_params, dev)
     lat = torch.linspace(0, 1, n_lat).to(dev)              # torch's CPU linspace: the reference's lattice, point for point
-    d, N, T, B = topo.dev, topo.n_nodes, topo.n_tris, topo.n_meshes
-    Q = n_lat * n_lat
-    window = topo.route == 'window'
-    rhs, coeffs = torch.empty(N, device=dev), torch.empty(N, device=dev)
-    lfac = _workspace(topo, dev) if window else torch.empty(topo.band_floats, device=dev)
-    sol, g_sol, loss = torch.empty(B * Q, device=dev), torch.empty(B * Q, device=dev), torch.empty(B, device=dev)
+    N, Q = topo.n_nodes, topo.n_meshes * n_lat * n_lat
+    rhs, coeffs, lfac = torch.empty(N, device=dev), torch.empty(N, device=dev), topo.factor_buffer(dev)
+    sol, g_sol, loss = torch.empty(Q, device=dev), torch.empty(Q, device=dev), torch.empty(topo.n_meshes, device=dev)
     stream = current_stream(dev)
-    head = (B, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['int_idx'].data_ptr(),
-            d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(), gpar.data_ptr(), x.data_ptr(),
-            lat.data_ptr(), lat.data_ptr(), n_lat, topo.lds_bytes, topo.max_tris, _REDUCTIONS[reduction], rhs.data_ptr(),
-            coeffs.data_ptr(), lfac.data_ptr())
-    tail = (sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(), stream)
-    if window:
-        _nf.check(lib.gadapt_fem_modular_forward_window(*head, tri_slab, *tail), 'gadapt_fem_modular_forward_window')
-    else:
-        _nf.check(lib.gadapt_fem_modular_forward(*head, *tail), 'gadapt_fem_modular_forward')
-    gc, mu, tgrad, gx = torch.empty(N, device=dev), torch.empty(N, device=dev), torch.empty(T * 6, device=dev), torch.empty(N, 2, device=dev)
-    name = 'gadapt_fem_backward_window' if window else 'gadapt_fem_backward'
-    _nf.check(getattr(lib, name)(
-        B, N, T, d['meta'].data_ptr(), d['cells'].data_ptr(), d['node_mesh'].data_ptr(), d['tri_mesh'].data_ptr(),
-        d['int_idx'].data_ptr(), d['int_node'].data_ptr(), d['nt_ptr'].data_ptr(), d['nt_idx'].data_ptr(), gptr.data_ptr(),
-        gpar.data_ptr(), x.data_ptr(), lat.data_ptr(), lat.data_ptr(), n_lat, topo.lds_bytes, coeffs.data_ptr(), lfac.data_ptr(),
-        None, g_sol.data_ptr(), gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), stream), name)
-    return loss, gx
+    _nf.call(ENTRY_POINTS['modular_forward'][topo.route], *topo.head(gptr, gpar, x, lat, lat, n_lat), _REDUCTIONS[reduction],
+             *_solve_tail(topo, rhs, coeffs, lfac, tri_slab), sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(), stream)
+    return loss, _backward(topo, gptr, gpar, x, lat, lat, n_lat, coeffs, lfac, None, g_sol, stream)
 
 
 def _modular_quadrature(opt, gt: str) -> Tuple[int, int, str]:

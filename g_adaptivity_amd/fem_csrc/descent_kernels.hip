@@ -1,20 +1,19 @@
 // descent_kernels.hip - gradient descent of the mesh nodes on the FEM error (the reference's backFEM baselines:
 // train_step_adjoint, difFEM_2d.py:593-685, and train_step_vec, difFEM_1d.py:241-292), all epochs enqueued by one call.
 //
-// An epoch is the launches the modular loss already has - gadapt_fem_modular_forward + gadapt_fem_backward in 2-D,
+// An epoch is the launches the modular loss already has - fem_launch_modular_forward + fem_launch_backward (fem_host.h) in 2-D,
 // gadapt_fem1d_poisson_forward + the L2 seed below + gadapt_fem1d_poisson_backward in 1-D - followed by one step launch that
 // does what torch.optim.SGD does (x - lr * g, the product rounded before the subtraction), keeps the epoch's loss and mesh
 // and watches for tangling.  One workgroup per mesh in the step launches; every reduction runs in a fixed order.
 #include <math.h>
 #include <stdio.h>
 #include "fem_common.h"
+#include "fem_host.h"
 
 #pragma clang fp contract(off)
 
 using fem::V2;
 using fem::ld2;
-
-int fem_fail(int code, const char* msg);   // fem_kernels.hip
 
 #define DESC_THREADS 256
 #define DESC_MAX_WAVES 16                  // a 1024-lane workgroup
@@ -117,24 +116,22 @@ extern "C" int gadapt_fem_descend(int B, int N, int T, const int32_t* meta, cons
     if (nlat < 3 || !(nlat & 1)) return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem_descend: the Simpson rule needs an odd nlat >= 3");
     if (max_lds_bytes <= 0 || max_lds_bytes > GADAPT_FEM_LDS_BUDGET || gadapt_fem_eval_lds_bytes(max_tris) > GADAPT_FEM_LDS_BUDGET)
         return fem_fail(GADAPT_FEM_E_LDS, "gadapt_fem_descend: band factor or triangle bin mask outside the LDS budget");
+    // the lattice loss's row sums, as gadapt_fem_modular_forward refuses them in an epoch (and under its name)
+    if (epochs > 0 && (int64_t)nlat * 4 > GADAPT_FEM_LDS_BUDGET)
+        return fem_fail(GADAPT_FEM_E_LDS, "gadapt_fem_modular_forward: the lattice's row sums exceed the LDS budget");
+    const FemBatch b = FEM_BATCH(tri_mesh, max_tris);
+    const FemScratch sc{rhs, coeffs, lfac};
+    const FemAdjoint adj{gc, mu, tgrad, gx};
+    const FemPlan P{max_lds_bytes, gadapt_fem_eval_lds_bytes(max_tris), 0};
     hipStream_t s = (hipStream_t)stream;
     const int n_init = T > B ? T : B;
-    fem_descent_sign_kernel<<<(n_init + DESC_THREADS - 1) / DESC_THREADS, DESC_THREADS, 0, s>>>(T, B, cells, x_ref ? x_ref : x, sign,
-                                                                                                first_tangled, min_area);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
+    FEM_LAUNCH(fem_descent_sign_kernel, (n_init + DESC_THREADS - 1) / DESC_THREADS, DESC_THREADS, 0, T, B, cells, x_ref ? x_ref : x, sign,
+               first_tangled, min_area);
     for (int j = 0; j < epochs; ++j) {
-        int rc = gadapt_fem_modular_forward(B, N, T, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y,
-                                            nlat, max_lds_bytes, max_tris, GADAPT_FEM_LOSS_SIMPSON, rhs, coeffs, lfac, sol, loss, g_sol,
-                                            stream);
-        if (rc) return rc;
-        rc = gadapt_fem_backward(B, N, T, meta, cells, node_mesh, tri_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y,
-                                 nlat, max_lds_bytes, coeffs, lfac, nullptr, g_sol, gc, mu, tgrad, gx, stream);
-        if (rc) return rc;
-        fem_descent_step_kernel<<<B, DESC_THREADS, 0, s>>>(meta, cells, int_idx, sign, gx, loss, lr, j, B, N, x, loss_hist, mesh_hist,
-                                                           first_tangled, min_area);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
+        int rc = fem_launch_modular_forward(Band::lds, b, P, sc, GADAPT_FEM_LOSS_SIMPSON, sol, loss, g_sol, s);
+        if (rc || (rc = fem_launch_backward(Band::lds, b, P, sc, nullptr, g_sol, adj, s))) return rc;
+        FEM_LAUNCH(fem_descent_step_kernel, B, DESC_THREADS, 0, meta, cells, int_idx, sign, gx, loss, lr, j, B, N, x, loss_hist, mesh_hist,
+                   first_tangled, min_area);
     }
     return GADAPT_FEM_OK;
 }

@@ -8,10 +8,9 @@
 // points must round as in the fp32 reference.
 #include <stdio.h>
 #include "fem_common.h"
+#include "fem_host.h"
 
 #pragma clang fp contract(off)
-
-int fem_fail(int code, const char* msg);   // fem_kernels.hip
 
 namespace f1 {
 

@@ -7,7 +7,9 @@
 // (stiffness, load vector, evaluation), per-node gather.  Every sum runs in a fixed order: results are bit-reproducible.
 #include <stdio.h>
 #include <string.h>
+#include <initializer_list>
 #include "fem_common.h"
+#include "fem_host.h"
 
 #pragma clang fp contract(off)
 
@@ -16,15 +18,20 @@ using fem::ld2;
 
 static thread_local char g_err[256] = "";
 
-static int fail(int code, const char* msg) {
+// every translation unit of the library reports through this message slot (fem_host.h)
+int fem_fail(int code, const char* msg) {
     snprintf(g_err, sizeof(g_err), "%s", msg);
     return code;
 }
 
-// the 1-D tail (fem1d_kernels.hip) reports through the same message slot
-int fem_fail(int code, const char* msg) { return fail(code, msg); }
+// "<who>: <what>", who being the entry point that refuses
+static int fail_as(int code, const char* who, const char* what) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return fem_fail(code, msg);
+}
 
-static int launched(const char* what) {
+int fem_launched(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
@@ -590,88 +597,209 @@ __global__ void __launch_bounds__(256) fem_gather_kernel(int n_nodes, const int3
     gx[2 * v + 1] = sy;
 }
 
-// ---------------------------------------------------------------------------------------------------- C-ABI
-extern "C" int64_t gadapt_fem_factor_lds_bytes(int n_int, int band);
+// The route for meshes beyond the resident band (band='window') is compiled in this translation unit: its solve and slabbed
+// evaluation with their launch plan, then its adjoint solve.  Both call this file's device helpers; the entry points of
+// both routes follow below.
+#include "fem_window_kernels.hip"
+#include "fem_window_grad_kernels.hip"
 
-static int check_lat(const float* lat_x, const float* lat_y, int nlat) {
-    if (!lat_x || !lat_y || nlat < 2) return fail(GADAPT_FEM_E_BADARG, "evaluation lattice: need lat_x, lat_y and nlat >= 2");
+// ---------------------------------------------------------------------------------------------------- checks
+// Every entry point: fill a FemBatch from the arguments, check (check_batch, make_plan and what only it checks, in the
+// order its refusals have always had), then the launch sequences.  Nothing is launched before the last check has passed.
+enum : unsigned { NEED_TRI_MESH = 1, NEED_MAX_TRIS = 2, NEED_WORK = 4, NLAT_RANGE = 8 };
+
+// Sizes and pointers in one refusal under the entry point's name - the batch, `required` (the entry point's own buffers),
+// and with NEED_WORK the fp64 workspace, present and 8-byte aligned - then the lattice, then with NLAT_RANGE nlat * nlat.
+static int check_batch(const char* who, const FemBatch& b, unsigned needs, std::initializer_list<const void*> required,
+                       const void* work = nullptr) {
+    bool bad = b.B <= 0 || b.N <= 0 || b.T <= 0 || !b.meta || !b.cells || !b.node_mesh || !b.int_idx || !b.int_node || !b.nt_ptr ||
+               !b.nt_idx || !b.gptr || !b.gpar || !b.x;
+    bad |= (needs & NEED_TRI_MESH) && !b.tri_mesh;
+    bad |= (needs & NEED_MAX_TRIS) && b.max_tris <= 0;
+    bad |= (needs & NEED_WORK) && (!work || ((uintptr_t)work & 7));
+    for (const void* p : required) bad |= !p;
+    if (bad) return fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size");
+    if (!b.lat_x || !b.lat_y || b.nlat < 2) return fem_fail(GADAPT_FEM_E_BADARG, "evaluation lattice: need lat_x, lat_y and nlat >= 2");
+    if ((needs & NLAT_RANGE) && b.nlat > 46340) return fail_as(GADAPT_FEM_E_BADARG, who, "nlat * nlat exceeds the int range");
     return GADAPT_FEM_OK;
 }
 
-static int check_lds(int max_lds_bytes) {
-    if (max_lds_bytes <= 0 || max_lds_bytes > GADAPT_FEM_LDS_BUDGET)
-        return fail(GADAPT_FEM_E_LDS, "band factor: LDS bytes outside (0, GADAPT_FEM_LDS_BUDGET]");
+// what a modular forward checks of its loss arguments, before the shared ones
+static int check_loss(const char* who, const FemBatch& b, int reduction, const float* loss, const float* g_sol) {
+    if (b.B <= 0 || !loss || !g_sol || (reduction != GADAPT_FEM_LOSS_MSE && reduction != GADAPT_FEM_LOSS_SIMPSON))
+        return fail_as(GADAPT_FEM_E_BADARG, who, "null output or unknown reduction");
+    if (reduction == GADAPT_FEM_LOSS_SIMPSON && (b.nlat < 3 || !(b.nlat & 1)))
+        return fail_as(GADAPT_FEM_E_BADARG, who, "the Simpson rule needs an odd nlat >= 3");
+    if (b.nlat > 0 && (int64_t)b.nlat * 4 > GADAPT_FEM_LDS_BUDGET)
+        return fail_as(GADAPT_FEM_E_LDS, who, "the lattice's row sums exceed the LDS budget");
     return GADAPT_FEM_OK;
 }
 
-// everything gadapt_fem_forward and gadapt_fem_eval_errors check alike, before anything is launched
-static int check_solve_args(const char* who, int B, int N, int T, const void* meta, const void* cells, const void* node_mesh, const void* int_idx,
-                            const void* int_node, const void* nt_ptr, const void* nt_idx, const void* gptr, const void* gpar, const void* x,
-                            const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris, const void* rhs,
-                            const void* coeffs, int64_t* eval_lds) {
-    if (B <= 0 || N <= 0 || T <= 0 || !meta || !cells || !node_mesh || !int_idx || !int_node || !nt_ptr || !nt_idx || !gptr || !gpar || !x ||
-        !rhs || !coeffs || max_tris <= 0) {
-        char msg[96];
-        snprintf(msg, sizeof msg, "%s: null pointer or bad size", who);
-        return fail(GADAPT_FEM_E_BADARG, msg);
+// The LDS of a route's launches.  eval: the entry point evaluates on the lattice (else only the solve's share is planned).
+static int make_plan(Band band, const char* who, const FemBatch& b, int tri_slab, bool eval, FemPlan* P) {
+    if (band == Band::window)
+        return eval ? win_plan(who, b.nlat, b.max_lds_bytes, b.max_tris, tri_slab, P) : win_ring_plan(b.max_lds_bytes, &P->solve_lds);
+    if (b.max_lds_bytes <= 0 || b.max_lds_bytes > GADAPT_FEM_LDS_BUDGET)
+        return fem_fail(GADAPT_FEM_E_LDS, "band factor: LDS bytes outside (0, GADAPT_FEM_LDS_BUDGET]");
+    P->solve_lds = b.max_lds_bytes;
+    P->eval_lds = eval ? gadapt_fem_eval_lds_bytes(b.max_tris) : 0;
+    P->slab = 0;
+    if (P->eval_lds > GADAPT_FEM_LDS_BUDGET) return fem_fail(GADAPT_FEM_E_LDS, "evaluation: triangle bin mask exceeds the LDS budget");
+    return GADAPT_FEM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- launch sequences
+// Each takes the stream as `s` (FEM_LAUNCH) and returns at the first launch that fails.
+// load vector and banded Cholesky solve -> coeffs; the factor goes to sc.factor (Band::lds: may be NULL, it is not kept then)
+static int launch_solve(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, hipStream_t s) {
+    const int nb = (b.N + 255) / 256;
+    if (band == Band::window) {
+        FEM_LAUNCH(fem_window_rhs_kernel, nb, 256, 0, b.N, b.cells, b.node_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x, sc.rhs);
+        FEM_LAUNCH(fem_window_solve_kernel, b.B, FEM_WIN_THREADS, (size_t)P.solve_lds, b.meta, b.cells, b.int_idx, b.int_node, b.nt_ptr, b.nt_idx,
+                   b.x, sc.rhs, sc.coeffs, reinterpret_cast<double*>(sc.factor), (int)P.solve_lds);
+    } else {
+        FEM_LAUNCH(fem_rhs_kernel, nb, 256, 0, b.N, b.cells, b.node_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x, sc.rhs);
+        FEM_LAUNCH(fem_factor_kernel, b.B, FEM_SOLVE_THREADS, (size_t)P.solve_lds, b.meta, b.cells, b.int_idx, b.int_node, b.nt_ptr, b.nt_idx, b.x,
+                   sc.rhs, sc.coeffs, sc.factor);
     }
-    int rc = check_lat(lat_x, lat_y, nlat);
-    if (rc) return rc;
-    if ((rc = check_lds(max_lds_bytes))) return rc;
-    *eval_lds = gadapt_fem_eval_lds_bytes(max_tris);
-    if (*eval_lds > GADAPT_FEM_LDS_BUDGET) return fail(GADAPT_FEM_E_LDS, "evaluation: triangle bin mask exceeds the LDS budget");
     return GADAPT_FEM_OK;
 }
 
-// load vector and banded Cholesky solve -> coeffs (lfac may be NULL: the factor is not kept)
-static int launch_solve(int B, int N, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh, const int32_t* int_idx,
-                        const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx, const int32_t* gptr, const float* gpar,
-                        const float* x, int max_lds_bytes, float* rhs, float* coeffs, float* lfac, hipStream_t s) {
-    fem_rhs_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, cells, node_mesh, int_idx, nt_ptr, nt_idx, gptr, gpar, x, rhs);
-    int rc = launched("fem_rhs_kernel");
-    if (rc) return rc;
-    fem_factor_kernel<<<B, FEM_SOLVE_THREADS, max_lds_bytes, s>>>(meta, cells, int_idx, int_node, nt_ptr, nt_idx, x, rhs, coeffs, lfac);
-    return launched("fem_factor_kernel");
+// the solution on the lattice -> sol
+static int launch_eval(Band band, const FemBatch& b, const FemPlan& P, const float* coeffs, float* sol, hipStream_t s) {
+    const dim3 grid(b.B, FEM_EVAL_CHUNKS);
+    if (band == Band::window)
+        FEM_LAUNCH(fem_eval_slab_kernel, grid, FEM_EVAL_THREADS, (size_t)P.eval_lds, b.meta, b.cells, b.nt_ptr, b.nt_idx, b.x, coeffs, b.lat_x,
+                   b.lat_y, b.nlat, P.slab, sol);
+    else
+        FEM_LAUNCH(fem_eval_kernel, grid, FEM_EVAL_THREADS, (size_t)P.eval_lds, b.meta, b.cells, b.nt_ptr, b.nt_idx, b.x, coeffs, b.lat_x, b.lat_y,
+                   b.nlat, sol);
+    return GADAPT_FEM_OK;
 }
 
+// the lattice evaluation fused with the two error norms' chunk partials, then their sum -> err
+static int launch_eval_errors(Band band, const FemBatch& b, const FemPlan& P, const float* coeffs, float* partials, float* err, hipStream_t s) {
+    const dim3 grid(b.B, FEM_EVAL_CHUNKS);
+    if (band == Band::window)
+        FEM_LAUNCH(fem_eval_err_slab_kernel, grid, FEM_EVAL_THREADS, (size_t)P.eval_lds, b.meta, b.cells, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x,
+                   coeffs, b.lat_x, b.lat_y, b.nlat, P.slab, partials);
+    else
+        FEM_LAUNCH(fem_eval_err_kernel, grid, FEM_EVAL_THREADS, (size_t)P.eval_lds, b.meta, b.cells, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x, coeffs,
+                   b.lat_x, b.lat_y, b.nlat, partials);
+    FEM_LAUNCH(fem_err_finish_kernel, (b.B + 255) / 256, 256, 0, b.B, FEM_EVAL_CHUNKS, b.lat_x, b.lat_y, b.nlat, partials, err);
+    return GADAPT_FEM_OK;
+}
+
+static int launch_forward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, float* sol, hipStream_t s) {
+    const int rc = launch_solve(band, b, P, sc, s);
+    return rc ? rc : launch_eval(band, b, P, sc.coeffs, sol, s);
+}
+
+int fem_launch_modular_forward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, int reduction, float* sol, float* loss,
+                               float* g_sol, hipStream_t s) {
+    const int rc = launch_forward(band, b, P, sc, sol, s);
+    if (rc) return rc;
+    FEM_LAUNCH(fem_loss_kernel, b.B, FEM_LOSS_THREADS, (size_t)b.nlat * 4, b.gptr, b.gpar, b.lat_x, b.lat_y, b.nlat, reduction, sol, loss, g_sol);
+    return GADAPT_FEM_OK;
+}
+
+int fem_launch_backward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, const float* g_coeffs, const float* g_sol,
+                        const FemAdjoint& a, hipStream_t s) {
+    const int nb = (b.N + 255) / 256;
+    FEM_LAUNCH(fem_gc_kernel, nb, 256, 0, b.N, b.cells, b.node_mesh, b.nt_ptr, b.nt_idx, b.x, b.lat_x, b.lat_y, b.nlat, g_coeffs, g_sol, a.gc);
+    if (band == Band::window)
+        FEM_LAUNCH(fem_window_adjoint_kernel, b.B, FEM_WIN_THREADS, (size_t)P.solve_lds, b.meta, b.int_idx, b.int_node, a.gc, a.mu,
+                   reinterpret_cast<double*>(sc.factor), (int)P.solve_lds);
+    else
+        FEM_LAUNCH(fem_adjoint_kernel, b.B, FEM_SOLVE_THREADS, (size_t)P.solve_lds, b.meta, b.int_idx, b.int_node, sc.factor, a.gc, a.mu);
+    FEM_LAUNCH(fem_tri_bwd_kernel, (b.T + 255) / 256, 256, 0, b.T, b.cells, b.tri_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x,
+               b.lat_x, b.lat_y, b.nlat, sc.coeffs, a.mu, g_sol, a.tgrad);
+    FEM_LAUNCH(fem_gather_kernel, nb, 256, 0, b.N, b.nt_ptr, b.nt_idx, a.tgrad, a.gx);
+    return GADAPT_FEM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- C-ABI
+extern "C" int gadapt_fem_eval_partials_floats(int n_meshes) { return n_meshes > 0 ? n_meshes * FEM_EVAL_CHUNKS * 2 : 0; }
+
+// One function per operation: the checks in the order the entry points' refusals have, then the launch sequence.  A late check
+// that only one route reaches (the other has refused the same thing earlier) is written once, without an `if`.
+// Band::lds refuses lfac and sol only after the LDS, and puts no upper limit on nlat.
+static int check_forward(Band band, const char* who, const FemBatch& b, const FemScratch& sc, int tri_slab, const float* sol, FemPlan* P) {
+    int rc = band == Band::window ? check_batch(who, b, NEED_MAX_TRIS | NEED_WORK | NLAT_RANGE, {sc.rhs, sc.coeffs, sol}, sc.factor)
+                                  : check_batch(who, b, NEED_MAX_TRIS, {sc.rhs, sc.coeffs});
+    if (rc || (rc = make_plan(band, who, b, tri_slab, true, P))) return rc;
+    return !sc.factor || !sol ? fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size") : GADAPT_FEM_OK;
+}
+
+static int forward(Band band, const char* who, const FemBatch& b, const FemScratch& sc, int tri_slab, float* sol, hipStream_t s) {
+    FemPlan P;
+    const int rc = check_forward(band, who, b, sc, tri_slab, sol, &P);
+    return rc ? rc : launch_forward(band, b, P, sc, sol, s);
+}
+
+// the loss arguments first; Band::lds has always reported the shared ones under gadapt_fem_forward's name
+static int modular_forward(Band band, const char* who, const FemBatch& b, const FemScratch& sc, int reduction, int tri_slab, float* sol,
+                           float* loss, float* g_sol, hipStream_t s) {
+    FemPlan P;
+    int rc = check_loss(who, b, reduction, loss, g_sol);
+    if (rc || (rc = check_forward(band, band == Band::lds ? "gadapt_fem_forward" : who, b, sc, tri_slab, sol, &P))) return rc;
+    return fem_launch_modular_forward(band, b, P, sc, reduction, sol, loss, g_sol, s);
+}
+
+// Band::lds takes a NULL lfac (the factor is not kept), refuses partials and err only after the LDS, and nlat's range last
+static int eval_errors(Band band, const char* who, const FemBatch& b, const FemScratch& sc, int tri_slab, float* partials, float* err,
+                       hipStream_t s) {
+    FemPlan P;
+    int rc = band == Band::window ? check_batch(who, b, NEED_MAX_TRIS | NEED_WORK | NLAT_RANGE, {sc.rhs, sc.coeffs, partials, err}, sc.factor)
+                                  : check_batch(who, b, NEED_MAX_TRIS, {sc.rhs, sc.coeffs});
+    if (rc || (rc = make_plan(band, who, b, tri_slab, true, &P))) return rc;
+    if (!partials || !err) return fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size");
+    if (b.nlat > 46340) return fail_as(GADAPT_FEM_E_BADARG, who, "nlat * nlat exceeds the int range");
+    if ((rc = launch_solve(band, b, P, sc, s))) return rc;
+    return launch_eval_errors(band, b, P, sc.coeffs, partials, err, s);
+}
+
+// sc.coeffs and, on Band::lds, sc.factor are only read; g_coeffs and g_sol may be NULL (no gradient flows in through them)
+static int backward(Band band, const char* who, const FemBatch& b, const FemScratch& sc, const float* g_coeffs, const float* g_sol,
+                    const FemAdjoint& a, hipStream_t s) {
+    FemPlan P;
+    int rc = check_batch(who, b, NEED_TRI_MESH | (band == Band::window ? NEED_WORK : 0), {sc.coeffs, sc.factor, a.gc, a.mu, a.tgrad, a.gx},
+                         sc.factor);
+    if (rc || (rc = make_plan(band, who, b, 0, false, &P))) return rc;
+    return fem_launch_backward(band, b, P, sc, g_coeffs, g_sol, a, s);
+}
+
+// The entry points fill the batch and the scratch from their positional arguments and do nothing else with them.
 extern "C" int gadapt_fem_forward(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
                                   const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
                                   const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
                                   int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* sol, void* stream) {
-    int64_t eval_lds = 0;
-    int rc = check_solve_args("gadapt_fem_forward", B, N, T, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x,
-                              lat_y, nlat, max_lds_bytes, max_tris, rhs, coeffs, &eval_lds);
-    if (rc) return rc;
-    if (!lfac || !sol) return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_forward: null pointer or bad size");
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = launch_solve(B, N, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, max_lds_bytes, rhs, coeffs, lfac, s)))
-        return rc;
-    fem_eval_kernel<<<dim3(B, FEM_EVAL_CHUNKS), FEM_EVAL_THREADS, (size_t)eval_lds, s>>>(meta, cells, nt_ptr, nt_idx, x, coeffs, lat_x, lat_y,
-                                                                                         nlat, sol);
-    return launched("fem_eval_kernel");
+    return forward(Band::lds, "gadapt_fem_forward", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, lfac}, 0, sol, (hipStream_t)stream);
 }
 
-extern "C" int gadapt_fem_eval_partials_floats(int n_meshes) { return n_meshes > 0 ? n_meshes * FEM_EVAL_CHUNKS * 2 : 0; }
+extern "C" int gadapt_fem_forward_window(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                         const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                                         const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y,
+                                         int nlat, int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* work, int tri_slab,
+                                         float* sol, void* stream) {
+    return forward(Band::window, "gadapt_fem_forward_window", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, work}, tri_slab, sol, (hipStream_t)stream);
+}
 
 extern "C" int gadapt_fem_eval_errors(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
                                       const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
                                       const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
                                       int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* partials, float* err,
                                       void* stream) {
-    int64_t eval_lds = 0;
-    int rc = check_solve_args("gadapt_fem_eval_errors", B, N, T, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x,
-                              lat_y, nlat, max_lds_bytes, max_tris, rhs, coeffs, &eval_lds);
-    if (rc) return rc;
-    if (!partials || !err) return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_eval_errors: null pointer or bad size");
-    if (nlat > 46340) return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_eval_errors: nlat * nlat exceeds the int range");
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = launch_solve(B, N, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, max_lds_bytes, rhs, coeffs, lfac, s)))
-        return rc;
-    fem_eval_err_kernel<<<dim3(B, FEM_EVAL_CHUNKS), FEM_EVAL_THREADS, (size_t)eval_lds, s>>>(meta, cells, nt_ptr, nt_idx, gptr, gpar, x, coeffs,
-                                                                                             lat_x, lat_y, nlat, partials);
-    if ((rc = launched("fem_eval_err_kernel"))) return rc;
-    fem_err_finish_kernel<<<(B + 255) / 256, 256, 0, s>>>(B, FEM_EVAL_CHUNKS, lat_x, lat_y, nlat, partials, err);
-    return launched("fem_err_finish_kernel");
+    return eval_errors(Band::lds, "gadapt_fem_eval_errors", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, lfac}, 0, partials, err, (hipStream_t)stream);
+}
+
+extern "C" int gadapt_fem_eval_errors_window(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                             const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                                             const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x,
+                                             const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris, float* rhs,
+                                             float* coeffs, float* work, int tri_slab, float* partials, float* err, void* stream) {
+    return eval_errors(Band::window, "gadapt_fem_eval_errors_window", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, work}, tri_slab, partials, err,
+                       (hipStream_t)stream);
 }
 
 extern "C" int gadapt_fem_modular_forward(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
@@ -679,19 +807,18 @@ extern "C" int gadapt_fem_modular_forward(int B, int N, int T, const int32_t* me
                                           const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y,
                                           int nlat, int max_lds_bytes, int max_tris, int reduction, float* rhs, float* coeffs, float* lfac,
                                           float* sol, float* loss, float* g_sol, void* stream) {
-    if (B <= 0 || !loss || !g_sol || (reduction != GADAPT_FEM_LOSS_MSE && reduction != GADAPT_FEM_LOSS_SIMPSON))
-        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_modular_forward: null output or unknown reduction");
-    if (reduction == GADAPT_FEM_LOSS_SIMPSON && (nlat < 3 || !(nlat & 1)))
-        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_modular_forward: the Simpson rule needs an odd nlat >= 3");
-    if (nlat > 0 && (int64_t)nlat * 4 > GADAPT_FEM_LDS_BUDGET)
-        return fail(GADAPT_FEM_E_LDS, "gadapt_fem_modular_forward: the lattice's row sums exceed the LDS budget");
-    // gadapt_fem_forward checks the rest of its arguments before it launches anything
-    int rc = gadapt_fem_forward(B, N, T, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y, nlat,
-                                max_lds_bytes, max_tris, rhs, coeffs, lfac, sol, stream);
-    if (rc) return rc;
-    fem_loss_kernel<<<B, FEM_LOSS_THREADS, (size_t)nlat * 4, (hipStream_t)stream>>>(gptr, gpar, lat_x, lat_y, nlat, reduction, sol, loss,
-                                                                                    g_sol);
-    return launched("fem_loss_kernel");
+    return modular_forward(Band::lds, "gadapt_fem_modular_forward", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, lfac}, reduction, 0, sol, loss, g_sol,
+                           (hipStream_t)stream);
+}
+
+extern "C" int gadapt_fem_modular_forward_window(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                                 const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                                                 const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x,
+                                                 const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris,
+                                                 int reduction, float* rhs, float* coeffs, float* work, int tri_slab, float* sol, float* loss,
+                                                 float* g_sol, void* stream) {
+    return modular_forward(Band::window, "gadapt_fem_modular_forward_window", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, work}, reduction, tri_slab, sol,
+                           loss, g_sol, (hipStream_t)stream);
 }
 
 extern "C" int gadapt_fem_backward(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
@@ -699,27 +826,16 @@ extern "C" int gadapt_fem_backward(int B, int N, int T, const int32_t* meta, con
                                    const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
                                    const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs, const float* lfac,
                                    const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad, float* gx, void* stream) {
-    if (B <= 0 || N <= 0 || T <= 0 || !meta || !cells || !node_mesh || !tri_mesh || !int_idx || !int_node || !nt_ptr || !nt_idx || !gptr ||
-        !gpar || !x || !coeffs || !lfac || !gc || !mu || !tgrad || !gx)
-        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_backward: null pointer or bad size");
-    int rc = check_lat(lat_x, lat_y, nlat);
-    if (rc) return rc;
-    if ((rc = check_lds(max_lds_bytes))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    fem_gc_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, cells, node_mesh, nt_ptr, nt_idx, x, lat_x, lat_y, nlat, g_coeffs, g_sol, gc);
-    if ((rc = launched("fem_gc_kernel"))) return rc;
-    fem_adjoint_kernel<<<B, FEM_SOLVE_THREADS, max_lds_bytes, s>>>(meta, int_idx, int_node, lfac, gc, mu);
-    if ((rc = launched("fem_adjoint_kernel"))) return rc;
-    fem_tri_bwd_kernel<<<(T + 255) / 256, 256, 0, s>>>(T, cells, tri_mesh, int_idx, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y, nlat, coeffs,
-                                                       mu, g_sol, tgrad);
-    if ((rc = launched("fem_tri_bwd_kernel"))) return rc;
-    fem_gather_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, nt_ptr, nt_idx, tgrad, gx);
-    return launched("fem_gather_kernel");
+    return backward(Band::lds, "gadapt_fem_backward", FEM_BATCH(tri_mesh, 0), {nullptr, const_cast<float*>(coeffs), const_cast<float*>(lfac)}, g_coeffs,
+                    g_sol, {gc, mu, tgrad, gx}, (hipStream_t)stream);
 }
 
-// the windowed band solve and slabbed evaluation of band='window' (gadapt_fem_eval_errors_window): same translation unit, new code only
-#include "fem_window_kernels.hip"
-
-// the differentiable tail of the windowed route (gadapt_fem_forward_window, gadapt_fem_modular_forward_window,
-// gadapt_fem_backward_window): same translation unit, new code only
-#include "fem_window_grad_kernels.hip"
+extern "C" int gadapt_fem_backward_window(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                          const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                                          const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
+                                          const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs, float* work,
+                                          const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad, float* gx,
+                                          void* stream) {
+    return backward(Band::window, "gadapt_fem_backward_window", FEM_BATCH(tri_mesh, 0), {nullptr, const_cast<float*>(coeffs), work}, g_coeffs, g_sol,
+                    {gc, mu, tgrad, gx}, (hipStream_t)stream);
+}

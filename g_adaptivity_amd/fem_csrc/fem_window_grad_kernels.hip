@@ -2,10 +2,10 @@
 // gadapt_fem_modular_forward_window, gadapt_fem_backward_window in include/gadapt_fem.h) for meshes whose band does not stay
 // resident in LDS.
 //
-// This file is compiled as the tail of fem_kernels.hip's translation unit, after fem_window_kernels.hip: it launches that
-// file's fem_window_rhs_kernel and fem_window_solve_kernel as they are, calls its win_eval_point_add, win_prefetch and
-// win_back_substitute, shares its launch plan (win_plan, win_ring_plan), and launches fem_loss_kernel, fem_gc_kernel,
-// fem_tri_bwd_kernel and fem_gather_kernel of fem_kernels.hip unchanged.
+// This file is compiled inside fem_kernels.hip's translation unit, after fem_window_kernels.hip: it calls that file's
+// win_eval_point_add, win_prefetch and win_back_substitute.  The entry points and the launch sequences, which run these
+// kernels between the load vector, solve, loss, chain-rule and gather kernels both routes share, are at the end of
+// fem_kernels.hip.
 //
 // Forward.  The solve leaves the fp64 factor L (n rows of w + 1, entry d of row k = L[k][k-d]) and y in the workspace;
 // fem_eval_slab_kernel is fem_eval_err_slab_kernel's slab walk with each lattice point's sum stored to sol: one chain of
@@ -131,102 +131,4 @@ __global__ void __launch_bounds__(FEM_WIN_THREADS) fem_window_adjoint_kernel(con
     double* yg = work + ((int64_t)mt[GADAPT_FEM_M_BAND_OFF] + io) + (int64_t)n * L.ld;
     win_forward_substitute(n, w, io, L, A, bv, int_node, gc, Lg, yg);
     win_back_substitute(n, w, io, L, A, bv, int_node, Lg, yg, mu);
-}
-
-// ---------------------------------------------------------------------------------------------------- C-ABI
-static int check_window_forward(const char* who, int B, int N, int T, const void* meta, const void* cells, const void* node_mesh,
-                                const void* int_idx, const void* int_node, const void* nt_ptr, const void* nt_idx, const void* gptr,
-                                const void* gpar, const void* x, const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes,
-                                int max_tris, const void* rhs, const void* coeffs, const void* work, int tri_slab, const void* sol, WinPlan* P) {
-    char msg[96];
-    if (B <= 0 || N <= 0 || T <= 0 || !meta || !cells || !node_mesh || !int_idx || !int_node || !nt_ptr || !nt_idx || !gptr || !gpar || !x ||
-        !rhs || !coeffs || !work || ((uintptr_t)work & 7) || !sol || max_tris <= 0) {
-        snprintf(msg, sizeof msg, "%s: null pointer or bad size", who);
-        return fail(GADAPT_FEM_E_BADARG, msg);
-    }
-    int rc = check_lat(lat_x, lat_y, nlat);
-    if (rc) return rc;
-    if (nlat > 46340) {
-        snprintf(msg, sizeof msg, "%s: nlat * nlat exceeds the int range", who);
-        return fail(GADAPT_FEM_E_BADARG, msg);
-    }
-    return win_plan(who, nlat, max_lds_bytes, max_tris, tri_slab, P);
-}
-
-static int launch_window_forward(int B, int N, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh, const int32_t* int_idx,
-                                 const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx, const int32_t* gptr,
-                                 const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat, const WinPlan& P,
-                                 float* rhs, float* coeffs, float* work, float* sol, hipStream_t s) {
-    fem_window_rhs_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, cells, node_mesh, int_idx, nt_ptr, nt_idx, gptr, gpar, x, rhs);
-    int rc = launched("fem_window_rhs_kernel");
-    if (rc) return rc;
-    fem_window_solve_kernel<<<B, FEM_WIN_THREADS, (size_t)P.solve_lds, s>>>(meta, cells, int_idx, int_node, nt_ptr, nt_idx, x, rhs, coeffs,
-                                                                            reinterpret_cast<double*>(work), (int)P.solve_lds);
-    if ((rc = launched("fem_window_solve_kernel"))) return rc;
-    fem_eval_slab_kernel<<<dim3(B, FEM_EVAL_CHUNKS), FEM_EVAL_THREADS, (size_t)P.eval_lds, s>>>(meta, cells, nt_ptr, nt_idx, x, coeffs, lat_x,
-                                                                                                lat_y, nlat, P.slab, sol);
-    return launched("fem_eval_slab_kernel");
-}
-
-extern "C" int gadapt_fem_forward_window(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
-                                         const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
-                                         const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y,
-                                         int nlat, int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* work, int tri_slab,
-                                         float* sol, void* stream) {
-    WinPlan P;
-    int rc = check_window_forward("gadapt_fem_forward_window", B, N, T, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar,
-                                  x, lat_x, lat_y, nlat, max_lds_bytes, max_tris, rhs, coeffs, work, tri_slab, sol, &P);
-    if (rc) return rc;
-    return launch_window_forward(B, N, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y, nlat, P, rhs,
-                                 coeffs, work, sol, (hipStream_t)stream);
-}
-
-extern "C" int gadapt_fem_modular_forward_window(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
-                                                 const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
-                                                 const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x,
-                                                 const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris,
-                                                 int reduction, float* rhs, float* coeffs, float* work, int tri_slab, float* sol, float* loss,
-                                                 float* g_sol, void* stream) {
-    if (B <= 0 || !loss || !g_sol || (reduction != GADAPT_FEM_LOSS_MSE && reduction != GADAPT_FEM_LOSS_SIMPSON))
-        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_modular_forward_window: null output or unknown reduction");
-    if (reduction == GADAPT_FEM_LOSS_SIMPSON && (nlat < 3 || !(nlat & 1)))
-        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_modular_forward_window: the Simpson rule needs an odd nlat >= 3");
-    if (nlat > 0 && (int64_t)nlat * 4 > GADAPT_FEM_LDS_BUDGET)
-        return fail(GADAPT_FEM_E_LDS, "gadapt_fem_modular_forward_window: the lattice's row sums exceed the LDS budget");
-    WinPlan P;
-    int rc = check_window_forward("gadapt_fem_modular_forward_window", B, N, T, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx,
-                                  gptr, gpar, x, lat_x, lat_y, nlat, max_lds_bytes, max_tris, rhs, coeffs, work, tri_slab, sol, &P);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = launch_window_forward(B, N, meta, cells, node_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y, nlat, P, rhs,
-                                    coeffs, work, sol, s)))
-        return rc;
-    fem_loss_kernel<<<B, FEM_LOSS_THREADS, (size_t)nlat * 4, s>>>(gptr, gpar, lat_x, lat_y, nlat, reduction, sol, loss, g_sol);
-    return launched("fem_loss_kernel");
-}
-
-extern "C" int gadapt_fem_backward_window(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
-                                          const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
-                                          const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
-                                          const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs, float* work,
-                                          const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad, float* gx,
-                                          void* stream) {
-    if (B <= 0 || N <= 0 || T <= 0 || !meta || !cells || !node_mesh || !tri_mesh || !int_idx || !int_node || !nt_ptr || !nt_idx || !gptr ||
-        !gpar || !x || !coeffs || !work || ((uintptr_t)work & 7) || !gc || !mu || !tgrad || !gx)
-        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_backward_window: null pointer or bad size");
-    int rc = check_lat(lat_x, lat_y, nlat);
-    if (rc) return rc;
-    int64_t solve_lds = 0;
-    if ((rc = win_ring_plan(max_lds_bytes, &solve_lds))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    fem_gc_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, cells, node_mesh, nt_ptr, nt_idx, x, lat_x, lat_y, nlat, g_coeffs, g_sol, gc);
-    if ((rc = launched("fem_gc_kernel"))) return rc;
-    fem_window_adjoint_kernel<<<B, FEM_WIN_THREADS, (size_t)solve_lds, s>>>(meta, int_idx, int_node, gc, mu, reinterpret_cast<double*>(work),
-                                                                            (int)solve_lds);
-    if ((rc = launched("fem_window_adjoint_kernel"))) return rc;
-    fem_tri_bwd_kernel<<<(T + 255) / 256, 256, 0, s>>>(T, cells, tri_mesh, int_idx, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y, nlat, coeffs,
-                                                       mu, g_sol, tgrad);
-    if ((rc = launched("fem_tri_bwd_kernel"))) return rc;
-    fem_gather_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, nt_ptr, nt_idx, tgrad, gx);
-    return launched("fem_gather_kernel");
 }

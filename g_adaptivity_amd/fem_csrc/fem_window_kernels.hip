@@ -2,9 +2,9 @@
 // (gadapt_fem_eval_errors_window in include/gadapt_fem.h; the differentiable tail on the same solve is fem_window_grad_kernels.hip): a banded Cholesky that keeps a ring of band rows in LDS and
 // streams the finished factor through a global workspace, and a lattice evaluation that takes the triangles slab by slab.
 //
-// This file is compiled as the tail of fem_kernels.hip's translation unit (it is #included there, after the last existing
-// line): it calls that file's device helpers (tri_geometry, fill_pairs, build_bin_mask, the bin-mask walk's helpers,
-// wave_sum, simpson_box) and launches its fem_err_finish_kernel as it is.  Nothing above the #include changes.
+// This file is compiled inside fem_kernels.hip's translation unit (it is #included there, after the last kernel): it calls
+// that file's device helpers (tri_geometry, fill_pairs, build_bin_mask, the bin-mask walk's helpers, wave_sum, simpson_box).
+// The entry points, their checks and the launch sequences of both routes are at the end of fem_kernels.hip.
 //
 // Arithmetic.  The order of fem_factor_kernel / band_factor / band_solve: row-wise assembly in increasing incidence,
 // column-oriented updates in increasing k, forward substitution in increasing k, back substitution in decreasing k, no FMA
@@ -74,7 +74,7 @@ extern "C" int64_t gadapt_fem_window_lds_bytes(int n_int, int band) {
 }
 
 extern "C" int64_t gadapt_fem_window_workspace_floats(int n_meshes, const int32_t* meta) {
-    if (n_meshes <= 0 || !meta) return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_window_workspace_floats: null pointer or bad size");
+    if (n_meshes <= 0 || !meta) return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem_window_workspace_floats: null pointer or bad size");
     int64_t tot = 0;
     for (int b = 0; b < n_meshes; ++b) {
         const int32_t* mt = meta + b * GADAPT_FEM_META;
@@ -400,17 +400,14 @@ __global__ void __launch_bounds__(FEM_EVAL_THREADS) fem_eval_err_slab_kernel(con
     }
 }
 
-// ---------------------------------------------------------------------------------------------------- C-ABI
-// The LDS of a windowed launch, checked before anything is launched and shared by every windowed entry point: the ring of
-// the solve (and of the adjoint solve on the kept workspace) with its slack rows, and the slab of the evaluation.
-struct WinPlan {
-    int64_t solve_lds, eval_lds;
-    int slab;
-};
+// ---------------------------------------------------------------------------------------------------- launch plan
+// The LDS of a windowed launch (the windowed half of make_plan in fem_kernels.hip), checked before anything is launched and
+// shared by every windowed entry point: the ring of the solve (and of the adjoint solve on the kept workspace) with its
+// slack rows, and the slab of the evaluation.
 
 static int win_ring_plan(int max_lds_bytes, int64_t* solve_lds) {
     if (max_lds_bytes <= 0 || max_lds_bytes > GADAPT_FEM_LDS_BUDGET)
-        return fail(GADAPT_FEM_E_LDS, "windowed band: the ring's LDS bytes are outside (0, GADAPT_FEM_LDS_BUDGET]");
+        return fem_fail(GADAPT_FEM_E_LDS, "windowed band: the ring's LDS bytes are outside (0, GADAPT_FEM_LDS_BUDGET]");
     // the widest band max_lds_bytes stands for, then room for FEM_WIN_MAX_S slack rows on it (what the budget leaves of them)
     int w_max = 0;
     while (gadapt_fem_window_lds_bytes(1, w_max + 1) <= max_lds_bytes) ++w_max;
@@ -421,12 +418,8 @@ static int win_ring_plan(int max_lds_bytes, int64_t* solve_lds) {
     return GADAPT_FEM_OK;
 }
 
-static int win_plan(const char* who, int nlat, int max_lds_bytes, int max_tris, int tri_slab, WinPlan* P) {
-    if (tri_slab < 0 || (tri_slab & 31)) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: tri_slab must be 0 or a positive multiple of 32", who);
-        return fail(GADAPT_FEM_E_BADARG, msg);
-    }
+static int win_plan(const char* who, int nlat, int max_lds_bytes, int max_tris, int tri_slab, FemPlan* P) {
+    if (tri_slab < 0 || (tri_slab & 31)) return fail_as(GADAPT_FEM_E_BADARG, who, "tri_slab must be 0 or a positive multiple of 32");
     int rc = win_ring_plan(max_lds_bytes, &P->solve_lds);
     if (rc) return rc;
     // the slab: acc and the mask share the budget
@@ -434,37 +427,11 @@ static int win_plan(const char* who, int nlat, int max_lds_bytes, int max_tris, 
     const int64_t per_word = (int64_t)FEM_NB * FEM_NB * 4;                       // mask bytes per 32 triangles
     const int64_t fit_words = (GADAPT_FEM_LDS_BUDGET - acc_bytes) / per_word;
     if (acc_bytes > GADAPT_FEM_LDS_BUDGET || fit_words < 1)
-        return fail(GADAPT_FEM_E_LDS, "windowed evaluation: the lattice's running sums leave no room for a triangle slab in the LDS budget");
+        return fem_fail(GADAPT_FEM_E_LDS, "windowed evaluation: the lattice's running sums leave no room for a triangle slab in the LDS budget");
     int64_t words = tri_slab ? tri_slab / 32 : fit_words;
-    if (words > fit_words) return fail(GADAPT_FEM_E_LDS, "windowed evaluation: tri_slab's bin mask exceeds the LDS budget");
+    if (words > fit_words) return fem_fail(GADAPT_FEM_E_LDS, "windowed evaluation: tri_slab's bin mask exceeds the LDS budget");
     if (words > eval_words(max_tris)) words = eval_words(max_tris);
     P->eval_lds = acc_bytes + words * per_word;
     P->slab = (int)words * 32;
     return GADAPT_FEM_OK;
-}
-
-extern "C" int gadapt_fem_eval_errors_window(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
-                                             const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
-                                             const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x,
-                                             const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris, float* rhs,
-                                             float* coeffs, float* work, int tri_slab, float* partials, float* err, void* stream) {
-    if (B <= 0 || N <= 0 || T <= 0 || !meta || !cells || !node_mesh || !int_idx || !int_node || !nt_ptr || !nt_idx || !gptr || !gpar || !x ||
-        !rhs || !coeffs || !work || ((uintptr_t)work & 7) || !partials || !err || max_tris <= 0)
-        return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_eval_errors_window: null pointer or bad size");
-    int rc = check_lat(lat_x, lat_y, nlat);
-    if (rc) return rc;
-    if (nlat > 46340) return fail(GADAPT_FEM_E_BADARG, "gadapt_fem_eval_errors_window: nlat * nlat exceeds the int range");
-    WinPlan P;
-    if ((rc = win_plan("gadapt_fem_eval_errors_window", nlat, max_lds_bytes, max_tris, tri_slab, &P))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    fem_window_rhs_kernel<<<(N + 255) / 256, 256, 0, s>>>(N, cells, node_mesh, int_idx, nt_ptr, nt_idx, gptr, gpar, x, rhs);
-    if ((rc = launched("fem_window_rhs_kernel"))) return rc;
-    fem_window_solve_kernel<<<B, FEM_WIN_THREADS, (size_t)P.solve_lds, s>>>(meta, cells, int_idx, int_node, nt_ptr, nt_idx, x, rhs, coeffs,
-                                                                          reinterpret_cast<double*>(work), (int)P.solve_lds);
-    if ((rc = launched("fem_window_solve_kernel"))) return rc;
-    fem_eval_err_slab_kernel<<<dim3(B, FEM_EVAL_CHUNKS), FEM_EVAL_THREADS, (size_t)P.eval_lds, s>>>(meta, cells, nt_ptr, nt_idx, gptr, gpar, x,
-                                                                                                  coeffs, lat_x, lat_y, nlat, P.slab, partials);
-    if ((rc = launched("fem_eval_err_slab_kernel"))) return rc;
-    fem_err_finish_kernel<<<(B + 255) / 256, 256, 0, s>>>(B, FEM_EVAL_CHUNKS, lat_x, lat_y, nlat, partials, err);
-    return launched("fem_err_finish_kernel");
 }

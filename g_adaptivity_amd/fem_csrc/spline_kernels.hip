@@ -19,11 +19,9 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
-#include "gadapt_fem.h"
+#include "fem_host.h"
 
 #pragma clang fp contract(off)
-
-int fem_fail(int code, const char* msg);   // fem_kernels.hip
 
 namespace {
 
