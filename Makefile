@@ -20,7 +20,7 @@ HIPFLAGS   += -DGADAPT_DEV_C=$(DEV_C)
 endif
 UNITS      := gadapt_kernels gadapt_tu_fwd gadapt_tu_bwd_target gadapt_tu_bwd_source gadapt_tu_smallmesh gadapt_tu_sparse gadapt_tu_gat
 OBJS       := $(UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/csr_build.o
-SHARED     := $(CSRC)/gadapt_internal.h $(CSRC)/gadapt_common.inc include/gadapt_hip.h
+SHARED     := $(CSRC)/gadapt_internal.h $(CSRC)/gadapt_common.inc $(CSRC)/gadapt_block_plan.h include/gadapt_hip.h
 
 all: $(LIB) $(FEM_LIB) $(MESH_LIB)
 
@@ -62,7 +62,7 @@ $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
 
 $(OBJDIR)/gadapt_kernels.o: $(CSRC)/gadapt_small.inc
-$(OBJDIR)/gadapt_tu_fwd.o: $(CSRC)/gadapt_fwd.inc $(CSRC)/gadapt_wide.inc $(CSRC)/gadapt_narrow_fwd.inc
+$(OBJDIR)/gadapt_tu_fwd.o: $(CSRC)/gadapt_fwd.inc $(CSRC)/gadapt_wide.inc $(CSRC)/gadapt_narrow_fwd.inc $(CSRC)/gadapt_narrow_node.inc
 $(OBJDIR)/gadapt_tu_bwd_target.o: $(CSRC)/gadapt_bwd_target.inc $(CSRC)/gadapt_narrow_bwd.inc
 $(OBJDIR)/gadapt_tu_bwd_source.o: $(CSRC)/gadapt_bwd_source.inc
 $(OBJDIR)/gadapt_tu_smallmesh.o: $(CSRC)/gadapt_smallmesh.inc
@@ -74,7 +74,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(SHARED)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -c -o $@ $<
 
-$(OBJDIR)/csr_build.o: $(CSRC)/csr_build.cpp include/gadapt_hip.h
+$(OBJDIR)/csr_build.o: $(CSRC)/csr_build.cpp $(CSRC)/gadapt_block_plan.h include/gadapt_hip.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 

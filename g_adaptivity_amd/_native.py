@@ -38,6 +38,10 @@ PROTOTYPES = {
     'gadapt_tile_meta_host': (_I, [_P, _P, _L, _I, _P]),
     'gadapt_ell_build_host': (_I, [_P, _P, _L, _P, _P]),
     'gadapt_wide_window_host': (_I, [_P, _P, _L, _I, _I, _I, _P]),
+    'gadapt_narrow_block_halo_host': (_I, [_P, _P, _L, _P]),
+    'gadapt_narrow_block_range_host': (_I, [_L, _I, _I, _L, _I, _P, _P]),
+    'gadapt_narrow_block_register': (_I, [_G, _I]),
+    'gadapt_narrow_block_halo': (_I, [_G, _I]),
     'gadapt_coeffs_forward': (_I, [_P, _P, _P, _P, _P, _I, _P]),
     'gadapt_coeffs_backward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'gadapt_encode_linear': (_I, [_P, _P, _P, _P, _L, _I, _I, _P]),

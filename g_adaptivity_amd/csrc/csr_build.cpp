@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <vector>
 #include "gadapt_hip.h"
+#include "gadapt_block_plan.h"
 
 extern "C" int gadapt_csr_build_host(const int64_t* src, const int64_t* dst, int64_t n_edges, int64_t n_nodes,
                                      int32_t* rowptr_t, int32_t* col_t, int32_t* eid_t,
@@ -94,5 +95,29 @@ extern "C" int gadapt_wide_window_host(const int32_t* rowptr, const int32_t* col
         }
     }
     *max_deg_out = ok ? longest : 0;
+    return GADAPT_OK;
+}
+
+// Halo of the narrow route's one-launch forward (gadapt_block_plan.h): the smallest h in {32, 64} such that every row of the
+// target-ordered CSR has at most 8 entries and every in-neighbour of node i lies in [32*(i/32) - h, 32*(i/32) + 32 + h); 0 when neither
+// does (the graph keeps the per-layer launches).  Row-major meshes up to 32 nodes wide give 32, up to 64 wide 64.
+extern "C" int gadapt_narrow_block_halo_host(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int32_t* halo_out) {
+    if (!rowptr || !col || !halo_out || n_nodes <= 0) return GADAPT_E_BADARG;
+    *halo_out = 0;
+    for (int h = 32; h <= 64; h += 32) {
+        int32_t md = 0;
+        if (int rc = gadapt_wide_window_host(rowptr, col, n_nodes, 32, h, 8, &md)) return rc;
+        if (md > 0) { *halo_out = h; break; }
+    }
+    return GADAPT_OK;
+}
+
+// Compute range [*lo_out, *hi_out) of layer `layer` of tile `tile` in a group of n_layers layers (layer = -1: the load range):
+// gadapt_block_range, the arithmetic the kernel uses.
+extern "C" int gadapt_narrow_block_range_host(int64_t n_nodes, int halo, int n_layers, int64_t tile, int layer, int64_t* lo_out, int64_t* hi_out) {
+    if (n_nodes <= 0 || (halo != 32 && halo != 64) || n_layers < 1 || n_layers > GADAPT_NARROW_BLOCK_LAYERS || layer < -1 || layer >= n_layers ||
+        tile < 0 || tile * GADAPT_NARROW_TILE >= n_nodes || !lo_out || !hi_out)
+        return GADAPT_E_BADARG;
+    gadapt_block_range(n_nodes, halo, n_layers, tile, layer, lo_out, hi_out);
     return GADAPT_OK;
 }

@@ -5,7 +5,8 @@
 // family rebuilds one unit (the hot kernels are large templates instantiated for six hidden sizes; as ONE unit the build took
 // 2 min 20 s on one core):
 //   gadapt_kernels.hip         C-ABI of layers / blocks / small per-step kernels, error + profiling state
-//   gadapt_tu_fwd.hip          grand_fwd_kernel<C> (gadapt_fwd.inc), wide::fwd_kernel (gadapt_wide.inc)
+//   gadapt_tu_fwd.hip          grand_fwd_kernel<C> (gadapt_fwd.inc), wide::fwd_kernel (gadapt_wide.inc), wide::fwd_narrow_kernel and
+//                              wide::fwd_narrow_block_kernel (gadapt_narrow_fwd.inc, gadapt_narrow_node.inc)
 //   gadapt_tu_bwd_target.hip   grand_bwd_target_kernel<C,...>, grand_bwd_target_compact_kernel (gadapt_bwd_target.inc),
 //                              grand_bwd_target_fused_narrow_kernel (gadapt_narrow_bwd.inc)
 //   gadapt_tu_bwd_source.hip   grand_bwd_source_kernel<C,...>, grand_bwd_source4_kernel (gadapt_bwd_source.inc)
@@ -26,6 +27,7 @@
 #include <utility>
 #include <vector>
 #include "gadapt_hip.h"
+#include "gadapt_block_plan.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -196,6 +198,12 @@ int gadapt_narrow_takes_c(const gadapt_graph* g, int c);
 // its forward layer: [N,4] slot in, [N,4] rows out in x_top4 (extra: layer-0 fields / coefficients, last-layer loss)
 int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* a, const float* p0, const float* lp, float* alpha_out,
                                int residual_only, float* x_top4, hipStream_t st, const FwdExtra* extra);
+// up to 4 consecutive forward layers in one launch (wide::fwd_narrow_block_kernel; halo: gadapt_narrow_block_halo_host of the graph);
+// gadapt_narrow_block_tiles_ok_c: the batch's 512-node tiles keep the loss partials within GADAPT_LOSS_PARTIALS_MAX
+int gadapt_narrow_block_tiles_ok_c(const gadapt_graph* g);
+int gadapt_launch_fwd_narrow_block_c(int c, const gadapt_graph* g, int halo, int n_layers, const float* x_in, float* x_out0, int64_t slot_stride,
+                                     float* x_last, const float* a, const float* p0, const float* lp, float* alpha_out, int64_t alpha_stride,
+                                     hipStream_t st, const FwdExtra* extra);
 int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* alpha,
                                       const float* a, const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, hipStream_t st,
                                       int slab_packed = 0);

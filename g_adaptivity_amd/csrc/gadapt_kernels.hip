@@ -416,19 +416,55 @@ extern "C" int gadapt_adam_step_dev(float* param, const float* grad, float* exp_
 // ------------------------------------------------------------------------------------------------
 // L-step Euler block (GNN.py:273-291)
 // ------------------------------------------------------------------------------------------------
-// Narrow-route forward layers: wide::fwd_narrow_kernel (one node per lane, default) or wide::fwd_kernel<XC = true>, bit-identical
-// (tests/test_gpu_narrow_forward.py).  GADAPT_NARROW_FWD=0 / gadapt_debug_set_narrow_forward(0): the wide kernel.
+// Narrow-route forward layers.  GADAPT_NARROW_FWD / gadapt_debug_set_narrow_forward:
+//   1 (default)  the default choice: groups of up to 4 layers in one launch (wide::fwd_narrow_block_kernel) where the graph is
+//                registered with a halo and the conv is shared, else one wide::fwd_narrow_kernel launch per layer;
+//   2            wide::fwd_narrow_kernel per layer everywhere;
+//   0            wide::fwd_kernel<XC = true> per layer.
+// All three are bit-identical (tests/test_gpu_narrow_forward.py, tests/test_gpu_narrow_block_forward.py).
 static std::atomic<int> g_narrow_fwd{-1};
-static bool narrow_fwd_enabled() {
+static int narrow_fwd_mode() {
     int v = g_narrow_fwd.load(std::memory_order_relaxed);
     if (v < 0) {
         const char* e = getenv("GADAPT_NARROW_FWD");
-        v = (e && e[0] == '0') ? 0 : 1;
+        v = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1);
         g_narrow_fwd.store(v, std::memory_order_relaxed);
     }
-    return v == 1;
+    return v;
 }
-extern "C" int gadapt_debug_set_narrow_forward(int on) { g_narrow_fwd.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
+extern "C" int gadapt_debug_set_narrow_forward(int on) { g_narrow_fwd.store(on == 0 ? 0 : (on == 2 ? 2 : 1), std::memory_order_relaxed); return GADAPT_OK; }
+// The halo of the block launch is a property of the graph that only the host build can know (gadapt_narrow_block_halo_host reads the
+// CSR on the host; gadapt_graph holds device pointers and its layout is frozen at ABI 9).  The caller registers it once per graph,
+// keyed by what identifies the graph's device arrays; an unregistered graph has halo 0 and keeps the per-layer launches.
+struct BlockHaloEntry { const void* rowptr_t; const void* ell_t; int32_t n_nodes, n_edges; int halo; };
+static std::mutex g_block_halo_mu;
+static std::vector<BlockHaloEntry> g_block_halo;
+static bool block_halo_is(const BlockHaloEntry& e, const gadapt_graph* g) {
+    return e.rowptr_t == g->rowptr_t && e.ell_t == g->ell_t && e.n_nodes == g->n_nodes && e.n_edges == g->n_edges;
+}
+extern "C" int gadapt_narrow_block_register(const gadapt_graph* g, int halo) {
+    if (!g || !g->rowptr_t || !g->ell_t || g->n_nodes <= 0 || (halo != 0 && halo != 32 && halo != 64))
+        return fail(GADAPT_E_BADARG, "narrow_block_register: a graph with its ELL copy, halo 0 (forget), 32 or 64");
+    std::lock_guard<std::mutex> lk(g_block_halo_mu);
+    for (size_t k = 0; k < g_block_halo.size(); ++k)
+        if (block_halo_is(g_block_halo[k], g)) { g_block_halo[k] = g_block_halo.back(); g_block_halo.pop_back(); break; }
+    if (halo) g_block_halo.push_back(BlockHaloEntry{g->rowptr_t, g->ell_t, g->n_nodes, g->n_edges, halo});
+    return GADAPT_OK;
+}
+// Batches of fewer tiles than this keep the per-layer launches.  1: none do - a tile's chain of four layers is as long in a small
+// batch as in a large one, and the per-layer launches pay their four kernel boundaries either way (docs/measurements.md, "One launch
+// for the forward layers").
+#define GADAPT_NARROW_BLOCK_MIN_TILES 1
+// the halo the block launch runs with on this graph at this hidden size under the current forward choice, or 0: per-layer launches
+static int narrow_block_halo(const gadapt_graph* g, int c) {
+    if (!g || narrow_fwd_mode() != 1 || !gadapt_narrow_takes_c(g, c) || !gadapt_narrow_block_tiles_ok_c(g)) return 0;
+    if ((g->n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE < GADAPT_NARROW_BLOCK_MIN_TILES) return 0;
+    std::lock_guard<std::mutex> lk(g_block_halo_mu);
+    for (const BlockHaloEntry& e : g_block_halo)
+        if (block_halo_is(e, g)) return e.halo;
+    return 0;
+}
+extern "C" int gadapt_narrow_block_halo(const gadapt_graph* g, int c) { return narrow_block_halo(g, c); }
 // Narrow-route backward: each source pass inside the next layer's target pass (grand_bwd_target_fused_narrow_kernel, default), or the
 // pair of launches per layer, bit-identical (tests/test_gpu_narrow_backward.py).  GADAPT_NARROW_BWD_FUSED=0 /
 // gadapt_debug_set_narrow_backward_fused(0): the pairs.
@@ -453,6 +489,27 @@ static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n
         return fail(GADAPT_E_BADARG, "block_forward (narrow): compact x0, head rows, hidden 64 on a graph the wide forward takes (gadapt_narrow_route)");
     const size_t nc = (size_t)g->n_nodes * c;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // narrow route, one shared conv, a registered halo: groups of up to 4 layers, one launch each (L = 4: one, L = 6: two).  The node
+    // fields and the in-kernel coefficients go to the first group, the loss to the last; a later group reads its input slot from
+    // global memory, where the owners of the group before wrote it (the backward needs it there anyway).
+    const int halo = (narrow && a_stride == 0 && p0_stride == 0) ? narrow_block_halo(g, c) : 0;
+    if (halo) {
+        for (int l0 = 0; l0 < n_layers; l0 += GADAPT_NARROW_BLOCK_LAYERS) {
+            const int kl = n_layers - l0 < GADAPT_NARROW_BLOCK_LAYERS ? n_layers - l0 : GADAPT_NARROW_BLOCK_LAYERS;
+            const bool last = (l0 + kl == n_layers);
+            FwdExtra ex_g{};
+            const FwdExtra* ex = nullptr;
+            if (extra) {
+                if (l0 == 0) { ex_g.fs = extra->fs; ex_g.x0c = extra->x0c; ex_g.cw = extra->cw; ex_g.a_out = extra->a_out; ex_g.p0_out = extra->p0_out; }
+                if (last) { ex_g.loss = extra->loss; ex_g.n_partials_out = extra->n_partials_out; }
+                ex = &ex_g;
+            }
+            if (int rc = gadapt_launch_fwd_narrow_block_c(c, g, halo, kl, x_all + l0 * nc, x_all + (l0 + 1) * nc, (int64_t)nc, last ? x_top4 : nullptr, a, p0,
+                                                          layer_params + 2 * l0, alpha_all ? alpha_all + (size_t)l0 * g->n_edges : nullptr, g->n_edges, st, ex))
+                return rc;
+        }
+        return GADAPT_OK;
+    }
     for (int l = 0; l < n_layers; ++l) {
         const bool last = (l == n_layers - 1);
         float* alpha_l = alpha_all ? alpha_all + (size_t)l * g->n_edges : nullptr;
@@ -467,7 +524,7 @@ static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n
             if (last) { ex_l.loss = extra->loss; ex_l.n_partials_out = extra->n_partials_out; }
             ex = &ex_l;
         }
-        if (narrow && narrow_fwd_enabled())                      // [N,4] slot in, [N,4] slot out (the last layer: the head rows)
+        if (narrow && narrow_fwd_mode() != 0)                    // [N,4] slot in, [N,4] slot out (the last layer: the head rows)
             rc = gadapt_launch_fwd_narrow_c(c, g, x_all + l * nc, a + l * a_stride, p0 + l * p0_stride, layer_params + 2 * l, alpha_l, 0,
                                             last ? x_top4 : x_all + (l + 1) * nc, st, ex);
         else if (narrow)                                         // the same through the wide kernel (gadapt_debug_set_narrow_forward(0))
@@ -513,10 +570,10 @@ static int block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
     // x_all slot 0 starts with the compact [N,4] layer-0 input (written by the layer-0 launch for the layer-0 backward)
     if (param && !gadapt_forward_computes_coeffs_c(g, c))
         return fail(GADAPT_E_BADARG, "block_forward_loss: param given, but this graph / hidden size does not compute the coefficients in its layer-0 launch (gadapt_forward_computes_coeffs)");
-    // narrow route: wide::fwd_narrow_kernel leaves one row of A / p0 per workgroup 0..63 and has one workgroup per 256-node step, so a
-    // batch of fewer than 64 steps gets its coefficients from the coefficient launch first (the same arithmetic: coeffs_fwd_body) and
+    // narrow route: the layer-0 launch leaves one row of A / p0 per workgroup 0..63 and has one workgroup per 256-node step
+    // (wide::fwd_narrow_kernel) or per 512-node tile (wide::fwd_narrow_block_kernel), so a batch of fewer than 64 of them gets its coefficients from the coefficient launch first (the same arithmetic: coeffs_fwd_body) and
     // the layers take them as given
-    if (narrow && param && (g->n_nodes + 255) / 256 < 64) {
+    if (narrow && param && (narrow_block_halo(g, c) ? (g->n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE : (g->n_nodes + 255) / 256) < 64) {
         if (!a || !p0) return fail(GADAPT_E_BADARG, "block_forward_loss (narrow): param given without the coefficient buffers");
         if (int rc = gadapt_coeffs_forward(param, param + c * c, param + c * c + c, a, p0, c, stream)) return rc;
         param = nullptr;

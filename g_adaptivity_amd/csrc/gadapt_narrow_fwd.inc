@@ -1,5 +1,6 @@
-// gadapt_narrow_fwd.inc - forward layer of the narrow route (gadapt_block_forward_narrow), included by gadapt_tu_fwd.hip after
-// gadapt_wide.inc.
+// gadapt_narrow_fwd.inc - forward of the narrow route (gadapt_block_forward_narrow), included by gadapt_tu_fwd.hip after gadapt_wide.inc:
+// wide::fwd_narrow_kernel, one layer per launch (described first), and wide::fwd_narrow_block_kernel, up to four layers per launch by halo
+// recompute (at the end of the file).  Both run the per-node statements of gadapt_narrow_node.inc.
 //
 // On the narrow route every layer reads and writes [N,4] slots: columns 4.. stay exactly zero behind the zero-pad encoder
 // (DESIGN.md section 4), so of the wide kernel's work (wide::fwd_kernel<XC = true>) only channels 0..3 of P, one 16-byte chunk per
@@ -187,72 +188,7 @@ __global__ __launch_bounds__(NRW_NT) void fwd_narrow_kernel(FwdArgs p) {
     for (;;) {
         const int i = s * NRW_NT + 64 * wave + lane;             // this lane's node
 
-        // ---- P[0..3] = (A x + p0)[0..3] on the matrix cores, two 32-node groups
-        const float4 own = t1.own;
-        float xa[4] = {own.x, own.y, own.z, own.w}, xb[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) swap32(xa[c], xb[c]);      // xa: own row in lanes 0..31, zeros above; xb: rows of lanes 32..63, moved down
-        const float va[8] = {xa[0], xa[1], xa[2], xa[3], 0.f, 0.f, 0.f, 0.f};
-        const float vb[8] = {xb[0], xb[1], xb[2], xb[3], 0.f, 0.f, 0.f, 0.f};
-        const Split3 ba = split8(va), bb = split8(vb);
-        f32x16 Pa, Pb;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) { Pa[q] = (q < 4 && h == 0) ? pv[q & 3] : 0.f; Pb[q] = Pa[q]; }
-        mfma6r(Pa, af, ba);
-        mfma6r(Pb, af, bb);
-        float P4[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { float a = Pa[r], b = Pb[r]; swap32(a, b); P4[r] = a; }
-
-        // ---- edge walk (wide::fwd_kernel's expressions on chunk 0)
-        const int kmax = opaque(p.kmax);
-        const int deg = (i < N) ? t1.rp1 - t1.rp0 : 0;
-        v2f acc[2] = {v2f{0.f, 0.f}, v2f{0.f, 0.f}};
-        float w[8];
-        float mref = 0.f, den = 0.f;
-        const v2f plo = {P4[0], P4[1]}, phi = {P4[2], P4[3]};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            w[k] = 0.f;
-            if (k < kmax) {
-                v2f d[4] = {v2f{0.f, 0.f}, v2f{0.f, 0.f}, v2f{0.f, 0.f}, v2f{0.f, 0.f}};
-                d[0] += plo * xv[k].xy;
-                d[1] += phi * xv[k].zw;
-                const v2f dd = (d[0] + d[1]) + (d[2] + d[3]);
-                const float sk = ((dd.x + dd.y) + 0.f) * sc;     // (+ the wide kernel's other half: an exact +0)
-                const bool valid = k < deg;
-                float wk;
-                if (k == 0) {
-                    mref = valid ? sk : 0.f;
-                    wk = valid ? 1.f : 0.f;
-                } else {
-                    float dlt = sk - mref;
-                    const unsigned long long bal = __builtin_amdgcn_ballot_w64(valid && dlt > REBASE);
-                    if ((h ? (unsigned)(bal >> 32) : (unsigned)bal) != 0u) {   // rare: re-base every node of the 32-node group
-                        const float nref = valid ? fmaxf(mref, sk) : mref;
-                        const float corr = sm_exp(mref - nref);
-                        den *= corr;
-                        acc[0] *= corr; acc[1] *= corr;
-#pragma unroll
-                        for (int kk = 0; kk < k; ++kk) w[kk] *= corr;
-                        mref = nref;
-                        dlt = sk - mref;
-                    }
-                    wk = valid ? sm_exp(dlt) : 0.f;
-                }
-                w[k] = wk;
-                den += wk;
-                acc[0] += xv[k].xy * wk;
-                acc[1] += xv[k].zw * wk;
-            }
-        }
-        // ---- x' = x + dt (m - x), alpha = w / (sum + 1e-16)
-        const float inv = sm_rcp(den + 1e-16f);
-        const v4f xc = v4f{own.x, own.y, own.z, own.w};
-        v2f lo = acc[0] * inv - xc.xy, hi = acc[1] * inv - xc.zw;
-        if (!p.residual_only) { lo = xc.xy + lo * dt; hi = xc.zw + hi * dt; }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) w[k] *= inv;
+#include "gadapt_narrow_node.inc"                                 // own, xc, deg, lo | hi, w[0..7] of node i
 
         if (i < N) {
             *reinterpret_cast<v4f*>(p.x_top4 + 4 * (size_t)i) = v4f{lo.x, lo.y, hi.x, hi.y};
@@ -282,6 +218,235 @@ __global__ __launch_bounds__(NRW_NT) void fwd_narrow_kernel(FwdArgs p) {
         narrow_issue2<FLD>(xv, t1, p, cx, s * NRW_NT + 64 * wave + lane);
     }
     if constexpr (HEAD) { if (p.loss.target) loss_wave_partial<4>(p.loss, loss_lv, tid); }   // every wave of the grid owns a slot
+}
+
+// The weights of a block launch: fwd_narrow_kernel's prologue on an eight-wave workgroup.  Given coefficients: this lane's A fragment
+// rows and p0[0..3].  cw (layer 0 with the flat parameter bucket): A = Wk^T Wq, p0 = Wk^T bq with coeffs_fwd_body's arithmetic - waves
+// 0..3 each carry one of the four interleaved partial sums over r, one entry per thread, waves 4..7 only take the results; workgroup
+// `row` < 64 also forms row `row` of the full A / p0 for a_out / p0_out.  narrow_w_issue requests them, narrow_w_finish (one workgroup
+// barrier with cw) gives the fragment fa and p0[0..3] in t.pv; the caller puts its own first loads between the two.
+// (A copy of that prologue with the wave guard, not a shared function: fwd_narrow_kernel keeps its text, and with it its instruction stream.)
+struct NarrowW { float kv[16], wv[16], kr[16], wr[16]; float4 k4, a0, a1; float bqv, wkr; float pv[4]; };
+struct NarrowWLds {
+    float cpart[4][64];                                          // partial sums of A[o][cc], o < 4, cc < 16 (index 16 o + cc) ...
+    float rpart[4][64];                                          // ... and of the row of A this workgroup writes to a_out
+    float cst[64][6];                                            // Wk[r][0..3], bq[r], Wk[r][row]
+    float p0s[4];
+};
+__device__ __forceinline__ void narrow_w_issue(NarrowW& t, const FwdArgs& p, int row, int wave, int lane) {
+    const int h = lane >> 5;
+    t.k4 = f4zero(); t.a0 = f4zero(); t.a1 = f4zero();
+    t.bqv = 0.f; t.wkr = 0.f;
+    const float* gwq = p.cw; const float* gbq = p.cw + C * C; const float* gwk = gbq + C;
+    if (p.cw) {
+        const bool part = wave < 4;
+        // thread t: the partial sum over r = t / 64 (mod 4) of A[o][cc], (o, cc) = (lane / 16, lane % 16) ...
+        if (part) {
+#pragma unroll
+            for (int q = 0; q < 16; ++q) { t.kv[q] = gwk[(4 * q + wave) * C + (lane >> 4)]; t.wv[q] = gwq[(4 * q + wave) * C + (lane & 15)]; }
+        }
+        if (part && row < C) {                                           // ... and of A[row][lane]
+#pragma unroll
+            for (int q = 0; q < 16; ++q) { t.kr[q] = gwk[(4 * q + wave) * C + row]; t.wr[q] = gwq[(4 * q + wave) * C + lane]; }
+        }
+        if (wave == 0) { t.k4 = *reinterpret_cast<const float4*>(gwk + lane * C); t.bqv = gbq[lane]; }
+        if (wave == 1 && row < C) { t.wkr = gwk[lane * C + row]; t.bqv = gbq[lane]; }
+    } else {
+        const int o = min(lane & 31, 3);
+        t.a0 = *reinterpret_cast<const float4*>(p.A + o * C + 8 * h);
+        t.a1 = *reinterpret_cast<const float4*>(p.A + o * C + 8 * h + 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t.pv[r] = p.p0[r];
+    }
+}
+__device__ __forceinline__ void narrow_w_finish(float (&fa)[8], NarrowW& t, NarrowWLds& ws, const FwdArgs& p, int row, int tid) {
+    const int lane = tid & 63, wave = tid >> 6, h = lane >> 5;
+    if (p.cw) {
+        // coeffs_fwd_body's arithmetic: four interleaved partial sums over r of fmaf(Wk[r][o], Wq[r][cc], .), p0 one chain over r
+        const bool part = wave < 4;
+        if (part) {
+            float v = 0.f;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) v = fmaf(t.kv[q], t.wv[q], v);
+            ws.cpart[wave][lane] = v;
+        }
+        if (part && row < C) {
+            float vr = 0.f;
+#pragma unroll
+            for (int q = 0; q < 16; ++q) vr = fmaf(t.kr[q], t.wr[q], vr);
+            ws.rpart[wave][lane] = vr;
+        }
+        if (wave == 0) {                                         // p0[o], o < 4: lanes 0..3
+            ws.cst[lane][0] = t.k4.x; ws.cst[lane][1] = t.k4.y; ws.cst[lane][2] = t.k4.z; ws.cst[lane][3] = t.k4.w; ws.cst[lane][4] = t.bqv;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same wave: LDS operations complete in order
+            if (lane < 4) {
+                float p0v = 0.f;
+#pragma unroll 8
+                for (int r = 0; r < C; ++r) p0v = fmaf(ws.cst[r][lane], ws.cst[r][4], p0v);
+                ws.p0s[lane] = p0v;
+            }
+        }
+        if (wave == 1 && row < C) {                              // p0[row] for p0_out: lane 0
+            ws.cst[lane][5] = t.wkr; ws.cst[lane][4] = t.bqv;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (lane == 0) {
+                float p0v = 0.f;
+#pragma unroll 8
+                for (int r = 0; r < C; ++r) p0v = fmaf(ws.cst[r][5], ws.cst[r][4], p0v);
+                p.p0_out[row] = p0v;
+            }
+        }
+        __syncthreads();
+        const int o = lane & 31;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int L = 16 * min(o, 3) + 8 * h + e;
+            const float av = (ws.cpart[0][L] + ws.cpart[1][L]) + (ws.cpart[2][L] + ws.cpart[3][L]);
+            fa[e] = o < 4 ? av : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t.pv[r] = ws.p0s[r];
+        if (row < C && tid < C) p.a_out[row * C + tid] = (ws.rpart[0][tid] + ws.rpart[1][tid]) + (ws.rpart[2][tid] + ws.rpart[3][tid]);
+    } else {
+        const float av[8] = {t.a0.x, t.a0.y, t.a0.z, t.a0.w, t.a1.x, t.a1.y, t.a1.z, t.a1.w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) fa[e] = (lane & 31) < 4 ? av[e] : 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// K <= 4 consecutive layers in ONE launch by halo recompute (gadapt_block_plan.h).  A workgroup of eight waves owns
+// GADAPT_NARROW_TILE = 512 consecutive nodes.  Layer k + 1 of node i needs layer k of i's in-neighbours, all within `halo` nodes of i's
+// aligned 32-node group (gadapt_narrow_block_halo_host), so the workgroup computes layer k on its owned range widened by
+// (K - 1 - k) halo on each side, for itself: no workgroup waits for another, the only barriers are workgroup barriers.
+//   one global round trip: the input rows of the frame (layer 0 of a fused step: from the node fields) into LDS, the ELL rows and CSR
+//   row bounds of this lane's two nodes into registers, the loss target row, the weights;
+//   per layer: own row and neighbour rows from LDS (16-byte rows, consecutive lanes read consecutive own rows), the per-node
+//   statements of fwd_narrow_kernel (gadapt_narrow_node.inc), the new row into the other LDS buffer, one workgroup barrier.
+// Frame: row r holds node frame0 + r, frame0 = 512 t - margin, margin = K halo rounded up to 64.  Thread `tid` owns frame rows tid and
+// tid + 512 at every layer (wave w: the 64-node blocks w and w + 8), so the indices stay in registers and exactly one of a wave's two
+// blocks is owned, whole.  A block runs a layer when one of its halves lies in that layer's range; each half is one aligned 32-node
+// group, the groups fwd_narrow_kernel ballots over, so every stored value is bit-identical with the per-layer launches.  Rows outside
+// a layer's range are computed on stale rows and dropped: nothing in a later range reads them.
+// Only owned nodes store to global memory: the [N,4] rows of every layer, alpha, the layer-0 input rows, the loss seed; one loss
+// partial per wave (8 per workgroup).
+struct BlockArgs {
+    FwdArgs f;                  // x_in: the group's input rows; x_top4, lp, alpha_out: output rows, {dt, scale} and alpha of its FIRST layer
+    int K, halo;
+    long long slot_stride, alpha_stride;    // floats from one layer's output rows / alpha to the next layer's
+    float* x_last;              // nullable: the group's last layer stores its rows here instead (the head rows)
+};
+constexpr int NRB_NT = GADAPT_NARROW_TILE;     // threads per workgroup = nodes a workgroup owns
+constexpr int NRB_ROWS = 2 * NRB_NT;           // frame rows: 512 + 2 margin <= 1024
+
+template <bool HEAD, bool FLD>
+__global__ __launch_bounds__(NRB_NT) void fwd_narrow_block_kernel(BlockArgs q) {
+    __shared__ float4 rows[2][NRB_ROWS];                         // layer input rows / layer output rows, ping-pong
+    __shared__ float astage[NRB_NT / 64][NRW_AST];
+    __shared__ NarrowWLds wl;
+    const FwdArgs& p = q.f;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5;
+    const int N = p.n_nodes, K = q.K;
+    const int margin = gadapt_block_frame_margin(q.halo, K);
+    const int own0 = NRB_NT * blockIdx.x, frame0 = own0 - margin, last_row = NRB_NT + 2 * margin - 1;
+    const Cols4 cx = make_cols4(p.x_in, p.fs);                   // FLD: where the layer-0 rows come from
+    const float* tgt_base = (HEAD && p.loss.target) ? p.loss.target : p.x_in;
+    const int tgt_d = (HEAD && p.loss.target) ? p.loss.d : 1;
+    const int row = blockIdx.x;                                  // cw: the row of A / p0 this workgroup writes (row < 64)
+
+    // ---- the one global round trip: weights, {dt, scale} of every layer, this lane's two nodes, the loss target row of the owned one
+    NarrowW wt;
+    narrow_w_issue(wt, p, row, wave, lane);
+    float dts[GADAPT_NARROW_BLOCK_LAYERS], scs[GADAPT_NARROW_BLOCK_LAYERS];
+#pragma unroll
+    for (int k = 0; k < GADAPT_NARROW_BLOCK_LAYERS; ++k) { dts[k] = p.lp[2 * min(k, K - 1)]; scs[k] = p.lp[2 * min(k, K - 1) + 1]; }
+    NarrowIn tn[2];
+    const int ell_rows = (N + 255) & ~255;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int i = frame0 + tid + NRB_NT * s, ie = min(max(i, 0), ell_rows - 1);   // (nodes outside [0, N) are in no layer's range)
+        tn[s].ea = *reinterpret_cast<const int4*>(p.ell + 8 * (size_t)ie);
+        tn[s].eb = *reinterpret_cast<const int4*>(p.ell + 8 * (size_t)ie + 4);
+        tn[s].rp0 = p.rowptr[min(max(i, 0), N)];
+        tn[s].rp1 = p.rowptr[min(max(i + 1, 0), N)];
+        rows[0][tid + NRB_NT * s] = ld_x4<FLD>(cx, p.x_in, min(max(i, 0), N - 1));
+    }
+    const int so = 64 * wave < margin ? 1 : 0;                   // which of this wave's two blocks is owned
+    float4 tgt = f4zero();
+    if constexpr (HEAD) tgt = loss_target4(tgt_base, opaque(tgt_d), min(frame0 + tid + NRB_NT * so, N - 1));
+    float fa[8];
+    narrow_w_finish(fa, wt, wl, p, row, tid);
+    float pv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pv[r] = wt.pv[r];
+    const Split3 af = split8(fa);
+    __syncthreads();                                             // the frame is in LDS
+
+    float loss_lv = 0.f;                                         // fused loss: this lane's terms
+    float* sa = astage[wave];
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) {
+        int64_t lo64, hi64;
+        gadapt_block_range(N, q.halo, K, blockIdx.x, k, &lo64, &hi64);
+        const int klo = (int)lo64, khi = (int)hi64;
+        const float dt = k == 0 ? dts[0] : (k == 1 ? dts[1] : (k == 2 ? dts[2] : dts[3]));
+        const float sc = k == 0 ? scs[0] : (k == 1 ? scs[1] : (k == 2 ? scs[2] : scs[3]));
+        const float4* cur = rows[k & 1];
+        float4* nxt = rows[(k + 1) & 1];
+        float* x_out = (k == K - 1 && q.x_last) ? q.x_last : p.x_top4 + k * q.slot_stride;
+        float* alpha_out = p.alpha_out ? p.alpha_out + k * q.alpha_stride : nullptr;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int b0 = frame0 + 64 * wave + NRB_NT * s;      // this wave's block: nodes b0 .. b0 + 63
+            if (b0 + 64 <= klo || b0 >= khi) continue;           // (workgroup barriers stay outside: every wave runs K of them)
+            const int r = tid + NRB_NT * s, i = frame0 + r;      // this lane's frame row and node
+            NarrowIn t1 = tn[s];
+            t1.own = cur[r];
+            v4f xv[8];
+            {
+                const int kmax = opaque(p.kmax);
+                const int jn[8] = {t1.ea.x, t1.ea.y, t1.ea.z, t1.ea.w, t1.eb.x, t1.eb.y, t1.eb.z, t1.eb.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    if (e < kmax) {                              // (an index outside the frame - never on an eligible graph - is clamped into it)
+                        const float4 v = cur[jn[e] < 0 ? r : (int)min((unsigned)max(jn[e] - frame0, 0), (unsigned)last_row)];
+                        xv[e] = v4f{v.x, v.y, v.z, v.w};
+                    }
+                }
+            }
+            // (this kernel's accumulators are VGPRs: 16 wait states between the last MFMA and the swaps that read it - an 8-pass MFMA needs 11)
+#define GADAPT_NARROW_NODE_SETTLE(pa, pb) asm volatile("s_nop 15" : "+v"(pa), "+v"(pb))
+#include "gadapt_narrow_node.inc"                                 // own, xc, deg, lo | hi, w[0..7] of node i
+#undef GADAPT_NARROW_NODE_SETTLE
+
+            if (i >= klo && i < khi) nxt[r] = make_float4(lo.x, lo.y, hi.x, hi.y);
+            if (s != so) continue;                               // halo lanes store nothing
+            if (i < N) {
+                *reinterpret_cast<v4f*>(x_out + 4 * (size_t)i) = v4f{lo.x, lo.y, hi.x, hi.y};
+                if (k == 0 && p.x0c) *reinterpret_cast<v4f*>(p.x0c + 4 * (size_t)i) = xc;   // the layer-0 input rows, for the layer-0 backward
+                if constexpr (HEAD) {
+                    if (k == K - 1 && p.loss.target) {
+                        LossArgs la = p.loss;
+                        la.d = opaque(tgt_d);                    // (= p.loss.d where there is a target)
+                        loss_lv = loss_node(la, i, make_float4(lo.x, lo.y, hi.x, hi.y), tgt, loss_lv);
+                    }
+                }
+            }
+            // ---- alpha in CSR order: staged per wave, then coalesced stores
+            if (alpha_out) {
+                const int e_first = __builtin_amdgcn_readfirstlane(t1.rp0), e_cnt = __builtin_amdgcn_readlane(t1.rp1, 63) - e_first;
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (e < deg) sa[t1.rp0 - e_first + e] = w[e];
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // same wave: LDS operations complete in order
+#pragma unroll
+                for (int t = 0; t < 8; ++t)
+                    if (64 * t + lane < e_cnt) alpha_out[e_first + 64 * t + lane] = sa[64 * t + lane];
+            }
+        }
+        if (k + 1 < K) __syncthreads();                          // layer k is in LDS; its input buffer is free for layer k + 1's output
+    }
+    if constexpr (HEAD) { if (p.loss.target) loss_wave_partial<NRB_NT / 64>(p.loss, loss_lv, tid); }   // every wave of the grid owns a slot
 }
 
 }  // namespace wide

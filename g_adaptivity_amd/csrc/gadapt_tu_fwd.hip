@@ -103,6 +103,52 @@ int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const float* x_in, 
     return check_launch("wide::fwd_narrow_kernel");
 }
 
+// The same for n_layers <= 4 consecutive layers in one launch (wide::fwd_narrow_block_kernel): one 512-thread workgroup per 512-node
+// tile, halo from gadapt_narrow_block_halo_host (32 or 64; the caller has it from the graph's registration).  x_in: the group's [N,4]
+// input slot; the rows of layer k go to x_out0 + k * slot_stride, those of the last layer to x_last where given (head rows); lp and
+// alpha_out (nullable) are the first layer's, the next layers' follow at + 2 and + alpha_stride.  extra: layer-0 fields / coefficients
+// (a group that starts the block), loss (a group that ends it).  Everything is checked before the launch.
+int gadapt_narrow_block_tiles_ok_c(const gadapt_graph* g) {
+    const int64_t tiles = ((int64_t)g->n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE;
+    return tiles >= 1 && tiles * (wide::NRB_NT / 64) <= GADAPT_LOSS_PARTIALS_MAX;      // one loss partial per wave
+}
+int gadapt_launch_fwd_narrow_block_c(int c, const gadapt_graph* g, int halo, int n_layers, const float* x_in, float* x_out0, int64_t slot_stride,
+                                     float* x_last, const float* a, const float* p0, const float* lp, float* alpha_out, int64_t alpha_stride,
+                                     hipStream_t st, const FwdExtra* ex) {
+    if (c != 64 || !g || !gadapt_narrow_takes_c(g, c) || (halo != 32 && halo != 64) || n_layers < 1 || n_layers > GADAPT_NARROW_BLOCK_LAYERS ||
+        !x_in || !lp || (!x_out0 && !(x_last && n_layers == 1)) || slot_stride < 4 * (int64_t)g->n_nodes || (alpha_out && alpha_stride < g->n_edges))
+        return fail(GADAPT_E_BADARG, "narrow block forward: hidden 64, halo 32 or 64, 1..4 layers, output slots, a graph the wide forward takes");
+    if (!gadapt_narrow_block_tiles_ok_c(g))
+        return fail(GADAPT_E_BADARG, "narrow block forward: more loss partials than GADAPT_LOSS_PARTIALS_MAX (8 per 512-node tile)");
+    const bool big = g->wide_deg_t <= 0, half = !big && wide_half(g);
+    const int grid = (g->n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE;
+    wide::BlockArgs q{};
+    q.f = wide::FwdArgs{x_in, nullptr, a, p0, lp, g->ell_t, g->rowptr_t, alpha_out, g->n_nodes, grid, 0,
+                        big ? g->wide_big_deg_t : (half ? g->wide_half_deg_t : g->wide_deg_t), nullptr, x_out0};
+    q.K = n_layers; q.halo = halo; q.slot_stride = slot_stride; q.alpha_stride = alpha_stride; q.x_last = x_last;
+    wide::FwdArgs& p = q.f;
+    if (ex) {
+        p.fs = ex->fs; p.x0c = ex->x0c;
+        if (ex->cw) {
+            if (!gadapt_forward_computes_coeffs_c(g, c)) return fail(GADAPT_E_BADARG, "narrow block forward: the coefficients are given on this graph (gadapt_forward_computes_coeffs)");
+            if (!ex->a_out || !ex->p0_out) return fail(GADAPT_E_BADARG, "narrow block forward: in-kernel coefficients without their destination");
+            p.cw = ex->cw; p.a_out = ex->a_out; p.p0_out = ex->p0_out;
+        }
+        if (ex->loss.target) {
+            if (!x_last || !ex->loss.seed || !ex->loss.partials) return fail(GADAPT_E_BADARG, "narrow block forward: a loss needs the head rows, the seed and the partials");
+            p.loss = ex->loss; if (ex->n_partials_out) *ex->n_partials_out = (wide::NRB_NT / 64) * grid;
+        }
+    }
+    if (!p.cw && (!a || !p0)) return fail(GADAPT_E_BADARG, "narrow block forward: no coefficients");
+    if (p.cw && grid < 64) return fail(GADAPT_E_BADARG, "narrow block forward: in-kernel coefficients need 64 workgroups (one row of A each)");
+    ProfScope prof(0, st, 6 | 32);                              // compact input, head-only output, bit 5: several layers in the launch
+    const bool fld = p.fs.x_comp != nullptr, head = p.loss.target != nullptr;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(wide::NRB_NT), 0, st, q); };
+    if (head) { if (fld) go(wide::fwd_narrow_block_kernel<true, true>); else go(wide::fwd_narrow_block_kernel<true, false>); }
+    else { if (fld) go(wide::fwd_narrow_block_kernel<false, true>); else go(wide::fwd_narrow_block_kernel<false, false>); }
+    return check_launch("wide::fwd_narrow_block_kernel");
+}
+
 template <int C> static int launch_fwd(const gadapt_graph* g, const float* x_in, float* x_out, const float* a, const float* p0,
                                        const float* lp, float* alpha_out, int residual_only, int x_cols, float* x_top4, hipStream_t st, const FwdExtra* ex) {
     using K = Cfg<C>;

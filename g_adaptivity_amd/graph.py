@@ -209,6 +209,22 @@ class MeshGraph:
                                     (C.c_void_p * 3)(*[metas[('s', tm)].data_ptr() for tm in _native.TILE_HEIGHTS]),
                                     ells['t'].data_ptr(), ells['s'].data_ptr(), wide_deg['t'], wide_deg['s'], self.wide_big_deg, self.wide_half_deg)
         self.c_ref = C.byref(self.c_struct)
+        # one launch for up to four forward layers of the narrow route (csrc/gadapt_block_plan.h): the halo is found on the host copy of
+        # the CSR and registered with the library, which sees device arrays only
+        self.narrow_block_halo = 0
+        if wide_deg['t'] > 0 or self.wide_big_deg > 0:
+            hl = C.c_int32(0)
+            if _native.lib().gadapt_narrow_block_halo_host(rowptr_t.data_ptr(), col_t.data_ptr(), n, C.addressof(hl)) != 0:
+                raise _native.NativeError("gadapt_narrow_block_halo_host failed")
+            self.narrow_block_halo = int(hl.value)
+        _native.check(_native.lib().gadapt_narrow_block_register(self.c_ref, self.narrow_block_halo), "gadapt_narrow_block_register")
+
+    def __del__(self):
+        try:                                                # the device arrays go back to the allocator: forget their registration
+            if getattr(self, 'narrow_block_halo', 0):
+                _native.lib().gadapt_narrow_block_register(self.c_ref, 0)
+        except Exception:
+            pass
 
     def narrow_route(self, c: int) -> bool:
         """Whether the block runs on the four live columns at hidden size `c` on this graph (`gadapt_narrow_route`: hidden 64 where the

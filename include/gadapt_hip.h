@@ -111,6 +111,26 @@ int gadapt_ell_build_host(const int32_t* rowptr, const int32_t* col, int64_t n_n
  * 5); step 128 / halo 64 / max_row 8 what its four-wave form takes (gadapt_graph::wide_half_deg_t). */
 int gadapt_wide_window_host(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int step, int halo, int max_row, int32_t* max_deg_out);
 
+/* One launch for up to 4 consecutive forward layers of the narrow route (gadapt_block_forward_narrow / _loss_narrow), by halo recompute:
+ * a workgroup owns 512 consecutive nodes and computes layer k on them widened by (K - 1 - k) * halo on each side, so no workgroup waits
+ * for another.  *halo_out = the smallest h in {32, 64} such that every row of the target-ordered CSR has at most 8 entries and every
+ * in-neighbour of node i lies in [32*(i/32) - h, 32*(i/32) + 32 + h) (gadapt_wide_window_host(step 32, h, max_row 8)); 0: neither, the
+ * graph keeps one launch per layer.  Row-major meshes up to 32 nodes wide give 32, up to 64 wide 64.  Host pointers. */
+int gadapt_narrow_block_halo_host(const int32_t* rowptr, const int32_t* col, int64_t n_nodes, int32_t* halo_out);
+/* The plan the kernel follows, for checking it on the host: [*lo_out, *hi_out) = the nodes tile `tile` (512 nodes each) computes at
+ * layer `layer` (0 .. n_layers-1) of a group of n_layers <= 4 layers - its owned range widened by (n_layers - 1 - layer) * halo, clamped
+ * to [0, round_up(n_nodes, 32)); layer = -1: the range of input rows it loads, one halo wider than layer 0's. */
+int gadapt_narrow_block_range_host(int64_t n_nodes, int halo, int n_layers, int64_t tile, int layer, int64_t* lo_out, int64_t* hi_out);
+/* gadapt_graph holds device arrays, so the library cannot find the halo itself: the caller tells it once per graph, after filling the
+ * structure (halo = gadapt_narrow_block_halo_host's result; 0 = forget the graph - call it before the arrays are freed or reused for
+ * another graph).  The entry is keyed by (rowptr_t, ell_t, n_nodes, n_edges).  A graph that was never registered runs one launch per
+ * layer; results are bit-identical either way. */
+int gadapt_narrow_block_register(const gadapt_graph* g, int halo);
+/* The halo the narrow route's forward would run its one-launch groups with on this graph at hidden size c right now (the registered
+ * halo, the forward choice of gadapt_debug_set_narrow_forward, at most 512 tiles), or 0: one launch per layer.  Per-layer convs
+ * (a_stride != 0) keep one launch per layer as well. */
+int gadapt_narrow_block_halo(const gadapt_graph* g, int c);
+
 /* ------------------------------------------------------------------ weights
  * A[o][c] = sum_r Wk[r][o] Wq[r][c],  p0[o] = sum_r Wk[r][o] bq[r].
  * Wq,Wk are torch Linear weights [out,in] (GRAND_plus.py:146-147). */
@@ -477,9 +497,11 @@ int gadapt_profile_calibrate(int n, void* stream);
  * same row of g_out - so a layer pair touches two [N,C] work buffers instead of three (dxd_ws then only serves layer 0 and the
  * 4-column pair).  Results are bit-identical either way (tests/test_gpu_ops.py::test_block_backward_inplace_is_bit_identical). */
 int gadapt_debug_set_backward_inplace(int on);
-/* Switch: 1 (the default; GADAPT_NARROW_FWD=0 in the environment starts with 0) runs the forward layers of the narrow route
- * (gadapt_block_forward_narrow, gadapt_block_forward_loss_narrow) on the one-node-per-lane kernel; 0 on the wide kernel with its
- * compact input.  Results are bit-identical either way (tests/test_gpu_narrow_forward.py). */
+/* Forward choice of the narrow route (gadapt_block_forward_narrow, gadapt_block_forward_loss_narrow); GADAPT_NARROW_FWD=0 / =2 in the
+ * environment starts with that value.  1 (the default): the default choice - groups of up to 4 layers in one launch each where the
+ * graph is registered with a halo (gadapt_narrow_block_register) and the conv is shared, else the one-node-per-lane kernel, one launch
+ * per layer; 2: one launch per layer everywhere; 0: the wide kernel with its compact input, one launch per layer.  Results are
+ * bit-identical all three ways (tests/test_gpu_narrow_forward.py, tests/test_gpu_narrow_block_forward.py). */
 int gadapt_debug_set_narrow_forward(int on);
 /* Switch: 1 (the default; GADAPT_NARROW_BWD_FUSED=0 in the environment starts with 0) lets gadapt_block_backward_narrow run the source
  * pass of each layer inside the target pass of the layer below (L launches instead of 2L - 1; the second edge buffer the fused launches
