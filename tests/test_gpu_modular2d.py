@@ -1,6 +1,11 @@
 """loss_type='modular' in 2-D on the MI355X: gradient_meshpoints_2D (g_adaptivity_amd/fem.py, libgadapt_fem.so) against the
 test-side restatement of the reference's three gradient types (tests/modular2d_restatement.py), and the model trained
-through its pseudo-loss."""
+through its pseudo-loss.
+
+The gradient rule here, rel <= max(1e-4, 1.5 x the fp32 restatement's own deviation), is taken over ALL nodes, and there it is
+loose: the fp32 restatement itself is 1e-3 to 3e-2 from fp64 on jittered meshes, from the boundary nodes, whose Simpson points
+lie on element edges that fp32 and fp64 class differently.  tests/fem_lattices.py and tests/test_gpu_fem_lattices.py hold
+the same kernels to 1e-4 on the interior nodes, where that deviation stays under 6.6e-5 (5 x 5 and 7 x 7 meshes)."""
 import os
 import sys
 
