@@ -1,5 +1,6 @@
 // gadapt_internal.h - what the translation units of libgadapt_hip.so share on the host side: build-time geometry parameters, error
-// reporting, the optional per-launch event pairs, launch helpers, and the entry points one unit offers the others.
+// reporting, the optional per-launch event pairs, launch helpers, the descriptions of a layer's forward and backward (LayerFwd, LayerBwd),
+// and the entry points one unit offers the others in terms of them.
 //
 // The library is built from several .hip files so that `make -j` compiles the kernel families in parallel and an edit to one
 // family rebuilds one unit (the hot kernels are large templates instantiated for six hidden sizes; as ONE unit the build took
@@ -182,37 +183,42 @@ template <int C> static int tiles_for(int64_t n_nodes) { return (int)((n_nodes +
 struct FwdExtra { FieldSrc fs; float* x0c; LossArgs loss; int* n_partials_out; const float* cw; float* a_out; float* p0_out; };
 int gadapt_forward_computes_coeffs_c(const gadapt_graph* g, int c);
 #define GADAPT_LOSS_PARTIALS_MAX 4096  /* waves of a forward launch: GADAPT_FWD_MAX_BLOCKS workgroups of up to 8 waves */
-int gadapt_launch_fwd_c(int c, const gadapt_graph* g, const float* x_in, float* x_out, const float* a, const float* p0, const float* lp,
-                        float* alpha_out, int residual_only, int x_cols, float* x_top4, hipStream_t st, const FwdExtra* extra = nullptr);
-// target pass (always) ...
-int gadapt_launch_bwd_target_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, const float* alpha, const float* a,
-                               const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, float* sums_out, float* sums_sc_out,
-                               int want_source, int residual_only, int g_cols, int x_cols, int out4, int g_stride, int sums_partials,
-                               hipStream_t st, int slab_packed = 0);
-// (slab_packed, here and below: GADAPT_NARROW_SLAB_ROW-float slab rows - the compact layer-0 launch and the narrow route's launches only)
-// ... and the source pass of the same layer (g_out != NULL)
-int gadapt_launch_bwd_source_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, const float* edge_ws, const float* dxd,
-                               const float* a, const float* p0, float* g_out, int g_cols, int out4, hipStream_t st);
+// One layer's forward launch: x_in -> x_out (NULL: head-only) and / or the [N,4] head rows x_top4; x_cols = 4: x_in is a compact [N,4] slot.
+// The narrow launches read and write [N,4] rows only: x_in, and x_top4 as their output rows (x_out unused).
+struct LayerFwd {
+    const float* x_in; float* x_out; float* x_top4; const float* a; const float* p0; const float* lp; float* alpha_out;
+    int residual_only, x_cols; const FwdExtra* extra;
+};
+// One layer's backward: the target pass (always) and - g_out != NULL - the source pass of the same layer.
+//   g_cols          g_in is the compact [N,g_cols] top gradient (0: [N,C], or [N,4] on the narrow route)
+//   x_cols = 4      x_in is the compact [N,4] layer-0 input (no g_out); g_stride: row pitch of its g_in in floats (0 = C)
+//   out4            only columns 0..3 of g_out are wanted: dxd and g_out are [N,4]
+//   sums_out / sums_sc_out (nullable)  d dt / d score_scale of the layer: one float each, added atomically, or - sums_partials - one per workgroup
+//   slab_packed     GADAPT_NARROW_SLAB_ROW-float slab rows - the compact layer-0 launch and the narrow route's launches only
+struct LayerBwd {
+    const float* x_in; const float* g_in; const float* alpha; const float* a; const float* p0; const float* lp;
+    float* edge_ws; float* dxd; float* slab; int accumulate; float* sums_out; float* sums_sc_out; float* g_out;
+    int residual_only, g_cols, x_cols, out4, g_stride, sums_partials, slab_packed;
+};
+int gadapt_launch_fwd_c(int c, const gadapt_graph* g, const LayerFwd& f, hipStream_t st);
+int gadapt_launch_bwd_target_c(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st);
+int gadapt_launch_bwd_source_c(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st);
 // the narrow route (every layer input an [N,4] slot; hidden 64 on graphs the wide forward takes: gadapt_narrow_takes_c)
 int gadapt_narrow_takes_c(const gadapt_graph* g, int c);
-// its forward layer: [N,4] slot in, [N,4] rows out in x_top4 (extra: layer-0 fields / coefficients, last-layer loss)
-int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* a, const float* p0, const float* lp, float* alpha_out,
-                               int residual_only, float* x_top4, hipStream_t st, const FwdExtra* extra);
-// up to 4 consecutive forward layers in one launch (wide::fwd_narrow_block_kernel; halo: gadapt_narrow_block_halo_host of the graph);
+int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const LayerFwd& f, hipStream_t st);
+// up to 4 consecutive forward layers in one launch (wide::fwd_narrow_block_kernel; halo: gadapt_narrow_block_halo_host of the graph).
+// first: the group's first layer, x_top4 its output slot; the next layers' slots, {dt, scale} and alpha follow at + slot_stride, + 2 and
+// + alpha_stride; x_last (nullable): the head rows of the group's last layer.
 // gadapt_narrow_block_tiles_ok_c: the batch's 512-node tiles keep the loss partials within GADAPT_LOSS_PARTIALS_MAX
 int gadapt_narrow_block_tiles_ok_c(const gadapt_graph* g);
-int gadapt_launch_fwd_narrow_block_c(int c, const gadapt_graph* g, int halo, int n_layers, const float* x_in, float* x_out0, int64_t slot_stride,
-                                     float* x_last, const float* a, const float* p0, const float* lp, float* alpha_out, int64_t alpha_stride,
-                                     hipStream_t st, const FwdExtra* extra);
-int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* alpha,
-                                      const float* a, const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, hipStream_t st,
-                                      int slab_packed = 0);
-int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* edge_ws,
-                                      const float* dxd, const float* a, const float* p0, float* g_out, hipStream_t st);
-// source pass of one layer and target pass of the layer below in one launch (gadapt_narrow_bwd.inc; gadapt_debug_set_narrow_backward_fused)
-int gadapt_launch_bwd_fused_narrow_c(int c, const gadapt_graph* g, const float* x_src, const float* g_in, int g_cols, const float* edge_in,
-                                     const float* a_src, const float* p0_src, float* g_out, const float* x_tgt, const float* alpha, const float* a_tgt, const float* lp_tgt,
-                                     float* edge_out, float* dxd, float* slab, int accumulate, int layer0, hipStream_t st, int slab_packed = 0);
+int gadapt_launch_fwd_narrow_block_c(int c, const gadapt_graph* g, const LayerFwd& first, int halo, int n_layers, int64_t slot_stride,
+                                     int64_t alpha_stride, float* x_last, hipStream_t st);
+int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st);
+int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st);
+// source pass of one layer (src) and target pass of the layer below (tgt) in one launch (gadapt_narrow_bwd.inc;
+// gadapt_debug_set_narrow_backward_fused): the launch reads src's {alpha dt, ds} pairs from edge_in and scatters tgt's into edge_out
+int gadapt_launch_bwd_fused_narrow_c(int c, const gadapt_graph* g, const LayerBwd& src, const LayerBwd& tgt, const float* edge_in, float* edge_out,
+                                     int layer0, hipStream_t st);
 int gadapt_slab_rows_c(int64_t n_nodes, int c);
 int gadapt_occupancy_fwd_c(int c);
 int gadapt_occupancy_bwd_target_c(int c);

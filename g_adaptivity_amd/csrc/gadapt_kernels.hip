@@ -130,29 +130,45 @@ extern "C" int gadapt_profile_reset(void) {
 
 #include "gadapt_small.inc"
 
+// One launch of a small per-step kernel template at hidden size c: STMT runs with CC = c as a constant.  A c the kernels are not built
+// for runs nothing (the entry points refuse it before they come here).
+#define GADAPT_FOR_C(c, ...)                                                 \
+    switch (c) {                                                             \
+        case 4:   { constexpr int CC = 4;   __VA_ARGS__; } break;            \
+        case 8:   { constexpr int CC = 8;   __VA_ARGS__; } break;            \
+        case 16:  { constexpr int CC = 16;  __VA_ARGS__; } break;            \
+        case 32:  { constexpr int CC = 32;  __VA_ARGS__; } break;            \
+        case 64:  { constexpr int CC = 64;  __VA_ARGS__; } break;            \
+        case 128: { constexpr int CC = 128; __VA_ARGS__; } break;            \
+        default: break;                                                      \
+    }
+
+// A switch of the launch sequence: 1 unless the environment variable starts with one of `others` ('0', or '0' / '2'), read at first
+// use - or whatever its setter (gadapt_debug_set_*) stored before or since.
+static int env_switch(std::atomic<int>& s, const char* name, const char* others) {
+    int v = s.load(std::memory_order_relaxed);
+    if (v < 0) {
+        const char* e = getenv(name);
+        v = (e && e[0] && strchr(others, e[0])) ? e[0] - '0' : 1;
+        s.store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
 // Block backward: the source pass writes g_out over the dxd rows it has just read (same row, same lanes: read-then-write), so a
 // layer pair touches two [N,C] buffers instead of three.  GADAPT_BWD_INPLACE=0 / gadapt_debug_set_backward_inplace(0): separate buffers.
 static std::atomic<int> g_bwd_inplace{-1};
-static bool bwd_inplace_enabled() {
-    int v = g_bwd_inplace.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = getenv("GADAPT_BWD_INPLACE");
-        v = (e && e[0] == '0') ? 0 : 1;
-        g_bwd_inplace.store(v, std::memory_order_relaxed);
-    }
-    return v == 1;
-}
+static bool bwd_inplace_enabled() { return env_switch(g_bwd_inplace, "GADAPT_BWD_INPLACE", "0") == 1; }
 extern "C" int gadapt_debug_set_backward_inplace(int on) { g_bwd_inplace.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
 
 // one layer's backward: target pass, then - when a gradient is to be passed on - the source pass
-static int launch_bwd(int c, const gadapt_graph* g, const float* x_in, const float* g_in, const float* alpha, const float* a, const float* p0,
-                      const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, float* sums_out, float* sums_sc_out, float* g_out,
-                      int residual_only, int g_cols, int x_cols, int out4, int g_stride, int sums_partials, hipStream_t st) {
-    if (int rc = gadapt_launch_bwd_target_c(c, g, x_in, g_in, alpha, a, lp, edge_ws, dxd, slab, accumulate, sums_out, sums_sc_out, g_out != nullptr,
-                                            residual_only, g_cols, x_cols, out4, g_stride, sums_partials, st)) return rc;
-    if (!g_out) return GADAPT_OK;
-    return gadapt_launch_bwd_source_c(c, g, x_in, g_in, edge_ws, dxd, a, p0, g_out, g_cols, out4, st);
+static int launch_bwd(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st) {
+    if (int rc = gadapt_launch_bwd_target_c(c, g, b, st)) return rc;
+    return b.g_out ? gadapt_launch_bwd_source_c(c, g, b, st) : GADAPT_OK;
 }
+
+// The flat parameter bucket [Wq | bq | Wk | bk] at hidden size c - and the flat gradient, laid out alike: float offsets of its parts
+struct BucketAt { int bq, wk, bk; };
+static BucketAt bucket_at(int c) { return {c * c, c * c + c, 2 * c * c + c}; }
 
 static int check_graph(const gadapt_graph* g, int c) {
     if (!g || g->n_nodes <= 0 || g->n_edges < 0 || !g->rowptr_t || !g->col_t) return fail(GADAPT_E_BADARG, "bad graph");
@@ -174,7 +190,8 @@ extern "C" int gadapt_layer_forward(const gadapt_graph* g, const float* x_in, fl
     if (int rc = check_graph(g, c)) return rc;
     if (!x_in || !x_out || !a || !p0 || !layer_params || x_in == x_out) return fail(GADAPT_E_BADARG, "layer_forward: null or aliased pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    return gadapt_launch_fwd_c(c, g, x_in, x_out, a, p0, layer_params, alpha_out, residual_only, 0, nullptr, st);
+    return gadapt_launch_fwd_c(c, g, LayerFwd{.x_in = x_in, .x_out = x_out, .a = a, .p0 = p0, .lp = layer_params, .alpha_out = alpha_out,
+                                              .residual_only = residual_only}, st);
 }
 
 extern "C" int gadapt_backward_slab_rows(int64_t n_nodes, int c) {
@@ -196,8 +213,9 @@ extern "C" int gadapt_layer_backward(const gadapt_graph* g, const float* x_in, c
     if (g_out == g_in || g_out == dxd_ws) return fail(GADAPT_E_BADARG, "layer_backward: g_out aliases an input");
     hipStream_t st = static_cast<hipStream_t>(stream);
     // {d dt, d score_scale} side by side, atomically accumulated
-    return launch_bwd(c, g, x_in, g_in, alpha, a, p0, layer_params, edge_ws, dxd_ws, slab, accumulate, sums_out, sums_out ? sums_out + 1 : nullptr, g_out,
-                      residual_only, 0, 0, 0, 0, 0, st);
+    return launch_bwd(c, g, LayerBwd{.x_in = x_in, .g_in = g_in, .alpha = alpha, .a = a, .p0 = p0, .lp = layer_params, .edge_ws = edge_ws, .dxd = dxd_ws,
+                                     .slab = slab, .accumulate = accumulate, .sums_out = sums_out, .sums_sc_out = sums_out ? sums_out + 1 : nullptr,
+                                     .g_out = g_out, .residual_only = residual_only}, st);
 }
 
 extern "C" int gadapt_layer_params_reduce(const float* partials, int n_rows, int n_layers, int want_d_scale, float* d_layer_params, void* stream) {
@@ -217,6 +235,16 @@ extern "C" int gadapt_slab_reduce(const float* slab, int n_rows, float* scratch,
     return check_launch("slab_reduce");
 }
 
+// second-level slab sums + chain rule to the Linear parameters (every workgroup repeats the second-level sums)
+static void launch_reduce2_coeffs_bwd(int c, const float* scratch, const float* wq, const float* bq, const float* wk, float* d_wq, float* d_bq,
+                                      float* d_wk, float* d_bk, hipStream_t st) {
+    const int lds = (c * (c + 1) + c) * 4;
+    int blocks = (2 * c * c + 2 * c + 1023) / 1024;             // one entry of the flat gradient per thread
+    if (blocks > 33) blocks = 33;
+    GADAPT_FOR_C(c, allow_lds(reduce2_coeffs_bwd_kernel<CC>, lds);
+                 hipLaunchKernelGGL(reduce2_coeffs_bwd_kernel<CC>, dim3(blocks), dim3(1024), lds, st, scratch, wq, bq, wk, d_wq, d_bq, d_wk, d_bk));
+}
+
 // slab -> d_wq | d_bq | d_wk | d_bk in two launches (first-level partial sums, then second level + chain rule together)
 extern "C" int gadapt_slab_reduce_coeffs_backward(const float* slab, int n_rows, float* scratch, const float* wq, const float* bq,
                                                   const float* wk, float* d_wq, float* d_bq, float* d_wk, float* d_bk, int c, void* stream,
@@ -229,13 +257,7 @@ extern "C" int gadapt_slab_reduce_coeffs_backward(const float* slab, int n_rows,
     if (lp_partials && (n_layers <= 0 || !d_layer_params)) return fail(GADAPT_E_BADARG, "slab_reduce_coeffs_backward: layer-parameter partials without a destination");
     hipLaunchKernelGGL(slab_reduce1_kernel, dim3(nbx + (lp_partials ? 2 * n_layers : 0), GADAPT_SLAB_CHUNKS), dim3(256), 0, st, slab, scratch, n_rows, row_len,
                        nbx, lp_partials, n_layers, want_d_scale, d_layer_params);
-    const int lds = (c * (c + 1) + c) * 4;
-    int blocks = (2 * c * c + 2 * c + 1023) / 1024;
-    if (blocks > 33) blocks = 33;                               // every workgroup repeats the second-level sums
-#define CASE_C(CC) case CC: allow_lds(reduce2_coeffs_bwd_kernel<CC>, lds); \
-        hipLaunchKernelGGL(reduce2_coeffs_bwd_kernel<CC>, dim3(blocks), dim3(1024), lds, st, scratch, wq, bq, wk, d_wq, d_bq, d_wk, d_bk); break;
-    switch (c) { CASE_C(4) CASE_C(8) CASE_C(16) CASE_C(32) CASE_C(64) CASE_C(128) default: break; }
-#undef CASE_C
+    launch_reduce2_coeffs_bwd(c, scratch, wq, bq, wk, d_wq, d_bq, d_wk, d_bk, st);
     return check_launch("slab_reduce_coeffs_backward");
 }
 
@@ -244,9 +266,7 @@ extern "C" int gadapt_coeffs_forward(const float* wq, const float* bq, const flo
     if (!gadapt_supported_hidden_dim(c)) return fail(GADAPT_E_BADARG, "coeffs_forward: unsupported hidden_dim");
     const int n = c * c + c;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define CASE_C(CC) case CC: hipLaunchKernelGGL(coeffs_fwd_kernel<CC>, dim3((n + 255) / 256), dim3(256), 0, st, wq, bq, wk, a_out, p0_out); break;
-    switch (c) { CASE_C(4) CASE_C(8) CASE_C(16) CASE_C(32) CASE_C(64) CASE_C(128) default: break; }
-#undef CASE_C
+    GADAPT_FOR_C(c, hipLaunchKernelGGL(coeffs_fwd_kernel<CC>, dim3((n + 255) / 256), dim3(256), 0, st, wq, bq, wk, a_out, p0_out));
     return check_launch("coeffs_fwd_kernel");
 }
 extern "C" int gadapt_coeffs_backward(const float* wq, const float* bq, const float* wk, const float* d_a, const float* d_p0,
@@ -255,9 +275,7 @@ extern "C" int gadapt_coeffs_backward(const float* wq, const float* bq, const fl
     if (!gadapt_supported_hidden_dim(c)) return fail(GADAPT_E_BADARG, "coeffs_backward: unsupported hidden_dim");
     const int n = 2 * c * c + 2 * c;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#define CASE_C(CC) case CC: hipLaunchKernelGGL(coeffs_bwd_kernel<CC>, dim3((n + 255) / 256), dim3(256), 0, st, wq, bq, wk, d_a, d_p0, d_wq, d_bq, d_wk, d_bk); break;
-    switch (c) { CASE_C(4) CASE_C(8) CASE_C(16) CASE_C(32) CASE_C(64) CASE_C(128) default: break; }
-#undef CASE_C
+    GADAPT_FOR_C(c, hipLaunchKernelGGL(coeffs_bwd_kernel<CC>, dim3((n + 255) / 256), dim3(256), 0, st, wq, bq, wk, d_a, d_p0, d_wq, d_bq, d_wk, d_bk));
     return check_launch("coeffs_bwd_kernel");
 }
 
@@ -277,12 +295,10 @@ static int launch_encode(const float* feats, int f0, const float* e1, const floa
         hipLaunchKernelGGL(encode_linear_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), p);
         return check_launch("encode_linear_kernel");
     }
+    if (!gadapt_supported_hidden_dim(cf->c)) return fail(GADAPT_E_BADARG, "encode_features_coeffs: unsupported hidden_dim");
     const int cblocks = (cf->c * cf->c + cf->c + 255) / 256;
-#define CASE_C(CC) case CC: hipLaunchKernelGGL(encode_coeffs_kernel<CC>, dim3((unsigned)blocks + cblocks), dim3(256), 0, static_cast<hipStream_t>(stream), \
-                                                      p, (int)blocks, cf->wq, cf->bq, cf->wk, cf->a, cf->p0); break;
-    switch (cf->c) { CASE_C(4) CASE_C(8) CASE_C(16) CASE_C(32) CASE_C(64) CASE_C(128)
-                     default: return fail(GADAPT_E_BADARG, "encode_features_coeffs: unsupported hidden_dim"); }
-#undef CASE_C
+    GADAPT_FOR_C(cf->c, hipLaunchKernelGGL(encode_coeffs_kernel<CC>, dim3((unsigned)blocks + cblocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                                           p, (int)blocks, cf->wq, cf->bq, cf->wk, cf->a, cf->p0));
     return check_launch("encode_coeffs_kernel");
 }
 extern "C" int gadapt_encode_linear(const float* feats, const float* w, const float* b, float* x0, int64_t n_nodes, int f, int c, void* stream) {
@@ -423,15 +439,7 @@ extern "C" int gadapt_adam_step_dev(float* param, const float* grad, float* exp_
 //   0            wide::fwd_kernel<XC = true> per layer.
 // All three are bit-identical (tests/test_gpu_narrow_forward.py, tests/test_gpu_narrow_block_forward.py).
 static std::atomic<int> g_narrow_fwd{-1};
-static int narrow_fwd_mode() {
-    int v = g_narrow_fwd.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = getenv("GADAPT_NARROW_FWD");
-        v = (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1);
-        g_narrow_fwd.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
+static int narrow_fwd_mode() { return env_switch(g_narrow_fwd, "GADAPT_NARROW_FWD", "02"); }
 extern "C" int gadapt_debug_set_narrow_forward(int on) { g_narrow_fwd.store(on == 0 ? 0 : (on == 2 ? 2 : 1), std::memory_order_relaxed); return GADAPT_OK; }
 // The halo of the block launch is a property of the graph that only the host build can know (gadapt_narrow_block_halo_host reads the
 // CSR on the host; gadapt_graph holds device pointers and its layout is frozen at ABI 9).  The caller registers it once per graph,
@@ -469,16 +477,35 @@ extern "C" int gadapt_narrow_block_halo(const gadapt_graph* g, int c) { return n
 // pair of launches per layer, bit-identical (tests/test_gpu_narrow_backward.py).  GADAPT_NARROW_BWD_FUSED=0 /
 // gadapt_debug_set_narrow_backward_fused(0): the pairs.
 static std::atomic<int> g_narrow_bwd_fused{-1};
-static bool narrow_bwd_fused_enabled() {
-    int v = g_narrow_bwd_fused.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = getenv("GADAPT_NARROW_BWD_FUSED");
-        v = (e && e[0] == '0') ? 0 : 1;
-        g_narrow_bwd_fused.store(v, std::memory_order_relaxed);
-    }
-    return v == 1;
-}
+static bool narrow_bwd_fused_enabled() { return env_switch(g_narrow_bwd_fused, "GADAPT_NARROW_BWD_FUSED", "0") == 1; }
 extern "C" int gadapt_debug_set_narrow_backward_fused(int on) { g_narrow_bwd_fused.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
+
+// A block of n_layers Euler steps as its entry points see it (built once their checks have passed): where layer l finds its input slot,
+// coefficients, {dt, scale}, alpha, slab and gradient buffer.  x_all and alpha_all are written by the forward and read by the backward;
+// the slab fields and g_ws are the backward's.
+struct Block {
+    const gadapt_graph* g; int c, n_layers;
+    float* x_all; size_t nc;                                    // slot l: [N,C] rows (compact / narrow: [N,4] rows at its start), nc = N * C
+    const float* a_all; int64_t a_stride; const float* p0_all; int64_t p0_stride;   // stride 0: one shared conv
+    const float* layer_params; float* alpha_all;                // alpha_all nullable (forward)
+    float* slab_all; int64_t slab_floats; bool shared;          // shared: one slab, accumulated over the layers; else one per layer
+    float* g_ws;                                                // two [N,C] buffers the layers alternate between
+    float* x(int l) const { return x_all + l * nc; }
+    const float* a(int l) const { return a_all + l * a_stride; }
+    const float* p0(int l) const { return p0_all + l * p0_stride; }
+    const float* lp(int l) const { return layer_params + 2 * l; }
+    float* alpha(int l) const { return alpha_all ? alpha_all + (size_t)l * g->n_edges : nullptr; }
+    float* slab(int l) const { return shared ? slab_all : slab_all + (size_t)l * slab_floats; }
+    float* g_buf(int l) const { return g_ws + ((n_layers - 1 - l) & 1) * nc; }
+};
+// The extras of a fused step for one launch of its block: the node fields and the weights (in-kernel coefficients) go to the first
+// launch, the loss to the last
+static FwdExtra slice_extra(const FwdExtra& e, bool first, bool last) {
+    FwdExtra s{};
+    if (first) { s.fs = e.fs; s.x0c = e.x0c; s.cw = e.cw; s.a_out = e.a_out; s.p0_out = e.p0_out; }
+    if (last) { s.loss = e.loss; s.n_partials_out = e.n_partials_out; }
+    return s;
+}
 static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers, const float* a, int64_t a_stride,
                          const float* p0, int64_t p0_stride, const float* layer_params, float* alpha_all, float* x_top4,
                          int c, void* stream, const FwdExtra* extra, bool narrow = false) {
@@ -487,55 +514,35 @@ static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n
     if (x0_cols != 0 && (x0_cols != 4 || n_layers < 2 || c < 8)) return fail(GADAPT_E_BADARG, "block_forward: compact x0 needs 4 columns, >= 2 layers, hidden >= 8");
     if (narrow && (x0_cols != 4 || !x_top4 || !gadapt_narrow_takes_c(g, c)))
         return fail(GADAPT_E_BADARG, "block_forward (narrow): compact x0, head rows, hidden 64 on a graph the wide forward takes (gadapt_narrow_route)");
-    const size_t nc = (size_t)g->n_nodes * c;
+    const Block b{.g = g, .c = c, .n_layers = n_layers, .x_all = x_all, .nc = (size_t)g->n_nodes * c, .a_all = a, .a_stride = a_stride, .p0_all = p0,
+                  .p0_stride = p0_stride, .layer_params = layer_params, .alpha_all = alpha_all};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // narrow route, one shared conv, a registered halo: groups of up to 4 layers, one launch each (L = 4: one, L = 6: two).  The node
-    // fields and the in-kernel coefficients go to the first group, the loss to the last; a later group reads its input slot from
-    // global memory, where the owners of the group before wrote it (the backward needs it there anyway).
+    // narrow route, one shared conv, a registered halo: groups of up to 4 layers, one launch each (L = 4: one, L = 6: two).  A later
+    // group reads its input slot from global memory, where the owners of the group before wrote it (the backward needs it there anyway).
     const int halo = (narrow && a_stride == 0 && p0_stride == 0) ? narrow_block_halo(g, c) : 0;
-    if (halo) {
-        for (int l0 = 0; l0 < n_layers; l0 += GADAPT_NARROW_BLOCK_LAYERS) {
-            const int kl = n_layers - l0 < GADAPT_NARROW_BLOCK_LAYERS ? n_layers - l0 : GADAPT_NARROW_BLOCK_LAYERS;
-            const bool last = (l0 + kl == n_layers);
-            FwdExtra ex_g{};
-            const FwdExtra* ex = nullptr;
-            if (extra) {
-                if (l0 == 0) { ex_g.fs = extra->fs; ex_g.x0c = extra->x0c; ex_g.cw = extra->cw; ex_g.a_out = extra->a_out; ex_g.p0_out = extra->p0_out; }
-                if (last) { ex_g.loss = extra->loss; ex_g.n_partials_out = extra->n_partials_out; }
-                ex = &ex_g;
-            }
-            if (int rc = gadapt_launch_fwd_narrow_block_c(c, g, halo, kl, x_all + l0 * nc, x_all + (l0 + 1) * nc, (int64_t)nc, last ? x_top4 : nullptr, a, p0,
-                                                          layer_params + 2 * l0, alpha_all ? alpha_all + (size_t)l0 * g->n_edges : nullptr, g->n_edges, st, ex))
-                return rc;
-        }
-        return GADAPT_OK;
-    }
-    for (int l = 0; l < n_layers; ++l) {
-        const bool last = (l == n_layers - 1);
-        float* alpha_l = alpha_all ? alpha_all + (size_t)l * g->n_edges : nullptr;
-        int rc;
-        // extras of a fused training step, per layer: the node fields and the weights (in-kernel coefficients) for layer 0, the loss for
-        // the last layer
+    const int per_launch = halo ? GADAPT_NARROW_BLOCK_LAYERS : 1;
+    for (int l = 0; l < n_layers; l += per_launch) {
+        const int kl = n_layers - l < per_launch ? n_layers - l : per_launch;
+        const bool last = (l + kl == n_layers);
         FwdExtra ex_l{};
-        const FwdExtra* ex = nullptr;
-        if (extra) {
-            if (l == 0) { ex_l.fs = extra->fs; ex_l.x0c = extra->x0c; }
-            if (l == 0) { ex_l.cw = extra->cw; ex_l.a_out = extra->a_out; ex_l.p0_out = extra->p0_out; }
-            if (last) { ex_l.loss = extra->loss; ex_l.n_partials_out = extra->n_partials_out; }
-            ex = &ex_l;
+        if (extra) ex_l = slice_extra(*extra, l == 0, last);
+        LayerFwd f{.x_in = b.x(l), .a = b.a(l), .p0 = b.p0(l), .lp = b.lp(l), .alpha_out = b.alpha(l), .extra = extra ? &ex_l : nullptr};
+        int rc;
+        if (halo) {
+            f.x_top4 = b.x(l + 1);
+            rc = gadapt_launch_fwd_narrow_block_c(c, g, f, halo, kl, (int64_t)b.nc, g->n_edges, last ? x_top4 : nullptr, st);
+        } else if (narrow) {                                     // [N,4] slot in, [N,4] slot out (the last layer: the head rows)
+            f.x_top4 = last ? x_top4 : b.x(l + 1);
+            f.x_cols = 4;                                        // (read by the wide kernel only: gadapt_debug_set_narrow_forward(0))
+            rc = narrow_fwd_mode() != 0 ? gadapt_launch_fwd_narrow_c(c, g, f, st) : gadapt_launch_fwd_c(c, g, f, st);
+        } else if ((l == 0 && x0_cols) || (last && x_top4)) {    // compact input and/or compact-only output
+            f.x_out = (last && x_top4) ? nullptr : b.x(l + 1);
+            f.x_top4 = last ? x_top4 : nullptr;
+            f.x_cols = l == 0 ? x0_cols : 0;
+            rc = gadapt_launch_fwd_c(c, g, f, st);
+        } else {
+            rc = gadapt_layer_forward(g, b.x(l), b.x(l + 1), b.a(l), b.p0(l), b.lp(l), b.alpha(l), 0, c, stream);
         }
-        if (narrow && narrow_fwd_mode() != 0)                    // [N,4] slot in, [N,4] slot out (the last layer: the head rows)
-            rc = gadapt_launch_fwd_narrow_c(c, g, x_all + l * nc, a + l * a_stride, p0 + l * p0_stride, layer_params + 2 * l, alpha_l, 0,
-                                            last ? x_top4 : x_all + (l + 1) * nc, st, ex);
-        else if (narrow)                                         // the same through the wide kernel (gadapt_debug_set_narrow_forward(0))
-            rc = gadapt_launch_fwd_c(c, g, x_all + l * nc, nullptr, a + l * a_stride, p0 + l * p0_stride, layer_params + 2 * l, alpha_l, 0, 4,
-                                     last ? x_top4 : x_all + (l + 1) * nc, st, ex);
-        else if ((l == 0 && x0_cols) || (last && x_top4))        // compact input and/or compact-only output
-            rc = gadapt_launch_fwd_c(c, g, x_all + l * nc, (last && x_top4) ? nullptr : x_all + (l + 1) * nc, a + l * a_stride, p0 + l * p0_stride,
-                                     layer_params + 2 * l, alpha_l, 0, l == 0 ? x0_cols : 0, last ? x_top4 : nullptr, st, ex);
-        else
-            rc = gadapt_layer_forward(g, x_all + l * nc, x_all + (l + 1) * nc, a + l * a_stride, p0 + l * p0_stride,
-                                      layer_params + 2 * l, alpha_l, 0, c, stream);
         if (rc) return rc;
     }
     return GADAPT_OK;
@@ -575,7 +582,8 @@ static int block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
     // the layers take them as given
     if (narrow && param && (narrow_block_halo(g, c) ? (g->n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE : (g->n_nodes + 255) / 256) < 64) {
         if (!a || !p0) return fail(GADAPT_E_BADARG, "block_forward_loss (narrow): param given without the coefficient buffers");
-        if (int rc = gadapt_coeffs_forward(param, param + c * c, param + c * c + c, a, p0, c, stream)) return rc;
+        const BucketAt at = bucket_at(c);
+        if (int rc = gadapt_coeffs_forward(param, param + at.bq, param + at.wk, a, p0, c, stream)) return rc;
         param = nullptr;
     }
     FwdExtra ex{FieldSrc{x_comp, f_tensor, uu_tensor, dim}, x_all,
@@ -611,7 +619,7 @@ extern "C" int gadapt_step_tail(const float* slab, int n_rows, float* scratch, f
         return fail(GADAPT_E_BADARG, "step_tail: loss partials need a count, a destination and the slab launch they ride in");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int row_len = c * c + c;
-    int blocks = (2 * c * c + 2 * c + 1023) / 1024;                // one entry of the flat gradient / bucket per thread
+    const BucketAt at = bucket_at(c);
     if (slab) {
         const int nbx = (row_len + 255) / 256;
         // (+ one workgroup: the step count for the Adam launch of this step, and the loss value)
@@ -622,25 +630,17 @@ extern "C" int gadapt_step_tail(const float* slab, int n_rows, float* scratch, f
         hipLaunchKernelGGL(step_count_kernel, dim3(1), dim3(64), 0, st, state);
     }
     if (gradient_only) {                                            // second-level sums + chain rule, as gadapt_slab_reduce_coeffs_backward
-        const int c2 = c * c, lds2 = (c * (c + 1) + c) * 4;
-#define CASE_C(CC) case CC: allow_lds(reduce2_coeffs_bwd_kernel<CC>, lds2); \
-        hipLaunchKernelGGL(reduce2_coeffs_bwd_kernel<CC>, dim3(blocks), dim3(1024), lds2, st, scratch, param, param + c2, param + c2 + c, \
-                           grad, grad + c2, grad + c2 + c, grad + 2 * c2 + c); break;
-        switch (c) { CASE_C(4) CASE_C(8) CASE_C(16) CASE_C(32) CASE_C(64) CASE_C(128) default: break; }
-#undef CASE_C
+        launch_reduce2_coeffs_bwd(c, scratch, param, param + at.bq, param + at.wk, grad, grad + at.bq, grad + at.wk, grad + at.bk, st);
         return check_launch("step_tail (gradient)");
     }
     TailArgs p{slab ? scratch : nullptr, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, grad_scale, state};
-#define CASE_C(CC) case CC: { constexpr int lds = tail_lds_floats<CC>() * 4; allow_lds(step_tail_kernel<CC>, lds); \
-        hipLaunchKernelGGL(step_tail_kernel<CC>, dim3(tail_blocks<CC>()), dim3(1024), lds, st, p); } break;
-    switch (c) { CASE_C(4) CASE_C(8) CASE_C(16) CASE_C(32) CASE_C(64) CASE_C(128) default: break; }
-#undef CASE_C
+    GADAPT_FOR_C(c, constexpr int lds = tail_lds_floats<CC>() * 4; allow_lds(step_tail_kernel<CC>, lds);
+                 hipLaunchKernelGGL(step_tail_kernel<CC>, dim3(tail_blocks<CC>()), dim3(1024), lds, st, p));
     if (int rc = check_launch("step_tail")) return rc;
     // the composite coefficients of the UPDATED weights for the next step's forward - unless that forward computes them itself
     // (a_out = p0_out = NULL: gadapt_forward_computes_coeffs)
     if (!a_out) return GADAPT_OK;
-    const int c2 = c * c;
-    return gadapt_coeffs_forward(param, param + c2, param + c2 + c, a_out, p0_out, c, stream);
+    return gadapt_coeffs_forward(param, param + at.bq, param + at.wk, a_out, p0_out, c, stream);
 }
 
 // The narrow route's tail over the PACKED slab (gadapt_block_backward_narrow_packed) as ONE launch, hidden 64: step_tail_narrow_kernel.
@@ -663,8 +663,8 @@ extern "C" int gadapt_step_tail_narrow(const float* slab, int n_rows, float* scr
     hipLaunchKernelGGL(step_tail_narrow_kernel, dim3(loss_partials ? 2 : 1), dim3(1024), 0, st, p);
     if (int rc = check_launch("step_tail_narrow")) return rc;
     if (gradient_only || !a_out) return GADAPT_OK;
-    const int c2 = c * c;
-    return gadapt_coeffs_forward(param, param + c2, param + c2 + c, a_out, p0_out, c, stream);
+    const BucketAt at = bucket_at(c);
+    return gadapt_coeffs_forward(param, param + at.bq, param + at.wk, a_out, p0_out, c, stream);
 }
 
 extern "C" int gadapt_block_backward(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top, int g_top_cols, int n_layers,
@@ -676,35 +676,37 @@ extern "C" int gadapt_block_backward(const gadapt_graph* g, const float* x_all, 
         return fail(GADAPT_E_BADARG, "block_backward: bad argument");
     if (x0_cols != 0 && (x0_cols != 4 || n_layers < 2 || c < 8 || d_x0))
         return fail(GADAPT_E_BADARG, "block_backward: compact x0 needs 4 columns, >= 2 layers, hidden >= 8, no d_x0");
-    const size_t nc = (size_t)g->n_nodes * c;
-    const bool shared = (a_stride == 0);
     const int64_t slab_floats = gadapt_backward_slab_floats(g->n_nodes, c);
     if (slab_floats < 0) return (int)slab_floats;
     const int slab_rows = gadapt_backward_slab_rows(g->n_nodes, c);
+    // (x_all and alpha_all: read only)
+    const Block b{.g = g, .c = c, .n_layers = n_layers, .x_all = const_cast<float*>(x_all), .nc = (size_t)g->n_nodes * c, .a_all = a, .a_stride = a_stride,
+                  .p0_all = p0, .p0_stride = p0_stride, .layer_params = layer_params, .alpha_all = const_cast<float*>(alpha_all), .slab_all = slab,
+                  .slab_floats = slab_floats, .shared = (a_stride == 0), .g_ws = g_ws};
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    // Layer 1 above a compact layer 0: that layer's backward contracts over the four live columns of its input, so all it
+    // reads of this layer's g_out are columns 0..3 - this layer runs the 4-column pair (dxd and g_out as [N,4]).
+    // (not for a two-layer block with learnable steps / temperature: layer 1 is then also the top layer, and the SUMS + GC + D4
+    // instantiation spills at hidden 32 - that corner keeps the dense pair)
+    const bool pair4 = x0_cols && c >= 8 && n_layers >= 2 && !(n_layers == 2 && g_top_cols > 0 && d_layer_params);
     const float* g_cur = g_top;
     for (int l = n_layers - 1; l >= 0; --l) {
-        float* g_next = (l == 0) ? d_x0 : g_ws + ((n_layers - 1 - l) & 1) * nc;
-        float* slab_l = shared ? slab : slab + (size_t)l * slab_floats;
-        const int accumulate = (shared && l != n_layers - 1) ? 1 : 0;
-        // per-workgroup partials [2][L][G] (G = gadapt_backward_slab_rows: the grid of every target-pass launch), d dt block first
-        float* d_dt = d_layer_params ? d_layer_params + (size_t)l * slab_rows : nullptr;
-        float* d_sc = (d_layer_params && want_d_scale) ? d_layer_params + ((size_t)n_layers + l) * slab_rows : nullptr;
-        const hipStream_t st = static_cast<hipStream_t>(stream);
-        const int g_cols = (l == n_layers - 1) ? g_top_cols : 0, x_cols = (l == 0) ? x0_cols : 0;
+        float* g_next = (l == 0) ? d_x0 : b.g_buf(l);
         if (!g->tpos_s || (g_next && (!g->rowptr_s || !g->col_s))) return fail(GADAPT_E_BADARG, "block_backward: source CSR missing");
-        // compact upstream gradient [N,g_top_cols] (top layer) / compact layer-0 input [N,4] (no d x0: checked in launch_bwd).
-        // Layer 1 above a compact layer 0: that layer's backward contracts over the four live columns of its input, so all it
-        // reads of this layer's g_out are columns 0..3 - this layer runs the 4-column pair (dxd and g_out as [N,4]).
-        // (not for a two-layer block with learnable steps / temperature: layer 1 is then also the top layer, and the SUMS + GC + D4
-        // instantiation spills at hidden 32 - that corner keeps the dense pair)
-        const bool pair4 = x0_cols && c >= 8 && n_layers >= 2 && !(n_layers == 2 && g_top_cols > 0 && d_layer_params);
         const int out4 = (pair4 && l == 1) ? 1 : 0;
-        const int g_stride = (pair4 && l == 0) ? 4 : 0;
         // dense layers that hand their result to the next layer of the block: dxd lives in the g_out buffer (see bwd_inplace_enabled)
         const bool inplace = bwd_inplace_enabled() && l > 0 && g_next && !out4;
-        int rc = launch_bwd(c, g, x_all + l * nc, g_cur, alpha_all + (size_t)l * g->n_edges, a + l * a_stride, p0 + l * p0_stride, layer_params + 2 * l,
-                            edge_ws, inplace ? g_next : dxd_ws, slab_l, accumulate, d_dt, d_sc, g_next, 0, g_cols, x_cols, out4, g_stride, 1, st);
-        if (rc) return rc;
+        const LayerBwd lb{
+            .x_in = b.x(l), .g_in = g_cur, .alpha = b.alpha(l), .a = b.a(l), .p0 = b.p0(l), .lp = b.lp(l), .edge_ws = edge_ws,
+            .dxd = inplace ? g_next : dxd_ws, .slab = b.slab(l), .accumulate = (b.shared && l != n_layers - 1) ? 1 : 0,
+            // per-workgroup partials [2][L][G] (G = gadapt_backward_slab_rows: the grid of every target-pass launch), d dt block first
+            .sums_out = d_layer_params ? d_layer_params + (size_t)l * slab_rows : nullptr,
+            .sums_sc_out = (d_layer_params && want_d_scale) ? d_layer_params + ((size_t)n_layers + l) * slab_rows : nullptr,
+            .g_out = g_next,
+            // compact upstream gradient [N,g_top_cols] (top layer) / compact layer-0 input [N,4] (no d x0: checked by the target launch)
+            .g_cols = (l == n_layers - 1) ? g_top_cols : 0, .x_cols = (l == 0) ? x0_cols : 0, .out4 = out4,
+            .g_stride = (pair4 && l == 0) ? 4 : 0, .sums_partials = 1};
+        if (int rc = launch_bwd(c, g, lb, st)) return rc;
         g_cur = g_next;
     }
     return GADAPT_OK;
@@ -733,45 +735,42 @@ static int block_backward_narrow(const gadapt_graph* g, const float* x_all, int 
         return fail(GADAPT_E_BADARG, "block_backward (narrow): compact x0, compact top gradient, no d_x0, fixed steps and temperature, "
                                      "hidden 64 on a graph the wide forward takes (gadapt_narrow_route)");
     if (packed && (a_stride != 0 || p0_stride != 0)) return fail(GADAPT_E_BADARG, "block_backward (narrow, packed slab): one shared conv (a_stride = p0_stride = 0)");
-    const size_t nc = (size_t)g->n_nodes * c;
-    const bool shared = (a_stride == 0);
     const int64_t slab_floats = gadapt_backward_slab_floats(g->n_nodes, c);
     if (slab_floats < 0) return (int)slab_floats;
+    // (x_all and alpha_all: read only)
+    const Block b{.g = g, .c = c, .n_layers = n_layers, .x_all = const_cast<float*>(x_all), .nc = (size_t)g->n_nodes * c, .a_all = a, .a_stride = a_stride,
+                  .p0_all = p0, .p0_stride = p0_stride, .layer_params = layer_params, .alpha_all = const_cast<float*>(alpha_all), .slab_all = slab,
+                  .slab_floats = slab_floats, .shared = (a_stride == 0), .g_ws = g_ws};
     const hipStream_t st = static_cast<hipStream_t>(stream);
+    // layer l of the route: [N,4] rows; g_in: the top gradient [N,g_top_cols] at the top layer, the [N,4] result of the layer above below it
+    auto layer = [&](int l, const float* g_in, float* edge, int accumulate) {
+        return LayerBwd{.x_in = b.x(l), .g_in = g_in, .alpha = b.alpha(l), .a = b.a(l), .p0 = b.p0(l), .lp = b.lp(l), .edge_ws = edge, .dxd = dxd_ws,
+                        .slab = b.slab(l), .accumulate = accumulate, .g_out = l > 0 ? b.g_buf(l) : nullptr,
+                        .g_cols = (l == n_layers - 1) ? g_top_cols : 0, .slab_packed = packed};
+    };
     const float* g_cur = g_top;
-    int g_cols = g_top_cols;
     if (narrow_bwd_fused_enabled() && g->ell_s && g->rowptr_s && g->col_s && 2 * (int64_t)g->n_edges <= (int64_t)(c - 4) * g->n_nodes) {
         float* edge_buf[2] = {edge_ws, dxd_ws + 4 * (size_t)g->n_nodes};
         int l = n_layers - 1, eb = 0;
-        int rc = gadapt_launch_bwd_target_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, alpha_all + (size_t)l * g->n_edges, a + l * a_stride,
-                                                   layer_params + 2 * l, edge_buf[eb], dxd_ws, shared ? slab : slab + (size_t)l * slab_floats, 0, st, packed);
+        int rc = gadapt_launch_bwd_target_narrow_c(c, g, layer(l, g_cur, edge_buf[eb], 0), st);
         for (; !rc && l >= 1; --l, eb ^= 1) {                   // source pass of layer l + target pass of layer l-1
-            float* g_next = g_ws + ((n_layers - 1 - l) & 1) * nc;
-            rc = gadapt_launch_bwd_fused_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, edge_buf[eb], a + l * a_stride, p0 + l * p0_stride, g_next,
-                                                  x_all + (l - 1) * nc, alpha_all + (size_t)(l - 1) * g->n_edges, a + (l - 1) * a_stride,
-                                                  layer_params + 2 * (l - 1), edge_buf[eb ^ 1], dxd_ws,
-                                                  shared ? slab : slab + (size_t)(l - 1) * slab_floats, shared ? 1 : 0, l == 1 ? 1 : 0, st, packed);
-            g_cur = g_next;
-            g_cols = 0;
+            const LayerBwd src = layer(l, g_cur, edge_buf[eb], 0);
+            rc = gadapt_launch_bwd_fused_narrow_c(c, g, src, layer(l - 1, nullptr, edge_buf[eb ^ 1], b.shared ? 1 : 0), edge_buf[eb], edge_buf[eb ^ 1],
+                                                  l == 1 ? 1 : 0, st);
+            g_cur = src.g_out;
         }
         return rc;
     }
     for (int l = n_layers - 1; l >= 0; --l) {
-        float* slab_l = shared ? slab : slab + (size_t)l * slab_floats;
-        const int accumulate = (shared && l != n_layers - 1) ? 1 : 0;
-        const float* alpha_l = alpha_all + (size_t)l * g->n_edges;
+        LayerBwd lb = layer(l, g_cur, edge_ws, (b.shared && l != n_layers - 1) ? 1 : 0);
         int rc;
-        if (l == 0) {                                           // g_cur: layer 1's [N,4] result
-            rc = gadapt_launch_bwd_target_c(c, g, x_all, g_cur, alpha_l, a, layer_params, edge_ws, dxd_ws, slab_l, accumulate, nullptr, nullptr, 0, 0,
-                                            0, 4, 0, 4, 1, st, packed);
+        if (l == 0) {                                           // g_cur: layer 1's [N,4] result; the compact layer-0 launch of the tiled route
+            lb.x_cols = 4; lb.g_stride = 4; lb.sums_partials = 1;
+            rc = gadapt_launch_bwd_target_c(c, g, lb, st);
         } else {
-            float* g_next = g_ws + ((n_layers - 1 - l) & 1) * nc;
-            rc = gadapt_launch_bwd_target_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, alpha_l, a + l * a_stride, layer_params + 2 * l, edge_ws,
-                                                   dxd_ws, slab_l, accumulate, st, packed);
-            if (!rc) rc = gadapt_launch_bwd_source_narrow_c(c, g, x_all + l * nc, g_cur, g_cols, edge_ws, dxd_ws, a + l * a_stride, p0 + l * p0_stride,
-                                                            g_next, st);
-            g_cur = g_next;
-            g_cols = 0;
+            rc = gadapt_launch_bwd_target_narrow_c(c, g, lb, st);
+            if (!rc) rc = gadapt_launch_bwd_source_narrow_c(c, g, lb, st);
+            g_cur = lb.g_out;
         }
         if (rc) return rc;
     }

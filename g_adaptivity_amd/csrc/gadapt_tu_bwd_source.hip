@@ -12,27 +12,21 @@
 // neighbouring tile's step.  128-wide meshes (no tile windowed): 61 -> 80 us.
 constexpr bool source_window(int c) { return c == 128; }
 
-template <int C> static int launch_bwd_source(const gadapt_graph* g, const float* x_in, const float* g_in, const float* edge_ws, const float* dxd,
-                                              const float* a, const float* p0, float* g_out, int g_cols, int out4, hipStream_t st) {
+template <int C> static int launch_bwd_source(const gadapt_graph* g, const LayerBwd& b, hipStream_t st) {
     using K = Cfg<C>;
-    const int n_tiles = tiles_for<C>(g->n_nodes);
-    BwdSArgs ps{x_in, g_in, edge_ws, dxd, a, p0, g->rowptr_s, g->col_s, meta_for<K::TM>(g->meta_s), g_out, g->n_nodes, n_tiles, g->n_edges, nullptr, g_cols};
+    const int n_tiles = tiles_for<C>(g->n_nodes), g_cols = b.g_cols, out4 = b.out4;
+    BwdSArgs ps{b.x_in, b.g_in, b.edge_ws, b.dxd, b.a, b.p0, g->rowptr_s, g->col_s, meta_for<K::TM>(g->meta_s), b.g_out, g->n_nodes, n_tiles, g->n_edges, nullptr, g_cols};
 #ifdef GADAPT_STAMPS
     ps.stamps = g_stamp_buf ? g_stamp_buf + 2 * 1024 * 32 : nullptr;
 #endif
     ProfScope prof(2, st, (g_cols ? 1 : 0) | (out4 ? 8 : 0));
+    auto go = [&](auto kern, dim3 grid, int lds) { allow_lds(kern, lds); hipLaunchKernelGGL(kern, grid, dim3(K::NT), lds, st, ps); };
     if constexpr (C >= 8) {
         if (out4) {
             constexpr int lds_4 = K::lds_bytes(2, 0);
             constexpr int res4 = (C > 64 || K::NT != 256) ? 512 : 256 * GADAPT_WAVES_BWD_S4;   // resident workgroups: waves per SIMD x 256 CUs
             const dim3 grid4(grid_for(n_tiles, res4));
-            if (g_cols) {
-                allow_lds(grand_bwd_source4_kernel<C, true>, lds_4);
-                hipLaunchKernelGGL((grand_bwd_source4_kernel<C, true>), grid4, dim3(K::NT), lds_4, st, ps);
-            } else {
-                allow_lds(grand_bwd_source4_kernel<C, false>, lds_4);
-                hipLaunchKernelGGL((grand_bwd_source4_kernel<C, false>), grid4, dim3(K::NT), lds_4, st, ps);
-            }
+            if (g_cols) go(grand_bwd_source4_kernel<C, true>, grid4, lds_4); else go(grand_bwd_source4_kernel<C, false>, grid4, lds_4);
             return check_launch("grand_bwd_source4_kernel");
         }
     }
@@ -43,31 +37,16 @@ template <int C> static int launch_bwd_source(const gadapt_graph* g, const float
         // the slabs would be staged for nothing
         if (g->wide_deg_s > 0) {
             constexpr int lds_sw = K::lds_bytes(2, 4, 1);       // window (3 slabs) + y tile; ext = ring offsets
-            if (g_cols) {
-                allow_lds(grand_bwd_source_kernel<C, true, true>, lds_sw);
-                hipLaunchKernelGGL((grand_bwd_source_kernel<C, true, true>), grid, dim3(K::NT), lds_sw, st, ps);
-            } else {
-                allow_lds(grand_bwd_source_kernel<C, false, true>, lds_sw);
-                hipLaunchKernelGGL((grand_bwd_source_kernel<C, false, true>), grid, dim3(K::NT), lds_sw, st, ps);
-            }
+            if (g_cols) go(grand_bwd_source_kernel<C, true, true>, grid, lds_sw); else go(grand_bwd_source_kernel<C, false, true>, grid, lds_sw);
             return check_launch("grand_bwd_source_kernel");
         }
     }
     constexpr int lds_s = K::lds_bytes(2);
-    if (g_cols) {
-        allow_lds(grand_bwd_source_kernel<C, true>, lds_s);
-        hipLaunchKernelGGL((grand_bwd_source_kernel<C, true>), grid, dim3(K::NT), lds_s, st, ps);
-    } else {
-        allow_lds(grand_bwd_source_kernel<C>, lds_s);
-        hipLaunchKernelGGL(grand_bwd_source_kernel<C>, grid, dim3(K::NT), lds_s, st, ps);
-    }
+    if (g_cols) go(grand_bwd_source_kernel<C, true>, grid, lds_s); else go(grand_bwd_source_kernel<C>, grid, lds_s);
     return check_launch("grand_bwd_source_kernel");
 }
 
-int gadapt_launch_bwd_source_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, const float* edge_ws, const float* dxd,
-                               const float* a, const float* p0, float* g_out, int g_cols, int out4, hipStream_t st) {
-    GADAPT_DISPATCH_C(c, launch_bwd_source<CC>(g, x_in, g_in, edge_ws, dxd, a, p0, g_out, g_cols, out4, st));
-}
+int gadapt_launch_bwd_source_c(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st) { GADAPT_DISPATCH_C(c, launch_bwd_source<CC>(g, b, st)); }
 
 template <int C> static int occupancy_bwd_source() {
     using K = Cfg<C>;
@@ -81,10 +60,9 @@ template <int C> static int occupancy_bwd_source() {
 int gadapt_occupancy_bwd_source_c(int c) { GADAPT_DISPATCH_C(c, occupancy_bwd_source<CC>()); }
 
 // narrow route (grand_bwd_source_narrow_kernel): x_in, dxd, g_out [N,4]; g_in [N,4] or the compact [N,g_cols] top gradient
-int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* edge_ws,
-                                      const float* dxd, const float* a, const float* p0, float* g_out, hipStream_t st) {
-    if (c != 64 || !g->ell_s || !g->rowptr_s || !g->col_s || g_cols < 0 || g_cols > 4) return fail(GADAPT_E_BADARG, "narrow source pass: hidden 64, ELL graph, 0..4 g columns");
-    BwdSArgs ps{x_in, g_in, edge_ws, dxd, a, p0, g->rowptr_s, g->col_s, nullptr, g_out, g->n_nodes, 0, g->n_edges, nullptr, g_cols};
+int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st) {
+    if (c != 64 || !g->ell_s || !g->rowptr_s || !g->col_s || b.g_cols < 0 || b.g_cols > 4) return fail(GADAPT_E_BADARG, "narrow source pass: hidden 64, ELL graph, 0..4 g columns");
+    BwdSArgs ps{b.x_in, b.g_in, b.edge_ws, b.dxd, b.a, b.p0, g->rowptr_s, g->col_s, nullptr, b.g_out, g->n_nodes, 0, g->n_edges, nullptr, b.g_cols};
     ps.c = c;
     ps.ell = g->ell_s;
     const int grid = (int)std::min<int64_t>(((int64_t)g->n_nodes + 255) / 256, 4096);

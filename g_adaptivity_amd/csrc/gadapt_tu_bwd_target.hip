@@ -5,37 +5,44 @@
 #include "gadapt_bwd_target.inc"
 #include "gadapt_narrow_bwd.inc"
 
-// out4: only columns 0..3 of g_out are wanted (dxd is [N,4]: D4 target pass, then grand_bwd_source4_kernel).
-// g_stride: row pitch of g_in in floats for the compact-input launch (0 = C).
-template <int C> static int launch_bwd_target(const gadapt_graph* g, const float* x_in, const float* g_in, const float* alpha, const float* a,
-                                              const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, float* sums_out,
-                                              float* sums_sc_out, int want_source, int residual_only, int g_cols, int x_cols, int out4,
-                                              int g_stride, int sums_partials, hipStream_t st, int slab_packed) {
+// The slab holds one row per workgroup of a target pass: every target launch of a block at hidden size C uses this grid, so every
+// row is visited (gadapt_slab_rows_c)
+template <int C> static int target_grid(int64_t n_nodes) { return grid_for(tiles_for<C>(n_nodes), resident_blocks_bwd_t<C>(GADAPT_BWD_T_MAX_BLOCKS)); }
+int gadapt_slab_rows_c(int64_t n_nodes, int c) { GADAPT_DISPATCH_C(c, target_grid<CC>(n_nodes)); }
+
+// The kernel arguments of a target pass of layer b at hidden size C.  The tiled kernels read the tile metadata (meta) and, compact,
+// a g_in of row pitch b.g_stride (0 = C); the one-node-per-lane kernels (compact layer 0, narrow route) read the ELL table.
+template <int C> static BwdTArgs target_args(const gadapt_graph* g, const LayerBwd& b, int n_tiles, bool tiled) {
+    BwdTArgs pt{b.x_in, b.g_in, b.alpha, b.a, b.lp, g->rowptr_t, g->col_t, g->tpos_s, tiled ? meta_for<Cfg<C>::TM>(g->meta_t) : nullptr,
+                reinterpret_cast<float2*>(b.edge_ws), b.dxd, b.slab, b.sums_out, g->n_nodes, n_tiles, b.accumulate, b.residual_only, g->n_edges, nullptr, b.g_cols};
+    pt.sums_sc_out = b.sums_sc_out;
+    pt.c = C;
+    pt.g_stride = b.g_stride ? b.g_stride : C;
+    pt.sums_partials = b.sums_partials;
+    pt.slab_packed = b.slab_packed ? 1 : 0;
+    return pt;
+}
+
+template <int C> static int launch_bwd_target(const gadapt_graph* g, const LayerBwd& b, hipStream_t st) {
     using K = Cfg<C>;
-    const int n_tiles = tiles_for<C>(g->n_nodes);
+    const int g_cols = b.g_cols, x_cols = b.x_cols, out4 = b.out4, want_source = b.g_out != nullptr;
+    float* const sums_out = b.sums_out;
     if (g_cols < 0 || g_cols > 4) return fail(GADAPT_E_BADARG, "compact upstream gradient: 1..4 columns");
     if ((x_cols != 0 && x_cols != 4) || (x_cols && (g_cols || want_source)))
         return fail(GADAPT_E_BADARG, "compact layer input: 4 columns, layer 0 of a block of >= 2 layers, no d x0");
-    if (x_cols && residual_only) return fail(GADAPT_E_BADARG, "compact layer input: Euler-step layers only");
-    if (slab_packed && (!x_cols || sums_out)) return fail(GADAPT_E_BADARG, "packed slab rows: the compact layer-0 launch with fixed steps and temperature");
-    if (out4 && (!want_source || x_cols || residual_only || C < 8 || (g_cols && sums_out)))
+    if (x_cols && b.residual_only) return fail(GADAPT_E_BADARG, "compact layer input: Euler-step layers only");
+    if (b.slab_packed && (!x_cols || sums_out)) return fail(GADAPT_E_BADARG, "packed slab rows: the compact layer-0 launch with fixed steps and temperature");
+    if (out4 && (!want_source || x_cols || b.residual_only || C < 8 || (g_cols && sums_out)))
         return fail(GADAPT_E_BADARG, "4-column backward: a layer with a gradient to pass on, hidden >= 8, not compact-g with d dt / d scale");
-    BwdTArgs pt{x_in, g_in, alpha, a, lp, g->rowptr_t, g->col_t, g->tpos_s, meta_for<K::TM>(g->meta_t), reinterpret_cast<float2*>(edge_ws), dxd, slab, sums_out,
-                g->n_nodes, n_tiles, accumulate, residual_only, g->n_edges, nullptr, g_cols};
-    pt.sums_sc_out = sums_sc_out;
-    pt.c = C;
-    pt.g_stride = g_stride ? g_stride : C;
-    pt.sums_partials = sums_partials;
-    pt.slab_packed = slab_packed ? 1 : 0;
+    BwdTArgs pt = target_args<C>(g, b, tiles_for<C>(g->n_nodes), true);
 #ifdef GADAPT_STAMPS
     pt.stamps = g_stamp_buf ? g_stamp_buf + 1024 * 32 : nullptr;
 #endif
-    // the slab holds one row per workgroup of the target pass: every launch of a block uses this grid, so every row is visited
-    const dim3 grid(grid_for(n_tiles, resident_blocks_bwd_t<C>(GADAPT_BWD_T_MAX_BLOCKS)));
+    const dim3 grid(target_grid<C>(g->n_nodes));
     if (x_cols) {                                                // layer 0 on the compact [N,4] input: one node per lane
         ProfScope prof(1, st, 2);
         pt.ell = g->ell_t;
-        if (sums_out && sums_sc_out) hipLaunchKernelGGL((grand_bwd_target_compact_kernel<2>), grid, dim3(256), 0, st, pt);
+        if (sums_out && pt.sums_sc_out) hipLaunchKernelGGL((grand_bwd_target_compact_kernel<2>), grid, dim3(256), 0, st, pt);
         else if (sums_out) hipLaunchKernelGGL((grand_bwd_target_compact_kernel<1>), grid, dim3(256), 0, st, pt);
         else if (pt.ell) hipLaunchKernelGGL((grand_bwd_target_compact_kernel<0, true>), grid, dim3(256), 0, st, pt);
         else hipLaunchKernelGGL((grand_bwd_target_compact_kernel<0>), grid, dim3(256), 0, st, pt);
@@ -59,21 +66,11 @@ template <int C> static int launch_bwd_target(const gadapt_graph* g, const float
             go(grand_bwd_target_kernel<C, S>);
         }
     };
-    if (sums_out && sums_sc_out) pick(IntTag<2>{}); else if (sums_out) pick(IntTag<1>{}); else pick(IntTag<0>{});
+    if (sums_out && pt.sums_sc_out) pick(IntTag<2>{}); else if (sums_out) pick(IntTag<1>{}); else pick(IntTag<0>{});
     return check_launch("grand_bwd_target_kernel");
 }
 
-int gadapt_launch_bwd_target_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, const float* alpha, const float* a,
-                               const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, float* sums_out, float* sums_sc_out,
-                               int want_source, int residual_only, int g_cols, int x_cols, int out4, int g_stride, int sums_partials,
-                               hipStream_t st, int slab_packed) {
-    GADAPT_DISPATCH_C(c, launch_bwd_target<CC>(g, x_in, g_in, alpha, a, lp, edge_ws, dxd, slab, accumulate, sums_out, sums_sc_out, want_source,
-                                               residual_only, g_cols, x_cols, out4, g_stride, sums_partials, st, slab_packed));
-}
-
-int gadapt_slab_rows_c(int64_t n_nodes, int c) {
-    GADAPT_DISPATCH_C(c, grid_for(tiles_for<CC>(n_nodes), resident_blocks_bwd_t<CC>(GADAPT_BWD_T_MAX_BLOCKS)));
-}
+int gadapt_launch_bwd_target_c(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st) { GADAPT_DISPATCH_C(c, launch_bwd_target<CC>(g, b, st)); }
 
 template <int C> static int occupancy_bwd_target() {
     int n = -1;
@@ -82,48 +79,45 @@ template <int C> static int occupancy_bwd_target() {
 }
 int gadapt_occupancy_bwd_target_c(int c) { GADAPT_DISPATCH_C(c, occupancy_bwd_target<CC>()); }
 
+// The narrow route's arguments of a target pass: [N,4] rows of pitch 4, no d dt / d scale, Euler-step layers, the ELL table
+static BwdTArgs narrow_target_args(const gadapt_graph* g, const LayerBwd& b) {
+    LayerBwd n = b;
+    n.sums_out = n.sums_sc_out = nullptr; n.residual_only = 0; n.g_stride = 4; n.sums_partials = 0;
+    BwdTArgs pt = target_args<64>(g, n, tiles_for<64>(g->n_nodes), false);
+    pt.ell = g->ell_t;
+    return pt;
+}
+
 // narrow route, layers 1..L-1 (grand_bwd_target_narrow_kernel): x_in, dxd [N,4]; g_in [N,4] or the compact [N,g_cols] top gradient.  The
 // slab row layout and grid of every other target-pass launch of the block (hidden c), so the layer-0 launch accumulates onto these rows.
-int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const float* x_in, const float* g_in, int g_cols, const float* alpha,
-                                      const float* a, const float* lp, float* edge_ws, float* dxd, float* slab, int accumulate, hipStream_t st,
-                                      int slab_packed) {
-    if (c != 64 || !g->ell_t || !g->tpos_s || g_cols < 0 || g_cols > 4) return fail(GADAPT_E_BADARG, "narrow target pass: hidden 64, ELL graph, 0..4 g columns");
-    BwdTArgs pt{x_in, g_in, alpha, a, lp, g->rowptr_t, g->col_t, g->tpos_s, nullptr, reinterpret_cast<float2*>(edge_ws), dxd, slab, nullptr,
-                g->n_nodes, tiles_for<64>(g->n_nodes), accumulate, 0, g->n_edges, nullptr, g_cols};
-    pt.c = c;
-    pt.g_stride = 4;
-    pt.ell = g->ell_t;
-    pt.slab_packed = slab_packed ? 1 : 0;
-    const dim3 grid(grid_for(pt.n_tiles, resident_blocks_bwd_t<64>(GADAPT_BWD_T_MAX_BLOCKS)));
-    ProfScope prof(1, st, g_cols ? 3 : 2);                     // compact input (and compact upstream gradient at the top layer)
-    hipLaunchKernelGGL(grand_bwd_target_narrow_kernel, grid, dim3(256), 0, st, pt);
+int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st) {
+    if (c != 64 || !g->ell_t || !g->tpos_s || b.g_cols < 0 || b.g_cols > 4) return fail(GADAPT_E_BADARG, "narrow target pass: hidden 64, ELL graph, 0..4 g columns");
+    const BwdTArgs pt = narrow_target_args(g, b);
+    ProfScope prof(1, st, b.g_cols ? 3 : 2);                   // compact input (and compact upstream gradient at the top layer)
+    hipLaunchKernelGGL(grand_bwd_target_narrow_kernel, dim3(target_grid<64>(g->n_nodes)), dim3(256), 0, st, pt);
     return check_launch("grand_bwd_target_narrow_kernel");
 }
 
-// narrow route, fused launch (grand_bwd_target_fused_narrow_kernel, gadapt_narrow_bwd.inc): the source pass of layer l (x_src, g_in [N,4]
-// or - g_cols > 0 - the compact [N,g_cols] top gradient, the pairs in edge_in, a_src / p0_src; its dxd row is read from dxd) and, in the same lane, the target pass of layer l-1 (x_tgt, alpha,
-// a_tgt, lp_tgt) on the result.  layer0 = 0: g_out [N,4], dxd and the pairs of layer l-1 (edge_out, NOT edge_in: lanes of one launch
-// read one and scatter into the other) are written; layer0 = 1 (l-1 = 0): slab partials only.  Grid and slab rows of every target launch.
-int gadapt_launch_bwd_fused_narrow_c(int c, const gadapt_graph* g, const float* x_src, const float* g_in, int g_cols, const float* edge_in,
-                                     const float* a_src, const float* p0_src, float* g_out, const float* x_tgt, const float* alpha, const float* a_tgt, const float* lp_tgt,
-                                     float* edge_out, float* dxd, float* slab, int accumulate, int layer0, hipStream_t st, int slab_packed) {
-    if (c != 64 || !g->ell_t || !g->tpos_s || !g->ell_s || !g->rowptr_s || !g->col_s || g_cols < 0 || g_cols > 4)
+// narrow route, fused launch (grand_bwd_target_fused_narrow_kernel, gadapt_narrow_bwd.inc): the source pass of layer l (src: x_in, g_in [N,4]
+// or - g_cols > 0 - the compact [N,g_cols] top gradient, a / p0, g_out; the pairs in edge_in; its dxd row is read from tgt.dxd) and, in the
+// same lane, the target pass of layer l-1 (tgt: x_in, alpha, a, lp, dxd, slab) on the result.  layer0 = 0: g_out [N,4], dxd and the pairs of
+// layer l-1 (edge_out, NOT edge_in: lanes of one launch read one and scatter into the other) are written; layer0 = 1 (l-1 = 0): slab
+// partials only.  Grid and slab rows of every target launch.
+int gadapt_launch_bwd_fused_narrow_c(int c, const gadapt_graph* g, const LayerBwd& src, const LayerBwd& tgt, const float* edge_in, float* edge_out,
+                                     int layer0, hipStream_t st) {
+    if (c != 64 || !g->ell_t || !g->tpos_s || !g->ell_s || !g->rowptr_s || !g->col_s || src.g_cols < 0 || src.g_cols > 4)
         return fail(GADAPT_E_BADARG, "fused narrow backward: hidden 64, ELL graph, 0..4 g columns");
-    if (!layer0 && (!g_out || !edge_out || edge_out == edge_in)) return fail(GADAPT_E_BADARG, "fused narrow backward: a second edge buffer and g_out above layer 0");
+    if (!layer0 && (!src.g_out || !edge_out || edge_out == edge_in)) return fail(GADAPT_E_BADARG, "fused narrow backward: a second edge buffer and g_out above layer 0");
+    LayerBwd t = tgt;
+    t.g_in = nullptr; t.edge_ws = edge_out; t.g_cols = 0;
     BwdFusedNarrowArgs pf{};
-    pf.t = BwdTArgs{x_tgt, nullptr, alpha, a_tgt, lp_tgt, g->rowptr_t, g->col_t, g->tpos_s, nullptr, reinterpret_cast<float2*>(edge_out), dxd, slab, nullptr,
-                    g->n_nodes, tiles_for<64>(g->n_nodes), accumulate, 0, g->n_edges, nullptr, 0};
-    pf.t.c = c;
-    pf.t.g_stride = 4;
-    pf.t.ell = g->ell_t;
-    pf.t.slab_packed = slab_packed ? 1 : 0;
-    pf.x_src = x_src; pf.g_in = g_in; pf.edge_in = edge_in; pf.A_src = a_src; pf.p0_src = p0_src;
+    pf.t = narrow_target_args(g, t);
+    pf.x_src = src.x_in; pf.g_in = src.g_in; pf.edge_in = edge_in; pf.A_src = src.a; pf.p0_src = src.p0;
     pf.rowptr_s = g->rowptr_s; pf.col_s = g->col_s; pf.ell_s = g->ell_s;
-    pf.g_out = g_out; pf.g_cols = g_cols;
-    const dim3 grid(grid_for(pf.t.n_tiles, resident_blocks_bwd_t<64>(GADAPT_BWD_T_MAX_BLOCKS)));
+    pf.g_out = src.g_out; pf.g_cols = src.g_cols;
     ProfScope prof(1, st, 2);                                   // a target-pass launch on compact input (the source pass rides in it)
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, pf); };
-    if (layer0) { if (g_cols) go(grand_bwd_target_fused_narrow_kernel<true, true>); else go(grand_bwd_target_fused_narrow_kernel<true, false>); }
-    else { if (g_cols) go(grand_bwd_target_fused_narrow_kernel<false, true>); else go(grand_bwd_target_fused_narrow_kernel<false, false>); }
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(target_grid<64>(g->n_nodes)), dim3(256), 0, st, pf); };
+    if (layer0) { if (src.g_cols) go(grand_bwd_target_fused_narrow_kernel<true, true>); else go(grand_bwd_target_fused_narrow_kernel<true, false>); }
+    else { if (src.g_cols) go(grand_bwd_target_fused_narrow_kernel<false, true>); else go(grand_bwd_target_fused_narrow_kernel<false, false>); }
     return check_launch("grand_bwd_target_fused_narrow_kernel");
 }
