@@ -121,3 +121,22 @@ extern "C" int gadapt_narrow_block_range_host(int64_t n_nodes, int halo, int n_l
     gadapt_block_range(n_nodes, halo, n_layers, tile, layer, lo_out, hi_out);
     return GADAPT_OK;
 }
+
+// The slab rows tile `tile` owes when the top layer's target pass runs in the launch: gadapt_block_slab_plan / gadapt_block_owned_block,
+// the arithmetic the kernel uses.  plan_out: rows[2], waves[2][4], zero_first, zero_step.
+extern "C" int gadapt_narrow_block_slab_plan_host(int64_t n_nodes, int halo, int n_layers, int64_t tile, int32_t* plan_out) {
+    if (n_nodes <= 0 || (halo != 32 && halo != 64) || n_layers < 1 || n_layers > GADAPT_NARROW_BLOCK_LAYERS || tile < 0 ||
+        tile * GADAPT_NARROW_TILE >= n_nodes || !plan_out)
+        return GADAPT_E_BADARG;
+    const gadapt_block_slab s = gadapt_block_slab_plan(n_nodes, gadapt_block_frame_margin(halo, n_layers), tile);
+    for (int j = 0; j < 2; ++j) {
+        plan_out[j] = s.rows[j];
+        for (int b = 0; b < 4; ++b) plan_out[2 + 4 * j + b] = s.waves[j][b];
+    }
+    plan_out[10] = s.zero_first; plan_out[11] = s.zero_step;
+    return GADAPT_OK;
+}
+extern "C" int gadapt_narrow_block_owned_block_host(int halo, int n_layers, int wave) {
+    if ((halo != 32 && halo != 64) || n_layers < 1 || n_layers > GADAPT_NARROW_BLOCK_LAYERS || wave < 0 || wave >= GADAPT_NARROW_TILE / 64) return -1;
+    return gadapt_block_owned_block(gadapt_block_frame_margin(halo, n_layers), wave);
+}

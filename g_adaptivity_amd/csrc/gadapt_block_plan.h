@@ -30,4 +30,27 @@ GADAPT_PLAN_FN void gadapt_block_range(int64_t n_nodes, int halo, int K, int64_t
 // whole 64-node wave blocks so that the owned range starts on a wave boundary of the frame.  At most 1024 rows (K = 4, halo 64).
 GADAPT_PLAN_FN int gadapt_block_frame_margin(int halo, int K) { return (K * halo + 63) / 64 * 64; }
 
+// The top layer's backward target pass inside the block launch (fwd_narrow_block_kernel<., ., TOP>): the packed slab rows a tile owes.
+// Slab row r holds the sums over nodes 256 r .. 256 r + 255 (the workgroup of grand_bwd_target_narrow_kernel that visits them): the
+// wave sums of its four 64-node blocks as (b0 + b1) + (b2 + b3), blocks in node order.  A tile's eight waves own its eight 64-node
+// blocks in ROTATED order - wave w owns frame block w or w + 8, whichever starts the owned range (margin / 64 waves in) - so:
+//   gadapt_block_owned_block   the owned block (0..7, node order within the tile) of wave w;
+//   gadapt_block_slab_plan     of tile t of n_tiles: rows[j] = 2 t + j (j = 0, 1), fed by the waves waves[j][0..3] in that order, and the
+//                              rows beyond the last tile's that it fills with zeros: zero_first, zero_first + zero_step, ... < n_rows
+//                              (every target launch of the step accumulates onto all n_rows = gadapt_backward_slab_rows rows and the
+//                              tail sums them all, so each is written by exactly one tile).  A row index >= n_rows is not written.
+GADAPT_PLAN_FN int gadapt_block_owned_block(int margin, int wave) { return (wave + 8 - margin / 64) & 7; }
+struct gadapt_block_slab { int rows[2]; int waves[2][4]; int zero_first, zero_step; };
+GADAPT_PLAN_FN struct gadapt_block_slab gadapt_block_slab_plan(int64_t n_nodes, int margin, int64_t t) {
+    const int n_tiles = (int)((n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE);
+    struct gadapt_block_slab s;
+    for (int j = 0; j < 2; ++j) {
+        s.rows[j] = 2 * (int)t + j;
+        for (int b = 0; b < 4; ++b) s.waves[j][b] = (4 * j + b + margin / 64) & 7;     // the wave whose owned block is 4 j + b
+    }
+    s.zero_first = 2 * n_tiles + (int)t;
+    s.zero_step = n_tiles;
+    return s;
+}
+
 #endif  // GADAPT_BLOCK_PLAN_H

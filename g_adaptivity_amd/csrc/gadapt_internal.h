@@ -7,7 +7,8 @@
 // 2 min 20 s on one core):
 //   gadapt_kernels.hip         C-ABI of layers / blocks / small per-step kernels, error + profiling state
 //   gadapt_tu_fwd.hip          grand_fwd_kernel<C> (gadapt_fwd.inc), wide::fwd_kernel (gadapt_wide.inc), wide::fwd_narrow_kernel and
-//                              wide::fwd_narrow_block_kernel (gadapt_narrow_fwd.inc, gadapt_narrow_node.inc)
+//                              wide::fwd_narrow_block_kernel (gadapt_narrow_fwd.inc, gadapt_narrow_node.inc; its TOP instantiations also run
+//                              the top layer's backward target pass of a fused step)
 //   gadapt_tu_bwd_target.hip   grand_bwd_target_kernel<C,...>, grand_bwd_target_compact_kernel (gadapt_bwd_target.inc),
 //                              grand_bwd_target_fused_narrow_kernel (gadapt_narrow_bwd.inc)
 //   gadapt_tu_bwd_source.hip   grand_bwd_source_kernel<C,...>, grand_bwd_source4_kernel (gadapt_bwd_source.inc)
@@ -180,7 +181,12 @@ template <int C> static int tiles_for(int64_t n_nodes) { return (int)((n_nodes +
 // produces the loss derivative and one loss partial per wave (loss; *n_partials_out = the grid of that launch).
 // cw / a_out / p0_out (nullable): the flat parameter bucket - the layer-0 launch computes the composite coefficients itself when it is
 // the wide kernel (gadapt_forward_computes_coeffs_c) and writes them to a_out / p0_out for the launches that follow.
-struct FwdExtra { FieldSrc fs; float* x0c; LossArgs loss; int* n_partials_out; const float* cw; float* a_out; float* p0_out; };
+// top (nullable; with a loss, on a block launch that covers the top layer): that launch also runs the top layer's backward target pass,
+// one node per lane - dxd [N,4], the {alpha dt, ds} pairs in source order into edge_out, and ALL slab_rows packed slab rows
+// (GADAPT_NARROW_SLAB_ROW floats each), as grand_bwd_target_narrow_kernel with accumulate = 0 writes them.
+// *ran (nullable) is set to 1 by the launch that did.
+struct NarrowTop { float* dxd; float* edge_out; float* slab; int slab_rows; int* ran; };
+struct FwdExtra { FieldSrc fs; float* x0c; LossArgs loss; int* n_partials_out; const float* cw; float* a_out; float* p0_out; const NarrowTop* top; };
 int gadapt_forward_computes_coeffs_c(const gadapt_graph* g, int c);
 #define GADAPT_LOSS_PARTIALS_MAX 4096  /* waves of a forward launch: GADAPT_FWD_MAX_BLOCKS workgroups of up to 8 waves */
 // One layer's forward launch: x_in -> x_out (NULL: head-only) and / or the [N,4] head rows x_top4; x_cols = 4: x_in is a compact [N,4] slot.
@@ -211,6 +217,7 @@ int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const LayerFwd& f, 
 // + alpha_stride; x_last (nullable): the head rows of the group's last layer.
 // gadapt_narrow_block_tiles_ok_c: the batch's 512-node tiles keep the loss partials within GADAPT_LOSS_PARTIALS_MAX
 int gadapt_narrow_block_tiles_ok_c(const gadapt_graph* g);
+int gadapt_narrow_kmax_c(const gadapt_graph* g);                // the longest in-row the narrow forward launches walk (<= 8: the ELL row)
 int gadapt_launch_fwd_narrow_block_c(int c, const gadapt_graph* g, const LayerFwd& first, int halo, int n_layers, int64_t slot_stride,
                                      int64_t alpha_stride, float* x_last, hipStream_t st);
 int gadapt_launch_bwd_target_narrow_c(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st);

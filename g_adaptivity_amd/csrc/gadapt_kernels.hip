@@ -479,6 +479,21 @@ extern "C" int gadapt_narrow_block_halo(const gadapt_graph* g, int c) { return n
 static std::atomic<int> g_narrow_bwd_fused{-1};
 static bool narrow_bwd_fused_enabled() { return env_switch(g_narrow_bwd_fused, "GADAPT_NARROW_BWD_FUSED", "0") == 1; }
 extern "C" int gadapt_debug_set_narrow_backward_fused(int on) { g_narrow_bwd_fused.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
+// Narrow route, fused step: the top layer's backward target pass T_{L-1} inside the block forward launch that seeds the loss
+// (wide::fwd_narrow_block_kernel<., ., TOP>, gadapt_block_forward_loss_narrow_top), default; bit-identical with the launch it replaces
+// (tests/test_gpu_narrow_top_in_forward.py).  GADAPT_NARROW_TOP_FWD=0 / gadapt_debug_set_narrow_top_in_forward(0): the separate launch.
+static std::atomic<int> g_narrow_top_fwd{-1};
+static bool narrow_top_fwd_enabled() { return env_switch(g_narrow_top_fwd, "GADAPT_NARROW_TOP_FWD", "0") == 1; }
+extern "C" int gadapt_debug_set_narrow_top_in_forward(int on) { g_narrow_top_fwd.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
+// THE eligibility rule of that form, for a fused step on graph g at hidden size c whose forward is a block launch of halo `halo` over one
+// shared conv: a loss target and the three backward buffers; the ELL in-table with rows of at most 8 and the source-order positions;
+// edges; and a slab grid that gives every lane of the standalone launch at most one node (N <= 256 rows - with the 512-row cap N <= 131072),
+// so that a slab row is the sum over ONE 256-node range.  Everything else keeps today's launches.
+static bool narrow_top_eligible(const gadapt_graph* g, int c, int halo, const float* target, const NarrowTop& t) {
+    if (!narrow_top_fwd_enabled() || !halo || !target || !t.dxd || !t.edge_out || !t.slab) return false;
+    if (!g->ell_t || !g->tpos_s || g->n_edges <= 0 || gadapt_narrow_kmax_c(g) > GADAPT_MAXD) return false;
+    return t.slab_rows > 0 && (int64_t)g->n_nodes <= 256 * (int64_t)t.slab_rows;
+}
 
 // A block of n_layers Euler steps as its entry points see it (built once their checks have passed): where layer l finds its input slot,
 // coefficients, {dt, scale}, alpha, slab and gradient buffer.  x_all and alpha_all are written by the forward and read by the backward;
@@ -503,7 +518,7 @@ struct Block {
 static FwdExtra slice_extra(const FwdExtra& e, bool first, bool last) {
     FwdExtra s{};
     if (first) { s.fs = e.fs; s.x0c = e.x0c; s.cw = e.cw; s.a_out = e.a_out; s.p0_out = e.p0_out; }
-    if (last) { s.loss = e.loss; s.n_partials_out = e.n_partials_out; }
+    if (last) { s.loss = e.loss; s.n_partials_out = e.n_partials_out; s.top = e.top; }
     return s;
 }
 static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers, const float* a, int64_t a_stride,
@@ -526,6 +541,7 @@ static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n
         const bool last = (l + kl == n_layers);
         FwdExtra ex_l{};
         if (extra) ex_l = slice_extra(*extra, l == 0, last);
+        if (!halo) ex_l.top = nullptr;                           // (the block launch only: narrow_top_eligible)
         LayerFwd f{.x_in = b.x(l), .a = b.a(l), .p0 = b.p0(l), .lp = b.lp(l), .alpha_out = b.alpha(l), .extra = extra ? &ex_l : nullptr};
         int rc;
         if (halo) {
@@ -567,7 +583,8 @@ extern "C" int gadapt_loss_partials_max(void) { return GADAPT_LOSS_PARTIALS_MAX;
 extern "C" int gadapt_forward_computes_coeffs(const gadapt_graph* g, int c) { return g ? gadapt_forward_computes_coeffs_c(g, c) : 0; }
 static int block_forward_loss(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor, const float* uu_tensor,
                               int n_layers, float* a, float* p0, const float* param, const float* layer_params, float* alpha_all, float* x_top4,
-                              const float* target, int d, int l1, float* seed, float* loss_partials, int c, void* stream, bool narrow) {
+                              const float* target, int d, int l1, float* seed, float* loss_partials, int c, void* stream, bool narrow,
+                              NarrowTop* top = nullptr) {       // top: the backward buffers (its slab_rows is filled in here); *top->ran reports
     if (!x_comp || dim < 1 || dim > 4 || dim + (f_tensor ? 1 : 0) + (uu_tensor ? 1 : 0) > 4)
         return fail(GADAPT_E_BADARG, "block_forward_loss: 1..4 coordinates, coordinates + extras <= 4 columns");
     // target == NULL: no loss - the evaluation forward on the node fields (inference.GraphedForward issues it as this one call)
@@ -588,6 +605,10 @@ static int block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
     }
     FwdExtra ex{FieldSrc{x_comp, f_tensor, uu_tensor, dim}, x_all,
                 LossArgs{target, seed, loss_partials, d, l1 ? 1 : 0, 1.0f / (float)((int64_t)g->n_nodes * (d > 0 ? d : 1))}, &n_partials, param, a, p0};
+    if (top && narrow && c == 64) {                              // the top layer's target pass in the last forward launch, where eligible
+        top->slab_rows = gadapt_slab_rows_c(g->n_nodes, c);
+        if (narrow_top_eligible(g, c, narrow_block_halo(g, c), target, *top)) ex.top = top;
+    }
     if (int rc = block_forward(g, x_all, 4, n_layers, a, 0, p0, 0, layer_params, alpha_all, x_top4, c, stream, &ex, narrow)) return rc;
     if (!target) return 0;
     if (n_partials <= 0 || n_partials > GADAPT_LOSS_PARTIALS_MAX) return fail(GADAPT_E_RUNTIME, "block_forward_loss: loss partial count out of range");
@@ -605,6 +626,20 @@ extern "C" int gadapt_block_forward_loss_narrow(const gadapt_graph* g, float* x_
                                                 int c, void* stream) {
     return block_forward_loss(g, x_all, x_comp, dim, f_tensor, uu_tensor, n_layers, a, p0, param, layer_params, alpha_all, x_top4, target, d, l1,
                               seed, loss_partials, c, stream, true);
+}
+// gadapt_block_forward_loss_narrow given the backward's buffers: where the step is eligible (narrow_top_eligible) its last forward launch
+// also runs the top layer's backward target pass - dxd_ws, the pairs in edge_ws and every row of the packed slab as T_{L-1} of
+// gadapt_block_backward_narrow_packed leaves them - and *top_ran = 1: the backward then starts below it
+// (gadapt_block_backward_narrow_packed_below_top).  Otherwise today's launches and *top_ran = 0.
+extern "C" int gadapt_block_forward_loss_narrow_top(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor,
+                                                    const float* uu_tensor, int n_layers, float* a, float* p0, const float* param, const float* layer_params,
+                                                    float* alpha_all, float* x_top4, const float* target, int d, int l1, float* seed, float* loss_partials,
+                                                    float* dxd_ws, float* edge_ws, float* slab, int* top_ran, int c, void* stream) {
+    if (!top_ran) return fail(GADAPT_E_BADARG, "block_forward_loss_narrow_top: nowhere to report whether the top target pass ran");
+    *top_ran = 0;
+    NarrowTop top{dxd_ws, edge_ws, slab, 0, top_ran};
+    return block_forward_loss(g, x_all, x_comp, dim, f_tensor, uu_tensor, n_layers, a, p0, param, layer_params, alpha_all, x_top4, target, d, l1,
+                              seed, loss_partials, c, stream, true, n_layers >= 2 ? &top : nullptr);
 }
 
 extern "C" int gadapt_step_tail(const float* slab, int n_rows, float* scratch, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
@@ -727,7 +762,7 @@ extern "C" int gadapt_block_backward(const gadapt_graph* g, const float* x_all, 
 static int block_backward_narrow(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top,
                                  int g_top_cols, int n_layers, const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
                                  const float* layer_params, float* g_ws, float* dxd_ws, float* edge_ws, float* slab, float* d_layer_params,
-                                 float* d_x0, int c, void* stream, int packed) {
+                                 float* d_x0, int c, void* stream, int packed, bool top_done = false) {
     if (int rc = check_graph(g, c)) return rc;
     if (!x_all || !alpha_all || !g_top || n_layers < 2 || !a || !p0 || !layer_params || !g_ws || !dxd_ws || !edge_ws || !slab)
         return fail(GADAPT_E_BADARG, "block_backward (narrow): bad argument");
@@ -752,7 +787,8 @@ static int block_backward_narrow(const gadapt_graph* g, const float* x_all, int 
     if (narrow_bwd_fused_enabled() && g->ell_s && g->rowptr_s && g->col_s && 2 * (int64_t)g->n_edges <= (int64_t)(c - 4) * g->n_nodes) {
         float* edge_buf[2] = {edge_ws, dxd_ws + 4 * (size_t)g->n_nodes};
         int l = n_layers - 1, eb = 0;
-        int rc = gadapt_launch_bwd_target_narrow_c(c, g, layer(l, g_cur, edge_buf[eb], 0), st);
+        // (top_done: T_{L-1} ran in the forward launch and left dxd_ws, the pairs in edge_buf[0] and the slab rows as this launch does)
+        int rc = top_done ? GADAPT_OK : gadapt_launch_bwd_target_narrow_c(c, g, layer(l, g_cur, edge_buf[eb], 0), st);
         for (; !rc && l >= 1; --l, eb ^= 1) {                   // source pass of layer l + target pass of layer l-1
             const LayerBwd src = layer(l, g_cur, edge_buf[eb], 0);
             rc = gadapt_launch_bwd_fused_narrow_c(c, g, src, layer(l - 1, nullptr, edge_buf[eb ^ 1], b.shared ? 1 : 0), edge_buf[eb], edge_buf[eb ^ 1],
@@ -768,7 +804,7 @@ static int block_backward_narrow(const gadapt_graph* g, const float* x_all, int 
             lb.x_cols = 4; lb.g_stride = 4; lb.sums_partials = 1;
             rc = gadapt_launch_bwd_target_c(c, g, lb, st);
         } else {
-            rc = gadapt_launch_bwd_target_narrow_c(c, g, lb, st);
+            rc = (top_done && l == n_layers - 1) ? GADAPT_OK : gadapt_launch_bwd_target_narrow_c(c, g, lb, st);
             if (!rc) rc = gadapt_launch_bwd_source_narrow_c(c, g, lb, st);
             g_cur = lb.g_out;
         }
@@ -795,4 +831,15 @@ extern "C" int gadapt_block_backward_narrow_packed(const gadapt_graph* g, const 
     (void)want_d_scale;
     return block_backward_narrow(g, x_all, x0_cols, alpha_all, g_top, g_top_cols, n_layers, a, a_stride, p0, p0_stride, layer_params, g_ws, dxd_ws,
                                  edge_ws, slab, d_layer_params, d_x0, c, stream, 1);
+}
+// ... behind gadapt_block_forward_loss_narrow_top with *top_ran = 1: the same arguments, the same launches without the first - the top
+// layer's target pass ran in the forward launch; the edge buffers alternate as if it had just written edge_ws.
+extern "C" int gadapt_block_backward_narrow_packed_below_top(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all,
+                                                             const float* g_top, int g_top_cols, int n_layers, const float* a, int64_t a_stride,
+                                                             const float* p0, int64_t p0_stride, const float* layer_params, float* g_ws, float* dxd_ws,
+                                                             float* edge_ws, float* slab, float* d_layer_params, int want_d_scale, float* d_x0, int c,
+                                                             void* stream) {
+    (void)want_d_scale;
+    return block_backward_narrow(g, x_all, x0_cols, alpha_all, g_top, g_top_cols, n_layers, a, a_stride, p0, p0_stride, layer_params, g_ws, dxd_ws,
+                                 edge_ws, slab, d_layer_params, d_x0, c, stream, 1, true);
 }

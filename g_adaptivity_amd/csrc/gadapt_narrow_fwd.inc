@@ -1,6 +1,7 @@
 // gadapt_narrow_fwd.inc - forward of the narrow route (gadapt_block_forward_narrow), included by gadapt_tu_fwd.hip after gadapt_wide.inc:
 // wide::fwd_narrow_kernel, one layer per launch (described first), and wide::fwd_narrow_block_kernel, up to four layers per launch by halo
-// recompute (at the end of the file).  Both run the per-node statements of gadapt_narrow_node.inc.
+// recompute (at the end of the file; its TOP instantiations also run the top layer's backward target pass, narrow_top_target).  Both run
+// the per-node statements of gadapt_narrow_node.inc.
 //
 // On the narrow route every layer reads and writes [N,4] slots: columns 4.. stay exactly zero behind the zero-pad encoder
 // (DESIGN.md section 4), so of the wide kernel's work (wide::fwd_kernel<XC = true>) only channels 0..3 of P, one 16-byte chunk per
@@ -330,20 +331,107 @@ __device__ __forceinline__ void narrow_w_finish(float (&fa)[8], NarrowW& t, Narr
 // a layer's range are computed on stale rows and dropped: nothing in a later range reads them.
 // Only owned nodes store to global memory: the [N,4] rows of every layer, alpha, the layer-0 input rows, the loss seed; one loss
 // partial per wave (8 per workgroup).
+// TOP (with HEAD and a loss target; gadapt_block_forward_loss_narrow_top): the launch also runs the top layer's backward target pass -
+// the first launch of the narrow backward, grand_bwd_target_narrow_kernel with accumulate = 0, which needs nothing from another workgroup.
+// The lane that owns node i has, after the last layer, all that pass reads: the seed row it has just computed, the layer's input row,
+// neighbour rows and alpha, {dt, scale}, the 4 x 4 corner of A (given, or this launch's own sums); it requests the positions of its edges
+// in source order at the top of the last layer, runs narrow_top_target and stores dxd[i] and its {alpha dt, ds} pairs.  The 20 slab
+// partials go through the standalone kernel's wave butterfly and, per owned 64-node block, through LDS; after one more workgroup barrier
+// the tile writes packed slab rows 2 t and 2 t + 1 as (b0 + b1) + (b2 + b3) over their blocks in node order, and zeros to its share of
+// the rows past the last tile's (gadapt_block_slab_plan) - every row of the slab is written, each by one tile, with the bits the
+// standalone launch writes.  The launcher takes this form only where a lane of that launch has at most one node (N <= 256 rows).
 struct BlockArgs {
     FwdArgs f;                  // x_in: the group's input rows; x_top4, lp, alpha_out: output rows, {dt, scale} and alpha of its FIRST layer
     int K, halo;
     long long slot_stride, alpha_stride;    // floats from one layer's output rows / alpha to the next layer's
     float* x_last;              // nullable: the group's last layer stores its rows here instead (the head rows)
+    // TOP instantiations only (behind the fields every instantiation reads): the top layer's backward target pass
+    const int32_t* tpos; float2* edge_out; float* dxd; float* slab;   // gadapt_graph::tpos_s, the pairs' buffer, dxd [N,4], packed slab rows
+    int slab_rows, n_edges;
 };
 constexpr int NRB_NT = GADAPT_NARROW_TILE;     // threads per workgroup = nodes a workgroup owns
 constexpr int NRB_ROWS = 2 * NRB_NT;           // frame rows: 512 + 2 margin <= 1024
 
-template <bool HEAD, bool FLD>
+// TOP: this node's terms of the loss as loss_node (same expressions), which also hands the seed row back - zero beyond L.d columns, as
+// ld_row4_compact reads it - for the target pass that follows in the same lane
+__device__ __forceinline__ float loss_node_seed(const LossArgs& L, int row, const float4& pred, const float4& tgt, float lv, float4& seed) {
+    const float pv[4] = {pred.x, pred.y, pred.z, pred.w}, tv[4] = {tgt.x, tgt.y, tgt.z, tgt.w};
+    float sv[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k < L.d) {
+            const float diff = pv[k] - tv[k];
+            if (L.l1) { lv += fabsf(diff); sv[k] = (diff > 0.f ? L.inv : (diff < 0.f ? -L.inv : 0.f)); }
+            else      { lv = fmaf(diff, diff, lv); sv[k] = 2.0f * diff * L.inv; }
+            L.seed[(size_t)row * L.d + k] = sv[k];
+        }
+    }
+    seed = make_float4(sv[0], sv[1], sv[2], sv[3]);
+    return lv;
+}
+
+// TOP: the target pass of the top layer for ONE node, in the lane that has just run its forward - the NARROW, SUMS = 0, deg <= 8
+// branch of bwd_target_compact_body (gadapt_bwd_target.inc) on operands the forward still holds: g4 = the seed row, xi = the layer's
+// input row, xn[k] / al[k] = the neighbour rows and alpha of the edge walk, a4 = A[o][c] (o, c < 4).  Same expressions in the same
+// order, fmaf where that body calls fmaf and nowhere else (no contraction: that kernel's instruction stream has none either), so every
+// value stored carries the bits grand_bwd_target_narrow_kernel stores.  Entries k >= deg: weight 0 on a zero difference (that kernel
+// multiplies its zero weight with the difference to some valid row; either way the terms are zeros that leave every sum as it is).
+// live = the lane owns a node of the batch: only then it stores, and only then part[] (dA[o][c] at 4 o + c, dp0[o] at 16 + o) is its
+// node's share of the slab row - else zeros, as for a lane of that kernel whose node loop runs no iteration.
+// (A copy of those statements, not a shared function: the standalone kernels keep their text, and with it their instruction streams.)
+__device__ __forceinline__ void narrow_top_target(float (&part)[20], const float4& g4, const float4& xi, const v4f (&xn)[8], const float (&al)[8],
+                                                  int deg, float dt, float sc, const float (&a4)[4][4], const int (&tp)[8], bool live, int i,
+                                                  float2* __restrict__ edge_out, float* __restrict__ dxd) {
+#pragma clang fp contract(off)
+    const float w1 = 1.0f - dt;
+    const float4 dm = make_float4(dt * g4.x, dt * g4.y, dt * g4.z, dt * g4.w);
+    float D = 0.f;
+    float4 dP = f4zero();
+    float ak[8], da[8];
+    float4 xk[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const bool on = k < deg;
+        ak[k] = on ? al[k] : 0.f;
+        xk[k] = on ? make_float4(xn[k].x - xi.x, xn[k].y - xi.y, xn[k].z - xi.z, xn[k].w - xi.w) : f4zero();
+        da[k] = dot4(dm, xk[k]);
+        D = fmaf(ak[k], da[k], D);
+    }
+    float dsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float ds = ak[k] * (da[k] - D) * sc;
+        dsum += ds;
+        axpy4(dP, ds, xk[k]);
+        if (live && k < deg) edge_out[tp[k]] = make_float2(ak[k] * dt, ds);
+    }
+    axpy4(dP, dsum, xi);
+    const float dp[4] = {dP.x, dP.y, dP.z, dP.w}, xv4[4] = {xi.x, xi.y, xi.z, xi.w};
+    float t4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) t4[c] = fmaf(dp[o], a4[o][c], t4[c]);
+    if (live)
+        *reinterpret_cast<float4*>(dxd + 4 * (size_t)i) =
+            make_float4(fmaf(w1, g4.x, t4[0]), fmaf(w1, g4.y, t4[1]), fmaf(w1, g4.z, t4[2]), fmaf(w1, g4.w, t4[3]));
+    float zero = 0.f;
+    asm volatile("" : "+v"(zero));                               // the sums start at +0 and ADD their one node (the standalone kernel's loop): not folded
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) part[4 * o + c] = live ? fmaf(dp[o], xv4[c], zero) : 0.f;
+        part[16 + o] = live ? zero + dp[o] : 0.f;
+    }
+}
+
+template <bool HEAD, bool FLD, bool TOP = false>
 __global__ __launch_bounds__(NRB_NT) void fwd_narrow_block_kernel(BlockArgs q) {
+    static_assert(!TOP || HEAD, "the top layer's target pass rides in the launch that seeds the loss");
     __shared__ float4 rows[2][NRB_ROWS];                         // layer input rows / layer output rows, ping-pong
     __shared__ float astage[NRB_NT / 64][NRW_AST];
     __shared__ NarrowWLds wl;
+    __shared__ float tred[TOP ? NRB_NT / 64 : 1][32];           // TOP: the 20 slab partials of each owned 64-node block, by block in node order
     const FwdArgs& p = q.f;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h = lane >> 5;
     const int N = p.n_nodes, K = q.K;
@@ -372,6 +460,9 @@ __global__ __launch_bounds__(NRB_NT) void fwd_narrow_block_kernel(BlockArgs q) {
         rows[0][tid + NRB_NT * s] = ld_x4<FLD>(cx, p.x_in, min(max(i, 0), N - 1));
     }
     const int so = 64 * wave < margin ? 1 : 0;                   // which of this wave's two blocks is owned
+    if constexpr (TOP) {                                         // an owned block past ceil32(N) runs no layer: its partials are zeros
+        if (lane < 32) tred[gadapt_block_owned_block(margin, wave)][lane] = 0.f;   // (the same wave writes them again: LDS operations complete in order)
+    }
     float4 tgt = f4zero();
     if constexpr (HEAD) tgt = loss_target4(tgt_base, opaque(tgt_d), min(frame0 + tid + NRB_NT * so, N - 1));
     float fa[8];
@@ -414,6 +505,27 @@ __global__ __launch_bounds__(NRB_NT) void fwd_narrow_block_kernel(BlockArgs q) {
                     }
                 }
             }
+            // TOP, the owned block of the last layer: what the target pass needs beyond the forward's operands is requested here, ahead of
+            // the layer's arithmetic - the positions of this node's edges in source order (the one new global read: unconditional,
+            // clamped as in bwd_target_compact_body) and the 4 x 4 corner of A (given, or this launch's own sums: the bits of a_out)
+            [[maybe_unused]] int tp[8];
+            [[maybe_unused]] float a4[4][4];
+            if constexpr (TOP) {
+                if (k == K - 1 && s == so) {
+                    const int last = q.n_edges - 1;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) tp[e] = q.tpos[min(t1.rp0 + e, last)];
+                    if (p.cw) {
+#pragma unroll
+                        for (int L = 0; L < 16; ++L)             // entry 16 o + c of the partial sums, o < 4, c < 4 of 16
+                            a4[L >> 2][L & 3] = (wl.cpart[0][4 * L - 3 * (L & 3)] + wl.cpart[1][4 * L - 3 * (L & 3)]) +
+                                                (wl.cpart[2][4 * L - 3 * (L & 3)] + wl.cpart[3][4 * L - 3 * (L & 3)]);
+                    } else {
+#pragma unroll
+                        for (int L = 0; L < 16; ++L) a4[L >> 2][L & 3] = p.A[(L >> 2) * C + (L & 3)];
+                    }
+                }
+            }
             // (this kernel's accumulators are VGPRs: 16 wait states between the last MFMA and the swaps that read it - an 8-pass MFMA needs 11)
 #define GADAPT_NARROW_NODE_SETTLE(pa, pb) asm volatile("s_nop 15" : "+v"(pa), "+v"(pb))
 #include "gadapt_narrow_node.inc"                                 // own, xc, deg, lo | hi, w[0..7] of node i
@@ -421,6 +533,7 @@ __global__ __launch_bounds__(NRB_NT) void fwd_narrow_block_kernel(BlockArgs q) {
 
             if (i >= klo && i < khi) nxt[r] = make_float4(lo.x, lo.y, hi.x, hi.y);
             if (s != so) continue;                               // halo lanes store nothing
+            [[maybe_unused]] float4 g4 = f4zero();               // TOP: the seed row of this lane's node
             if (i < N) {
                 *reinterpret_cast<v4f*>(x_out + 4 * (size_t)i) = v4f{lo.x, lo.y, hi.x, hi.y};
                 if (k == 0 && p.x0c) *reinterpret_cast<v4f*>(p.x0c + 4 * (size_t)i) = xc;   // the layer-0 input rows, for the layer-0 backward
@@ -428,7 +541,8 @@ __global__ __launch_bounds__(NRB_NT) void fwd_narrow_block_kernel(BlockArgs q) {
                     if (k == K - 1 && p.loss.target) {
                         LossArgs la = p.loss;
                         la.d = opaque(tgt_d);                    // (= p.loss.d where there is a target)
-                        loss_lv = loss_node(la, i, make_float4(lo.x, lo.y, hi.x, hi.y), tgt, loss_lv);
+                        if constexpr (TOP) loss_lv = loss_node_seed(la, i, make_float4(lo.x, lo.y, hi.x, hi.y), tgt, loss_lv, g4);
+                        else loss_lv = loss_node(la, i, make_float4(lo.x, lo.y, hi.x, hi.y), tgt, loss_lv);
                     }
                 }
             }
@@ -443,10 +557,44 @@ __global__ __launch_bounds__(NRB_NT) void fwd_narrow_block_kernel(BlockArgs q) {
                 for (int t = 0; t < 8; ++t)
                     if (64 * t + lane < e_cnt) alpha_out[e_first + 64 * t + lane] = sa[64 * t + lane];
             }
+            // ---- TOP: the backward target pass of the top layer on this node (every lane of the owned block; lanes past N add zeros)
+            if constexpr (TOP) {
+                if (k == K - 1) {
+                    __builtin_amdgcn_sched_barrier(0);           // behind the node statements: nothing of it among the MFMA results' readers
+                    float part[20];
+                    narrow_top_target(part, g4, own, xv, w, deg, dt, sc, a4, tp, i < N, i, q.edge_out, q.dxd);
+                    const int ob = gadapt_block_owned_block(margin, wave);
+                    // the wave sum of bwd_target_compact_body, butterfly 32, 16, .., 1 - the same additions, stage by stage over the 20
+                    // independent values (entry by entry with the store in between, as that body has it, every exchange is waited
+                    // for on its own: 120 dependent LDS-crossbar trips per wave instead of 6)
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+                        for (int e = 0; e < 20; ++e) part[e] += __shfl_xor(part[e], off, 64);
+                    if (lane == 0) {
+#pragma unroll
+                        for (int e = 0; e < 20; ++e) tred[ob][e] = part[e];
+                    }
+                }
+            }
         }
         if (k + 1 < K) __syncthreads();                          // layer k is in LDS; its input buffer is free for layer k + 1's output
     }
     if constexpr (HEAD) { if (p.loss.target) loss_wave_partial<NRB_NT / 64>(p.loss, loss_lv, tid); }   // every wave of the grid owns a slot
+    if constexpr (TOP) {
+        // ---- the slab rows this tile owes (gadapt_block_slab_plan): rows 2 t and 2 t + 1 = (b0 + b1) + (b2 + b3) over their four blocks in
+        // node order, entries 20..31 zero; then its share of the rows no tile has nodes for.  Every wave arrives: each owns one block.
+        __syncthreads();
+        const gadapt_block_slab sp = gadapt_block_slab_plan(N, margin, blockIdx.x);
+        if (tid < 2 * GADAPT_NARROW_SLAB_ROW) {
+            const int j = tid >> 5, e = tid & 31, r = j ? sp.rows[1] : sp.rows[0];   // (a select: indexed, the plan would live in scratch)
+            if (r < q.slab_rows)
+                q.slab[(size_t)r * GADAPT_NARROW_SLAB_ROW + e] =
+                    e < 20 ? (tred[4 * j][e] + tred[4 * j + 1][e]) + (tred[4 * j + 2][e] + tred[4 * j + 3][e]) : 0.f;
+        }
+        if (tid < GADAPT_NARROW_SLAB_ROW)
+            for (int r = sp.zero_first; r < q.slab_rows; r += sp.zero_step) q.slab[(size_t)r * GADAPT_NARROW_SLAB_ROW + tid] = 0.f;
+    }
 }
 
 }  // namespace wide

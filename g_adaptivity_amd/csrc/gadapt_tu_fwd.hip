@@ -106,7 +106,10 @@ int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const LayerFwd& f, 
 // tile, halo from gadapt_narrow_block_halo_host (32 or 64; the caller has it from the graph's registration).  first.x_in: the group's [N,4]
 // input slot; the rows of layer k go to first.x_top4 + k * slot_stride, those of the last layer to x_last where given (head rows); lp and
 // alpha_out (nullable) are the first layer's, the next layers' follow at + 2 and + alpha_stride.  extra: layer-0 fields / coefficients
-// (a group that starts the block), loss (a group that ends it).  Everything is checked before the launch.
+// (a group that starts the block), loss (a group that ends it) and, with the loss, extra->top: the top layer's backward target pass in the
+// same launch (the TOP instantiations; profiled as this forward launch only).  Everything is checked before the launch.
+// gadapt_narrow_kmax_c: the longest in-row the narrow launches walk on this graph.
+int gadapt_narrow_kmax_c(const gadapt_graph* g) { return wide_fwd_args(g, LayerFwd{}, 0).kmax; }
 int gadapt_narrow_block_tiles_ok_c(const gadapt_graph* g) {
     const int64_t tiles = ((int64_t)g->n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE;
     return tiles >= 1 && tiles * (wide::NRB_NT / 64) <= GADAPT_LOSS_PARTIALS_MAX;      // one loss partial per wave
@@ -137,11 +140,22 @@ int gadapt_launch_fwd_narrow_block_c(int c, const gadapt_graph* g, const LayerFw
     }
     if (!p.cw && (!first.a || !first.p0)) return fail(GADAPT_E_BADARG, "narrow block forward: no coefficients");
     if (p.cw && grid < 64) return fail(GADAPT_E_BADARG, "narrow block forward: in-kernel coefficients need 64 workgroups (one row of A each)");
+    // the top layer's backward target pass in this launch (the C-ABI unit decides: narrow_top_plan): one node per lane of the slab grid
+    const NarrowTop* top = first.extra ? first.extra->top : nullptr;
+    if (top) {
+        if (!p.loss.target || !top->dxd || !top->edge_out || !top->slab || !g->tpos_s || g->n_edges <= 0 || p.kmax > GADAPT_MAXD ||
+            top->slab_rows != gadapt_slab_rows_c(g->n_nodes, c) || (int64_t)g->n_nodes > 256 * (int64_t)top->slab_rows)
+            return fail(GADAPT_E_BADARG, "narrow block forward (top target pass): a loss, dxd / edge / slab buffers, edges, in-rows of at most 8, one node per lane of the slab grid");
+        q.tpos = g->tpos_s; q.edge_out = reinterpret_cast<float2*>(top->edge_out); q.dxd = top->dxd; q.slab = top->slab;
+        q.slab_rows = top->slab_rows; q.n_edges = g->n_edges;
+    }
     ProfScope prof(0, st, 6 | 32);                              // compact input, head-only output, bit 5: several layers in the launch
     const bool fld = p.fs.x_comp != nullptr, head = p.loss.target != nullptr;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(wide::NRB_NT), 0, st, q); };
-    if (head) { if (fld) go(wide::fwd_narrow_block_kernel<true, true>); else go(wide::fwd_narrow_block_kernel<true, false>); }
+    if (top) { if (fld) go(wide::fwd_narrow_block_kernel<true, true, true>); else go(wide::fwd_narrow_block_kernel<true, false, true>); }
+    else if (head) { if (fld) go(wide::fwd_narrow_block_kernel<true, true>); else go(wide::fwd_narrow_block_kernel<true, false>); }
     else { if (fld) go(wide::fwd_narrow_block_kernel<false, true>); else go(wide::fwd_narrow_block_kernel<false, false>); }
+    if (top && top->ran) *top->ran = 1;
     return check_launch("wide::fwd_narrow_block_kernel");
 }
 

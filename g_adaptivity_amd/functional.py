@@ -8,6 +8,7 @@ the CPU and nothing falls back to torch ops.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Optional
 
@@ -607,6 +608,7 @@ class BlockForwardCall(_OneCall):
     except where the layer-0 launch computes them from weights laid out back to back (`in_forward`: hidden 64 on wide-forward graphs)."""
 
     _name, _at = 'gadapt_block_forward_loss', 2
+    _top = None                                                     # (dxd_ws, edge_ws, slab): see with_backward_buffers
 
     def __init__(self, model, graph, target=None, l1=False, coeffs=None, store=False, narrow=False):
         self.narrow = bool(narrow)                                 # the route's `narrow`: every slot holds [N,4] rows at its start
@@ -634,6 +636,22 @@ class BlockForwardCall(_OneCall):
         self.args = [self.graph.c_ref, ptr(self.x_all), None, self.d, None, None, self.L, ptr(self.coeffs[0]), ptr(self.coeffs[1]),
                      self.bucket if self.in_forward else None, ptr(self.lp), ptr(self.alpha), ptr(self.x_top4), ptr(self.target),
                      0 if self.target is None else self.d, self.l1, ptr(self.seed), ptr(self.partials), c, None]
+        if self._top is not None:                                  # gadapt_block_forward_loss_narrow_top: + dxd_ws, edge_ws, slab, top_ran
+            self.args[-2:-2] = [ptr(t) for t in self._top] + [ctypes.addressof(self._top_ran)]
+
+    def with_backward_buffers(self, dxd_ws, edge_ws, slab):
+        """Narrow route of a fused step (`training.FusedIteration`): the call becomes `gadapt_block_forward_loss_narrow_top`, whose last
+        forward launch also runs the top layer's backward target pass into the backward's buffers where the step is eligible;
+        `top_ran` then says whether it did, i.e. which backward entry point follows."""
+        assert self.narrow and self.target is not None
+        self._top, self._top_ran = (dxd_ws, edge_ws, slab), ctypes.c_int(0)
+        self._name = 'gadapt_block_forward_loss_narrow_top'
+        self._fn = getattr(lib(), self._name)
+        self.bind()
+
+    @property
+    def top_ran(self) -> bool:
+        return self._top is not None and self._top_ran.value != 0
 
     def compute_coeffs(self, stream):
         """(A, p0) of the weights as they are now: one launch."""

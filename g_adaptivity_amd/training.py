@@ -116,6 +116,10 @@ class FusedIteration:
             # narrow route: packed slab rows (32 floats: the 20 partials a target-pass workgroup owes) and the one-launch tail over them
             slab_floats = lib().gadapt_narrow_slab_floats(n) if r.narrow else lib().gadapt_backward_slab_floats(n, c)
             self.slab = torch.empty(slab_floats, **f32)
+            if r.narrow and self.fwd.L >= 2:
+                # ... and the forward call is given the backward's buffers: where the step is eligible (include/gadapt_hip.h,
+                # gadapt_block_forward_loss_narrow_top) its last launch also runs the top layer's backward target pass
+                self.fwd.with_backward_buffers(self.dxd_ws, self.edge_ws, self.slab)
             self.coeffs = self.fwd.coeffs
             # hidden 64 on a graph the wide forward takes: the layer-0 launch computes (A, p0) from the live weights itself - no
             # coefficient launch in the step (13 launches), and nothing to refresh when the weights change behind the step's back
@@ -162,6 +166,8 @@ class FusedIteration:
             self._bw = (getattr(L_, name), [self.graph.c_ref, ptr(fw.x_all), 4, ptr(fw.alpha), ptr(fw.seed), self.d, fw.L, ptr(a), 0, ptr(p0), 0,
                                             ptr(fw.lp), ptr(self.g_ws), ptr(self.dxd_ws), ptr(self.edge_ws), ptr(self.slab), None, 0, None, c, None],
                         name)
+            # (the same arguments, one launch fewer: behind a forward call that ran the top layer's target pass itself)
+            self._bw_below = (L_.gadapt_block_backward_narrow_packed_below_top, self._bw[1], 'gadapt_block_backward_narrow_packed_below_top')
             a_ptr, p0_ptr = (None, None) if self.coeffs_in_forward else (ptr(a), ptr(p0))
         # gadapt_step_tail in its three forms: (slab given, moments given) = the whole tail; (slab, no moments) = this rank's gradient;
         # (no slab, moments) = the gradient is given (all-reduced)
@@ -176,15 +182,16 @@ class FusedIteration:
         self._fn_tail = {k: (getattr(L_, name), name) for k, name in self._fn_tail.items()}
 
     def forward_backward(self):
-        """zero_grad + model(data) + loss + backward: 4 + 7 launches at 4 layers (narrow route: 4 + 4, each source pass inside the next
-        target pass, into packed slab rows; small-mesh batches: 1 + 1; the gradient of the conv
+        """zero_grad + model(data) + loss + backward: 4 + 7 launches at 4 layers (narrow route: 1 + 4 - the forward layers in one launch
+        where the graph has a halo, each source pass inside the next target pass, into packed slab rows - or 1 + 3 where the forward
+        launch also runs the top layer's target pass; small-mesh batches: 1 + 1; the gradient of the conv
         parameters is still in the slab: `finish()` sums it).  Data parallel: also the slab sums + chain rule, so that `flat` holds this
         rank's gradient."""
         if self.fwd.moved():
             self._plans()
         st = current_stream(self.device)
         self.n_part = self.fwd(*self._in, st)
-        fn, args, name = self._bw
+        fn, args, name = self._bw_below if (self.small is None and self.fwd.top_ran) else self._bw
         args[-1] = st
         rc = fn(*args)
         if rc:

@@ -121,6 +121,15 @@ int gadapt_narrow_block_halo_host(const int32_t* rowptr, const int32_t* col, int
  * layer `layer` (0 .. n_layers-1) of a group of n_layers <= 4 layers - its owned range widened by (n_layers - 1 - layer) * halo, clamped
  * to [0, round_up(n_nodes, 32)); layer = -1: the range of input rows it loads, one halo wider than layer 0's. */
 int gadapt_narrow_block_range_host(int64_t n_nodes, int halo, int n_layers, int64_t tile, int layer, int64_t* lo_out, int64_t* hi_out);
+/* ... and the packed slab rows a tile owes when the top layer's backward target pass runs in the launch (see
+ * gadapt_block_forward_loss_narrow_top below).  Slab row r sums nodes 256 r .. 256 r + 255 as (b0 + b1) + (b2 + b3) over its 64-node
+ * blocks in node order; the eight waves of a tile own its eight blocks in rotated order.  plan_out (12 ints): the two rows 2 tile and
+ * 2 tile + 1; the four waves that feed the first row, in summation order, then the four of the second; then zero_first and zero_step:
+ * the tile also writes zeros to rows zero_first, zero_first + zero_step, ... below the slab's row count - the rows beyond the last
+ * tile's - so that every row is written by exactly one tile.  owned_block_host: the block (0..7, node order within the tile) wave
+ * `wave` (0..7) owns, or -1 for a bad argument. */
+int gadapt_narrow_block_slab_plan_host(int64_t n_nodes, int halo, int n_layers, int64_t tile, int32_t* plan_out);
+int gadapt_narrow_block_owned_block_host(int halo, int n_layers, int wave);
 /* gadapt_graph holds device arrays, so the library cannot find the halo itself: the caller tells it once per graph, after filling the
  * structure (halo = gadapt_narrow_block_halo_host's result; 0 = forget the graph - call it before the arrays are freed or reused for
  * another graph).  The entry is keyed by (rowptr_t, ell_t, n_nodes, n_edges).  A graph that was never registered runs one launch per
@@ -327,6 +336,29 @@ int gadapt_step_tail_narrow(const float* slab, int n_rows, float* scratch, float
                             float grad_scale, float* a_out, float* p0_out,
                             const float* loss_partials /*nullable*/, int n_loss_partials, float* loss_out, int64_t loss_count,
                             int c, void* stream);
+/* The top layer's backward target pass inside the forward launch.  T_{L-1}, the first launch of gadapt_block_backward_narrow_packed, needs
+ * nothing from another workgroup: its g row is the loss seed, and the last layer's forward holds its x rows, alpha, {dt, scale} and A.
+ * gadapt_block_forward_loss_narrow_top is gadapt_block_forward_loss_narrow given the backward's dxd_ws, edge_ws and packed slab.  Where
+ * the step is eligible the last forward launch also writes what T_{L-1} writes - dxd_ws [N,4], the {alpha dt, ds} pairs in edge_ws, all
+ * gadapt_backward_slab_rows rows of the slab (rows without nodes: 32 zeros), the same bits - and *top_ran = 1; then
+ * gadapt_block_backward_narrow_packed_below_top (the arguments of gadapt_block_backward_narrow_packed) runs the remaining launches, its
+ * edge buffers alternating as if T_{L-1} had just written edge_ws.  Eligible: a block launch covers the top layer (a registered halo,
+ * see gadapt_narrow_block_halo), a target, n_layers >= 2, the three buffers given, rows of at most 8 in-neighbours, n_edges > 0,
+ * n_nodes <= 256 * gadapt_backward_slab_rows (one node per lane of T_{L-1}: n_nodes <= 131072), and the switch
+ * gadapt_debug_set_narrow_top_in_forward on.  Otherwise *top_ran = 0, nothing but gadapt_block_forward_loss_narrow's results is written
+ * and the backward is gadapt_block_backward_narrow_packed.  Returns the number of loss partials, like its namesake. */
+int gadapt_block_forward_loss_narrow_top(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor /*nullable*/,
+                                         const float* uu_tensor /*nullable*/, int n_layers, float* a, float* p0, const float* param /*nullable*/,
+                                         const float* layer_params, float* alpha_all, float* x_top4,
+                                         const float* target, int d, int l1, float* seed, float* loss_partials,
+                                         float* dxd_ws /*nullable*/, float* edge_ws /*nullable*/, float* slab /*nullable*/, int* top_ran,
+                                         int c, void* stream);
+int gadapt_block_backward_narrow_packed_below_top(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all,
+                                                  const float* g_top, int g_top_cols, int n_layers,
+                                                  const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
+                                                  const float* layer_params,
+                                                  float* g_ws, float* dxd_ws, float* edge_ws, float* slab,
+                                                  float* d_layer_params, int want_d_scale, float* d_x0, int c, void* stream);
 
 /* ------------------------------------------------------------------ small meshes: the whole evaluation forward in ONE launch
  * The reference's own sizes (params.py:37,56,107,130-134: 11x11 ... 23x23 meshes, hidden 8, 4 layers; evaluation one sample per call,
@@ -508,6 +540,10 @@ int gadapt_debug_set_narrow_forward(int on);
  * alternate with lives in the unused tail of dxd_ws); 0 runs the pair of launches per layer.  Results are bit-identical either way
  * (tests/test_gpu_narrow_backward.py). */
 int gadapt_debug_set_narrow_backward_fused(int on);
+/* Switch: 1 (the default; GADAPT_NARROW_TOP_FWD=0 in the environment starts with 0) lets gadapt_block_forward_loss_narrow_top run the top
+ * layer's backward target pass inside its last forward launch where the step is eligible; 0 keeps the separate launch.  Results are
+ * bit-identical either way (tests/test_gpu_narrow_top_in_forward.py). */
+int gadapt_debug_set_narrow_top_in_forward(int on);
 /* Diagnostic: runtime-reported workgroups per CU of {forward, backward target, backward source}. */
 int gadapt_debug_occupancy(int c, int* out3);
 
