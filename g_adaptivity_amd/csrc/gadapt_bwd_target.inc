@@ -734,12 +734,17 @@ __device__ __forceinline__ void bwd_target_compact_body(const BwdTArgs& p, const
             acc[16 + o] += dp[o];
         }
     }
+    // the wave butterfly 32, 16, .., 1 over the live entries on DPP / lane swaps (wave_sum_desc: the additions of __shfl_xor in that
+    // order, without its LDS-crossbar trips - entry by entry with the store in between, each of the 120 was waited for on its own).
+    // The node loop has ended for every lane: the whole wave is here.
+    constexpr int LIVE = SUMS == 0 ? 20 : (SUMS > 1 ? 22 : 21);
+    float part[LIVE];
 #pragma unroll
-    for (int k = 0; k < 22; ++k) {
-        if (k >= 20 && (SUMS == 0 || (k == 21 && SUMS < 2))) continue;
+    for (int k = 0; k < LIVE; ++k) part[k] = acc[k];
+    wave_sum_desc(part);
+    if (lane == 0) {
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
-        if (lane == 0) red[wave][k] = acc[k];
+        for (int k = 0; k < LIVE; ++k) red[wave][k] = part[k];
     }
     __syncthreads();
     if (!p.accumulate && p.slab_packed) {                       // accumulate = 0: the row is written whole - packed: its 12 spare entries

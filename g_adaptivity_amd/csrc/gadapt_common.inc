@@ -971,6 +971,43 @@ __device__ __forceinline__ float wave_sum(float v) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));   // xor 32
     return a + b;
 }
+// Sum over the 64 lanes of the wave for N independent values, result in every lane, in the order of the xor butterfly
+//     for (off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+// that the slab partials are defined by - bit for bit, in all 64 lanes - without the LDS crossbar (__shfl_xor lowers to ds_bpermute_b32).
+// (wave_sum above adds in ascending order, 1, 2, .., 32: other roundings.)  Stage by stage over the N values, so that an exchange
+// is N - 1 instructions away from the one that reads its result:
+//     xor 32  v_permlane32_swap_b32 on two copies: lanes 0..31 get own + other, lanes 32..63 other + own (fp32 addition commutes)
+//     xor 16  v_permlane16_swap_b32, likewise between rows 2r and 2r + 1
+//     xor 8   DPP row_ror:8 - exactly xor 8 inside a row of 16 lanes
+//     xor 4   DPP row_ror:4 - lane (i + 4) mod 16 of the row is i ^ 4 or (i ^ 4) ^ 8, which hold the same value after the xor-8 stage
+//     xor 2   DPP quad_perm [2,3,0,1]
+//     xor 1   DPP quad_perm [1,0,3,2]
+// (row_half_mirror / row_mirror, group_sum's steps, pair other lanes: valid in ascending order only.)
+// CONTRACT: every lane of the wave is active (no early return, no divergent branch around the call): a swap or a DPP read of an
+// inactive lane has no defined value.  The swaps are inline assembly, so their wait states are in the string: s_nop 1 covers a
+// vector write of either operand within the two instructions before (a single value; N >= 3 separates them by itself).
+template <int N> __device__ __forceinline__ void wave_sum_desc(float (&v)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        float a = v[k], b = v[k];
+        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));   // xor 32
+        v[k] = a + b;
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        float a = v[k], b = v[k];
+        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));   // xor 16
+        v[k] = a + b;
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = dpp_add<0x128>(v[k]);    // row_ror:8
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = dpp_add<0x124>(v[k]);    // row_ror:4
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = dpp_add<0x4E>(v[k]);     // quad_perm [2,3,0,1]
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = dpp_add<0xB1>(v[k]);     // quad_perm [1,0,3,2]
+}
 template <int NW> __device__ __forceinline__ void loss_wave_partial(const LossArgs& L, float lv, int tid) {
     const float t = wave_sum(lv);
     if ((tid & 63) == 0) L.partials[blockIdx.x * NW + (tid >> 6)] = t;

@@ -185,6 +185,33 @@ extern "C" int gadapt_debug_occupancy(int c, int* out3) {
     return GADAPT_OK;
 }
 
+// Diagnostic: wave_sum_desc (gadapt_common.inc) beside the butterfly it restates - the one place that still spells it with __shfl_xor.
+// One workgroup of n_waves waves; thread t holds in[t][0..N) and writes both sums of its wave, as its lane sees them.
+template <int N>
+__global__ void wave_sum_desc_debug_kernel(const float* __restrict__ in, float* __restrict__ out_shfl, float* __restrict__ out_desc) {
+    const size_t at = (size_t)threadIdx.x * N;
+    float a[N], b[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) a[k] = b[k] = in[at + k];
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) a[k] += __shfl_xor(a[k], off, 64);
+    wave_sum_desc(b);
+#pragma unroll
+    for (int k = 0; k < N; ++k) { out_shfl[at + k] = a[k]; out_desc[at + k] = b[k]; }
+}
+extern "C" int gadapt_debug_wave_sum_desc(const float* in, float* out_shfl, float* out_desc, int n_waves, int n_values, void* stream) {
+    if (!in || !out_shfl || !out_desc || n_waves < 1 || n_waves > 16) return fail(GADAPT_E_BADARG, "wave_sum_desc: null pointer, or not 1..16 waves");
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 block(64 * n_waves);
+    if (n_values == 1) hipLaunchKernelGGL(wave_sum_desc_debug_kernel<1>, dim3(1), block, 0, st, in, out_shfl, out_desc);
+    else if (n_values == 20) hipLaunchKernelGGL(wave_sum_desc_debug_kernel<20>, dim3(1), block, 0, st, in, out_shfl, out_desc);
+    else if (n_values == 22) hipLaunchKernelGGL(wave_sum_desc_debug_kernel<22>, dim3(1), block, 0, st, in, out_shfl, out_desc);
+    else return fail(GADAPT_E_BADARG, "wave_sum_desc: built for 1, 20 and 22 values per lane");
+    return check_launch("wave_sum_desc_debug_kernel");
+}
+
 extern "C" int gadapt_layer_forward(const gadapt_graph* g, const float* x_in, float* x_out, const float* a, const float* p0,
                                     const float* layer_params, float* alpha_out, int residual_only, int c, void* stream) {
     if (int rc = check_graph(g, c)) return rc;

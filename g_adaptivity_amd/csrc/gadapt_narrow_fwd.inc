@@ -564,13 +564,10 @@ __global__ __launch_bounds__(NRB_NT) void fwd_narrow_block_kernel(BlockArgs q) {
                     float part[20];
                     narrow_top_target(part, g4, own, xv, w, deg, dt, sc, a4, tp, i < N, i, q.edge_out, q.dxd);
                     const int ob = gadapt_block_owned_block(margin, wave);
-                    // the wave sum of bwd_target_compact_body, butterfly 32, 16, .., 1 - the same additions, stage by stage over the 20
-                    // independent values (entry by entry with the store in between, as that body has it, every exchange is waited
-                    // for on its own: 120 dependent LDS-crossbar trips per wave instead of 6)
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-                        for (int e = 0; e < 20; ++e) part[e] += __shfl_xor(part[e], off, 64);
+                    // the wave sum of bwd_target_compact_body, butterfly 32, 16, .., 1 - the same additions on DPP / lane swaps, stage by
+                    // stage over the 20 independent values (wave_sum_desc; every lane of the owned block's wave is here: halo waves left
+                    // at the `continue` above as a whole, lanes past N carry zeros)
+                    wave_sum_desc(part);
                     if (lane == 0) {
 #pragma unroll
                         for (int e = 0; e < 20; ++e) tred[ob][e] = part[e];

@@ -546,6 +546,11 @@ int gadapt_debug_set_narrow_backward_fused(int on);
 int gadapt_debug_set_narrow_top_in_forward(int on);
 /* Diagnostic: runtime-reported workgroups per CU of {forward, backward target, backward source}. */
 int gadapt_debug_occupancy(int c, int* out3);
+/* Diagnostic: the wave sum of the slab partials (wave_sum_desc: DPP and lane-swap steps) beside the xor butterfly 32, 16, .., 1 on
+ * __shfl_xor that defines it.  in [n_waves][64][n_values] (device): one workgroup of n_waves waves (1..16), lane l of wave w holds
+ * in[w][l][0..n_values); out_shfl / out_desc, same shape: both sums as that lane sees them.  n_values = 1, 20 or 22.  The two must
+ * agree bit for bit in every lane (tests/test_gpu_wave_sum_desc.py). */
+int gadapt_debug_wave_sum_desc(const float* in, float* out_shfl, float* out_desc, int n_waves, int n_values, void* stream);
 
 #ifdef __cplusplus
 }
