@@ -1,7 +1,7 @@
 # Builds the C-ABI shared library of the hot path for gfx950 (MI355X), in-tree.
 #   make -j8        -> g_adaptivity_amd/libgadapt_hip.so   (one object per kernel family: csrc/gadapt_internal.h)
 #                      g_adaptivity_amd/libgadapt_fem.so   (the FEM tails: 2-D pde_loss and 1-D Burgers / Poisson; fem_csrc/, include/gadapt_fem.h)
-#                      g_adaptivity_amd/libgadapt_mesh.so  (batched MMPDE5 target meshes; mesh_csrc/, include/gadapt_mesh.h)
+#                      g_adaptivity_amd/libgadapt_mesh.so  (batched MMPDE5 and Monge-Ampere target meshes; mesh_csrc/, include/gadapt_mesh.h)
 #   make resources  -> per-kernel VGPR/SGPR/LDS/occupancy report
 #   make DEV_C=64   -> development build: tiled kernels for one hidden size only (never shipped)
 HIPCC      ?= /opt/rocm/bin/hipcc
@@ -51,10 +51,16 @@ $(OBJDIR)/fem_topology.o: $(FEM_CSRC)/fem_topology.cpp include/gadapt_fem.h
 
 # the MMPDE5 target-mesh generator (include/gadapt_mesh.h): its own library, without FMA contraction like the FEM tails
 # (the stopping step of the fp32 iteration follows the rounding of its increments)
-$(MESH_LIB): $(OBJDIR)/mmpde5_kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $<
+MESH_OBJS  := $(OBJDIR)/mmpde5_kernels.o $(OBJDIR)/ma_kernels.o
+$(MESH_LIB): $(MESH_OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(MESH_OBJS)
 
-$(OBJDIR)/mmpde5_kernels.o: $(MESH_CSRC)/mmpde5_kernels.hip include/gadapt_mesh.h
+$(OBJDIR)/mmpde5_kernels.o: $(MESH_CSRC)/mmpde5_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+
+# the Monge-Ampere target meshes (2-D): the same library and the same flags
+$(OBJDIR)/ma_kernels.o: $(MESH_CSRC)/ma_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 

@@ -9,6 +9,7 @@ error reduction of the last two, with the model's time per sample.
     python examples/evaluate_poisson.py --mesh 64 --band window  # beyond 26 x 26: the windowed band solve
     python examples/evaluate_poisson.py --mesh 64 --band window --mmpde5_route strided --mmpde5_cfl 0.5 --mmpde5_max_steps 40000
                                                                  # ... with real MMPDE5 targets beyond 32 x 32
+    python examples/evaluate_poisson.py --target monge_ampere    # the MA columns on Monge-Ampere meshes (2-D, at most 32 x 32)
 """
 import argparse
 import os
@@ -57,6 +58,9 @@ if __name__ == '__main__':
                     help="MMPDE5 targets: 'lane' stops at 32 a side in 2-D (beyond it the noise stand-in is used), 'strided' at 81")
     ap.add_argument('--mmpde5_cfl', type=float, default=None, help='RK4 step of MMPDE5 is cfl / N^3 (default: the reference 0.05)')
     ap.add_argument('--mmpde5_max_steps', type=int, default=None, help='step cap of MMPDE5 (default: the reference 10000)')
+    ap.add_argument('--target', choices=('mmpde5', 'monge_ampere'), default='mmpde5',
+                    help="the classical target behind the MA columns: MMPDE5 (default), or the finite-difference Monge-Ampere solve "
+                         "that stands for the reference's default 2-D target (2-D, --mesh <= 32)")
     ap.add_argument('--num_train', type=int, default=32)
     ap.add_argument('--num_test', type=int, default=16)
     ap.add_argument('--epochs', type=int, default=20)
@@ -73,6 +77,8 @@ if __name__ == '__main__':
     solver = {'route': opt['mmpde5_route']}
     solver.update({k: v for k, v in (('cfl', a.mmpde5_cfl), ('max_steps', a.mmpde5_max_steps)) if v is not None})
     target_params = {'solver': solver} if target == 'mmpde5' else None
+    if a.target == 'monge_ampere':                 # the reference's own 2-D configuration: 2-D, at most 32 a side, its own defaults
+        target, target_params = 'monge_ampere', None
     test = MeshDataset(dims, a.num_test, seed=1, target=target, target_params=target_params)
     torch.manual_seed(0)
     model = GNN(test, opt).to(opt['device'])

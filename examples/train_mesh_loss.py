@@ -86,9 +86,10 @@ if __name__ == '__main__':
     ap.add_argument('--cpu_loader', action='store_true', help='collate on the host every step, as the reference does')
     ap.add_argument('--torch_loss', action='store_true')
     ap.add_argument('--eager', action='store_true', help='eager launches instead of the captured training step')
-    ap.add_argument('--target', choices=('noise', 'mmpde5'), default='noise',
-                    help="x_phys of the samples: the noise stand-in, or the reference's MMPDE5 meshes (one batched GPU call; --mesh <= 32, "
-                         "or <= 81 with --mmpde5_route strided)")
+    ap.add_argument('--target', choices=('noise', 'mmpde5', 'monge_ampere'), default='noise',
+                    help="x_phys of the samples: the noise stand-in, the reference's MMPDE5 meshes (one batched GPU call; --mesh <= 32, "
+                         "or <= 81 with --mmpde5_route strided), or Monge-Ampere meshes, the reference's default 2-D target "
+                         "(finite differences, one batched GPU call; --mesh <= 32)")
     ap.add_argument('--mmpde5_route', choices=('lane', 'strided'), default='lane', help="route of the MMPDE5 generator (--target mmpde5)")
     ap.add_argument('--mmpde5_cfl', type=float, default=None, help='RK4 step of MMPDE5 is cfl / N^3 (default: the reference 0.05)')
     ap.add_argument('--mmpde5_max_steps', type=int, default=None, help='step cap of MMPDE5 (default: the reference 10000)')

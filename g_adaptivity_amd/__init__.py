@@ -7,6 +7,7 @@ Public surface mirrors the reference modules:
     from g_adaptivity_amd import gradient_meshpoints_1D, burgers_1d, fem_poisson_1d   # the 1-D modular loss (Burgers, Poisson)
     from g_adaptivity_amd import gradient_meshpoints_2D    # the 2-D modular loss (Poisson)
     from g_adaptivity_amd import MMPDE5_1d, MMPDE5_2d, mmpde5_batch   # the classical MMPDE5 target meshes, batched
+    from g_adaptivity_amd import MA2d, deform_mesh_ma2d, ma_batch   # Monge-Ampere target meshes (2-D), finite differences, batched
     from g_adaptivity_amd import evaluate_model_fine, eval_grid_MMPDE_MA, poisson_eval_errors   # the Poisson error-reduction tables
     from g_adaptivity_amd import evaluate_model_fine_burgers, evaluate_model_fine_burgers_time_step   # the Burgers one-step and rollout tables
     from g_adaptivity_amd import cubic_spline_1d            # batched not-a-knot cubic splines (scipy's UnivariateSpline(s=0))
@@ -31,6 +32,7 @@ from .mesh_graph import (DeviceMeshLoader, MeshData, MeshDataset, MeshLoader, Mi
                          square_mesh, synthetic_batch)
 from .mmpde5 import (MMPDE5_1d, MMPDE5_1d_burgers, MMPDE5_2d, deform_mesh_mmpde1d, deform_mesh_mmpde2d, mmpde5_batch, monitor_1d,
                      monitor_2d)
+from .monge_ampere import MA2d, MAResult, attach_ma_targets, deform_mesh_ma2d, ma_batch, monitor_ma
 from .params import hot_path_opt, model_defaults
 from .spline import cubic_spline_1d
 from .training import GraphedTrainStep
@@ -42,7 +44,7 @@ __all__ = ['GNN', 'MLP', 'get_conv', 'build_conv_list', 'get_enc', 'get_dec', 'g
            'fem_poisson', 'torch_FEM_2D', 'burgers_1d', 'fem_poisson_1d', 'gradient_meshpoints_1D', 'torch_FEM_Burgers_1D',
            'get_Burgers_initial_coeffs', 'fn_expansion', 'torch_FEM_1D', 'gradient_meshpoints_2D',
            'mmpde5_batch', 'monitor_1d', 'monitor_2d', 'MMPDE5_1d', 'MMPDE5_2d', 'MMPDE5_1d_burgers', 'deform_mesh_mmpde1d',
-           'deform_mesh_mmpde2d', 'poisson_eval_errors', 'eval_grid_MMPDE_MA', 'evaluate_model_fine', 'evaluate_error_np',
+           'deform_mesh_mmpde2d', 'ma_batch', 'monitor_ma', 'MA2d', 'MAResult', 'deform_mesh_ma2d', 'attach_ma_targets', 'poisson_eval_errors', 'eval_grid_MMPDE_MA', 'evaluate_model_fine', 'evaluate_error_np',
            'evaluate_error_np_2d', 'calculate_error_reduction', 'cubic_spline_1d', 'evaluate_model_fine_burgers',
            'evaluate_model_fine_burgers_time_step', 'burgers_project', 'backFEM_2D', 'backFEM_1D', 'Fixed_Mesh_2D', 'Fixed_Mesh_1D',
            'get_model', 'mesh_descent_2d', 'mesh_descent_1d', 'DescentResult', 'model_defaults']

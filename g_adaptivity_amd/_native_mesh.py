@@ -1,4 +1,4 @@
-"""ctypes binding of `libgadapt_mesh.so`, the batched MMPDE5 target-mesh generator (C-ABI in include/gadapt_mesh.h).
+"""ctypes binding of `libgadapt_mesh.so`, the batched MMPDE5 and Monge-Ampere target-mesh generators (C-ABI in include/gadapt_mesh.h).
 
 There is no CPU fallback: if the library is missing, or a call fails, this raises `NativeError`.
 """
@@ -19,6 +19,10 @@ MAX_STEPS = 10000000                                   # GADAPT_MMPDE5_MAX_STEPS
 DESC = 4                                               # GADAPT_MMPDE5_DESC: dim, N, node offset, cell offset
 E_SIZE = -3                                            # GADAPT_MESH_E_SIZE
 CONVERGED, CAP, STIFF = 0, 1, 2                        # GADAPT_MMPDE5_CONVERGED / _CAP / _STIFF
+MA_MAX_SIDE = 32                                       # gadapt_ma_max_side(): Monge-Ampere meshes are 2-D, N <= 32 a side
+MA_MAX_GAUSS = 8                                       # gadapt_ma_max_gauss()
+MA_DESC = 4                                            # GADAPT_MA_DESC: N, node offset, Gaussian offset, Gaussian count
+MA_CONVERGED, MA_CAP, MA_NONCONVEX = 0, 1, 2           # GADAPT_MA_CONVERGED / _CAP / _NONCONVEX
 
 _P, _I, _L, _D = C.c_void_p, C.c_int, C.c_int64, C.c_double
 
@@ -34,6 +38,10 @@ PROTOTYPES = {
     'gadapt_mmpde5_strided_max_side': (_I, []),
     'gadapt_mmpde5_strided_lds_bytes': (_L, [_I]),
     'gadapt_mmpde5_batch_strided': (_I, [_I] + [_P] * 7 + [_D, _D, _I] + [_P] * 6),
+    'gadapt_ma_max_side': (_I, []),
+    'gadapt_ma_max_gauss': (_I, []),
+    'gadapt_ma_lds_bytes': (_L, [_I]),
+    'gadapt_ma_batch': (_I, [_I] + [_P] * 4 + [_D, _D, _I] + [_P] * 6),
 }
 
 _lib = None
@@ -50,10 +58,15 @@ def lib():
         if handle.gadapt_mesh_abi_version() != ABI_VERSION:
             raise NativeError(f"{LIB_PATH}: ABI {handle.gadapt_mesh_abi_version()}, expected {ABI_VERSION}; rebuild it with `make`")
         for name, (res, args) in PROTOTYPES.items():
-            fn = getattr(handle, name)
+            fn = getattr(handle, name, None)
+            if fn is None:                                             # same ABI number, older build: the ABI grows by addition
+                raise NativeError(f"{LIB_PATH} lacks {name}: a stale build; rebuild it with `make`")
             fn.restype, fn.argtypes = res, args
         if handle.gadapt_mmpde5_strided_max_side() != STRIDED_MAX_SIDE:
             raise NativeError(f"{LIB_PATH}: strided route up to {handle.gadapt_mmpde5_strided_max_side()} a side, expected {STRIDED_MAX_SIDE}")
+        if (handle.gadapt_ma_max_side(), handle.gadapt_ma_max_gauss()) != (MA_MAX_SIDE, MA_MAX_GAUSS):
+            raise NativeError(f"{LIB_PATH}: Monge-Ampere limits {handle.gadapt_ma_max_side()} a side / {handle.gadapt_ma_max_gauss()} "
+                              f"Gaussians, expected {MA_MAX_SIDE} / {MA_MAX_GAUSS}; rebuild it with `make`")
         _lib = handle
     return _lib
 

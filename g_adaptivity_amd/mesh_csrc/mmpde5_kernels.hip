@@ -35,17 +35,13 @@
 #include <string.h>
 
 #include "gadapt_mesh.h"
+#include "mesh_common.h"
 
 #pragma clang fp contract(off)
 
+using namespace gadapt_mesh_shared;                      // g_err, mesh_fail, dpp_move, wave_sum
+
 namespace {
-
-thread_local char g_err[256] = "";
-
-int mesh_fail(int code, const char* msg) {
-    snprintf(g_err, sizeof g_err, "%s", msg);
-    return code;
-}
 
 constexpr int MAX_NODES = GADAPT_MMPDE5_MAX_NODES;
 constexpr int MAX_WAVES = MAX_NODES / 64;
@@ -55,25 +51,6 @@ __host__ __device__ inline int mmpde5_threads(int nodes) { return (nodes + 63) &
 
 // red[2][MAX_WAVES] in front, then the two images of (X, Y), each MAX of the batch's nodes long
 __host__ __device__ inline int64_t mmpde5_lds_floats(int nodes) { return 2 * MAX_WAVES + 4 * (int64_t)nodes; }
-
-template <int CTRL>
-__device__ inline float dpp_move(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-
-// Sum over the 64 lanes, the same bits in every lane: a butterfly inside each row of 16 (quad_perm [1,0,3,2], [2,3,0,1],
-// row_half_mirror, row_mirror: each lane adds its partner's value, and a + b == b + a), then the four rows in a fixed order.
-__device__ inline float wave_sum(float v) {
-    v = v + dpp_move<0xB1>(v);
-    v = v + dpp_move<0x4E>(v);
-    v = v + dpp_move<0x141>(v);
-    v = v + dpp_move<0x140>(v);
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return (r0 + r1) + (r2 + r3);
-}
 
 struct Params {
     float h, h6, tol, stiff;

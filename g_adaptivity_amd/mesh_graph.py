@@ -289,7 +289,10 @@ class MeshDataset:
         reference's classical target (`src/data.py:206-212`), the MMPDE5 mesh of the sample's own Gaussians, all samples in one
         batched GPU call at construction (`mmpde5.attach_mmpde5_targets`; `ma_its` per sample).  `target_params`: `mon_power` /
         `mon_reg` of the monitor and keyword arguments of `mmpde5_batch` under the key 'solver'.  2-D meshes of 33..81 a side
-        need `target_params={'solver': {'route': 'strided', ...}}`, and want `cfl` or `max_steps` raised there (`mmpde5.py`)."""
+        need `target_params={'solver': {'route': 'strided', ...}}`, and want `cfl` or `max_steps` raised there (`mmpde5.py`).
+        'monge_ampere': the reference's default 2-D target (`mesh_type = 'ma'`), a finite-difference Monge-Ampere solve of the
+        sample's own Gaussians (`monge_ampere.attach_ma_targets`; 2-D only, N <= 32; `target_params`: `mon_reg` / `mon_power` and
+        keyword arguments of `ma_batch` under 'solver')."""
         self.mesh_dims = list(mesh_dims)
         self.dim = len(self.mesh_dims)
         if self.dim == 1:
@@ -351,15 +354,21 @@ class MixedMeshDataset(MeshDataset):
 
 
 def _set_targets(ds, target: str, target_params: Optional[dict]):
-    """`target='mmpde5'`: every sample's `x_phys` from one batched MMPDE5 call (mixed mesh sizes share the launch)."""
+    """`target='mmpde5'` / `'monge_ampere'`: every sample's `x_phys` from one batched call of that generator (mixed mesh sizes
+    share the launch)."""
     if target == 'noise':
         return
-    if target != 'mmpde5':
-        raise ValueError(f"target = {target!r}; 'noise' or 'mmpde5'")
-    from .mmpde5 import attach_mmpde5_targets
+    if target not in ('mmpde5', 'monge_ampere'):
+        hint = " (the reference's mesh_type 'ma' is target='monge_ampere' here)" if target == 'ma' else ''
+        raise ValueError(f"target = {target!r}; 'noise', 'mmpde5' or 'monge_ampere'{hint}")
     params = dict(target_params or {})
     solver = params.pop('solver', {})
-    ds.target_result = attach_mmpde5_targets(ds.samples, params, **solver)
+    if target == 'mmpde5':
+        from .mmpde5 import attach_mmpde5_targets
+        ds.target_result = attach_mmpde5_targets(ds.samples, params, **solver)
+    else:
+        from .monge_ampere import attach_ma_targets
+        ds.target_result = attach_ma_targets(ds.samples, params, **solver)
 
 
 def _add_pde_loss_fields(ds, eval_quad_points: int):

@@ -288,15 +288,27 @@ def deform_mesh_mmpde2d(x_comp: torch.Tensor, n: int, m: int, pde_params, **solv
     `tol` go to `mmpde5_batch`, as in `MMPDE5_2d`."""
     if n != m:
         raise ValueError(f"deform_mesh_mmpde2d: {n} x {m} grid; square grids only")
-    lin = torch.linspace(0, 1, n, device=x_comp.device)
-    gx, gy = torch.meshgrid(lin, lin, indexing='ij')
+    gx, gy = unit_grid(n, x_comp.device)
     X, Y, j, build_time = MMPDE5_2d(gx, gy, n, pde_params, **solver)
+    return write_back_to_nodes(x_comp, gx, gy, X, Y), j + 1, build_time
+
+
+def unit_grid(n: int, device=None):
+    """(gx, gy) of the uniform n x n grid on the unit square, `indexing='ij'`."""
+    lin = torch.linspace(0, 1, n, device=device)
+    return torch.meshgrid(lin, lin, indexing='ij')
+
+
+def write_back_to_nodes(x_comp: torch.Tensor, gx: torch.Tensor, gy: torch.Tensor, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    """The write-back of `src/data.py:404-416`: the moved grid point (X, Y)[i, j] goes to the node of `x_comp` [n*n, 2] that is
+    nearest to the grid point (gx, gy)[i, j] after `x_comp` is scaled to the unit square.  Shared by `deform_mesh_mmpde2d` and
+    `monge_ampere.MA2d`."""
     lo, hi = x_comp.min(0).values, x_comp.max(0).values
     scaled = ((x_comp - lo) / (hi - lo)).to(torch.float32)
     node = torch.cdist(torch.stack([gx.reshape(-1), gy.reshape(-1)], 1), scaled).argmin(1)
     x_phys = torch.zeros_like(x_comp)
     x_phys[node] = torch.stack([X.reshape(-1), Y.reshape(-1)], 1).to(x_comp.dtype)
-    return x_phys, j + 1, build_time
+    return x_phys
 
 
 # --------------------------------------------------------------------------

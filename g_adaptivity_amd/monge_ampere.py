@@ -1,0 +1,243 @@
+"""Monge-Ampere target meshes on the GPU: the reference's default 2-D target (`classical_meshing/ma_mesh_2d.py:163-295`,
+`src/data.py:208-210`, `mesh_type = 'ma'`), batched.
+
+The reference hands the problem to Firedrake and `movement.MongeAmpereMover`.  Neither runs here, so its finite-element
+discretisation is not reproduced and PARITY WITH `movement` IS NOT PINNED.  What it solves is: a convex potential phi on the
+computational square with
+
+    x = xi + grad phi,    m(x) det(I + H phi) = theta,    grad phi . n = 0,
+
+and this module relaxes that equation by finite differences in pseudo-time (`include/gadapt_mesh.h` has the iteration operation
+for operation): phi += cfl h^2 min(1, lambda_min) (r - mean r) with r = log(m det), until max |r - mean r| <= tol.  The
+monitor is evaluated at the moving coordinates, from the sample's Gaussians, inside the kernel.  Its yardsticks are its own
+fp64 restatement (`tests/ma_restatement.py`) and the equidistribution it has to achieve, not the reference's meshes.
+
+`ma_batch` is the batched form: one launch of `libgadapt_mesh.so`, one workgroup per mesh, each to its own stopping step.
+`MA2d` and `deform_mesh_ma2d` keep the reference's names, argument lists and return tuples.  2-D only (the reference has no
+1-D MA), 3 <= N <= 32 a side, at most 8 Gaussians; anything else raises `ValueError`.  The iteration runs on the GPU only:
+`NativeError` without one.  The `M2N` monitors of `MA2d` are not built: they need a maximum over the moving nodes at every
+step and FEM solves.  Sides above 32 are not built either: the fp32 residual floor reaches `tol` near 64 x 64.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import time
+import warnings
+from collections import namedtuple
+from typing import Optional, Sequence
+
+import torch
+
+from . import _native_mesh
+from ._native import NativeError, current_stream
+from .mmpde5 import _gauss_dd, unit_grid, warn_unconverged, write_back_to_nodes
+
+CONVERGED, CAP, NONCONVEX = _native_mesh.MA_CONVERGED, _native_mesh.MA_CAP, _native_mesh.MA_NONCONVEX
+STATUS_NAMES = {CONVERGED: 'converged', CAP: 'cap reached', NONCONVEX: 'convexity lost'}
+MAX_SIDE, MAX_GAUSS = _native_mesh.MA_MAX_SIDE, _native_mesh.MA_MAX_GAUSS
+
+MAResult = namedtuple('MAResult', 'coords steps residual status')
+
+
+def monitor_constants(params):
+    """(mon_reg, mon_power) of `MA2d`'s monitor (`ma_mesh_2d.py:172-176`): with 'mon_power' the pair given ('mon_reg' is then
+    required, as in the reference, where its absence is a KeyError), else (1, 0.2)."""
+    if 'mon_power' in params:
+        if 'mon_reg' not in params:
+            raise ValueError("the Monge-Ampere monitor reads 'mon_reg' whenever 'mon_power' is given: pass both or neither")
+        return float(params['mon_reg']), float(params['mon_power'])
+    return 1.0, 0.2
+
+
+def monitor_ma(x: torch.Tensor, y: torch.Tensor, params) -> torch.Tensor:
+    """`MA2d`'s monitor: (mon_reg + sqrt(u_xx^2 + u_yy^2))^mon_power, or (1 + sqrt(...))^0.2 without 'mon_power', where u_xx and
+    u_yy are the SIGNED sums over the Gaussians (`diag_hessian_ma`), not `monitor_2d`'s per-Gaussian absolute values."""
+    reg, power = monitor_constants(params)
+    uxx, uyy = torch.zeros_like(x), torch.zeros_like(x)
+    for c, s in zip(params['centers'], params['scales']):
+        c0, c1, s0, s1 = float(c[0]), float(c[1]), float(s[0]), float(s[1])
+        g = torch.exp(-(x - c0) ** 2 / s0 ** 2 - (y - c1) ** 2 / s1 ** 2)
+        uxx = uxx + _gauss_dd(x, c0, s0) * g
+        uyy = uyy + _gauss_dd(y, c1, s1) * g
+    return (reg + torch.sqrt(uxx ** 2 + uyy ** 2)) ** power
+
+
+def _side(b: int, size) -> int:
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2 or int(size[0]) != int(size[1]):
+            raise ValueError(f"mesh {b}: size {tuple(size)}; square grids only")
+        size = size[0]
+    n = int(size)
+    if n < 3:
+        raise ValueError(f"mesh {b}: N = {n}; at least 3 nodes a side")
+    if n > MAX_SIDE:
+        raise ValueError(f"mesh {b}: N = {n}; Monge-Ampere meshes go up to {MAX_SIDE} a side (one lane per node, one workgroup per mesh)")
+    return n
+
+
+def _gaussians(b: int, params):
+    cs, ss = list(params.get('centers', [])), list(params.get('scales', []))
+    if len(cs) != len(ss):
+        raise ValueError(f"mesh {b}: {len(cs)} centres and {len(ss)} scales")
+    if len(cs) > MAX_GAUSS:
+        raise ValueError(f"mesh {b}: {len(cs)} Gaussians; at most {MAX_GAUSS}")
+    rows = []
+    for c, s in zip(cs, ss):
+        if len(c) != 2 or len(s) != 2:
+            raise ValueError(f"mesh {b}: a Gaussian of a 2-D mesh has two centre coordinates and two scales")
+        rows.append([float(c[0]), float(c[1]), float(s[0]), float(s[1])])
+    return rows
+
+
+def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000, device=None):
+    """The host side of `ma_batch`: checks, the batch's descriptors and Gaussians on the GPU, the argument list.  Returns
+    (launch, collect): `launch()` issues the one kernel (it may be issued again), `collect()` gives the MAResult."""
+    if len(sizes) == 0 or len(sizes) != len(pde_params):
+        raise ValueError(f"{len(sizes)} mesh sizes and {len(pde_params)} parameter sets")
+    if not (0 <= int(max_steps) <= _native_mesh.MAX_STEPS):
+        raise ValueError(f"max_steps = {max_steps}; 0..{_native_mesh.MAX_STEPS} (the loop has to end)")
+    if not (0 < cfl < float('inf') and 0 <= tol < float('inf')):
+        raise ValueError(f"cfl = {cfl}, tol = {tol}; cfl > 0 and tol >= 0 expected")
+    ns = [_side(b, s) for b, s in enumerate(sizes)]
+    gauss = [_gaussians(b, p) for b, p in enumerate(pde_params)]
+    mon = [monitor_constants(p) for p in pde_params]
+    B = len(ns)
+
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    if dev.type != 'cuda' or not torch.cuda.is_available():
+        raise NativeError("Monge-Ampere meshes are built on the GPU only (libgadapt_mesh.so): no CUDA/HIP device is visible; "
+                          "there is no CPU fallback")
+
+    desc, noff, goff = [], 0, 0
+    for n, g in zip(ns, gauss):
+        desc += [n, noff, goff, len(g)]
+        noff, goff = noff + n * n, goff + len(g)
+    if noff >= 2 ** 31:
+        raise ValueError("more than 2^31 nodes in one batch")
+    desc_host = (C.c_int32 * len(desc))(*desc)
+    desc_dev = torch.tensor(desc, dtype=torch.int32).to(dev)
+    rows = [r for g in gauss for r in g] or [[0.0] * 4]                  # never an empty allocation behind the pointer
+    gauss_dev = torch.tensor(rows, dtype=torch.float32).to(dev)
+    mon_dev = torch.tensor(mon, dtype=torch.float32).to(dev)
+    x = torch.empty(noff, dtype=torch.float32, device=dev)
+    y = torch.empty_like(x)
+    steps = torch.empty(B, dtype=torch.int32, device=dev)
+    residual = torch.empty(B, dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    args = (B, C.cast(desc_host, C.c_void_p), desc_dev.data_ptr(), gauss_dev.data_ptr(), mon_dev.data_ptr(), float(cfl), float(tol),
+            int(max_steps), x.data_ptr(), y.data_ptr(), steps.data_ptr(), residual.data_ptr(), status.data_ptr())
+    keep = (desc_host, desc_dev, gauss_dev, mon_dev)                     # what the argument list points into
+
+    def launch(_keep=keep):                                              # the closure keeps the inputs alive
+        with torch.cuda.device(dev):
+            _native_mesh.check(_native_mesh.lib().gadapt_ma_batch(*args, current_stream(dev)), 'gadapt_ma_batch')
+
+    def collect():
+        out, o = [], 0
+        for n in ns:
+            out.append(torch.stack([x[o:o + n * n].view(n, n), y[o:o + n * n].view(n, n)]))
+            o += n * n
+        return MAResult(out, steps, residual, status)
+
+    return launch, collect
+
+
+def ma_batch(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000,
+             device=None) -> MAResult:
+    """Monge-Ampere meshes of many samples, mixed sizes in one launch.
+
+    sizes[b]       N (or a pair (N, N)): the mesh is the N x N grid on the unit square, node (i, j) of meshgrid(..., indexing='ij')
+    pde_params[b]  'centers' and 'scales' of the sample's Gaussians (at most 8; none gives a constant monitor and the grid itself),
+                   optionally 'mon_reg' and 'mon_power' (`monitor_ma`)
+    cfl            the pseudo-time step is cfl h^2 min(1, lambda_min); 0.2 converged in every case tried up to 32 x 32, 0.5
+                   oscillates into the cap, 1 loses convexity at once
+    tol            stop when max |r - mean r| <= tol; 0 runs exactly `max_steps` updates
+    max_steps      the cap (32 x 32 needed up to 8 200 residual evaluations)
+
+    Returns MAResult(coords, steps, residual, status) on the GPU: coords[b] is [2, N, N], and per-mesh tensors of the number of
+    updates (int32), the last residual and CONVERGED / CAP / NONCONVEX.  A mesh's result does not depend on its batch.
+    """
+    launch, collect = _prepare(sizes, pde_params, cfl=cfl, tol=tol, max_steps=max_steps, device=device)
+    launch()
+    return collect()
+
+
+def warn_status(status, what: str = 'Monge-Ampere'):
+    """NONCONVEX and CAP as warnings (the reference swallows the mover's exception and prints nothing)."""
+    st = status.tolist() if torch.is_tensor(status) else list(status)
+    if NONCONVEX in st:
+        warnings.warn(f"{what} lost convexity for {st.count(NONCONVEX)} of {len(st)} meshes (min eigenvalue of I + H phi <= 0, or a "
+                      "residual that is not finite), please choose a smaller cfl", RuntimeWarning, stacklevel=3)
+    warn_unconverged([_native_mesh.CAP if s == CAP else _native_mesh.CONVERGED for s in st], what)
+
+
+def _solver_kwargs(solver: dict) -> dict:
+    extra = set(solver) - {'cfl', 'max_steps', 'tol', 'device'}
+    if extra:
+        raise TypeError(f"unexpected keyword arguments {sorted(extra)}; cfl, tol, max_steps and device go to ma_batch")
+    return solver
+
+
+# --------------------------------------------------------------------------
+# the reference's entry points
+# --------------------------------------------------------------------------
+
+def MA2d(x_comp: torch.Tensor, N: int, params, **solver):
+    """`MA2d(x_comp, N, params)` -> (x_phys, j, build_time): the Monge-Ampere mesh of the N x N grid written back in the node
+    order of `x_comp` [N*N, 2] (`mmpde5.write_back_to_nodes`), j the number of updates.  Lost convexity warns and gives zeros
+    and j = 0, as the reference's `except` branch does; a reached cap warns.  Keyword-only `cfl`, `tol`, `max_steps` go to `ma_batch`."""
+    _solver_kwargs(solver)
+    if x_comp.dim() != 2 or tuple(x_comp.shape) != (N * N, 2):
+        raise ValueError(f"MA2d: x_comp of shape {tuple(x_comp.shape)}; [{N * N}, 2] expected (square grids only)")
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    t0 = time.time()
+    res = ma_batch([N], [params], **solver)
+    status = res.status.tolist()                           # waits for the device
+    build_time = time.time() - t0
+    warn_status(status)
+    if status[0] == NONCONVEX:
+        return torch.zeros_like(x_comp), 0, build_time
+    gx, gy = unit_grid(N, x_comp.device)
+    xy = res.coords[0].to(x_comp.device)
+    return write_back_to_nodes(x_comp, gx, gy, xy[0], xy[1]), int(res.steps[0]), build_time
+
+
+def deform_mesh_ma2d(x_comp: torch.Tensor, n: int, m: int, pde_params, **solver):
+    """`src/data.py` `deform_mesh_ma2d`: `MA2d` on the n x m grid -> (x_phys, j + 1, build_time), the count plus one "to account
+    for the initial mesh".  Square grids only."""
+    if n != m:
+        raise ValueError(f"deform_mesh_ma2d: {n} x {m} grid; square grids only")
+    x_phys, j, build_time = MA2d(x_comp, n, pde_params, **solver)
+    return x_phys, j + 1, build_time
+
+
+# --------------------------------------------------------------------------
+# dataset targets
+# --------------------------------------------------------------------------
+
+def attach_ma_targets(samples, monitor_params: Optional[dict] = None, **solver):
+    """`x_phys` of every sample := its Monge-Ampere mesh, all samples in ONE batched call; `ma_its` = updates + 1 and
+    `build_time` (the batched call's wall time shared out evenly) as `attach_mmpde5_targets` sets them.  The monitor of a
+    sample is `monitor_ma` of its own `pde_params` with `monitor_params` (`mon_reg`, `mon_power`) added.  The samples' meshes
+    must be square grids in grid order (`square_mesh`).  A sample that lost convexity gets zeros and `ma_its` = 1."""
+    _solver_kwargs(solver)
+    sizes, params = [], []
+    for d in samples:
+        if d.x_comp.dim() != 2 or d.x_comp.shape[1] != 2:
+            raise ValueError("Monge-Ampere targets are 2-D only (the reference has no 1-D MA): use target='mmpde5' for 1-D meshes")
+        n = int(round(d.x_comp.shape[0] ** 0.5))
+        if n * n != d.x_comp.shape[0]:
+            raise ValueError(f"{d.x_comp.shape[0]} nodes: not a square grid")
+        sizes.append(n)
+        params.append(dict(d.pde_params, **(monitor_params or {})))
+    t0 = time.time()
+    res = ma_batch(sizes, params, **solver)
+    steps, status = res.steps.tolist(), res.status.tolist()   # waits for the device: the batched call is done
+    build_time = (time.time() - t0) / max(len(samples), 1)
+    warn_status(status, 'Monge-Ampere (dataset targets)')
+    for d, xy, j, st in zip(samples, res.coords, steps, status):
+        x_phys = xy.reshape(2, -1).t().contiguous().to(device=d.x_comp.device, dtype=d.x_comp.dtype)
+        d.x_phys, d.ma_its = (torch.zeros_like(x_phys), 1) if st == NONCONVEX else (x_phys, j + 1)
+        d.build_time = build_time
+    return res

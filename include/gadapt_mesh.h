@@ -1,5 +1,6 @@
 /*
- * gadapt_mesh.h - C-ABI of the classical target-mesh generator: batched MMPDE5 (libgadapt_mesh.so).
+ * gadapt_mesh.h - C-ABI of the classical target-mesh generators: batched MMPDE5 and, further down, batched Monge-Ampere
+ * (libgadapt_mesh.so).
  *
  * The reference builds the target mesh `x_phys` of loss_type='mesh_loss' with the moving-mesh PDE "MMPDE5"
  * (classical_meshing/ma_mesh_1d.py:7-134, ma_mesh_2d.py:11-103, called from src/data.py:394-416): classical RK4 in
@@ -98,6 +99,57 @@ int64_t gadapt_mmpde5_strided_lds_bytes(int nodes);
 int gadapt_mmpde5_batch_strided(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* x0, const float* y0,
                                 const float* ms, const float* m2, const double* step, double tau, double tol, int max_steps,
                                 float* x, float* y, int32_t* steps, float* measure, int32_t* status, void* stream);
+
+/*
+ * Monge-Ampere target meshes (2-D, up to 32 x 32): the reference's default 2-D target (classical_meshing/ma_mesh_2d.py:163-295,
+ * src/data.py:208-210) solves, with Firedrake and `movement`, for a convex potential phi on the computational square with
+ *   x = xi + grad phi,   m(x) det(I + H phi) = theta,   grad phi . n = 0.
+ * Here the same equation is relaxed by finite differences in pseudo-time; parity with `movement` is not pinned.
+ *
+ * Per mesh b (`desc` is int32 [B, GADAPT_MA_DESC], fields GADAPT_MA_D_*): N x N nodes, node = i * N + j, xi_i = (float)i / (float)(N - 1).
+ * phi [N, N] is fp32, starts at 0 and is continued by even reflection at every edge (phi[-1, j] = phi[1, j], phi[N, j] = phi[N-2, j],
+ * likewise in j, a corner's diagonal neighbour in both).  With n1 = N - 1 (h = 1 / n1), per node, fp32 without FMA contraction:
+ *   px  = (phi[i+1,j] - phi[i-1,j]) * (n1 / 2)                        py likewise in j
+ *   a   = 1 + (phi[i+1,j] - 2 phi[i,j] + phi[i-1,j]) * n1^2           b likewise in j
+ *   c   = (phi[i+1,j+1] - phi[i+1,j-1] - phi[i-1,j+1] + phi[i-1,j-1]) * (n1^2 / 4)
+ *   x   = xi_i + px,  y = xi_j + py          (the reflection makes px exactly 0 at i = 0 and i = N - 1: boundary nodes keep
+ *                                             their normal coordinate bit for bit, corners do not move)
+ *   det = a b - c^2,  lambda = ((a + b) - sqrt((a - b)^2 + 4 c^2)) / 2
+ *   per Gaussian k (gauss[k] = c0, c1, s0, s1;  q0 = s0^2, q1 = s1^2;  A0 = 4 / q0^2, B0 = 2 / q0, A1, B1 likewise, once per mesh):
+ *       dx2 = (x - c0)^2,  dy2 = (y - c1)^2,  g = expf(-(dx2 / q0) - dy2 / q1)   with the quotients as products by 1 / q0, 1 / q1
+ *       u_xx += (A0 dx2 - B0) g,   u_yy += (A1 dy2 - B1) g
+ *   m   = powf(mon[b][0] + sqrtf(u_xx^2 + u_yy^2), mon[b][1])         ((mon_reg, mon_power); (1, 0.2) is the default monitor)
+ *   r   = logf(m det)
+ * Per step: rbar = (sum of w r) / n1^2 with w = 1 inside, 1/2 on an edge, 1/4 at a corner (the 64 lanes of a wave as in the
+ * MMPDE5 sum, then the waves in increasing order); res = max(max r - rbar, rbar - min r); lmin = min lambda;
+ *   if (!(lmin > 0) || res is not finite) stop, NONCONVEX;  else if (tol > 0 && res <= tol) stop, CONVERGED;
+ *   else if (steps == max_steps) stop, CAP;  else phi += (float)(cfl / n1^2) * min(1, lmin) * (r - rbar), ++steps.
+ * Outputs: x, y of the last evaluated phi, the number of updates, res, status.  A mesh without Gaussians has a constant
+ * monitor: 0 steps and the grid itself.  tol == 0 runs exactly max_steps updates; max_steps <= GADAPT_MMPDE5_MAX_STEPS.
+ * One workgroup per mesh, one lane per node; the arithmetic of a mesh depends on its own size only.
+ */
+#define GADAPT_MA_D_N         0
+#define GADAPT_MA_D_NODE_OFF  1
+#define GADAPT_MA_D_GAUSS_OFF 2
+#define GADAPT_MA_D_GAUSS_N   3
+#define GADAPT_MA_DESC        4
+
+#define GADAPT_MA_CONVERGED 0   /* res <= tol */
+#define GADAPT_MA_CAP       1   /* max_steps updates done with res > tol (always, when tol == 0) */
+#define GADAPT_MA_NONCONVEX 2   /* min lambda <= 0 or res not finite: the map stopped being a convex potential's gradient */
+
+int gadapt_ma_max_side(void);    /* 32 */
+int gadapt_ma_max_gauss(void);   /* 8 */
+/* Dynamic LDS of a launch whose largest mesh has `nodes` nodes (9..1024). */
+int64_t gadapt_ma_lds_bytes(int nodes);
+
+/* One launch, one workgroup per mesh.
+ *   in   desc_host / desc [B, 4] (the same values on the host and on the device), gauss [G_total, 4] and mon [B, 2]
+ *        (device, fp32), cfl > 0, tol >= 0, max_steps
+ *   out  x, y (device, fp32, [total nodes]), steps [B] int32, residual [B] fp32, status [B] int32
+ * GADAPT_MESH_E_SIZE for N > 32, more than 8 Gaussians or max_steps beyond the cap; neither allocates nor synchronises. */
+int gadapt_ma_batch(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* gauss, const float* mon, double cfl,
+                    double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
