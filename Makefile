@@ -69,7 +69,7 @@ $(LIB): $(OBJS)
 
 $(OBJDIR)/gadapt_kernels.o: $(CSRC)/gadapt_small.inc
 $(OBJDIR)/gadapt_tu_fwd.o: $(CSRC)/gadapt_fwd.inc $(CSRC)/gadapt_wide.inc $(CSRC)/gadapt_narrow_fwd.inc $(CSRC)/gadapt_narrow_node.inc
-$(OBJDIR)/gadapt_tu_bwd_target.o: $(CSRC)/gadapt_bwd_target.inc $(CSRC)/gadapt_narrow_bwd.inc
+$(OBJDIR)/gadapt_tu_bwd_target.o: $(CSRC)/gadapt_bwd_target.inc $(CSRC)/gadapt_narrow_bwd.inc $(CSRC)/gadapt_narrow_bwd_block.inc
 $(OBJDIR)/gadapt_tu_bwd_source.o: $(CSRC)/gadapt_bwd_source.inc
 $(OBJDIR)/gadapt_tu_smallmesh.o: $(CSRC)/gadapt_smallmesh.inc
 $(OBJDIR)/gadapt_tu_sparse.o: $(CSRC)/gadapt_sparse.inc

@@ -43,6 +43,10 @@ PROTOTYPES = {
     'gadapt_narrow_block_slab_plan_host': (_I, [_L, _I, _I, _L, _P]),
     'gadapt_narrow_block_owned_block_host': (_I, [_I, _I, _I]),
     'gadapt_narrow_block_register': (_I, [_G, _I]),
+    'gadapt_narrow_block_register_source': (_I, [_G, _I]),
+    'gadapt_narrow_bwd_block_range_host': (_I, [_L, _I, _I, _L, _I, _P, _P, _P]),
+    'gadapt_narrow_bwd_block_margin_host': (_I, [_I, _I]),
+    'gadapt_narrow_bwd_block_groups_host': (_I, [_I, _I]),
     'gadapt_narrow_block_halo': (_I, [_G, _I]),
     'gadapt_coeffs_forward': (_I, [_P, _P, _P, _P, _P, _I, _P]),
     'gadapt_coeffs_backward': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
@@ -79,6 +83,8 @@ PROTOTYPES = {
     'gadapt_step_tail_narrow': (_I, [_P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _P, _P, _I, _P, _L, _I, _P]),
     'gadapt_block_forward_loss_narrow_top': (_I, [_G, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     'gadapt_block_backward_narrow_packed_below_top': (_I, [_G, _P, _I, _P, _P, _I, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    # ... (the same arguments), top_done, block_ran
+    'gadapt_block_backward_narrow_packed_block': (_I, [_G, _P, _I, _P, _P, _I, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P]),
     'gadapt_small_forward_lds_bytes': (_L, [_I, _I, _I]),
     'gadapt_small_forward': (_I, [_G, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _L, _L, _P, _I, _P, _I, _P, _P, _I, _P]),
     'gadapt_small_forward_loss': (_I, [_G, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _L, _L, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P]),
@@ -104,6 +110,7 @@ PROTOTYPES = {
     'gadapt_debug_set_narrow_forward': (_I, [_I]),
     'gadapt_debug_set_narrow_backward_fused': (_I, [_I]),
     'gadapt_debug_set_narrow_top_in_forward': (_I, [_I]),
+    'gadapt_debug_set_narrow_backward_block': (_I, [_I]),
     'gadapt_debug_occupancy': (_I, [_I, C.POINTER(C.c_int)]),
     'gadapt_debug_wave_sum_desc': (_I, [_P, _P, _P, _I, _I, _P]),
 }

@@ -140,3 +140,26 @@ extern "C" int gadapt_narrow_block_owned_block_host(int halo, int n_layers, int 
     if ((halo != 32 && halo != 64) || n_layers < 1 || n_layers > GADAPT_NARROW_BLOCK_LAYERS || wave < 0 || wave >= GADAPT_NARROW_TILE / 64) return -1;
     return gadapt_block_owned_block(gadapt_block_frame_margin(halo, n_layers), wave);
 }
+
+// The backward block launch (gadapt_narrow_bwd_block.inc): compute range [*lo_out, *hi_out) of fused stage `stage` of tile `tile` in a launch
+// of n_stages stages (gadapt_block_range on the halo of the source-ordered CSR), and - pair_cap_out, nullable - the {alpha dt, ds} pairs the
+// LDS buffer holds that the stage before fills for this one (0 for stage 0, which reads global memory): the arithmetic the kernel uses.
+extern "C" int gadapt_narrow_bwd_block_range_host(int64_t n_nodes, int halo, int n_stages, int64_t tile, int stage, int64_t* lo_out, int64_t* hi_out,
+                                                  int32_t* pair_cap_out) {
+    if (n_nodes <= 0 || (halo != 32 && halo != 64) || n_stages < 2 || n_stages > GADAPT_NARROW_BWD_BLOCK_STAGES || stage < 0 || stage >= n_stages ||
+        tile < 0 || tile * GADAPT_NARROW_TILE >= n_nodes || !lo_out || !hi_out)
+        return GADAPT_E_BADARG;
+    gadapt_block_range(n_nodes, halo, n_stages, tile, stage, lo_out, hi_out);
+    if (pair_cap_out) *pair_cap_out = stage ? gadapt_bwd_block_pair_cap(n_stages, stage) : 0;
+    return GADAPT_OK;
+}
+// ... the rows of its frame in front of the owned range (-1: bad argument), and the stages of the launch that starts at fused stage `done`
+// of n_stages = L - 1 (0: none left)
+extern "C" int gadapt_narrow_bwd_block_margin_host(int halo, int n_stages) {
+    if ((halo != 32 && halo != 64) || n_stages < 2 || n_stages > GADAPT_NARROW_BWD_BLOCK_STAGES) return -1;
+    return gadapt_bwd_block_margin(halo, n_stages);
+}
+extern "C" int gadapt_narrow_bwd_block_groups_host(int n_stages, int done) {
+    if (n_stages < 2 || done < 0) return -1;
+    return gadapt_bwd_block_groups(n_stages, done);
+}

@@ -53,4 +53,26 @@ GADAPT_PLAN_FN struct gadapt_block_slab gadapt_block_slab_plan(int64_t n_nodes, 
     return s;
 }
 
+// The backward layers below the top in one launch (grand_bwd_narrow_block_kernel, gadapt_narrow_bwd_block.inc): K <= 3 consecutive fused
+// stages [S_l + T_{l-1}], l descending, on the same 512-node tiles.  S_l of node j reads the g rows and {alpha dt, ds} pairs stage s - 1
+// left for j's OUT-neighbours, which lie within h (the halo of the source-ordered CSR) of j's aligned 32-node group: stage s runs on the
+// owned range widened by (K - 1 - s) h - gadapt_block_range with the stage for the layer.  There is no load range beyond stage 0's (it
+// reads what the launch above left in global memory), so the frame margin is that of K - 1 halos: at most 128 rows, 768 frame rows.
+//   gadapt_bwd_block_margin     rows of the frame in front of the owned range (a multiple of 64: the owned range starts on a wave block);
+//   gadapt_bwd_block_pair_cap   {alpha dt, ds} pairs the LDS buffer holds that stage s - 1 fills for stage s (s >= 1): the pairs whose
+//                               source lies in stage s's range, at most 8 per row - stage 1 of three has 512 + 2 * 64 rows at most, every
+//                               later stage (and stage 1 of two) the 512 owned ones;
+//   gadapt_bwd_block_groups     the launches of n_stages = L - 1 fused stages: groups of three, a remainder of one avoided (4 = 2 + 2), so
+//                               that every launch has at least one stage boundary to save.  Returns the size of the group that starts at
+//                               stage `done` (0 when none is left).
+#define GADAPT_NARROW_BWD_BLOCK_STAGES 3
+GADAPT_PLAN_FN int gadapt_bwd_block_margin(int halo, int K) { return gadapt_block_frame_margin(halo, K - 1); }
+GADAPT_PLAN_FN int gadapt_bwd_block_pair_cap(int K, int s) { return 8 * (GADAPT_NARROW_TILE + ((K == 3 && s == 1) ? 128 : 0)); }
+GADAPT_PLAN_FN int gadapt_bwd_block_groups(int n_stages, int done) {
+    const int left = n_stages - done;
+    if (left <= 0) return 0;
+    if (left <= GADAPT_NARROW_BWD_BLOCK_STAGES) return left;
+    return left == GADAPT_NARROW_BWD_BLOCK_STAGES + 1 ? 2 : GADAPT_NARROW_BWD_BLOCK_STAGES;
+}
+
 #endif  // GADAPT_BLOCK_PLAN_H

@@ -10,7 +10,8 @@
 //                              wide::fwd_narrow_block_kernel (gadapt_narrow_fwd.inc, gadapt_narrow_node.inc; its TOP instantiations also run
 //                              the top layer's backward target pass of a fused step)
 //   gadapt_tu_bwd_target.hip   grand_bwd_target_kernel<C,...>, grand_bwd_target_compact_kernel (gadapt_bwd_target.inc),
-//                              grand_bwd_target_fused_narrow_kernel (gadapt_narrow_bwd.inc)
+//                              grand_bwd_target_fused_narrow_kernel (gadapt_narrow_bwd.inc), grand_bwd_narrow_block_kernel
+//                              (gadapt_narrow_bwd_block.inc)
 //   gadapt_tu_bwd_source.hip   grand_bwd_source_kernel<C,...>, grand_bwd_source4_kernel (gadapt_bwd_source.inc)
 //   gadapt_tu_smallmesh.hip    one-launch small-mesh pair (gadapt_smallmesh.inc)
 //   gadapt_tu_sparse.hip       generic CSR primitives (gadapt_sparse.inc)
@@ -226,6 +227,16 @@ int gadapt_launch_bwd_source_narrow_c(int c, const gadapt_graph* g, const LayerB
 // gadapt_debug_set_narrow_backward_fused): the launch reads src's {alpha dt, ds} pairs from edge_in and scatters tgt's into edge_out
 int gadapt_launch_bwd_fused_narrow_c(int c, const gadapt_graph* g, const LayerBwd& src, const LayerBwd& tgt, const float* edge_in, float* edge_out,
                                      int layer0, hipStream_t st);
+// K = 2 or 3 consecutive fused stages in one launch (gadapt_narrow_bwd_block.inc; gadapt_debug_set_narrow_backward_block): x_src0, alpha0,
+// lp0 = the [N,4] rows of the first stage's source layer, alpha and {dt, scale} of its target layer - the next stages' lie slot_stride /
+// alpha_stride / 2 floats BELOW; g_in ([N,4], or g_cols > 0: the compact top gradient), edge_in, dxd_in = what the launch above left;
+// layer0 = 0: g_out, edge_out, dxd_out take the last stage's rows of owned nodes.  halo: of the source-ordered CSR.
+struct BwdBlockLaunch {
+    const float* x_src0; int64_t slot_stride; const float* alpha0; int64_t alpha_stride; const float* lp0; const float* a; const float* p0;
+    const float* g_in; int g_cols; const float* edge_in; const float* dxd_in; float* g_out; float* edge_out; float* dxd_out;
+    float* slab; int slab_rows, K, halo, layer0;
+};
+int gadapt_launch_bwd_narrow_block_c(int c, const gadapt_graph* g, const BwdBlockLaunch& b, hipStream_t st);
 int gadapt_slab_rows_c(int64_t n_nodes, int c);
 int gadapt_occupancy_fwd_c(int c);
 int gadapt_occupancy_bwd_target_c(int c);

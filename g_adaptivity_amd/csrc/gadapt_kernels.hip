@@ -522,6 +522,50 @@ static bool narrow_top_eligible(const gadapt_graph* g, int c, int halo, const fl
     return t.slab_rows > 0 && (int64_t)g->n_nodes <= 256 * (int64_t)t.slab_rows;
 }
 
+// The backward layers below the top in one launch (grand_bwd_narrow_block_kernel; gadapt_block_backward_narrow_packed_block), default;
+// the slab carries the bits of the launches it replaces (tests/test_gpu_narrow_block_backward.py).  GADAPT_NARROW_BWD_BLOCK=0 /
+// gadapt_debug_set_narrow_backward_block(0): those launches.
+static std::atomic<int> g_narrow_bwd_block{-1};
+static bool narrow_bwd_block_enabled() { return env_switch(g_narrow_bwd_block, "GADAPT_NARROW_BWD_BLOCK", "0") == 1; }
+extern "C" int gadapt_debug_set_narrow_backward_block(int on) { g_narrow_bwd_block.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
+// Its halo is that of the SOURCE-ordered CSR (gadapt_narrow_block_halo_host on (rowptr_s, col_s): rows of at most 8 out-edges, every
+// out-neighbour within the halo of the node's aligned 32-node group), registered like the forward's and keyed by the source arrays.
+static std::vector<BlockHaloEntry> g_block_halo_s;              // (rowptr_t / ell_t fields hold rowptr_s / ell_s; guarded by g_block_halo_mu)
+static bool block_halo_s_is(const BlockHaloEntry& e, const gadapt_graph* g) {
+    return e.rowptr_t == g->rowptr_s && e.ell_t == g->ell_s && e.n_nodes == g->n_nodes && e.n_edges == g->n_edges;
+}
+extern "C" int gadapt_narrow_block_register_source(const gadapt_graph* g, int halo) {
+    if (!g || !g->rowptr_s || !g->ell_s || g->n_nodes <= 0 || (halo != 0 && halo != 32 && halo != 64))
+        return fail(GADAPT_E_BADARG, "narrow_block_register_source: a graph with the ELL copy of its out-edges, halo 0 (forget), 32 or 64");
+    std::lock_guard<std::mutex> lk(g_block_halo_mu);
+    for (size_t k = 0; k < g_block_halo_s.size(); ++k)
+        if (block_halo_s_is(g_block_halo_s[k], g)) { g_block_halo_s[k] = g_block_halo_s.back(); g_block_halo_s.pop_back(); break; }
+    if (halo) g_block_halo_s.push_back(BlockHaloEntry{g->rowptr_s, g->ell_s, g->n_nodes, g->n_edges, halo});
+    return GADAPT_OK;
+}
+static int narrow_block_halo_source(const gadapt_graph* g) {
+    if (!g->rowptr_s || !g->ell_s) return 0;
+    std::lock_guard<std::mutex> lk(g_block_halo_mu);
+    for (const BlockHaloEntry& e : g_block_halo_s)
+        if (block_halo_s_is(e, g)) return e.halo;
+    return 0;
+}
+// THE eligibility rule of that launch, for the backward of n_layers layers on graph g (arguments already checked as
+// gadapt_block_backward_narrow_packed checks them): the switch, and the switch of the fused launches whose stages it runs
+// (gadapt_debug_set_narrow_backward_fused(0) asks for the pairs of launches); a registered source halo (which also says that no out-row is longer than
+// 8); the packed slab over one shared conv; edges; both ELL tables and the source-order positions, in-rows of at most 8; a slab row that
+// is the sum over ONE 256-node range; at least two fused stages; and the second edge buffer behind dxd (2 E <= (c - 4) N, as the fused
+// launches need it) - where the stages run as more than one launch (n_layers > 4), also a second dxd buffer behind that (2 E <= (c - 8) N).
+// Returns the halo, or 0: today's launches.
+static int narrow_bwd_block_eligible(const gadapt_graph* g, int c, int n_layers, int packed, int64_t a_stride, int64_t p0_stride) {
+    if (!narrow_bwd_block_enabled() || !narrow_bwd_fused_enabled() || !packed || a_stride != 0 || p0_stride != 0 || n_layers < 3 || c != 64) return 0;
+    if (g->n_edges <= 0 || !g->ell_t || !g->ell_s || !g->tpos_s || !g->rowptr_s || gadapt_narrow_kmax_c(g) > GADAPT_MAXD) return 0;
+    const int slab_rows = gadapt_slab_rows_c(g->n_nodes, c);
+    if (slab_rows <= 0 || (int64_t)g->n_nodes > 256 * (int64_t)slab_rows) return 0;
+    if (2 * (int64_t)g->n_edges > (int64_t)(c - (n_layers > GADAPT_NARROW_BWD_BLOCK_STAGES + 1 ? 8 : 4)) * g->n_nodes) return 0;
+    return narrow_block_halo_source(g);
+}
+
 // A block of n_layers Euler steps as its entry points see it (built once their checks have passed): where layer l finds its input slot,
 // coefficients, {dt, scale}, alpha, slab and gradient buffer.  x_all and alpha_all are written by the forward and read by the backward;
 // the slab fields and g_ws are the backward's.
@@ -789,7 +833,7 @@ extern "C" int gadapt_block_backward(const gadapt_graph* g, const float* x_all, 
 static int block_backward_narrow(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top,
                                  int g_top_cols, int n_layers, const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
                                  const float* layer_params, float* g_ws, float* dxd_ws, float* edge_ws, float* slab, float* d_layer_params,
-                                 float* d_x0, int c, void* stream, int packed, bool top_done = false) {
+                                 float* d_x0, int c, void* stream, int packed, bool top_done = false, int* block_ran = nullptr) {
     if (int rc = check_graph(g, c)) return rc;
     if (!x_all || !alpha_all || !g_top || n_layers < 2 || !a || !p0 || !layer_params || !g_ws || !dxd_ws || !edge_ws || !slab)
         return fail(GADAPT_E_BADARG, "block_backward (narrow): bad argument");
@@ -799,6 +843,43 @@ static int block_backward_narrow(const gadapt_graph* g, const float* x_all, int 
     if (packed && (a_stride != 0 || p0_stride != 0)) return fail(GADAPT_E_BADARG, "block_backward (narrow, packed slab): one shared conv (a_stride = p0_stride = 0)");
     const int64_t slab_floats = gadapt_backward_slab_floats(g->n_nodes, c);
     if (slab_floats < 0) return (int)slab_floats;
+    // block_ran (gadapt_block_backward_narrow_packed_block only): the layers below the top as one launch per group of up to three fused
+    // stages, where eligible - T_{L-1} as today unless the forward ran it, then the groups from the top down.  A group that is not the last
+    // hands g, dxd and the pairs of its owned nodes to the next through global memory, in buffers OTHER than the ones it reads: the halves
+    // of g_ws in turn (the first group reads g_top), the two edge buffers in turn, and dxd_ws / a second dxd [N,4] behind the second edge
+    // buffer (float offset 4 N + 2 E of dxd_ws) in turn.
+    if (block_ran) {
+        if (const int halo = narrow_bwd_block_eligible(g, c, n_layers, packed, a_stride, p0_stride)) {
+            const hipStream_t st = static_cast<hipStream_t>(stream);
+            const size_t nc = (size_t)g->n_nodes * c;
+            const int slab_rows = gadapt_slab_rows_c(g->n_nodes, c);
+            float* edge_buf[2] = {edge_ws, dxd_ws + 4 * (size_t)g->n_nodes};
+            float* dxd_buf[2] = {dxd_ws, dxd_ws + 4 * (size_t)g->n_nodes + 2 * (size_t)g->n_edges};
+            float* g_half[2] = {g_ws, g_ws + nc};
+            if (!top_done) {
+                const LayerBwd top{.x_in = x_all + (size_t)(n_layers - 1) * nc, .g_in = g_top, .alpha = alpha_all + (size_t)(n_layers - 1) * g->n_edges,
+                                   .a = a, .p0 = p0, .lp = layer_params + 2 * (n_layers - 1), .edge_ws = edge_ws, .dxd = dxd_ws, .slab = slab, .accumulate = 0,
+                                   .g_out = nullptr, .g_cols = g_top_cols, .slab_packed = 1};
+                if (int rc = gadapt_launch_bwd_target_narrow_c(c, g, top, st)) return rc;
+            }
+            const float* g_cur = g_top;
+            int turn = 0;                                        // launches so far: which of each buffer pair is read
+            for (int done = 0, k; (k = gadapt_bwd_block_groups(n_layers - 1, done)) > 0; done += k, ++turn) {
+                const int l = n_layers - 1 - done;               // the first stage's source layer
+                const bool fin = done + k == n_layers - 1;
+                const BwdBlockLaunch bl{.x_src0 = x_all + (size_t)l * nc, .slot_stride = (int64_t)nc, .alpha0 = alpha_all + (size_t)(l - 1) * g->n_edges,
+                                        .alpha_stride = g->n_edges, .lp0 = layer_params + 2 * (l - 1), .a = a, .p0 = p0, .g_in = g_cur,
+                                        .g_cols = done == 0 ? g_top_cols : 0, .edge_in = edge_buf[turn & 1], .dxd_in = dxd_buf[turn & 1],
+                                        .g_out = fin ? nullptr : g_half[turn & 1], .edge_out = fin ? nullptr : edge_buf[(turn + 1) & 1],
+                                        .dxd_out = fin ? nullptr : dxd_buf[(turn + 1) & 1], .slab = slab, .slab_rows = slab_rows, .K = k, .halo = halo,
+                                        .layer0 = fin ? 1 : 0};
+                if (int rc = gadapt_launch_bwd_narrow_block_c(c, g, bl, st)) return rc;
+                g_cur = bl.g_out;
+            }
+            *block_ran = 1;
+            return GADAPT_OK;
+        }
+    }
     // (x_all and alpha_all: read only)
     const Block b{.g = g, .c = c, .n_layers = n_layers, .x_all = const_cast<float*>(x_all), .nc = (size_t)g->n_nodes * c, .a_all = a, .a_stride = a_stride,
                   .p0_all = p0, .p0_stride = p0_stride, .layer_params = layer_params, .alpha_all = const_cast<float*>(alpha_all), .slab_all = slab,
@@ -869,4 +950,18 @@ extern "C" int gadapt_block_backward_narrow_packed_below_top(const gadapt_graph*
     (void)want_d_scale;
     return block_backward_narrow(g, x_all, x0_cols, alpha_all, g_top, g_top_cols, n_layers, a, a_stride, p0, p0_stride, layer_params, g_ws, dxd_ws,
                                  edge_ws, slab, d_layer_params, d_x0, c, stream, 1, true);
+}
+// gadapt_block_backward_narrow_packed (top_done = 0) or ..._below_top (top_done = 1) with the layers below the top in one launch per
+// group of up to three fused stages where the step is eligible (narrow_bwd_block_eligible; *block_ran = 1): the slab carries the same
+// bits, the work buffers are written only as include/gadapt_hip.h states.  Not eligible: exactly those entry points' launches, *block_ran = 0.
+extern "C" int gadapt_block_backward_narrow_packed_block(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all,
+                                                         const float* g_top, int g_top_cols, int n_layers, const float* a, int64_t a_stride,
+                                                         const float* p0, int64_t p0_stride, const float* layer_params, float* g_ws, float* dxd_ws,
+                                                         float* edge_ws, float* slab, float* d_layer_params, int want_d_scale, float* d_x0, int c,
+                                                         void* stream, int top_done, int* block_ran) {
+    (void)want_d_scale;
+    if (!block_ran) return fail(GADAPT_E_BADARG, "block_backward_narrow_packed_block: nowhere to report whether the block launch ran");
+    *block_ran = 0;
+    return block_backward_narrow(g, x_all, x0_cols, alpha_all, g_top, g_top_cols, n_layers, a, a_stride, p0, p0_stride, layer_params, g_ws, dxd_ws,
+                                 edge_ws, slab, d_layer_params, d_x0, c, stream, 1, top_done != 0, block_ran);
 }

@@ -4,6 +4,7 @@
 #include "gadapt_internal.h"
 #include "gadapt_bwd_target.inc"
 #include "gadapt_narrow_bwd.inc"
+#include "gadapt_narrow_bwd_block.inc"
 
 // The slab holds one row per workgroup of a target pass: every target launch of a block at hidden size C uses this grid, so every
 // row is visited (gadapt_slab_rows_c)
@@ -120,4 +121,35 @@ int gadapt_launch_bwd_fused_narrow_c(int c, const gadapt_graph* g, const LayerBw
     if (layer0) { if (src.g_cols) go(grand_bwd_target_fused_narrow_kernel<true, true>); else go(grand_bwd_target_fused_narrow_kernel<true, false>); }
     else { if (src.g_cols) go(grand_bwd_target_fused_narrow_kernel<false, true>); else go(grand_bwd_target_fused_narrow_kernel<false, false>); }
     return check_launch("grand_bwd_target_fused_narrow_kernel");
+}
+
+// narrow route, K = 2 or 3 consecutive fused stages [S_l + T_{l-1}] in one launch (grand_bwd_narrow_block_kernel, gadapt_narrow_bwd_block.inc):
+// one 512-thread workgroup per 512-node tile, halo of the source-ordered CSR (32 or 64; the caller has it from the graph's registration).
+// Everything is checked before the launch.  layer0 = 1: the last stage's target half is layer 0, the launch writes slab rows only;
+// layer0 = 0: its last stage also stores g_out, dxd_out and the pairs into edge_out for the nodes a tile owns - three buffers other than
+// the ones stage 0 reads.
+int gadapt_launch_bwd_narrow_block_c(int c, const gadapt_graph* g, const BwdBlockLaunch& b, hipStream_t st) {
+    if (c != 64 || !g || !g->ell_t || !g->tpos_s || !g->ell_s || !g->rowptr_s || !g->rowptr_t || g->n_edges <= 0 || g->n_nodes <= 0 ||
+        (b.halo != 32 && b.halo != 64) || b.K < 2 || b.K > GADAPT_NARROW_BWD_BLOCK_STAGES || b.g_cols < 0 || b.g_cols > 4)
+        return fail(GADAPT_E_BADARG, "narrow block backward: hidden 64, ELL graph with edges, halo 32 or 64, 2..3 stages, 0..4 g columns");
+    if (!b.x_src0 || !b.alpha0 || !b.lp0 || !b.a || !b.p0 || !b.g_in || !b.edge_in || !b.dxd_in || !b.slab ||
+        b.slot_stride < 4 * (int64_t)g->n_nodes || b.alpha_stride < g->n_edges)
+        return fail(GADAPT_E_BADARG, "narrow block backward: layer slots, alpha, {dt, scale}, coefficients, the buffers of the launch above, the slab");
+    if (!b.layer0 && (!b.g_out || !b.edge_out || !b.dxd_out || b.g_out == b.g_in || b.edge_out == b.edge_in || b.dxd_out == b.dxd_in))
+        return fail(GADAPT_E_BADARG, "narrow block backward: above layer 0 the last stage stores g, dxd and pairs to buffers other than the ones read");
+    if (b.slab_rows != gadapt_slab_rows_c(g->n_nodes, c) || (int64_t)g->n_nodes > 256 * (int64_t)b.slab_rows)
+        return fail(GADAPT_E_BADARG, "narrow block backward: the slab of the target launches, one 256-node range per row");
+    BwdBlockArgs q{};
+    q.x_src0 = b.x_src0; q.slot_stride = b.slot_stride; q.alpha0 = b.alpha0; q.alpha_stride = b.alpha_stride; q.lp0 = b.lp0;
+    q.A = b.a; q.p0 = b.p0; q.g_in = b.g_in; q.edge_in = reinterpret_cast<const float2*>(b.edge_in); q.dxd_in = b.dxd_in;
+    q.g_out = b.g_out; q.edge_out = reinterpret_cast<float2*>(b.edge_out); q.dxd_out = b.dxd_out;
+    q.rowptr_t = g->rowptr_t; q.ell_t = g->ell_t; q.tpos = g->tpos_s; q.rowptr_s = g->rowptr_s; q.ell_s = g->ell_s;
+    q.slab = b.slab;
+    q.n_nodes = g->n_nodes; q.n_edges = g->n_edges; q.K = b.K; q.halo = b.halo; q.c = c; q.g_cols = b.g_cols; q.slab_rows = b.slab_rows;
+    const int grid = (g->n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE;
+    ProfScope prof(1, st, 2 | 32);                              // a target-pass launch on compact input, bit 5: several layers in the launch
+    auto go = [&](auto kern) { allow_lds(kern, NBB_LDS_BYTES); hipLaunchKernelGGL(kern, dim3(grid), dim3(NBB_NT), NBB_LDS_BYTES, st, q); };
+    if (b.layer0) { if (b.g_cols) go(grand_bwd_narrow_block_kernel<true, true>); else go(grand_bwd_narrow_block_kernel<true, false>); }
+    else { if (b.g_cols) go(grand_bwd_narrow_block_kernel<false, true>); else go(grand_bwd_narrow_block_kernel<false, false>); }
+    return check_launch("grand_bwd_narrow_block_kernel");
 }

@@ -218,11 +218,22 @@ class MeshGraph:
                 raise _native.NativeError("gadapt_narrow_block_halo_host failed")
             self.narrow_block_halo = int(hl.value)
         _native.check(_native.lib().gadapt_narrow_block_register(self.c_ref, self.narrow_block_halo), "gadapt_narrow_block_register")
+        # ... and one launch for the backward layers below the top (csrc/gadapt_narrow_bwd_block.inc): the same test on the out-edges
+        self.narrow_block_halo_source = 0
+        if self.narrow_block_halo and e > 0:
+            hl = C.c_int32(0)
+            if _native.lib().gadapt_narrow_block_halo_host(rowptr_s.data_ptr(), col_s.data_ptr(), n, C.addressof(hl)) != 0:
+                raise _native.NativeError("gadapt_narrow_block_halo_host failed")
+            self.narrow_block_halo_source = int(hl.value)
+        _native.check(_native.lib().gadapt_narrow_block_register_source(self.c_ref, self.narrow_block_halo_source),
+                      "gadapt_narrow_block_register_source")
 
     def __del__(self):
         try:                                                # the device arrays go back to the allocator: forget their registration
             if getattr(self, 'narrow_block_halo', 0):
                 _native.lib().gadapt_narrow_block_register(self.c_ref, 0)
+            if getattr(self, 'narrow_block_halo_source', 0):
+                _native.lib().gadapt_narrow_block_register_source(self.c_ref, 0)
         except Exception:
             pass
 

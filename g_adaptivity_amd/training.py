@@ -15,6 +15,7 @@ counterpart.
 """
 from __future__ import annotations
 
+import ctypes
 import time
 from typing import Callable, Dict, Optional, Tuple
 
@@ -168,6 +169,13 @@ class FusedIteration:
                         name)
             # (the same arguments, one launch fewer: behind a forward call that ran the top layer's target pass itself)
             self._bw_below = (L_.gadapt_block_backward_narrow_packed_below_top, self._bw[1], 'gadapt_block_backward_narrow_packed_below_top')
+            if fw.narrow:
+                # narrow route: the entry point that runs the layers below the top as one launch where the step is eligible (and exactly
+                # the launches of the two above where it is not); its last two arguments: whether the forward ran T_{L-1}, and its report
+                self.block_ran = ctypes.c_int(0)
+                args = self._bw[1] + [0, ctypes.addressof(self.block_ran)]
+                name = 'gadapt_block_backward_narrow_packed_block'
+                self._bw = self._bw_below = (getattr(L_, name), args, name)
             a_ptr, p0_ptr = (None, None) if self.coeffs_in_forward else (ptr(a), ptr(p0))
         # gadapt_step_tail in its three forms: (slab given, moments given) = the whole tail; (slab, no moments) = this rank's gradient;
         # (no slab, moments) = the gradient is given (all-reduced)
@@ -192,7 +200,10 @@ class FusedIteration:
         st = current_stream(self.device)
         self.n_part = self.fwd(*self._in, st)
         fn, args, name = self._bw_below if (self.small is None and self.fwd.top_ran) else self._bw
-        args[-1] = st
+        if self.small is None and self.fwd.narrow:
+            args[-3], args[-2] = st, (1 if self.fwd.top_ran else 0)
+        else:
+            args[-1] = st
         rc = fn(*args)
         if rc:
             check(rc, name)

@@ -140,6 +140,20 @@ int gadapt_narrow_block_register(const gadapt_graph* g, int halo);
  * (a_stride != 0) keep one launch per layer as well. */
 int gadapt_narrow_block_halo(const gadapt_graph* g, int c);
 
+/* The backward layers below the top in one launch (gadapt_block_backward_narrow_packed_block below): the same tiles, K = 2 or 3 fused
+ * stages [S_l + T_{l-1}] per launch, stage s on the owned range widened by (K - 1 - s) * halo, where halo is that of the SOURCE-ordered
+ * CSR: gadapt_narrow_block_halo_host(rowptr_s, col_s, ...).  gadapt_narrow_block_register_source tells the library (0 = forget), keyed by
+ * (rowptr_s, ell_s, n_nodes, n_edges); gadapt_narrow_block_register and its meaning are unchanged.  The host copies of the plan:
+ * range_host = the nodes of stage `stage` (0 .. n_stages-1) of a launch of n_stages stages, and (pair_cap_out, nullable) how many
+ * {alpha dt, ds} pairs the LDS buffer holds that the stage before fills for it (0 for stage 0); margin_host = the frame rows in front of
+ * the owned range; groups_host = the stages of the launch that starts at fused stage `done` of n_stages = L - 1 (groups of three, a
+ * remainder of one avoided: 5 = 3 + 2, 4 = 2 + 2; 0 = none left). */
+int gadapt_narrow_block_register_source(const gadapt_graph* g, int halo);
+int gadapt_narrow_bwd_block_range_host(int64_t n_nodes, int halo, int n_stages, int64_t tile, int stage, int64_t* lo_out, int64_t* hi_out,
+                                       int32_t* pair_cap_out);
+int gadapt_narrow_bwd_block_margin_host(int halo, int n_stages);
+int gadapt_narrow_bwd_block_groups_host(int n_stages, int done);
+
 /* ------------------------------------------------------------------ weights
  * A[o][c] = sum_r Wk[r][o] Wq[r][c],  p0[o] = sum_r Wk[r][o] bq[r].
  * Wq,Wk are torch Linear weights [out,in] (GRAND_plus.py:146-147). */
@@ -360,6 +374,30 @@ int gadapt_block_backward_narrow_packed_below_top(const gadapt_graph* g, const f
                                                   float* g_ws, float* dxd_ws, float* edge_ws, float* slab,
                                                   float* d_layer_params, int want_d_scale, float* d_x0, int c, void* stream);
 
+/* The layers below the top in one launch.  gadapt_block_backward_narrow_packed_block takes the arguments of
+ * gadapt_block_backward_narrow_packed, runs T_{L-1} itself when top_done = 0 (top_done = 1: behind gadapt_block_forward_loss_narrow_top with
+ * *top_ran = 1) and then the fused stages [S_l + T_{l-1}], l = L-1 .. 1, as ONE launch per group of up to three stages (L = 3: one launch of
+ * two, L = 4: one of three, L = 6: 3 + 2; gadapt_narrow_bwd_block_groups_host), stages separated by workgroup barriers, and sets
+ * *block_ran = 1.  Eligible: the switches gadapt_debug_set_narrow_backward_block and gadapt_debug_set_narrow_backward_fused on; a source halo of 32 or 64 registered
+ * (gadapt_narrow_block_register_source); one shared conv; n_edges > 0; ell_t, ell_s and tpos_s present, rows of at most 8 in both tables;
+ * n_nodes <= 256 * gadapt_backward_slab_rows; n_layers >= 3; 2 E <= (c - 4) N (n_layers > 4: 2 E <= (c - 8) N).  Otherwise it runs exactly
+ * the launches of gadapt_block_backward_narrow_packed / _below_top and sets *block_ran = 0.
+ * Contract when *block_ran = 1 - the SLAB: entries 0..19 of rows 0 .. min(2 ceil(N / 512), rows) - 1 carry the bits those launches leave;
+ * every other entry of the slab is not written by the block launches (the rows beyond hold the zeros of T_{L-1}, to which those launches
+ * add +0).  Work buffers (N nodes, E edges, c = hidden):
+ *   top_done = 0: T_{L-1} writes dxd_ws[0, 4N), edge_ws[0, 2E) and every slab row, as today;
+ *   n_layers <= 4: nothing else - g_ws is not written at all, and with top_done = 1 neither are dxd_ws and edge_ws;
+ *   n_layers > 4: launch number m = 0, 1, .. that is not the last stores, for every node, what the next one reads:
+ *     g rows [N,4] to g_ws[(m & 1) N c, + 4N), dxd rows to dxd_ws[0, 4N) (m odd) or dxd_ws[4N + 2E, 8N + 2E) (m even), the pairs to
+ *     edge_ws[0, 2E) (m odd) or dxd_ws[4N, 4N + 2E) (m even); L = 6: g_ws[0, 4N), dxd_ws[4N, 8N + 2E).  Nothing else. */
+int gadapt_block_backward_narrow_packed_block(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all,
+                                              const float* g_top, int g_top_cols, int n_layers,
+                                              const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
+                                              const float* layer_params,
+                                              float* g_ws, float* dxd_ws, float* edge_ws, float* slab,
+                                              float* d_layer_params, int want_d_scale, float* d_x0, int c, void* stream,
+                                              int top_done, int* block_ran);
+
 /* ------------------------------------------------------------------ small meshes: the whole evaluation forward in ONE launch
  * The reference's own sizes (params.py:37,56,107,130-134: 11x11 ... 23x23 meshes, hidden 8, 4 layers; evaluation one sample per call,
  * utils_eval.py:128-130,193-201; the Burgers rollout, utils_eval_Burgers.py:282-300): encoder (GNN.py:225-239,270), composite
@@ -544,6 +582,10 @@ int gadapt_debug_set_narrow_backward_fused(int on);
  * layer's backward target pass inside its last forward launch where the step is eligible; 0 keeps the separate launch.  Results are
  * bit-identical either way (tests/test_gpu_narrow_top_in_forward.py). */
 int gadapt_debug_set_narrow_top_in_forward(int on);
+/* Switch: 1 (the default; GADAPT_NARROW_BWD_BLOCK=0 in the environment starts with 0) lets gadapt_block_backward_narrow_packed_block run the
+ * layers below the top as one launch per group of up to three fused stages where the step is eligible; 0: the launches of
+ * gadapt_block_backward_narrow_packed.  The slab carries the same bits either way. */
+int gadapt_debug_set_narrow_backward_block(int on);
 /* Diagnostic: runtime-reported workgroups per CU of {forward, backward target, backward source}. */
 int gadapt_debug_occupancy(int c, int* out3);
 /* Diagnostic: the wave sum of the slab partials (wave_sum_desc: DPP and lane-swap steps) beside the xor butterfly 32, 16, .., 1 on
