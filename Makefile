@@ -21,6 +21,7 @@ endif
 UNITS      := gadapt_kernels gadapt_tu_fwd gadapt_tu_bwd_target gadapt_tu_bwd_source gadapt_tu_smallmesh gadapt_tu_sparse gadapt_tu_gat
 OBJS       := $(UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/csr_build.o
 SHARED     := $(CSRC)/gadapt_internal.h $(CSRC)/gadapt_common.inc $(CSRC)/gadapt_block_plan.h include/gadapt_hip.h
+TAIL_PLAN  := $(CSRC)/gadapt_tail_plan.h
 
 all: $(LIB) $(FEM_LIB) $(MESH_LIB)
 
@@ -67,7 +68,7 @@ $(OBJDIR)/ma_kernels.o: $(MESH_CSRC)/ma_kernels.hip $(MESH_CSRC)/mesh_common.h i
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
 
-$(OBJDIR)/gadapt_kernels.o: $(CSRC)/gadapt_small.inc
+$(OBJDIR)/gadapt_kernels.o: $(CSRC)/gadapt_small.inc $(TAIL_PLAN)
 $(OBJDIR)/gadapt_tu_fwd.o: $(CSRC)/gadapt_fwd.inc $(CSRC)/gadapt_wide.inc $(CSRC)/gadapt_narrow_fwd.inc $(CSRC)/gadapt_narrow_node.inc
 $(OBJDIR)/gadapt_tu_bwd_target.o: $(CSRC)/gadapt_bwd_target.inc $(CSRC)/gadapt_narrow_bwd.inc $(CSRC)/gadapt_narrow_bwd_block.inc
 $(OBJDIR)/gadapt_tu_bwd_source.o: $(CSRC)/gadapt_bwd_source.inc
@@ -80,7 +81,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(SHARED)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -c -o $@ $<
 
-$(OBJDIR)/csr_build.o: $(CSRC)/csr_build.cpp $(CSRC)/gadapt_block_plan.h include/gadapt_hip.h
+$(OBJDIR)/csr_build.o: $(CSRC)/csr_build.cpp $(CSRC)/gadapt_block_plan.h $(TAIL_PLAN) include/gadapt_hip.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 

@@ -81,6 +81,10 @@ PROTOTYPES = {
     'gadapt_narrow_slab_floats': (_L, [_L]),
     'gadapt_block_backward_narrow_packed': (_I, [_G, _P, _I, _P, _P, _I, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
     'gadapt_step_tail_narrow': (_I, [_P, _I, _P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _P, _F, _P, _P, _P, _I, _P, _L, _I, _P]),
+    'gadapt_narrow_tail_plan_host': (_I, [_I, _P]),
+    'gadapt_narrow_tail_rows_host': (_I, [_I]),
+    'gadapt_narrow_tail_entry_host': (_I, [_I, _I, _I, _P]),
+    'gadapt_narrow_tail_owner_host': (_I, [_I, _P]),
     'gadapt_block_forward_loss_narrow_top': (_I, [_G, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     'gadapt_block_backward_narrow_packed_below_top': (_I, [_G, _P, _I, _P, _P, _I, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
     # ... (the same arguments), top_done, block_ran
@@ -111,6 +115,7 @@ PROTOTYPES = {
     'gadapt_debug_set_narrow_backward_fused': (_I, [_I]),
     'gadapt_debug_set_narrow_top_in_forward': (_I, [_I]),
     'gadapt_debug_set_narrow_backward_block': (_I, [_I]),
+    'gadapt_debug_set_narrow_tail_spread': (_I, [_I]),
     'gadapt_debug_occupancy': (_I, [_I, C.POINTER(C.c_int)]),
     'gadapt_debug_wave_sum_desc': (_I, [_P, _P, _P, _I, _I, _P]),
 }

@@ -9,6 +9,7 @@
 #include <vector>
 #include "gadapt_hip.h"
 #include "gadapt_block_plan.h"
+#include "gadapt_tail_plan.h"
 
 extern "C" int gadapt_csr_build_host(const int64_t* src, const int64_t* dst, int64_t n_edges, int64_t n_nodes,
                                      int32_t* rowptr_t, int32_t* col_t, int32_t* eid_t,
@@ -162,4 +163,34 @@ extern "C" int gadapt_narrow_bwd_block_margin_host(int halo, int n_stages) {
 extern "C" int gadapt_narrow_bwd_block_groups_host(int n_stages, int done) {
     if (n_stages < 2 || done < 0) return -1;
     return gadapt_bwd_block_groups(n_stages, done);
+}
+
+// The spread step tail of the narrow route (gadapt_tail_plan.h; step_tail_narrow_spread_kernel): the arithmetic the kernel and its launcher
+// use.  plan_out: rows per parameter workgroup, threads per workgroup, parameter workgroups, slots per thread, workgroups of the launch
+// and tickets taken with (has_loss != 0) or without loss partials.
+extern "C" int gadapt_narrow_tail_plan_host(int has_loss, int32_t* plan_out) {
+    if (!plan_out) return GADAPT_E_BADARG;
+    plan_out[0] = GADAPT_NARROW_TAIL_ROWS; plan_out[1] = GADAPT_NARROW_TAIL_THREADS; plan_out[2] = gadapt_narrow_tail_wgs();
+    plan_out[3] = gadapt_narrow_tail_slots(); plan_out[4] = gadapt_narrow_tail_grid(has_loss); plan_out[5] = gadapt_narrow_tail_tickets(has_loss);
+    return GADAPT_OK;
+}
+// rows of parameter workgroup wg (-1: no such workgroup)
+extern "C" int gadapt_narrow_tail_rows_host(int wg) {
+    if (wg < 0 || wg >= gadapt_narrow_tail_wgs()) return -1;
+    return gadapt_narrow_tail_rows_of(wg);
+}
+// out3 = {entry of the flat bucket or -1, row within the workgroup, place in the row} of (wg, thread, slot); {wg, thread, slot} of entry e
+extern "C" int gadapt_narrow_tail_entry_host(int wg, int thread, int slot, int32_t* out3) {
+    if (wg < 0 || wg >= gadapt_narrow_tail_wgs() || thread < 0 || thread >= GADAPT_NARROW_TAIL_THREADS || slot < 0 ||
+        slot >= gadapt_narrow_tail_slots() || !out3)
+        return GADAPT_E_BADARG;
+    const gadapt_tail_entry t = gadapt_narrow_tail_entry(wg, thread, slot);
+    out3[0] = t.e; out3[1] = t.ri; out3[2] = t.k;
+    return GADAPT_OK;
+}
+extern "C" int gadapt_narrow_tail_owner_host(int e, int32_t* out3) {
+    if (e < 0 || e >= GADAPT_NARROW_TAIL_C * GADAPT_NARROW_TAIL_ROW_ENTRIES || !out3) return GADAPT_E_BADARG;
+    const gadapt_tail_owner o = gadapt_narrow_tail_owner(e);
+    out3[0] = o.wg; out3[1] = o.thread; out3[2] = o.slot;
+    return GADAPT_OK;
 }

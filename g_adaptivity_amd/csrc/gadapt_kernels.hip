@@ -23,6 +23,7 @@
 // (A, p0) formulation described in include/gadapt_hip.h.
 
 #include "gadapt_internal.h"
+#include "gadapt_tail_plan.h"
 #include <atomic>
 
 // ------------------------------------------------------------------------------------------------
@@ -749,6 +750,13 @@ extern "C" int gadapt_step_tail(const float* slab, int n_rows, float* scratch, f
     return gadapt_coeffs_forward(param, param + at.bq, param + at.wk, a_out, p0_out, c, stream);
 }
 
+// The narrow route's tail spread over row-owning workgroups (step_tail_narrow_spread_kernel; gadapt_tail_plan.h) - the same bits as the
+// one-workgroup kernel (tests/test_gpu_narrow_tail_spread.py).  GADAPT_NARROW_TAIL_SPREAD=0 / gadapt_debug_set_narrow_tail_spread(0):
+// step_tail_narrow_kernel.
+static std::atomic<int> g_narrow_tail_spread{-1};
+static bool narrow_tail_spread_enabled() { return env_switch(g_narrow_tail_spread, "GADAPT_NARROW_TAIL_SPREAD", "0") == 1; }
+extern "C" int gadapt_debug_set_narrow_tail_spread(int on) { g_narrow_tail_spread.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
+
 // The narrow route's tail over the PACKED slab (gadapt_block_backward_narrow_packed) as ONE launch, hidden 64: step_tail_narrow_kernel.
 // The forms of gadapt_step_tail that read a slab - the whole tail, and (no moments) the flat gradient only; bit-identical to them on
 // the equivalent full-width slab (tests/test_gpu_narrow_tail.py).  The gradient-given form has no slab: gadapt_step_tail.
@@ -766,7 +774,11 @@ extern "C" int gadapt_step_tail_narrow(const float* slab, int n_rows, float* scr
     hipStream_t st = static_cast<hipStream_t>(stream);
     TailNarrowArgs p{slab, n_rows, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, grad_scale, gradient_only ? nullptr : state,
                      loss_partials, n_loss_partials, loss_partials ? 1.0f / (float)loss_count : 0.f, loss_out};
-    hipLaunchKernelGGL(step_tail_narrow_kernel, dim3(loss_partials ? 2 : 1), dim3(1024), 0, st, p);
+    if (narrow_tail_spread_enabled())
+        hipLaunchKernelGGL((step_tail_narrow_spread_kernel<GADAPT_NARROW_TAIL_THREADS, GADAPT_NARROW_TAIL_ROWS>),
+                           dim3(gadapt_narrow_tail_grid(loss_partials != nullptr)), dim3(GADAPT_NARROW_TAIL_THREADS), 0, st, p);
+    else
+        hipLaunchKernelGGL(step_tail_narrow_kernel, dim3(loss_partials ? 2 : 1), dim3(1024), 0, st, p);
     if (int rc = check_launch("step_tail_narrow")) return rc;
     if (gradient_only || !a_out) return GADAPT_OK;
     const BucketAt at = bucket_at(c);

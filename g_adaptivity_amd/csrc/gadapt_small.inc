@@ -568,6 +568,183 @@ __global__ __launch_bounds__(1024) void step_tail_narrow_kernel(TailNarrowArgs p
     if (adam && tid == 0) p.state[0] = step_now;
 }
 
+// The same tail SPREAD over row-owning workgroups (gadapt_tail_plan.h; gadapt_debug_set_narrow_tail_spread): the same bits as
+// step_tail_narrow_kernel from gadapt_narrow_tail_wgs() parameter workgroups of T threads and, with loss partials, the loss workgroup as
+// the LAST one.  One workgroup ran Adam on all 8320 entries there, nine per thread behind two powf on each of sixteen waves, while 255
+// CUs stood idle; here
+//   - every parameter workgroup computes the 20 sums itself from the whole packed slab (64 KB at 512 rows, served by L2 / MALL), in
+//     step_tail_narrow_kernel's order: thread (chunk q, entry en) of the first 256 holds all four interleaved sums v_j of its chunk
+//     (rows r0 + j + 4 m of the full 32-row groups, ascending; leftover rows one by one into v_0), (v0 + v1) + (v2 + v3), then the
+//     chunks in ascending order onto +0 - so all workgroups hold bit-identical sums and exchange nothing;
+//   - it owns R whole rows of the bucket (one or two entries per thread): the old Wq[r][0..3], Wk[r][0..3], bq[r] its chain rule reads
+//     are entries its own threads loaded - staged in LDS - and nothing it reads is written by another workgroup;
+//   - the step count: every workgroup reads state[0] with its first loads and uses state[0] + 1.  Behind the barriers that follow
+//     the sums - every thread of the workgroup has its count by then - ONE thread takes a ticket in state[1] (adam_step_dev_kernel's);
+//     the workgroup whose ticket is the last stores state[1] = 0 and state[0] = step_now.  Every other workgroup took its ticket after
+//     its reads, so none reads the new count; nothing is handed from workgroup to workgroup (the ticket orders a READ before a WRITE
+//     of one word), so there is no fence, no spin and no barrier across workgroups.  hipcc waits for a returned atomic where it is
+//     issued, so the ticket is the LAST thread's: its wave holds the fewest entries (none at the shipped geometry) and waits for the
+//     answer while the other waves run the chain rule and Adam.  Gradient only (p.m == nullptr): neither word is touched.
+// n_rows <= 512 (at most 64 rows per chunk): all 64 row loads of a thread go out before the first wait, with the step count and the
+// param / m / v loads, and the two powf run behind them - once per SIMD at T = 256; more rows: groups of 32 in a loop.
+template <int T, int R>
+__global__ __launch_bounds__(T) void step_tail_narrow_spread_kernel(TailNarrowArgs p) {
+    constexpr int C = 64, RW = GADAPT_NARROW_SLAB_ROW, Q = GADAPT_SLAB_CHUNKS, NS = gadapt_narrow_tail_slots(), NWG = gadapt_narrow_tail_wgs();
+    static_assert(C == GADAPT_NARROW_TAIL_C && T == GADAPT_NARROW_TAIL_THREADS && R == GADAPT_NARROW_TAIL_ROWS, "the plan's geometry");
+    static_assert(Q * RW == 256 && T % 256 == 0 && T <= 1024, "the first 256 threads: one per (chunk, entry)");
+    static_assert(NS >= 1 && NS <= 2, "one or two entries per thread");
+    __shared__ float part[Q * RW];                              // (chunk, entry)
+    __shared__ float sums[RW];                                  // dA[o][c] at 4 o + c, dp0[o] at 16 + o
+    __shared__ float wq4[R][4], wk4[R][4], bqs[R];              // old Wq[r][0..3], Wk[r][0..3], bq[r] of this workgroup's rows
+    __shared__ float lred[4];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x == NWG) {                               // the loss value: slab_reduce1_kernel's order (256 threads)
+        float v = 0.f;
+        if (tid < 256) {
+            float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+            for (int r = tid; r < p.n_loss; r += 1024) {
+                v0 += p.loss_partials[r];
+                if (r + 256 < p.n_loss) v1 += p.loss_partials[r + 256];
+                if (r + 512 < p.n_loss) v2 += p.loss_partials[r + 512];
+                if (r + 768 < p.n_loss) v3 += p.loss_partials[r + 768];
+            }
+            v = (v0 + v1) + (v2 + v3);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+            if ((tid & 63) == 0) lred[tid >> 6] = v;
+        }
+        __syncthreads();
+        if (tid == 0) p.loss_out[0] = ((lred[0] + lred[1]) + (lred[2] + lred[3])) * p.loss_scale;
+        return;
+    }
+    const bool adam = p.m != nullptr;
+    const int wg = blockIdx.x;
+    // Every request of the launch goes out before the first wait: the step count, this thread's slab rows, its entries of param / m / v.
+    // No request sits in a branch of its own (a wait would close the branch): gradient only reads the count and the moments from words
+    // that are there - the slab, the parameters - and drops them.  The count is a uniform read of a word nothing has written yet in
+    // this launch: it travels on the scalar path and returns on its own counter, not behind the 70 vector requests in front of it.
+    const int step_read = *(adam ? const_cast<const int*>(p.state) : reinterpret_cast<const int*>(p.slab));
+    const bool summer = tid < Q * RW;
+    const int q = (tid >> 5) & (Q - 1), en = tid & (RW - 1);
+    const int per = (p.n_rows + Q - 1) / Q;
+    const int r0 = q * per, r1 = min(p.n_rows, r0 + per), len = max(r1 - r0, 0);
+    const float* src = p.slab + en;
+    const bool flat = per <= 64;                                // (uniform) every row of the chunk in flight at once
+    float t[64];
+    if (summer && flat) {
+#pragma unroll
+        for (int k = 0; k < 64; ++k) t[k] = src[(size_t)min(r0 + k, p.n_rows - 1) * RW];   // (rows past the chunk: loaded, not added)
+    }
+    gadapt_tail_entry ent[NS];
+    float pv[NS], mm[NS], vv[NS];
+    const float* m_src = adam ? p.m : p.param;
+    const float* v_src = adam ? p.v : p.param;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        ent[i] = gadapt_narrow_tail_entry(wg, tid, i);
+        const int e = ent[i].e >= 0 ? ent[i].e : wg * R * C;   // (a slot that holds nothing reads the workgroup's first entry)
+        pv[i] = p.param[e];
+        mm[i] = m_src[e];
+        vv[i] = v_src[e];
+    }
+    const int step_now = adam ? step_read + 1 : 1;              // steps taken INCLUDING this one
+    float bc1 = 0.f, bc2_sqrt = 0.f;
+    if (adam) {
+        const float stepf = (float)step_now;
+        bc1 = 1.0f - powf(p.b1, stepf); bc2_sqrt = sqrtf(1.0f - powf(p.b2, stepf));
+        asm volatile("" : "+v"(bc1), "+v"(bc2_sqrt));           // (hipcc otherwise sinks them to their use, behind the sums)
+    }
+    if (summer && flat) asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));   // (... and hoists the first additions, with their wait, in front of them)
+    // the entries of its rows the chain rule reads, staged before anyone overwrites them
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int k = ent[i].k, ri = ent[i].ri;
+        if (ent[i].e < 0) continue;
+        if (k < 4) wq4[ri][k] = pv[i];
+        else if (k == C) bqs[ri] = pv[i];
+        else if (k > C && k < C + 5) wk4[ri][k - C - 1] = pv[i];
+    }
+    if (summer) {
+        float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;
+        if (flat) {
+            if (len == 64) {                                    // two full groups
+#pragma unroll
+                for (int k = 0; k < 64; k += 4) { v0 += t[k]; v1 += t[k + 1]; v2 += t[k + 2]; v3 += t[k + 3]; }
+            } else {                                            // at most one full group, then the leftover rows into v0
+                const bool full = len >= 32;
+#pragma unroll
+                for (int k = 0; k < 32; k += 4) {
+                    if (full) { v0 += t[k]; v1 += t[k + 1]; v2 += t[k + 2]; v3 += t[k + 3]; }
+                    else {
+#pragma unroll
+                        for (int kk = k; kk < k + 4; ++kk) if (kk < len) v0 += t[kk];
+                    }
+                }
+#pragma unroll
+                for (int k = 32; k < 64; ++k) if (k < len) v0 += t[k];
+            }
+        } else {
+            int r = r0;
+            for (; r + 32 <= r1; r += 32) {
+#pragma unroll
+                for (int k = 0; k < 32; ++k) t[k] = src[(size_t)(r + k) * RW];
+#pragma unroll
+                for (int k = 0; k < 32; k += 4) { v0 += t[k]; v1 += t[k + 1]; v2 += t[k + 2]; v3 += t[k + 3]; }
+            }
+            for (; r < r1; ++r) v0 += src[(size_t)r * RW];
+        }
+        part[tid] = (v0 + v1) + (v2 + v3);
+    }
+    __syncthreads();
+    if (tid < RW) {
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < Q; ++k) v += part[k * RW + tid];     // same order as slab_reduce2_kernel
+        sums[tid] = v;
+    }
+    __syncthreads();
+    int ticket = -1;
+    if (adam && tid == T - 1) ticket = __hip_atomic_fetch_add(p.state + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const float* da = sums;                                     // dA[o][cc] = da[4 o + cc]
+    const float* dp = sums + 16;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int e = ent[i].e, k = ent[i].k, ri = ent[i].ri;
+        if (e < 0) continue;
+        float g = 0.f;
+        if (k < C) {                            // d_wq[r][cc] = sum_o wk[r][o] dA[o][cc]
+            if (k < 4) {
+                float v[4];
+#pragma unroll
+                for (int o = 0; o < 4; ++o) v[o] = fmaf(wk4[ri][o], da[4 * o + k], 0.f);
+                g = (v[0] + v[1]) + (v[2] + v[3]);
+            }
+        } else if (k == C) {                    // d_bq[r] = sum_o wk[r][o] dp0[o]
+            float v = 0.f;
+#pragma unroll
+            for (int o = 0; o < 4; ++o) v = fmaf(wk4[ri][o], dp[o], v);
+            g = v;
+        } else if (k < 2 * C + 1) {             // d_wk[r][o] = sum_cc wq[r][cc] dA[o][cc] + bq[r] dp0[o]
+            const int o = k - C - 1;
+            if (o < 4) {
+                float v[4] = {bqs[ri] * dp[o], 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int cc = 0; cc < 4; ++cc) v[cc] = fmaf(wq4[ri][cc], da[4 * o + cc], v[cc]);
+                g = (v[0] + v[1]) + (v[2] + v[3]);
+            }
+        }                                       // d_bk = 0 (softmax shift invariance: d/d lin_key.bias vanishes identically)
+        p.grad[e] = g;
+        if (adam) {
+            const float pn = adam_update(pv[i], g * p.gscale, mm[i], vv[i], p.lr, p.b1, p.b2, p.eps, p.wd, bc1, bc2_sqrt);
+            p.m[e] = mm[i]; p.v[e] = vv[i]; p.param[e] = pn;
+        }
+    }
+    if (ticket == NWG - 1) {                                    // every parameter workgroup has read the count: advance it
+        __hip_atomic_store(p.state + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(p.state, step_now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 __global__ void mesh_loss_seed_kernel(const float* x_top, const float* target, float* x_phys, float* g_top, float* loss_out,
                                       int64_t n_nodes, int d, int c, int l1, float gscale) {
     __shared__ float red[256];

@@ -350,6 +350,21 @@ int gadapt_step_tail_narrow(const float* slab, int n_rows, float* scratch, float
                             float grad_scale, float* a_out, float* p0_out,
                             const float* loss_partials /*nullable*/, int n_loss_partials, float* loss_out, int64_t loss_count,
                             int c, void* stream);
+/* gadapt_step_tail_narrow spread over row-owning workgroups (step_tail_narrow_spread_kernel; csrc/gadapt_tail_plan.h): a parameter
+ * workgroup owns whole rows r of the bucket - Wq[r][:], bq[r], Wk[r][:], bk[r] - so the chain rule of its entries reads only parameters
+ * it owns; every such workgroup sums the whole packed slab itself, in the one-workgroup kernel's order (bit-identical sums, nothing
+ * exchanged), and runs Adam on its one or two entries per thread; with loss partials the loss workgroup is one more, the last.  The step
+ * count, state = int32[2] {steps taken, 0}: every parameter workgroup reads state[0] with its first loads and uses state[0] + 1; one thread
+ * then takes a ticket in state[1] (as gadapt_adam_step_dev does) and the workgroup whose ticket is the last stores state[1] = 0 and
+ * state[0] = the new count.  No workgroup waits for another.  Gradient only: neither word is touched.  The host copies of the plan:
+ * plan_host: plan_out[6] = {rows per parameter workgroup, threads per workgroup, parameter workgroups, slots per thread, workgroups of
+ * the launch, tickets taken} with (has_loss != 0) or without loss partials; rows_host: rows of workgroup wg (the last may be short; -1: no
+ * such workgroup); entry_host: out3 = {entry of the flat bucket or -1, row within the workgroup, place in the row: 0..63 Wq, 64 bq,
+ * 65..128 Wk, 129 bk} of (wg, thread, slot); owner_host: out3 = {wg, thread, slot} of entry e. */
+int gadapt_narrow_tail_plan_host(int has_loss, int32_t* plan_out);
+int gadapt_narrow_tail_rows_host(int wg);
+int gadapt_narrow_tail_entry_host(int wg, int thread, int slot, int32_t* out3);
+int gadapt_narrow_tail_owner_host(int e, int32_t* out3);
 /* The top layer's backward target pass inside the forward launch.  T_{L-1}, the first launch of gadapt_block_backward_narrow_packed, needs
  * nothing from another workgroup: its g row is the loss seed, and the last layer's forward holds its x rows, alpha, {dt, scale} and A.
  * gadapt_block_forward_loss_narrow_top is gadapt_block_forward_loss_narrow given the backward's dxd_ws, edge_ws and packed slab.  Where
@@ -586,6 +601,10 @@ int gadapt_debug_set_narrow_top_in_forward(int on);
  * layers below the top as one launch per group of up to three fused stages where the step is eligible; 0: the launches of
  * gadapt_block_backward_narrow_packed.  The slab carries the same bits either way. */
 int gadapt_debug_set_narrow_backward_block(int on);
+/* Switch: 1 (the default; GADAPT_NARROW_TAIL_SPREAD=0 in the environment starts with 0) lets gadapt_step_tail_narrow launch the tail
+ * spread over row-owning workgroups (step_tail_narrow_spread_kernel); 0: the one-workgroup step_tail_narrow_kernel.  Results are
+ * bit-identical either way (tests/test_gpu_narrow_tail_spread.py). */
+int gadapt_debug_set_narrow_tail_spread(int on);
 /* Diagnostic: runtime-reported workgroups per CU of {forward, backward target, backward source}. */
 int gadapt_debug_occupancy(int c, int* out3);
 /* Diagnostic: the wave sum of the slab partials (wave_sum_desc: DPP and lane-swap steps) beside the xor butterfly 32, 16, .., 1 on
