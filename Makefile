@@ -20,7 +20,7 @@ HIPFLAGS   += -DGADAPT_DEV_C=$(DEV_C)
 endif
 UNITS      := gadapt_kernels gadapt_tu_fwd gadapt_tu_bwd_target gadapt_tu_bwd_source gadapt_tu_smallmesh gadapt_tu_sparse gadapt_tu_gat
 OBJS       := $(UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/csr_build.o
-SHARED     := $(CSRC)/gadapt_internal.h $(CSRC)/gadapt_common.inc $(CSRC)/gadapt_block_plan.h include/gadapt_hip.h
+SHARED     := $(CSRC)/gadapt_internal.h $(CSRC)/gadapt_common.inc $(CSRC)/gadapt_block_plan.h $(CSRC)/gadapt_narrow_plan.h include/gadapt_hip.h
 TAIL_PLAN  := $(CSRC)/gadapt_tail_plan.h
 
 all: $(LIB) $(FEM_LIB) $(MESH_LIB)
@@ -81,7 +81,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $(SHARED)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -c -o $@ $<
 
-$(OBJDIR)/csr_build.o: $(CSRC)/csr_build.cpp $(CSRC)/gadapt_block_plan.h $(TAIL_PLAN) include/gadapt_hip.h
+$(OBJDIR)/csr_build.o: $(CSRC)/csr_build.cpp $(CSRC)/gadapt_block_plan.h $(CSRC)/gadapt_narrow_plan.h $(TAIL_PLAN) include/gadapt_hip.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 

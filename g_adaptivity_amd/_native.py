@@ -89,6 +89,8 @@ PROTOTYPES = {
     'gadapt_block_backward_narrow_packed_below_top': (_I, [_G, _P, _I, _P, _P, _I, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
     # ... (the same arguments), top_done, block_ran
     'gadapt_block_backward_narrow_packed_block': (_I, [_G, _P, _I, _P, _P, _I, _I, _P, _L, _P, _L, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _P]),
+    'gadapt_narrow_step_plan_host': (_I, [_P, _P, _P, _I]),
+    'gadapt_narrow_step_plan': (_I, [_G, _I, _I, _I, _P, _I]),
     'gadapt_small_forward_lds_bytes': (_L, [_I, _I, _I]),
     'gadapt_small_forward': (_I, [_G, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _L, _L, _P, _I, _P, _I, _P, _P, _I, _P]),
     'gadapt_small_forward_loss': (_I, [_G, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _P, _P, _L, _L, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P]),

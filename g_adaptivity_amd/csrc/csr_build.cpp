@@ -9,6 +9,7 @@
 #include <vector>
 #include "gadapt_hip.h"
 #include "gadapt_block_plan.h"
+#include "gadapt_narrow_plan.h"
 #include "gadapt_tail_plan.h"
 
 extern "C" int gadapt_csr_build_host(const int64_t* src, const int64_t* dst, int64_t n_edges, int64_t n_nodes,
@@ -163,6 +164,23 @@ extern "C" int gadapt_narrow_bwd_block_margin_host(int halo, int n_stages) {
 extern "C" int gadapt_narrow_bwd_block_groups_host(int n_stages, int done) {
     if (n_stages < 2 || done < 0) return -1;
     return gadapt_bwd_block_groups(n_stages, done);
+}
+
+// The launch sequence of a narrow step (gadapt_narrow_plan.h), the pure function: facts [GADAPT_NARROW_FACTS] and switches [4] in the
+// order of the structs' members -> the plan as int32 words (layout: include/gadapt_hip.h).  Returns the words written.
+extern "C" int gadapt_narrow_step_plan_host(const int64_t* facts, const int32_t* switches, int32_t* plan_out, int cap) {
+    if (!facts || !switches || !plan_out || cap < 0) return GADAPT_E_BADARG;
+    const int64_t* v = facts;
+    if (v[3] < 1 || v[3] > INT32_MAX || !gadapt_narrow_sizes_ok(v[0], v[1], (int)v[2])) return GADAPT_E_BADARG;
+    for (int k = 2; k < GADAPT_NARROW_FACTS; ++k) if (v[k] < 0 || v[k] > INT32_MAX) return GADAPT_E_BADARG;
+    if ((v[5] != 0 && v[5] != 32 && v[5] != 64) || (v[6] != 0 && v[6] != 32 && v[6] != 64)) return GADAPT_E_BADARG;
+    const gadapt_narrow_facts f = {v[0], v[1], (int)v[2], (int)v[3], (int)v[4], (int)v[5], (int)v[6], (int)v[7], (int)v[8], (int)v[9], (int)v[10], (int)v[11],
+                                   (int)v[12], (int)v[13], (int)v[14], (int)v[15], (int)v[16], (int)v[17], (int)v[18], (int)v[19], (int)v[20], (int)v[21]};
+    const gadapt_narrow_switches s = {switches[0], switches[1] != 0, switches[2] != 0, switches[3] != 0};
+    if (s.fwd < 0 || s.fwd > 2) return GADAPT_E_BADARG;
+    const gadapt_narrow_plan p = gadapt_narrow_plan_of(&f, &s);
+    const int n = gadapt_narrow_plan_write(&p, plan_out, cap);
+    return n < 0 ? GADAPT_E_BADARG : n;
 }
 
 // The spread step tail of the narrow route (gadapt_tail_plan.h; step_tail_narrow_spread_kernel): the arithmetic the kernel and its launcher

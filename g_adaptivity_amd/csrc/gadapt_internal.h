@@ -1,6 +1,6 @@
 // gadapt_internal.h - what the translation units of libgadapt_hip.so share on the host side: build-time geometry parameters, error
 // reporting, the optional per-launch event pairs, launch helpers, the descriptions of a layer's forward and backward (LayerFwd, LayerBwd),
-// and the entry points one unit offers the others in terms of them.
+// and the entry points one unit offers the others in terms of them.  Which of them a narrow step launches: gadapt_narrow_plan.h.
 //
 // The library is built from several .hip files so that `make -j` compiles the kernel families in parallel and an edit to one
 // family rebuilds one unit (the hot kernels are large templates instantiated for six hidden sizes; as ONE unit the build took
@@ -31,6 +31,7 @@
 #include <vector>
 #include "gadapt_hip.h"
 #include "gadapt_block_plan.h"
+#include "gadapt_narrow_plan.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -185,8 +186,8 @@ template <int C> static int tiles_for(int64_t n_nodes) { return (int)((n_nodes +
 // top (nullable; with a loss, on a block launch that covers the top layer): that launch also runs the top layer's backward target pass,
 // one node per lane - dxd [N,4], the {alpha dt, ds} pairs in source order into edge_out, and ALL slab_rows packed slab rows
 // (GADAPT_NARROW_SLAB_ROW floats each), as grand_bwd_target_narrow_kernel with accumulate = 0 writes them.
-// *ran (nullable) is set to 1 by the launch that did.
-struct NarrowTop { float* dxd; float* edge_out; float* slab; int slab_rows; int* ran; };
+// Whether a launch does is the plan's decision (gadapt_narrow_plan.h: top_in_fwd).
+struct NarrowTop { float* dxd; float* edge_out; float* slab; int slab_rows; };
 struct FwdExtra { FieldSrc fs; float* x0c; LossArgs loss; int* n_partials_out; const float* cw; float* a_out; float* p0_out; const NarrowTop* top; };
 int gadapt_forward_computes_coeffs_c(const gadapt_graph* g, int c);
 #define GADAPT_LOSS_PARTIALS_MAX 4096  /* waves of a forward launch: GADAPT_FWD_MAX_BLOCKS workgroups of up to 8 waves */

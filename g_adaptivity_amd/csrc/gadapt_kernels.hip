@@ -144,22 +144,42 @@ extern "C" int gadapt_profile_reset(void) {
         default: break;                                                      \
     }
 
-// A switch of the launch sequence: 1 unless the environment variable starts with one of `others` ('0', or '0' / '2'), read at first
-// use - or whatever its setter (gadapt_debug_set_*) stored before or since.
-static int env_switch(std::atomic<int>& s, const char* name, const char* others) {
-    int v = s.load(std::memory_order_relaxed);
+// The switches of the launch sequence, one row each: 1 unless the environment variable starts with one of `others` ('0', or '0' / '2'),
+// read at first use - or whatever its setter (gadapt_debug_set_*) stored before or since.  What each one chooses between:
+// include/gadapt_hip.h at its setter; every choice is bit-identical with the form it replaces (the tests named there).
+//   SW_BWD_INPLACE        block backward: the source pass writes g_out over the dxd rows it has just read (same row, same lanes)
+//   SW_NARROW_FWD         narrow forward: 1 groups of up to 4 layers where the graph has a halo, else one node per lane per layer; 2 the
+//                         latter everywhere; 0 wide::fwd_kernel<XC = true> per layer
+//   SW_NARROW_BWD_FUSED   narrow backward: each source pass inside the next layer's target pass, or the pair of launches
+//   SW_NARROW_TOP_FWD     fused step: the top layer's target pass inside the block forward launch that seeds the loss
+//   SW_NARROW_BWD_BLOCK   the backward layers below the top as one launch per group of up to three fused stages
+//   SW_NARROW_TAIL_SPREAD the narrow tail spread over row-owning workgroups, or the one-workgroup kernel
+enum { SW_BWD_INPLACE, SW_NARROW_FWD, SW_NARROW_BWD_FUSED, SW_NARROW_TOP_FWD, SW_NARROW_BWD_BLOCK, SW_NARROW_TAIL_SPREAD, SW_COUNT };
+struct EnvSwitch { const char* name; const char* others; std::atomic<int> state{-1}; };
+static EnvSwitch g_switch[SW_COUNT] = {{"GADAPT_BWD_INPLACE", "0"},        {"GADAPT_NARROW_FWD", "02"},      {"GADAPT_NARROW_BWD_FUSED", "0"},
+                                       {"GADAPT_NARROW_TOP_FWD", "0"},     {"GADAPT_NARROW_BWD_BLOCK", "0"}, {"GADAPT_NARROW_TAIL_SPREAD", "0"}};
+static int env_switch(int k) {
+    EnvSwitch& s = g_switch[k];
+    int v = s.state.load(std::memory_order_relaxed);
     if (v < 0) {
-        const char* e = getenv(name);
-        v = (e && e[0] && strchr(others, e[0])) ? e[0] - '0' : 1;
-        s.store(v, std::memory_order_relaxed);
+        const char* e = getenv(s.name);
+        v = (e && e[0] && strchr(s.others, e[0])) ? e[0] - '0' : 1;
+        s.state.store(v, std::memory_order_relaxed);
     }
     return v;
 }
-// Block backward: the source pass writes g_out over the dxd rows it has just read (same row, same lanes: read-then-write), so a
-// layer pair touches two [N,C] buffers instead of three.  GADAPT_BWD_INPLACE=0 / gadapt_debug_set_backward_inplace(0): separate buffers.
-static std::atomic<int> g_bwd_inplace{-1};
-static bool bwd_inplace_enabled() { return env_switch(g_bwd_inplace, "GADAPT_BWD_INPLACE", "0") == 1; }
-extern "C" int gadapt_debug_set_backward_inplace(int on) { g_bwd_inplace.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
+static int set_switch(int k, int v) { g_switch[k].state.store(v, std::memory_order_relaxed); return GADAPT_OK; }
+extern "C" int gadapt_debug_set_backward_inplace(int on) { return set_switch(SW_BWD_INPLACE, on ? 1 : 0); }
+extern "C" int gadapt_debug_set_narrow_forward(int on) { return set_switch(SW_NARROW_FWD, on == 0 ? 0 : (on == 2 ? 2 : 1)); }
+extern "C" int gadapt_debug_set_narrow_backward_fused(int on) { return set_switch(SW_NARROW_BWD_FUSED, on ? 1 : 0); }
+extern "C" int gadapt_debug_set_narrow_top_in_forward(int on) { return set_switch(SW_NARROW_TOP_FWD, on ? 1 : 0); }
+extern "C" int gadapt_debug_set_narrow_backward_block(int on) { return set_switch(SW_NARROW_BWD_BLOCK, on ? 1 : 0); }
+extern "C" int gadapt_debug_set_narrow_tail_spread(int on) { return set_switch(SW_NARROW_TAIL_SPREAD, on ? 1 : 0); }
+static bool bwd_inplace_enabled() { return env_switch(SW_BWD_INPLACE) == 1; }
+// the four that decide a narrow step's launches, read in one place
+static gadapt_narrow_switches narrow_switches() {
+    return {env_switch(SW_NARROW_FWD), env_switch(SW_NARROW_BWD_FUSED) == 1, env_switch(SW_NARROW_TOP_FWD) == 1, env_switch(SW_NARROW_BWD_BLOCK) == 1};
+}
 
 // one layer's backward: target pass, then - when a gradient is to be passed on - the source pass
 static int launch_bwd(int c, const gadapt_graph* g, const LayerBwd& b, hipStream_t st) {
@@ -460,111 +480,82 @@ extern "C" int gadapt_adam_step_dev(float* param, const float* grad, float* exp_
 // ------------------------------------------------------------------------------------------------
 // L-step Euler block (GNN.py:273-291)
 // ------------------------------------------------------------------------------------------------
-// Narrow-route forward layers.  GADAPT_NARROW_FWD / gadapt_debug_set_narrow_forward:
-//   1 (default)  the default choice: groups of up to 4 layers in one launch (wide::fwd_narrow_block_kernel) where the graph is
-//                registered with a halo and the conv is shared, else one wide::fwd_narrow_kernel launch per layer;
-//   2            wide::fwd_narrow_kernel per layer everywhere;
-//   0            wide::fwd_kernel<XC = true> per layer.
-// All three are bit-identical (tests/test_gpu_narrow_forward.py, tests/test_gpu_narrow_block_forward.py).
-static std::atomic<int> g_narrow_fwd{-1};
-static int narrow_fwd_mode() { return env_switch(g_narrow_fwd, "GADAPT_NARROW_FWD", "02"); }
-extern "C" int gadapt_debug_set_narrow_forward(int on) { g_narrow_fwd.store(on == 0 ? 0 : (on == 2 ? 2 : 1), std::memory_order_relaxed); return GADAPT_OK; }
-// The halo of the block launch is a property of the graph that only the host build can know (gadapt_narrow_block_halo_host reads the
-// CSR on the host; gadapt_graph holds device pointers and its layout is frozen at ABI 9).  The caller registers it once per graph,
-// keyed by what identifies the graph's device arrays; an unregistered graph has halo 0 and keeps the per-layer launches.
-struct BlockHaloEntry { const void* rowptr_t; const void* ell_t; int32_t n_nodes, n_edges; int halo; };
-static std::mutex g_block_halo_mu;
-static std::vector<BlockHaloEntry> g_block_halo;
-static bool block_halo_is(const BlockHaloEntry& e, const gadapt_graph* g) {
-    return e.rowptr_t == g->rowptr_t && e.ell_t == g->ell_t && e.n_nodes == g->n_nodes && e.n_edges == g->n_edges;
+// The narrow route (hidden 64, every layer on [N,4] rows).  Which launches a step runs is decided by gadapt_narrow_plan_of
+// (gadapt_narrow_plan.h) from the facts gathered here and the switches above; the entry points below walk the plan.
+//
+// The halo of a block launch is a property of the graph that only the host build can know (gadapt_narrow_block_halo_host reads the CSR
+// on the host; gadapt_graph holds device pointers and its layout is frozen at ABI 9).  The caller registers it once per graph and side
+// - target: the in-edges (rowptr_t, ell_t), the forward groups; source: the out-edges (rowptr_s, ell_s), the backward groups - keyed by
+// what identifies that side's device arrays; an unregistered graph has halo 0.
+struct HaloEntry { const void* rowptr; const void* ell; int32_t n_nodes, n_edges; int halo; };
+enum { SIDE_TARGET, SIDE_SOURCE };
+static std::mutex g_halo_mu;
+static std::vector<HaloEntry> g_halo[2];
+static HaloEntry halo_key(const gadapt_graph* g, int side) {
+    return side == SIDE_TARGET ? HaloEntry{g->rowptr_t, g->ell_t, g->n_nodes, g->n_edges, 0} : HaloEntry{g->rowptr_s, g->ell_s, g->n_nodes, g->n_edges, 0};
+}
+static bool halo_is(const HaloEntry& e, const HaloEntry& k) { return e.rowptr == k.rowptr && e.ell == k.ell && e.n_nodes == k.n_nodes && e.n_edges == k.n_edges; }
+static int halo_register(const gadapt_graph* g, int side, int halo, const char* refusal) {
+    if (!g || g->n_nodes <= 0 || (halo != 0 && halo != 32 && halo != 64)) return fail(GADAPT_E_BADARG, refusal);
+    HaloEntry k = halo_key(g, side);
+    if (!k.rowptr || !k.ell) return fail(GADAPT_E_BADARG, refusal);
+    std::vector<HaloEntry>& v = g_halo[side];
+    std::lock_guard<std::mutex> lk(g_halo_mu);
+    for (size_t i = 0; i < v.size(); ++i)
+        if (halo_is(v[i], k)) { v[i] = v.back(); v.pop_back(); break; }
+    k.halo = halo;
+    if (halo) v.push_back(k);
+    return GADAPT_OK;
+}
+static int halo_registered(const gadapt_graph* g, int side) {
+    const HaloEntry k = halo_key(g, side);
+    if (!k.rowptr || !k.ell) return 0;
+    std::lock_guard<std::mutex> lk(g_halo_mu);
+    for (const HaloEntry& e : g_halo[side])
+        if (halo_is(e, k)) return e.halo;
+    return 0;
 }
 extern "C" int gadapt_narrow_block_register(const gadapt_graph* g, int halo) {
-    if (!g || !g->rowptr_t || !g->ell_t || g->n_nodes <= 0 || (halo != 0 && halo != 32 && halo != 64))
-        return fail(GADAPT_E_BADARG, "narrow_block_register: a graph with its ELL copy, halo 0 (forget), 32 or 64");
-    std::lock_guard<std::mutex> lk(g_block_halo_mu);
-    for (size_t k = 0; k < g_block_halo.size(); ++k)
-        if (block_halo_is(g_block_halo[k], g)) { g_block_halo[k] = g_block_halo.back(); g_block_halo.pop_back(); break; }
-    if (halo) g_block_halo.push_back(BlockHaloEntry{g->rowptr_t, g->ell_t, g->n_nodes, g->n_edges, halo});
-    return GADAPT_OK;
-}
-// Batches of fewer tiles than this keep the per-layer launches.  1: none do - a tile's chain of four layers is as long in a small
-// batch as in a large one, and the per-layer launches pay their four kernel boundaries either way (docs/measurements.md, "One launch
-// for the forward layers").
-#define GADAPT_NARROW_BLOCK_MIN_TILES 1
-// the halo the block launch runs with on this graph at this hidden size under the current forward choice, or 0: per-layer launches
-static int narrow_block_halo(const gadapt_graph* g, int c) {
-    if (!g || narrow_fwd_mode() != 1 || !gadapt_narrow_takes_c(g, c) || !gadapt_narrow_block_tiles_ok_c(g)) return 0;
-    if ((g->n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE < GADAPT_NARROW_BLOCK_MIN_TILES) return 0;
-    std::lock_guard<std::mutex> lk(g_block_halo_mu);
-    for (const BlockHaloEntry& e : g_block_halo)
-        if (block_halo_is(e, g)) return e.halo;
-    return 0;
-}
-extern "C" int gadapt_narrow_block_halo(const gadapt_graph* g, int c) { return narrow_block_halo(g, c); }
-// Narrow-route backward: each source pass inside the next layer's target pass (grand_bwd_target_fused_narrow_kernel, default), or the
-// pair of launches per layer, bit-identical (tests/test_gpu_narrow_backward.py).  GADAPT_NARROW_BWD_FUSED=0 /
-// gadapt_debug_set_narrow_backward_fused(0): the pairs.
-static std::atomic<int> g_narrow_bwd_fused{-1};
-static bool narrow_bwd_fused_enabled() { return env_switch(g_narrow_bwd_fused, "GADAPT_NARROW_BWD_FUSED", "0") == 1; }
-extern "C" int gadapt_debug_set_narrow_backward_fused(int on) { g_narrow_bwd_fused.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
-// Narrow route, fused step: the top layer's backward target pass T_{L-1} inside the block forward launch that seeds the loss
-// (wide::fwd_narrow_block_kernel<., ., TOP>, gadapt_block_forward_loss_narrow_top), default; bit-identical with the launch it replaces
-// (tests/test_gpu_narrow_top_in_forward.py).  GADAPT_NARROW_TOP_FWD=0 / gadapt_debug_set_narrow_top_in_forward(0): the separate launch.
-static std::atomic<int> g_narrow_top_fwd{-1};
-static bool narrow_top_fwd_enabled() { return env_switch(g_narrow_top_fwd, "GADAPT_NARROW_TOP_FWD", "0") == 1; }
-extern "C" int gadapt_debug_set_narrow_top_in_forward(int on) { g_narrow_top_fwd.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
-// THE eligibility rule of that form, for a fused step on graph g at hidden size c whose forward is a block launch of halo `halo` over one
-// shared conv: a loss target and the three backward buffers; the ELL in-table with rows of at most 8 and the source-order positions;
-// edges; and a slab grid that gives every lane of the standalone launch at most one node (N <= 256 rows - with the 512-row cap N <= 131072),
-// so that a slab row is the sum over ONE 256-node range.  Everything else keeps today's launches.
-static bool narrow_top_eligible(const gadapt_graph* g, int c, int halo, const float* target, const NarrowTop& t) {
-    if (!narrow_top_fwd_enabled() || !halo || !target || !t.dxd || !t.edge_out || !t.slab) return false;
-    if (!g->ell_t || !g->tpos_s || g->n_edges <= 0 || gadapt_narrow_kmax_c(g) > GADAPT_MAXD) return false;
-    return t.slab_rows > 0 && (int64_t)g->n_nodes <= 256 * (int64_t)t.slab_rows;
-}
-
-// The backward layers below the top in one launch (grand_bwd_narrow_block_kernel; gadapt_block_backward_narrow_packed_block), default;
-// the slab carries the bits of the launches it replaces (tests/test_gpu_narrow_block_backward.py).  GADAPT_NARROW_BWD_BLOCK=0 /
-// gadapt_debug_set_narrow_backward_block(0): those launches.
-static std::atomic<int> g_narrow_bwd_block{-1};
-static bool narrow_bwd_block_enabled() { return env_switch(g_narrow_bwd_block, "GADAPT_NARROW_BWD_BLOCK", "0") == 1; }
-extern "C" int gadapt_debug_set_narrow_backward_block(int on) { g_narrow_bwd_block.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
-// Its halo is that of the SOURCE-ordered CSR (gadapt_narrow_block_halo_host on (rowptr_s, col_s): rows of at most 8 out-edges, every
-// out-neighbour within the halo of the node's aligned 32-node group), registered like the forward's and keyed by the source arrays.
-static std::vector<BlockHaloEntry> g_block_halo_s;              // (rowptr_t / ell_t fields hold rowptr_s / ell_s; guarded by g_block_halo_mu)
-static bool block_halo_s_is(const BlockHaloEntry& e, const gadapt_graph* g) {
-    return e.rowptr_t == g->rowptr_s && e.ell_t == g->ell_s && e.n_nodes == g->n_nodes && e.n_edges == g->n_edges;
+    return halo_register(g, SIDE_TARGET, halo, "narrow_block_register: a graph with its ELL copy, halo 0 (forget), 32 or 64");
 }
 extern "C" int gadapt_narrow_block_register_source(const gadapt_graph* g, int halo) {
-    if (!g || !g->rowptr_s || !g->ell_s || g->n_nodes <= 0 || (halo != 0 && halo != 32 && halo != 64))
-        return fail(GADAPT_E_BADARG, "narrow_block_register_source: a graph with the ELL copy of its out-edges, halo 0 (forget), 32 or 64");
-    std::lock_guard<std::mutex> lk(g_block_halo_mu);
-    for (size_t k = 0; k < g_block_halo_s.size(); ++k)
-        if (block_halo_s_is(g_block_halo_s[k], g)) { g_block_halo_s[k] = g_block_halo_s.back(); g_block_halo_s.pop_back(); break; }
-    if (halo) g_block_halo_s.push_back(BlockHaloEntry{g->rowptr_s, g->ell_s, g->n_nodes, g->n_edges, halo});
-    return GADAPT_OK;
+    return halo_register(g, SIDE_SOURCE, halo, "narrow_block_register_source: a graph with the ELL copy of its out-edges, halo 0 (forget), 32 or 64");
 }
-static int narrow_block_halo_source(const gadapt_graph* g) {
-    if (!g->rowptr_s || !g->ell_s) return 0;
-    std::lock_guard<std::mutex> lk(g_block_halo_mu);
-    for (const BlockHaloEntry& e : g_block_halo_s)
-        if (block_halo_s_is(e, g)) return e.halo;
-    return 0;
+
+// What is known about a step on graph g (not NULL) at hidden size c, gathered once per entry-point call: the graph's side (one registry
+// lookup per side) and the call's (flags).
+enum { NF_SHARED = 1, NF_PACKED = 2, NF_TARGET = 4, NF_BUFFERS = 8, NF_COEFFS = 16, NF_TOP_DONE = 32, NF_MAY_BLOCK = 64 };
+static_assert(GADAPT_NARROW_ROW_MAX == GADAPT_MAXD, "the rows the one-node-per-lane kernels take from registers");
+static gadapt_narrow_facts narrow_facts(const gadapt_graph* g, int c, int n_layers, int flags) {
+    gadapt_narrow_facts f{};
+    f.n_nodes = g->n_nodes; f.n_edges = g->n_edges; f.c = c; f.n_layers = n_layers;
+    f.ell_t = g->ell_t != nullptr; f.ell_s = g->ell_s != nullptr; f.tpos_s = g->tpos_s != nullptr;
+    f.rowptr_s = g->rowptr_s != nullptr; f.col_s = g->col_s != nullptr;
+    f.shared = (flags & NF_SHARED) != 0; f.packed = (flags & NF_PACKED) != 0; f.target = (flags & NF_TARGET) != 0;
+    f.buffers = (flags & NF_BUFFERS) != 0; f.coeffs = (flags & NF_COEFFS) != 0; f.top_done = (flags & NF_TOP_DONE) != 0;
+    f.may_block = (flags & NF_MAY_BLOCK) != 0;
+    f.takes = g->n_nodes > 0 && gadapt_narrow_takes_c(g, c);
+    if (!f.takes) return f;                                      // (no launches: the rest is not looked at)
+    f.halo_t = halo_registered(g, SIDE_TARGET); f.halo_s = halo_registered(g, SIDE_SOURCE);
+    f.kmax = gadapt_narrow_kmax_c(g);
+    f.slab_rows = gadapt_slab_rows_c(g->n_nodes, c);
+    f.tiles_ok = gadapt_narrow_block_tiles_ok_c(g);
+    return f;
 }
-// THE eligibility rule of that launch, for the backward of n_layers layers on graph g (arguments already checked as
-// gadapt_block_backward_narrow_packed checks them): the switch, and the switch of the fused launches whose stages it runs
-// (gadapt_debug_set_narrow_backward_fused(0) asks for the pairs of launches); a registered source halo (which also says that no out-row is longer than
-// 8); the packed slab over one shared conv; edges; both ELL tables and the source-order positions, in-rows of at most 8; a slab row that
-// is the sum over ONE 256-node range; at least two fused stages; and the second edge buffer behind dxd (2 E <= (c - 4) N, as the fused
-// launches need it) - where the stages run as more than one launch (n_layers > 4), also a second dxd buffer behind that (2 E <= (c - 8) N).
-// Returns the halo, or 0: today's launches.
-static int narrow_bwd_block_eligible(const gadapt_graph* g, int c, int n_layers, int packed, int64_t a_stride, int64_t p0_stride) {
-    if (!narrow_bwd_block_enabled() || !narrow_bwd_fused_enabled() || !packed || a_stride != 0 || p0_stride != 0 || n_layers < 3 || c != 64) return 0;
-    if (g->n_edges <= 0 || !g->ell_t || !g->ell_s || !g->tpos_s || !g->rowptr_s || gadapt_narrow_kmax_c(g) > GADAPT_MAXD) return 0;
-    const int slab_rows = gadapt_slab_rows_c(g->n_nodes, c);
-    if (slab_rows <= 0 || (int64_t)g->n_nodes > 256 * (int64_t)slab_rows) return 0;
-    if (2 * (int64_t)g->n_edges > (int64_t)(c - (n_layers > GADAPT_NARROW_BWD_BLOCK_STAGES + 1 ? 8 : 4)) * g->n_nodes) return 0;
-    return narrow_block_halo_source(g);
+static gadapt_narrow_plan narrow_plan(const gadapt_graph* g, int c, int n_layers, int flags) {
+    const gadapt_narrow_facts f = narrow_facts(g, c, n_layers, flags);
+    const gadapt_narrow_switches s = narrow_switches();
+    return gadapt_narrow_plan_of(&f, &s);
+}
+// the halo the forward groups run with on this graph at this hidden size under the current forward choice, or 0: per-layer launches
+extern "C" int gadapt_narrow_block_halo(const gadapt_graph* g, int c) { return g ? narrow_plan(g, c, 1, NF_SHARED).fwd_halo : 0; }
+// The plan the library would run right now on this graph (registered halos, live switches), as int32 words; nothing is launched.
+extern "C" int gadapt_narrow_step_plan(const gadapt_graph* g, int c, int n_layers, int flags, int32_t* plan_out, int cap) {
+    if (!g || !plan_out || n_layers < 1 || flags < 0 || flags >= 2 * NF_MAY_BLOCK || !gadapt_narrow_sizes_ok(g->n_nodes, g->n_edges, c))
+        return fail(GADAPT_E_BADARG, "narrow_step_plan: a graph, 1 or more layers, known flags, somewhere to write, sizes whose offsets fit 32 bits");
+    const gadapt_narrow_plan p = narrow_plan(g, c, n_layers, flags);
+    const int n = gadapt_narrow_plan_write(&p, plan_out, cap);
+    return n < 0 ? fail(GADAPT_E_BADARG, "narrow_step_plan: cap is smaller than the plan (18 + 39 n_layers words always hold one)") : n;
 }
 
 // A block of n_layers Euler steps as its entry points see it (built once their checks have passed): where layer l finds its input slot,
@@ -587,15 +578,39 @@ struct Block {
 };
 // The extras of a fused step for one launch of its block: the node fields and the weights (in-kernel coefficients) go to the first
 // launch, the loss to the last
-static FwdExtra slice_extra(const FwdExtra& e, bool first, bool last) {
+static FwdExtra slice_extra(const FwdExtra& e, bool first, bool last, bool top) {
     FwdExtra s{};
     if (first) { s.fs = e.fs; s.x0c = e.x0c; s.cw = e.cw; s.a_out = e.a_out; s.p0_out = e.p0_out; }
-    if (last) { s.loss = e.loss; s.n_partials_out = e.n_partials_out; s.top = e.top; }
+    if (last) { s.loss = e.loss; s.n_partials_out = e.n_partials_out; }
+    if (top) s.top = e.top;
     return s;
 }
+// The forward launches of a narrow plan: [N,4] slot in, [N,4] slot out (the last launch: the head rows).  A later group reads its input
+// slot from global memory, where the owners of the group before wrote it (the backward needs it there anyway).
+static int walk_forward_narrow(const Block& b, const gadapt_narrow_plan& plan, float* x_top4, const FwdExtra* extra, hipStream_t st) {
+    for (int i = 0; i < plan.n_fwd; ++i) {
+        const gadapt_narrow_launch r = gadapt_narrow_fwd_launch(&plan, i);
+        const int l = r.layer;
+        FwdExtra ex_l{};
+        if (extra) ex_l = slice_extra(*extra, r.first, r.last, r.top);
+        LayerFwd f{.x_in = b.x(l), .a = b.a(l), .p0 = b.p0(l), .lp = b.lp(l), .alpha_out = b.alpha(l), .extra = extra ? &ex_l : nullptr};
+        int rc;
+        if (r.kind == GADAPT_NARROW_L_FWD_GROUP) {
+            f.x_top4 = b.x(l + 1);
+            rc = gadapt_launch_fwd_narrow_block_c(b.c, b.g, f, plan.fwd_halo, r.count, (int64_t)b.nc, b.g->n_edges, r.last ? x_top4 : nullptr, st);
+        } else {
+            f.x_top4 = r.last ? x_top4 : b.x(l + 1);
+            f.x_cols = 4;                                        // (read by the wide kernel only)
+            rc = r.kind == GADAPT_NARROW_L_FWD_NODE ? gadapt_launch_fwd_narrow_c(b.c, b.g, f, st) : gadapt_launch_fwd_c(b.c, b.g, f, st);
+        }
+        if (rc) return rc;
+    }
+    return GADAPT_OK;
+}
+// narrow: the narrow route, by the plan its caller obtained - or, given none, by the one of a plain forward
 static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers, const float* a, int64_t a_stride,
                          const float* p0, int64_t p0_stride, const float* layer_params, float* alpha_all, float* x_top4,
-                         int c, void* stream, const FwdExtra* extra, bool narrow = false) {
+                         int c, void* stream, const FwdExtra* extra, bool narrow = false, const gadapt_narrow_plan* plan = nullptr) {
     if (int rc = check_graph(g, c)) return rc;
     if (!x_all || n_layers <= 0 || !a || !p0 || !layer_params) return fail(GADAPT_E_BADARG, "block_forward: bad argument");
     if (x0_cols != 0 && (x0_cols != 4 || n_layers < 2 || c < 8)) return fail(GADAPT_E_BADARG, "block_forward: compact x0 needs 4 columns, >= 2 layers, hidden >= 8");
@@ -604,30 +619,16 @@ static int block_forward(const gadapt_graph* g, float* x_all, int x0_cols, int n
     const Block b{.g = g, .c = c, .n_layers = n_layers, .x_all = x_all, .nc = (size_t)g->n_nodes * c, .a_all = a, .a_stride = a_stride, .p0_all = p0,
                   .p0_stride = p0_stride, .layer_params = layer_params, .alpha_all = alpha_all};
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // narrow route, one shared conv, a registered halo: groups of up to 4 layers, one launch each (L = 4: one, L = 6: two).  A later
-    // group reads its input slot from global memory, where the owners of the group before wrote it (the backward needs it there anyway).
-    const int halo = (narrow && a_stride == 0 && p0_stride == 0) ? narrow_block_halo(g, c) : 0;
-    const int per_launch = halo ? GADAPT_NARROW_BLOCK_LAYERS : 1;
-    for (int l = 0; l < n_layers; l += per_launch) {
-        const int kl = n_layers - l < per_launch ? n_layers - l : per_launch;
-        const bool last = (l + kl == n_layers);
-        FwdExtra ex_l{};
-        if (extra) ex_l = slice_extra(*extra, l == 0, last);
-        if (!halo) ex_l.top = nullptr;                           // (the block launch only: narrow_top_eligible)
-        LayerFwd f{.x_in = b.x(l), .a = b.a(l), .p0 = b.p0(l), .lp = b.lp(l), .alpha_out = b.alpha(l), .extra = extra ? &ex_l : nullptr};
+    if (narrow) return walk_forward_narrow(b, plan ? *plan : narrow_plan(g, c, n_layers, (a_stride == 0 && p0_stride == 0) ? NF_SHARED : 0), x_top4, extra, st);
+    for (int l = 0; l < n_layers; ++l) {
+        const bool last = (l + 1 == n_layers);
         int rc;
-        if (halo) {
-            f.x_top4 = b.x(l + 1);
-            rc = gadapt_launch_fwd_narrow_block_c(c, g, f, halo, kl, (int64_t)b.nc, g->n_edges, last ? x_top4 : nullptr, st);
-        } else if (narrow) {                                     // [N,4] slot in, [N,4] slot out (the last layer: the head rows)
-            f.x_top4 = last ? x_top4 : b.x(l + 1);
-            f.x_cols = 4;                                        // (read by the wide kernel only: gadapt_debug_set_narrow_forward(0))
-            rc = narrow_fwd_mode() != 0 ? gadapt_launch_fwd_narrow_c(c, g, f, st) : gadapt_launch_fwd_c(c, g, f, st);
-        } else if ((l == 0 && x0_cols) || (last && x_top4)) {    // compact input and/or compact-only output
-            f.x_out = (last && x_top4) ? nullptr : b.x(l + 1);
-            f.x_top4 = last ? x_top4 : nullptr;
-            f.x_cols = l == 0 ? x0_cols : 0;
-            rc = gadapt_launch_fwd_c(c, g, f, st);
+        if ((l == 0 && x0_cols) || (last && x_top4)) {           // compact input and/or compact-only output
+            FwdExtra ex_l{};
+            if (extra) ex_l = slice_extra(*extra, l == 0, last, false);
+            rc = gadapt_launch_fwd_c(c, g, LayerFwd{.x_in = b.x(l), .x_out = (last && x_top4) ? nullptr : b.x(l + 1), .x_top4 = last ? x_top4 : nullptr,
+                                                    .a = b.a(l), .p0 = b.p0(l), .lp = b.lp(l), .alpha_out = b.alpha(l), .x_cols = l == 0 ? x0_cols : 0,
+                                                    .extra = extra ? &ex_l : nullptr}, st);
         } else {
             rc = gadapt_layer_forward(g, b.x(l), b.x(l + 1), b.a(l), b.p0(l), b.lp(l), b.alpha(l), 0, c, stream);
         }
@@ -656,7 +657,7 @@ extern "C" int gadapt_forward_computes_coeffs(const gadapt_graph* g, int c) { re
 static int block_forward_loss(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor, const float* uu_tensor,
                               int n_layers, float* a, float* p0, const float* param, const float* layer_params, float* alpha_all, float* x_top4,
                               const float* target, int d, int l1, float* seed, float* loss_partials, int c, void* stream, bool narrow,
-                              NarrowTop* top = nullptr) {       // top: the backward buffers (its slab_rows is filled in here); *top->ran reports
+                              NarrowTop* top = nullptr, int* top_ran = nullptr) {   // top: the backward's buffers; *top_ran: the plan's report
     if (!x_comp || dim < 1 || dim > 4 || dim + (f_tensor ? 1 : 0) + (uu_tensor ? 1 : 0) > 4)
         return fail(GADAPT_E_BADARG, "block_forward_loss: 1..4 coordinates, coordinates + extras <= 4 columns");
     // target == NULL: no loss - the evaluation forward on the node fields (inference.GraphedForward issues it as this one call)
@@ -666,10 +667,17 @@ static int block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
     // x_all slot 0 starts with the compact [N,4] layer-0 input (written by the layer-0 launch for the layer-0 backward)
     if (param && !gadapt_forward_computes_coeffs_c(g, c))
         return fail(GADAPT_E_BADARG, "block_forward_loss: param given, but this graph / hidden size does not compute the coefficients in its layer-0 launch (gadapt_forward_computes_coeffs)");
-    // narrow route: the layer-0 launch leaves one row of A / p0 per workgroup 0..63 and has one workgroup per 256-node step
-    // (wide::fwd_narrow_kernel) or per 512-node tile (wide::fwd_narrow_block_kernel), so a batch of fewer than 64 of them gets its coefficients from the coefficient launch first (the same arithmetic: coeffs_fwd_body) and
-    // the layers take them as given
-    if (narrow && param && (narrow_block_halo(g, c) ? (g->n_nodes + GADAPT_NARROW_TILE - 1) / GADAPT_NARROW_TILE : (g->n_nodes + 255) / 256) < 64) {
+    gadapt_narrow_plan plan{};
+    if (narrow) {
+        const gadapt_narrow_facts f = narrow_facts(g, c, n_layers, NF_SHARED | (target ? NF_TARGET : 0) | (param ? NF_COEFFS : 0) |
+                                                                   ((top && top->dxd && top->edge_out && top->slab) ? NF_BUFFERS : 0));
+        const gadapt_narrow_switches s = narrow_switches();
+        plan = gadapt_narrow_plan_of(&f, &s);
+        if (top) top->slab_rows = f.slab_rows;
+    }
+    // narrow route: the layer-0 launch leaves one row of A / p0 per workgroup 0..63, so a batch of fewer workgroups than that gets its
+    // coefficients from the coefficient launch first (the same arithmetic: coeffs_fwd_body) and the layers take them as given
+    if (plan.coeffs_first) {
         if (!a || !p0) return fail(GADAPT_E_BADARG, "block_forward_loss (narrow): param given without the coefficient buffers");
         const BucketAt at = bucket_at(c);
         if (int rc = gadapt_coeffs_forward(param, param + at.bq, param + at.wk, a, p0, c, stream)) return rc;
@@ -677,11 +685,9 @@ static int block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
     }
     FwdExtra ex{FieldSrc{x_comp, f_tensor, uu_tensor, dim}, x_all,
                 LossArgs{target, seed, loss_partials, d, l1 ? 1 : 0, 1.0f / (float)((int64_t)g->n_nodes * (d > 0 ? d : 1))}, &n_partials, param, a, p0};
-    if (top && narrow && c == 64) {                              // the top layer's target pass in the last forward launch, where eligible
-        top->slab_rows = gadapt_slab_rows_c(g->n_nodes, c);
-        if (narrow_top_eligible(g, c, narrow_block_halo(g, c), target, *top)) ex.top = top;
-    }
-    if (int rc = block_forward(g, x_all, 4, n_layers, a, 0, p0, 0, layer_params, alpha_all, x_top4, c, stream, &ex, narrow)) return rc;
+    if (plan.top_in_fwd) ex.top = top;                           // the top layer's target pass in the last forward launch
+    if (int rc = block_forward(g, x_all, 4, n_layers, a, 0, p0, 0, layer_params, alpha_all, x_top4, c, stream, &ex, narrow, &plan)) return rc;
+    if (top_ran) *top_ran = plan.top_in_fwd;
     if (!target) return 0;
     if (n_partials <= 0 || n_partials > GADAPT_LOSS_PARTIALS_MAX) return fail(GADAPT_E_RUNTIME, "block_forward_loss: loss partial count out of range");
     return n_partials;
@@ -699,19 +705,19 @@ extern "C" int gadapt_block_forward_loss_narrow(const gadapt_graph* g, float* x_
     return block_forward_loss(g, x_all, x_comp, dim, f_tensor, uu_tensor, n_layers, a, p0, param, layer_params, alpha_all, x_top4, target, d, l1,
                               seed, loss_partials, c, stream, true);
 }
-// gadapt_block_forward_loss_narrow given the backward's buffers: where the step is eligible (narrow_top_eligible) its last forward launch
-// also runs the top layer's backward target pass - dxd_ws, the pairs in edge_ws and every row of the packed slab as T_{L-1} of
-// gadapt_block_backward_narrow_packed leaves them - and *top_ran = 1: the backward then starts below it
-// (gadapt_block_backward_narrow_packed_below_top).  Otherwise today's launches and *top_ran = 0.
+// gadapt_block_forward_loss_narrow given the backward's buffers: where the plan says so (top_in_fwd) its last forward launch also runs
+// the top layer's backward target pass - dxd_ws, the pairs in edge_ws and every row of the packed slab as T_{L-1} of
+// gadapt_block_backward_narrow_packed leaves them - and *top_ran = 1: the backward then starts below it (top_done).  Otherwise the
+// launches of gadapt_block_forward_loss_narrow and *top_ran = 0.
 extern "C" int gadapt_block_forward_loss_narrow_top(const gadapt_graph* g, float* x_all, const float* x_comp, int dim, const float* f_tensor,
                                                     const float* uu_tensor, int n_layers, float* a, float* p0, const float* param, const float* layer_params,
                                                     float* alpha_all, float* x_top4, const float* target, int d, int l1, float* seed, float* loss_partials,
                                                     float* dxd_ws, float* edge_ws, float* slab, int* top_ran, int c, void* stream) {
     if (!top_ran) return fail(GADAPT_E_BADARG, "block_forward_loss_narrow_top: nowhere to report whether the top target pass ran");
     *top_ran = 0;
-    NarrowTop top{dxd_ws, edge_ws, slab, 0, top_ran};
+    NarrowTop top{dxd_ws, edge_ws, slab, 0};
     return block_forward_loss(g, x_all, x_comp, dim, f_tensor, uu_tensor, n_layers, a, p0, param, layer_params, alpha_all, x_top4, target, d, l1,
-                              seed, loss_partials, c, stream, true, n_layers >= 2 ? &top : nullptr);
+                              seed, loss_partials, c, stream, true, &top, top_ran);
 }
 
 extern "C" int gadapt_step_tail(const float* slab, int n_rows, float* scratch, float* param, float* grad, float* exp_avg, float* exp_avg_sq,
@@ -750,13 +756,6 @@ extern "C" int gadapt_step_tail(const float* slab, int n_rows, float* scratch, f
     return gadapt_coeffs_forward(param, param + at.bq, param + at.wk, a_out, p0_out, c, stream);
 }
 
-// The narrow route's tail spread over row-owning workgroups (step_tail_narrow_spread_kernel; gadapt_tail_plan.h) - the same bits as the
-// one-workgroup kernel (tests/test_gpu_narrow_tail_spread.py).  GADAPT_NARROW_TAIL_SPREAD=0 / gadapt_debug_set_narrow_tail_spread(0):
-// step_tail_narrow_kernel.
-static std::atomic<int> g_narrow_tail_spread{-1};
-static bool narrow_tail_spread_enabled() { return env_switch(g_narrow_tail_spread, "GADAPT_NARROW_TAIL_SPREAD", "0") == 1; }
-extern "C" int gadapt_debug_set_narrow_tail_spread(int on) { g_narrow_tail_spread.store(on ? 1 : 0, std::memory_order_relaxed); return GADAPT_OK; }
-
 // The narrow route's tail over the PACKED slab (gadapt_block_backward_narrow_packed) as ONE launch, hidden 64: step_tail_narrow_kernel.
 // The forms of gadapt_step_tail that read a slab - the whole tail, and (no moments) the flat gradient only; bit-identical to them on
 // the equivalent full-width slab (tests/test_gpu_narrow_tail.py).  The gradient-given form has no slab: gadapt_step_tail.
@@ -774,7 +773,7 @@ extern "C" int gadapt_step_tail_narrow(const float* slab, int n_rows, float* scr
     hipStream_t st = static_cast<hipStream_t>(stream);
     TailNarrowArgs p{slab, n_rows, param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, grad_scale, gradient_only ? nullptr : state,
                      loss_partials, n_loss_partials, loss_partials ? 1.0f / (float)loss_count : 0.f, loss_out};
-    if (narrow_tail_spread_enabled())
+    if (env_switch(SW_NARROW_TAIL_SPREAD) == 1)                   // (bit-identical either way: tests/test_gpu_narrow_tail_spread.py)
         hipLaunchKernelGGL((step_tail_narrow_spread_kernel<GADAPT_NARROW_TAIL_THREADS, GADAPT_NARROW_TAIL_ROWS>),
                            dim3(gadapt_narrow_tail_grid(loss_partials != nullptr)), dim3(GADAPT_NARROW_TAIL_THREADS), 0, st, p);
     else
@@ -831,14 +830,10 @@ extern "C" int gadapt_block_backward(const gadapt_graph* g, const float* x_all, 
 }
 
 // Backward of the narrow route (gadapt_block_forward_narrow): every slot of x_all holds [N,4] rows at its start, g_top is the compact
-// [N,g_top_cols] top gradient.  Layers L-1 .. 1: narrow target pass (dxd [N,4] in dxd_ws, {alpha dt, ds} in edge_ws), narrow source pass
-// (g_out [N,4], alternating between the two halves of g_ws); layer 0: grand_bwd_target_compact_kernel as on the compact route.
-// By default (gadapt_debug_set_narrow_backward_fused) the source pass of layer l runs inside the target pass of layer l-1
-// (gadapt_launch_bwd_fused_narrow_c): T_{L-1}, [S_{L-1}+T_{L-2}], ..., [S_1+T_0] - L launches instead of 2L - 1, bit-identical.  Lanes
-// of a fused launch read one layer's {alpha dt, ds} pairs while others scatter the next layer's, so the launches alternate between
-// edge_ws and a second buffer of 2E floats carved out of dxd_ws (the caller's N c floats, of which this route uses the first 4N) at
-// float offset 4N; where that does not fit (2E > (c - 4) N) or the graph has no ELL table of out-neighbours, the pairs run.
-//
+// [N,g_top_cols] top gradient.  The launches are the plan's backward (gadapt_narrow_plan.h; DESIGN.md "How a message-passing entry point
+// is put together"): pairs T_{L-1}, S_{L-1}, .., S_1, T_0; fused T_{L-1}, [S_{L-1}+T_{L-2}], .., [S_1+T_0]; or T_{L-1} and the fused
+// stages in groups of up to three per launch - without T_{L-1} where the forward call ran it (top_done).  Every per-layer address is
+// Block's, every work buffer a member of a pair of the plan's layout.
 // packed (gadapt_block_backward_narrow_packed): the slab rows are GADAPT_NARROW_SLAB_ROW = 32 floats - the 20 partials a workgroup owes
 // and 12 zeros, one 128-byte line - instead of C*C + C of which 4140 are written zero: every launcher of the route passes the layout on,
 // the sums and their order are the same.  One shared conv only (one slab).
@@ -855,81 +850,54 @@ static int block_backward_narrow(const gadapt_graph* g, const float* x_all, int 
     if (packed && (a_stride != 0 || p0_stride != 0)) return fail(GADAPT_E_BADARG, "block_backward (narrow, packed slab): one shared conv (a_stride = p0_stride = 0)");
     const int64_t slab_floats = gadapt_backward_slab_floats(g->n_nodes, c);
     if (slab_floats < 0) return (int)slab_floats;
-    // block_ran (gadapt_block_backward_narrow_packed_block only): the layers below the top as one launch per group of up to three fused
-    // stages, where eligible - T_{L-1} as today unless the forward ran it, then the groups from the top down.  A group that is not the last
-    // hands g, dxd and the pairs of its owned nodes to the next through global memory, in buffers OTHER than the ones it reads: the halves
-    // of g_ws in turn (the first group reads g_top), the two edge buffers in turn, and dxd_ws / a second dxd [N,4] behind the second edge
-    // buffer (float offset 4 N + 2 E of dxd_ws) in turn.
-    if (block_ran) {
-        if (const int halo = narrow_bwd_block_eligible(g, c, n_layers, packed, a_stride, p0_stride)) {
-            const hipStream_t st = static_cast<hipStream_t>(stream);
-            const size_t nc = (size_t)g->n_nodes * c;
-            const int slab_rows = gadapt_slab_rows_c(g->n_nodes, c);
-            float* edge_buf[2] = {edge_ws, dxd_ws + 4 * (size_t)g->n_nodes};
-            float* dxd_buf[2] = {dxd_ws, dxd_ws + 4 * (size_t)g->n_nodes + 2 * (size_t)g->n_edges};
-            float* g_half[2] = {g_ws, g_ws + nc};
-            if (!top_done) {
-                const LayerBwd top{.x_in = x_all + (size_t)(n_layers - 1) * nc, .g_in = g_top, .alpha = alpha_all + (size_t)(n_layers - 1) * g->n_edges,
-                                   .a = a, .p0 = p0, .lp = layer_params + 2 * (n_layers - 1), .edge_ws = edge_ws, .dxd = dxd_ws, .slab = slab, .accumulate = 0,
-                                   .g_out = nullptr, .g_cols = g_top_cols, .slab_packed = 1};
-                if (int rc = gadapt_launch_bwd_target_narrow_c(c, g, top, st)) return rc;
-            }
-            const float* g_cur = g_top;
-            int turn = 0;                                        // launches so far: which of each buffer pair is read
-            for (int done = 0, k; (k = gadapt_bwd_block_groups(n_layers - 1, done)) > 0; done += k, ++turn) {
-                const int l = n_layers - 1 - done;               // the first stage's source layer
-                const bool fin = done + k == n_layers - 1;
-                const BwdBlockLaunch bl{.x_src0 = x_all + (size_t)l * nc, .slot_stride = (int64_t)nc, .alpha0 = alpha_all + (size_t)(l - 1) * g->n_edges,
-                                        .alpha_stride = g->n_edges, .lp0 = layer_params + 2 * (l - 1), .a = a, .p0 = p0, .g_in = g_cur,
-                                        .g_cols = done == 0 ? g_top_cols : 0, .edge_in = edge_buf[turn & 1], .dxd_in = dxd_buf[turn & 1],
-                                        .g_out = fin ? nullptr : g_half[turn & 1], .edge_out = fin ? nullptr : edge_buf[(turn + 1) & 1],
-                                        .dxd_out = fin ? nullptr : dxd_buf[(turn + 1) & 1], .slab = slab, .slab_rows = slab_rows, .K = k, .halo = halo,
-                                        .layer0 = fin ? 1 : 0};
-                if (int rc = gadapt_launch_bwd_narrow_block_c(c, g, bl, st)) return rc;
-                g_cur = bl.g_out;
-            }
-            *block_ran = 1;
-            return GADAPT_OK;
-        }
-    }
+    const gadapt_narrow_facts facts = narrow_facts(g, c, n_layers, ((a_stride == 0 && p0_stride == 0) ? NF_SHARED : 0) | (packed ? NF_PACKED : 0) |
+                                                                   (top_done ? NF_TOP_DONE : 0) | (block_ran ? NF_MAY_BLOCK : 0));
+    const gadapt_narrow_switches sw = narrow_switches();
+    const gadapt_narrow_plan plan = gadapt_narrow_plan_of(&facts, &sw);
     // (x_all and alpha_all: read only)
     const Block b{.g = g, .c = c, .n_layers = n_layers, .x_all = const_cast<float*>(x_all), .nc = (size_t)g->n_nodes * c, .a_all = a, .a_stride = a_stride,
                   .p0_all = p0, .p0_stride = p0_stride, .layer_params = layer_params, .alpha_all = const_cast<float*>(alpha_all), .slab_all = slab,
                   .slab_floats = slab_floats, .shared = (a_stride == 0), .g_ws = g_ws};
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    // layer l of the route: [N,4] rows; g_in: the top gradient [N,g_top_cols] at the top layer, the [N,4] result of the layer above below it
-    auto layer = [&](int l, const float* g_in, float* edge, int accumulate) {
-        return LayerBwd{.x_in = b.x(l), .g_in = g_in, .alpha = b.alpha(l), .a = b.a(l), .p0 = b.p0(l), .lp = b.lp(l), .edge_ws = edge, .dxd = dxd_ws,
-                        .slab = b.slab(l), .accumulate = accumulate, .g_out = l > 0 ? b.g_buf(l) : nullptr,
-                        .g_cols = (l == n_layers - 1) ? g_top_cols : 0, .slab_packed = packed};
-    };
-    const float* g_cur = g_top;
-    if (narrow_bwd_fused_enabled() && g->ell_s && g->rowptr_s && g->col_s && 2 * (int64_t)g->n_edges <= (int64_t)(c - 4) * g->n_nodes) {
-        float* edge_buf[2] = {edge_ws, dxd_ws + 4 * (size_t)g->n_nodes};
-        int l = n_layers - 1, eb = 0;
-        // (top_done: T_{L-1} ran in the forward launch and left dxd_ws, the pairs in edge_buf[0] and the slab rows as this launch does)
-        int rc = top_done ? GADAPT_OK : gadapt_launch_bwd_target_narrow_c(c, g, layer(l, g_cur, edge_buf[eb], 0), st);
-        for (; !rc && l >= 1; --l, eb ^= 1) {                   // source pass of layer l + target pass of layer l-1
-            const LayerBwd src = layer(l, g_cur, edge_buf[eb], 0);
-            rc = gadapt_launch_bwd_fused_narrow_c(c, g, src, layer(l - 1, nullptr, edge_buf[eb ^ 1], b.shared ? 1 : 0), edge_buf[eb], edge_buf[eb ^ 1],
-                                                  l == 1 ? 1 : 0, st);
-            g_cur = src.g_out;
-        }
-        return rc;
-    }
-    for (int l = n_layers - 1; l >= 0; --l) {
-        LayerBwd lb = layer(l, g_cur, edge_ws, (b.shared && l != n_layers - 1) ? 1 : 0);
+    // a record's buffers: member k of a pair (gadapt_narrow_layout), -1: none - and as the upstream gradient of a `first` launch, g_top
+    auto g_at = [&](int k) { return k < 0 ? nullptr : g_ws + plan.at.g[k]; };
+    auto dxd_at = [&](int k) { return k < 0 ? nullptr : dxd_ws + plan.at.dxd[k]; };
+    auto edge_at = [&](int k) { return k < 0 ? nullptr : (k == 0 ? edge_ws : dxd_ws) + plan.at.edge[k]; };
+    for (int i = 0; i < plan.n_bwd; ++i) {
+        const gadapt_narrow_launch r = gadapt_narrow_bwd_launch(&plan, i);
+        const int l = r.layer;
+        const float* g_in = r.first ? g_top : g_at(r.g_in);
+        // layer l of the route as a target pass (writes edge_out, dxd_out) or a source pass (reads edge_in, dxd_in; writes g_out)
+        auto layer = [&](int at, bool source) {
+            return LayerBwd{.x_in = b.x(at), .g_in = g_in, .alpha = b.alpha(at), .a = b.a(at), .p0 = b.p0(at), .lp = b.lp(at),
+                            .edge_ws = edge_at(source ? r.edge_in : r.edge_out), .dxd = dxd_at(source ? r.dxd_in : r.dxd_out), .slab = b.slab(at),
+                            .accumulate = r.accumulate, .g_out = source ? g_at(r.g_out) : nullptr, .g_cols = r.first ? g_top_cols : 0, .slab_packed = packed};
+        };
         int rc;
-        if (l == 0) {                                           // g_cur: layer 1's [N,4] result; the compact layer-0 launch of the tiled route
+        switch (r.kind) {
+        case GADAPT_NARROW_L_TARGET: rc = gadapt_launch_bwd_target_narrow_c(c, g, layer(l, false), st); break;
+        case GADAPT_NARROW_L_SOURCE: rc = gadapt_launch_bwd_source_narrow_c(c, g, layer(l, true), st); break;
+        case GADAPT_NARROW_L_TARGET0: {                          // the [N,4] result of layer 1 into the compact layer-0 launch of the tiled route
+            LayerBwd lb = layer(l, false);
             lb.x_cols = 4; lb.g_stride = 4; lb.sums_partials = 1;
             rc = gadapt_launch_bwd_target_c(c, g, lb, st);
-        } else {
-            rc = (top_done && l == n_layers - 1) ? GADAPT_OK : gadapt_launch_bwd_target_narrow_c(c, g, lb, st);
-            if (!rc) rc = gadapt_launch_bwd_source_narrow_c(c, g, lb, st);
-            g_cur = lb.g_out;
+        } break;
+        case GADAPT_NARROW_L_FUSED: {                            // source pass of layer l + target pass of layer l - 1 (its dxd row: read, then written)
+            LayerBwd tgt = layer(l - 1, false);
+            tgt.g_in = nullptr; tgt.g_cols = 0; tgt.dxd = dxd_at(r.dxd_in);
+            rc = gadapt_launch_bwd_fused_narrow_c(c, g, layer(l, true), tgt, edge_at(r.edge_in), edge_at(r.edge_out), r.last, st);
+        } break;
+        case GADAPT_NARROW_L_GROUP:
+            rc = gadapt_launch_bwd_narrow_block_c(c, g, BwdBlockLaunch{.x_src0 = b.x(l), .slot_stride = (int64_t)b.nc, .alpha0 = b.alpha(l - 1),
+                    .alpha_stride = g->n_edges, .lp0 = b.lp(l - 1), .a = b.a(l), .p0 = b.p0(l), .g_in = g_in, .g_cols = r.first ? g_top_cols : 0,
+                    .edge_in = edge_at(r.edge_in), .dxd_in = dxd_at(r.dxd_in), .g_out = g_at(r.g_out), .edge_out = edge_at(r.edge_out),
+                    .dxd_out = dxd_at(r.dxd_out), .slab = b.slab(l), .slab_rows = facts.slab_rows, .K = r.count, .halo = plan.bwd_halo, .layer0 = r.last}, st);
+            break;
+        default: rc = fail(GADAPT_E_RUNTIME, "block_backward (narrow): a launch kind the backward does not have");
         }
         if (rc) return rc;
     }
+    if (block_ran) *block_ran = plan.block_ran;
     return GADAPT_OK;
 }
 extern "C" int gadapt_block_backward_narrow(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all, const float* g_top,

@@ -137,7 +137,7 @@ int gadapt_launch_bwd_narrow_block_c(int c, const gadapt_graph* g, const BwdBloc
         return fail(GADAPT_E_BADARG, "narrow block backward: layer slots, alpha, {dt, scale}, coefficients, the buffers of the launch above, the slab");
     if (!b.layer0 && (!b.g_out || !b.edge_out || !b.dxd_out || b.g_out == b.g_in || b.edge_out == b.edge_in || b.dxd_out == b.dxd_in))
         return fail(GADAPT_E_BADARG, "narrow block backward: above layer 0 the last stage stores g, dxd and pairs to buffers other than the ones read");
-    if (b.slab_rows != gadapt_slab_rows_c(g->n_nodes, c) || (int64_t)g->n_nodes > 256 * (int64_t)b.slab_rows)
+    if (b.slab_rows != gadapt_slab_rows_c(g->n_nodes, c) || !gadapt_narrow_row_is_one_range(g->n_nodes, b.slab_rows))
         return fail(GADAPT_E_BADARG, "narrow block backward: the slab of the target launches, one 256-node range per row");
     BwdBlockArgs q{};
     q.x_src0 = b.x_src0; q.slot_stride = b.slot_stride; q.alpha0 = b.alpha0; q.alpha_stride = b.alpha_stride; q.lp0 = b.lp0;

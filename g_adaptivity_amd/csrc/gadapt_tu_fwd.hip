@@ -93,7 +93,7 @@ int gadapt_launch_fwd_narrow_c(int c, const gadapt_graph* g, const LayerFwd& f, 
         if (ex->cw && !gadapt_forward_computes_coeffs_c(g, c)) return fail(GADAPT_E_BADARG, "narrow forward: the coefficients are given on this graph (gadapt_forward_computes_coeffs)");
         put_extra(p, *ex, true, ex->cw != nullptr, ex->loss.target != nullptr, 4 * grid);
     }
-    if (p.cw && grid < 64) return fail(GADAPT_E_BADARG, "narrow forward: in-kernel coefficients need 64 workgroups (one row of A each)");
+    if (p.cw && grid < GADAPT_NARROW_COEFF_WGS) return fail(GADAPT_E_BADARG, "narrow forward: in-kernel coefficients need 64 workgroups (one row of A each)");
     ProfScope prof(0, st, 6);                                   // compact input, head-only output (the variant of the wide launch it replaces)
     const bool fld = p.fs.x_comp != nullptr, head = p.loss.target != nullptr;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(wide::NRW_NT), 0, st, p); };
@@ -139,12 +139,12 @@ int gadapt_launch_fwd_narrow_block_c(int c, const gadapt_graph* g, const LayerFw
         put_extra(p, *ex, true, ex->cw != nullptr, ex->loss.target != nullptr, (wide::NRB_NT / 64) * grid);
     }
     if (!p.cw && (!first.a || !first.p0)) return fail(GADAPT_E_BADARG, "narrow block forward: no coefficients");
-    if (p.cw && grid < 64) return fail(GADAPT_E_BADARG, "narrow block forward: in-kernel coefficients need 64 workgroups (one row of A each)");
-    // the top layer's backward target pass in this launch (the C-ABI unit decides: narrow_top_plan): one node per lane of the slab grid
+    if (p.cw && grid < GADAPT_NARROW_COEFF_WGS) return fail(GADAPT_E_BADARG, "narrow block forward: in-kernel coefficients need 64 workgroups (one row of A each)");
+    // the top layer's backward target pass in this launch (the C-ABI unit's plan decides): one node per lane of the slab grid
     const NarrowTop* top = first.extra ? first.extra->top : nullptr;
     if (top) {
-        if (!p.loss.target || !top->dxd || !top->edge_out || !top->slab || !g->tpos_s || g->n_edges <= 0 || p.kmax > GADAPT_MAXD ||
-            top->slab_rows != gadapt_slab_rows_c(g->n_nodes, c) || (int64_t)g->n_nodes > 256 * (int64_t)top->slab_rows)
+        if (!p.loss.target || !top->dxd || !top->edge_out || !top->slab || !g->tpos_s || g->n_edges <= 0 || p.kmax > GADAPT_NARROW_ROW_MAX ||
+            top->slab_rows != gadapt_slab_rows_c(g->n_nodes, c) || !gadapt_narrow_row_is_one_range(g->n_nodes, top->slab_rows))
             return fail(GADAPT_E_BADARG, "narrow block forward (top target pass): a loss, dxd / edge / slab buffers, edges, in-rows of at most 8, one node per lane of the slab grid");
         q.tpos = g->tpos_s; q.edge_out = reinterpret_cast<float2*>(top->edge_out); q.dxd = top->dxd; q.slab = top->slab;
         q.slab_rows = top->slab_rows; q.n_edges = g->n_edges;
@@ -155,7 +155,6 @@ int gadapt_launch_fwd_narrow_block_c(int c, const gadapt_graph* g, const LayerFw
     if (top) { if (fld) go(wide::fwd_narrow_block_kernel<true, true, true>); else go(wide::fwd_narrow_block_kernel<true, false, true>); }
     else if (head) { if (fld) go(wide::fwd_narrow_block_kernel<true, true>); else go(wide::fwd_narrow_block_kernel<true, false>); }
     else { if (fld) go(wide::fwd_narrow_block_kernel<false, true>); else go(wide::fwd_narrow_block_kernel<false, false>); }
-    if (top && top->ran) *top->ran = 1;
     return check_launch("wide::fwd_narrow_block_kernel");
 }
 

@@ -633,11 +633,11 @@ class BlockForwardCall(_OneCall):
         self._live = [(t, t.data_ptr()) for t in self._w]
         self.bucket = flat_bucket(wq, bq, wk)
         self.in_forward = self._computes and self.bucket is not None
+        # gadapt_block_forward_loss_narrow_top: + dxd_ws, edge_ws, slab, top_ran between the loss arguments and (c, stream)
+        top = [] if self._top is None else [ptr(t) for t in self._top] + [ctypes.addressof(self._top_ran)]
         self.args = [self.graph.c_ref, ptr(self.x_all), None, self.d, None, None, self.L, ptr(self.coeffs[0]), ptr(self.coeffs[1]),
                      self.bucket if self.in_forward else None, ptr(self.lp), ptr(self.alpha), ptr(self.x_top4), ptr(self.target),
-                     0 if self.target is None else self.d, self.l1, ptr(self.seed), ptr(self.partials), c, None]
-        if self._top is not None:                                  # gadapt_block_forward_loss_narrow_top: + dxd_ws, edge_ws, slab, top_ran
-            self.args[-2:-2] = [ptr(t) for t in self._top] + [ctypes.addressof(self._top_ran)]
+                     0 if self.target is None else self.d, self.l1, ptr(self.seed), ptr(self.partials)] + top + [c, None]
 
     def with_backward_buffers(self, dxd_ws, edge_ws, slab):
         """Narrow route of a fused step (`training.FusedIteration`): the call becomes `gadapt_block_forward_loss_narrow_top`, whose last

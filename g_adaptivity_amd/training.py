@@ -167,16 +167,19 @@ class FusedIteration:
             self._bw = (getattr(L_, name), [self.graph.c_ref, ptr(fw.x_all), 4, ptr(fw.alpha), ptr(fw.seed), self.d, fw.L, ptr(a), 0, ptr(p0), 0,
                                             ptr(fw.lp), ptr(self.g_ws), ptr(self.dxd_ws), ptr(self.edge_ws), ptr(self.slab), None, 0, None, c, None],
                         name)
-            # (the same arguments, one launch fewer: behind a forward call that ran the top layer's target pass itself)
-            self._bw_below = (L_.gadapt_block_backward_narrow_packed_below_top, self._bw[1], 'gadapt_block_backward_narrow_packed_below_top')
             if fw.narrow:
                 # narrow route: the entry point that runs the layers below the top as one launch where the step is eligible (and exactly
-                # the launches of the two above where it is not); its last two arguments: whether the forward ran T_{L-1}, and its report
+                # the launches of gadapt_block_backward_narrow_packed where it is not); its last two arguments: whether the forward ran
+                # T_{L-1} (filled in per step), and its report
                 self.block_ran = ctypes.c_int(0)
                 args = self._bw[1] + [0, ctypes.addressof(self.block_ran)]
                 name = 'gadapt_block_backward_narrow_packed_block'
-                self._bw = self._bw_below = (getattr(L_, name), args, name)
+                self._bw = (getattr(L_, name), args, name)
             a_ptr, p0_ptr = (None, None) if self.coeffs_in_forward else (ptr(a), ptr(p0))
+        # where the per-step values go in the backward's list: the stream, and (narrow route) top_done
+        narrow = self.small is None and fw.narrow
+        self._bw_stream = len(self._bw[1]) - (3 if narrow else 1)
+        self._bw_top_done = len(self._bw[1]) - 2 if narrow else None
         # gadapt_step_tail in its three forms: (slab given, moments given) = the whole tail; (slab, no moments) = this rank's gradient;
         # (no slab, moments) = the gradient is given (all-reduced)
         def tail(slab, moments):
@@ -185,7 +188,6 @@ class FusedIteration:
                     a_ptr, p0_ptr, ptr(fw.partials) if slab else None, 0, ptr(self.loss), self.n * self.d, c, None]
         self._tl = {(False, False): tail(True, True), (True, False): tail(True, False), (False, True): tail(False, True)}
         # (the narrow route's packed slab has its own tail, one launch; a given gradient has no slab: gadapt_step_tail)
-        narrow = self.small is None and fw.narrow
         self._fn_tail = {k: ('gadapt_step_tail_narrow' if narrow and not k[1] else 'gadapt_step_tail') for k in self._tl}
         self._fn_tail = {k: (getattr(L_, name), name) for k, name in self._fn_tail.items()}
 
@@ -199,11 +201,10 @@ class FusedIteration:
             self._plans()
         st = current_stream(self.device)
         self.n_part = self.fwd(*self._in, st)
-        fn, args, name = self._bw_below if (self.small is None and self.fwd.top_ran) else self._bw
-        if self.small is None and self.fwd.narrow:
-            args[-3], args[-2] = st, (1 if self.fwd.top_ran else 0)
-        else:
-            args[-1] = st
+        fn, args, name = self._bw
+        args[self._bw_stream] = st
+        if self._bw_top_done is not None:
+            args[self._bw_top_done] = 1 if self.fwd.top_ran else 0
         rc = fn(*args)
         if rc:
             check(rc, name)

@@ -295,8 +295,9 @@ int gadapt_block_forward_loss(const gadapt_graph* g, float* x_all, const float* 
  *     uses floats 4N .. 4N + 2E of dxd_ws (N c floats, as for gadapt_block_backward) as a second edge buffer.  Weight gradients land in the 4 x 4 corner of dA and entries 0..3 of dp0 of the slab rows; the rest of each row is
  *     written zero, so the slab reduction and gadapt_step_tail are the dense route's;
  *   - gadapt_block_forward_loss_narrow with param != NULL: the layer-0 launch spreads the rows of A / p0 over its first 64 workgroups
- *     (one per 256-node step), so on a graph of fewer than 64 steps the call issues gadapt_coeffs_forward first and the layers take
- *     (a, p0) as given - the same values, one launch more. */
+ *     (one per 256-node step, or per 512-node tile of a group launch), so on a graph of fewer than 64 of them the call issues
+ *     gadapt_coeffs_forward first and the layers take (a, p0) as given - the same values, one launch more.
+ * Which launches a step runs, rule by rule, and where their work buffers lie: gadapt_narrow_step_plan below. */
 int gadapt_narrow_route(const gadapt_graph* g, int c);
 int gadapt_block_forward_narrow(const gadapt_graph* g, float* x_all, int x0_cols, int n_layers,
                                 const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
@@ -399,12 +400,12 @@ int gadapt_block_backward_narrow_packed_below_top(const gadapt_graph* g, const f
  * the launches of gadapt_block_backward_narrow_packed / _below_top and sets *block_ran = 0.
  * Contract when *block_ran = 1 - the SLAB: entries 0..19 of rows 0 .. min(2 ceil(N / 512), rows) - 1 carry the bits those launches leave;
  * every other entry of the slab is not written by the block launches (the rows beyond hold the zeros of T_{L-1}, to which those launches
- * add +0).  Work buffers (N nodes, E edges, c = hidden):
- *   top_done = 0: T_{L-1} writes dxd_ws[0, 4N), edge_ws[0, 2E) and every slab row, as today;
+ * add +0).  Work buffers: each of g, dxd and the pairs has two members, laid out in csrc/gadapt_narrow_plan.h by gadapt_narrow_layout_of
+ * - words 12..17 of a serialised plan, below - and the launches write exactly what their records in gadapt_narrow_step_plan name:
+ *   top_done = 0: T_{L-1} writes member 0 of dxd and of the pairs, and every slab row;
  *   n_layers <= 4: nothing else - g_ws is not written at all, and with top_done = 1 neither are dxd_ws and edge_ws;
- *   n_layers > 4: launch number m = 0, 1, .. that is not the last stores, for every node, what the next one reads:
- *     g rows [N,4] to g_ws[(m & 1) N c, + 4N), dxd rows to dxd_ws[0, 4N) (m odd) or dxd_ws[4N + 2E, 8N + 2E) (m even), the pairs to
- *     edge_ws[0, 2E) (m odd) or dxd_ws[4N, 4N + 2E) (m even); L = 6: g_ws[0, 4N), dxd_ws[4N, 8N + 2E).  Nothing else. */
+ *   n_layers > 4: launch number m = 0, 1, .. below T_{L-1} that is not the last stores, for every node, what the next one reads: g rows
+ *     to member m & 1, dxd rows and the pairs to member (m + 1) & 1 - never a member it reads.  Nothing else. */
 int gadapt_block_backward_narrow_packed_block(const gadapt_graph* g, const float* x_all, int x0_cols, const float* alpha_all,
                                               const float* g_top, int g_top_cols, int n_layers,
                                               const float* a, int64_t a_stride, const float* p0, int64_t p0_stride,
@@ -412,6 +413,52 @@ int gadapt_block_backward_narrow_packed_block(const gadapt_graph* g, const float
                                               float* g_ws, float* dxd_ws, float* edge_ws, float* slab,
                                               float* d_layer_params, int want_d_scale, float* d_x0, int c, void* stream,
                                               int top_done, int* block_ran);
+
+/* The launch sequence of a narrow step, as the entry points above run it (csrc/gadapt_narrow_plan.h: one pure function of the facts of a
+ * step and the four launch-sequence switches; read-only queries, nothing is launched; resolved by name, ABI 9).
+ * The rules, all of them.  A step has launches only where gadapt_narrow_route = 1 and n_layers >= 1.  `One range`: n_nodes <= 256 *
+ * gadapt_backward_slab_rows.  `Short rows`: the longest in-row the narrow forward walks is at most 8.
+ *   FORWARD.  Groups of up to 4 consecutive layers, one launch each (L = 4: one, L = 6: 4 + 2), where gadapt_debug_set_narrow_forward is
+ *   1, the conv is shared, the target side has a registered halo and the 512-node tiles keep the loss partials within
+ *   gadapt_loss_partials_max; else one launch per layer - the one-node-per-lane kernel, or the wide kernel where the switch is 0.
+ *   COEFFICIENTS FIRST.  With param given (flag COEFFS) gadapt_coeffs_forward comes first where the layer-0 launch has fewer than 64
+ *   workgroups: one per 512-node tile of a group launch, one per 256-node step of a per-layer launch.
+ *   TOP IN FORWARD.  The last forward launch also runs T_{L-1} where gadapt_debug_set_narrow_top_in_forward is on, the forward runs in
+ *   groups, a target and the three backward buffers are given, n_layers >= 2, ell_t and tpos_s are present, n_edges > 0, short rows, one
+ *   range.
+ *   BACKWARD (n_layers >= 2), first T_{L-1} unless top_done, then one of:
+ *     groups - the fused stages [S_l + T_{l-1}], l = L-1 .. 1, in launches of gadapt_narrow_bwd_block_groups_host stages - where the entry
+ *       point reports *block_ran (flag MAY_BLOCK), gadapt_debug_set_narrow_backward_block and _backward_fused are on, the source side has a
+ *       registered halo, packed slab, shared conv, n_layers >= 3, n_edges > 0, ell_t, ell_s, tpos_s and rowptr_s present, short rows, one
+ *       range, and 2 E <= (c - 4) N (n_layers > 4: 2 E <= (c - 8) N);
+ *     fused - one launch per stage - where gadapt_debug_set_narrow_backward_fused is on, ell_s, rowptr_s and col_s are present and
+ *       2 E <= (c - 4) N;
+ *     pairs - T_l, S_l for l = L-1 .. 1 (T_{L-1} only unless top_done), then the compact layer-0 target pass T_0 - otherwise.
+ *   BUFFERS.  T_{L-1} (in either place) leaves dxd and the pairs in member 0 of their buffer pairs and writes every slab row (accumulate
+ *   = 0); every later target pass of a shared conv accumulates.  Pairs: one member of dxd and of the pairs throughout; S_l writes g member
+ *   (L - 1 - l) & 1.  Launch m = 0, 1, .. below T_{L-1} of fused / groups reads member m & 1 of the pairs and writes the other, writes g
+ *   member m & 1 and reads the one the launch before wrote (m = 0: the top gradient); a group does with dxd as with the pairs, a fused
+ *   launch keeps dxd in member 0 (row j is read and then written by the lane that owns node j).  The launch whose target half is layer 0
+ *   writes slab rows only.
+ * Serialised plan, int32 words.  Head [18]: 0 route (0: no launches), 1 forward launches, 2 backward launches, 3 forward kind (0 wide per
+ * layer, 1 one node per lane per layer, 2 groups), 4 forward halo, 5 coefficients first, 6 top in forward (= *top_ran), 7 backward kind
+ * (0 pairs, 1 fused, 2 groups), 8 backward halo, 9 top_done, 10 *block_ran, 11 words per record (13), 12..17 float offsets of the work
+ * buffers: g members 0, 1 in g_ws, dxd members 0, 1 in dxd_ws, pairs member 0 in edge_ws and member 1 in dxd_ws (extents 4N, 4N, 2E).
+ * Then one record per launch, forward first: 0 kind (0 wide forward, 1 one-node-per-lane forward, 2 forward group, 3 narrow target pass,
+ * 4 narrow source pass, 5 compact layer-0 target pass, 6 fused stage, 7 group of fused stages), 1 layer (forward: first layer; backward:
+ * the layer of the target pass, or of the (first) source pass), 2 layers / stages in the launch, 3 g read, 4 g written, 5 pairs read,
+ * 6 pairs written, 7 dxd read, 8 dxd written (members; -1: none), 9 accumulate, 10 first (forward: starts at layer 0; backward: reads the
+ * top gradient), 11 last (forward: ends the block; backward: target half is layer 0), 12 top (forward: T_{L-1} rides in the launch).
+ * 18 + 39 n_layers words always hold a plan.  Both return the words written, or GADAPT_E_BADARG: NULL output, cap too small, sizes whose
+ * offsets do not fit 32 bits (n_nodes c 4 >= 4 GiB, 8 N + 2 E >= 2^31), n_layers < 1.
+ * gadapt_narrow_step_plan_host: facts = int64[22] {n_nodes, n_edges, c, n_layers, route takes the graph, target halo, source halo (0, 32,
+ * 64), longest in-row, slab rows, tiles ok, ell_t, ell_s, tpos_s, rowptr_s, col_s present, shared conv, packed slab, target given,
+ * backward buffers given, param given, top_done, may run groups}; switches = int32[4] {narrow_forward (0, 1, 2), backward_fused,
+ * top_in_forward, backward_block}.
+ * gadapt_narrow_step_plan: the plan the library would run right now on g (its registered halos, the live switches); flags: 1 shared conv,
+ * 2 packed slab, 4 target given, 8 backward buffers given, 16 param given, 32 top_done, 64 may run groups. */
+int gadapt_narrow_step_plan_host(const int64_t* facts, const int32_t* switches, int32_t* plan_out, int cap);
+int gadapt_narrow_step_plan(const gadapt_graph* g, int c, int n_layers, int flags, int32_t* plan_out, int cap);
 
 /* ------------------------------------------------------------------ small meshes: the whole evaluation forward in ONE launch
  * The reference's own sizes (params.py:37,56,107,130-134: 11x11 ... 23x23 meshes, hidden 8, 4 layers; evaluation one sample per call,
