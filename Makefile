@@ -34,15 +34,15 @@ $(OBJDIR)/fem_kernels.o: $(FEM_CSRC)/fem_kernels.hip $(FEM_CSRC)/fem_window_kern
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
-$(OBJDIR)/fem1d_kernels.o: $(FEM_CSRC)/fem1d_kernels.hip $(FEM_CSRC)/fem_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
+$(OBJDIR)/fem1d_kernels.o: $(FEM_CSRC)/fem1d_kernels.hip $(FEM_CSRC)/fem_common.h $(FEM_CSRC)/fem1d_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
-$(OBJDIR)/spline_kernels.o: $(FEM_CSRC)/spline_kernels.hip $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
+$(OBJDIR)/spline_kernels.o: $(FEM_CSRC)/spline_kernels.hip $(FEM_CSRC)/fem1d_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
-$(OBJDIR)/descent_kernels.o: $(FEM_CSRC)/descent_kernels.hip $(FEM_CSRC)/fem_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
+$(OBJDIR)/descent_kernels.o: $(FEM_CSRC)/descent_kernels.hip $(FEM_CSRC)/fem_common.h $(FEM_CSRC)/fem1d_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 

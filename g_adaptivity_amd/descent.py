@@ -159,12 +159,10 @@ def mesh_descent_1d(x0: torch.Tensor, node_counts: Sequence[int], pde_params: Se
     mesh_hist = f(epochs, N) if keep_meshes else None
     first_tangled = torch.empty(B, dtype=torch.int32, device=dev)
     min_area = f(B)
-    _nf.check(_nf.lib().gadapt_fem1d_descend(
-        B, bt.nmax, bt.node_off.data_ptr(), x.data_ptr(), bt.gptr.data_ptr(), bt.gpar.data_ptr(),
-        int(opt.get('load_quad_points', 101)), int(opt.get('stiff_quad_points', 3)), P, pts.data_ptr(), epochs, float(lr),
-        _MESH_PARAMS[mesh_params], N, coeffs.data_ptr(), sol.data_ptr(), flags.data_ptr(), loss.data_ptr(), g_sol.data_ptr(),
-        gx.data_ptr(), loss_hist.data_ptr() if epochs else None, _ptr(mesh_hist), first_tangled.data_ptr(), min_area.data_ptr(),
-        current_stream(dev)), 'gadapt_fem1d_descend')
+    _nf.call('gadapt_fem1d_descend', *bt.head(x), int(opt.get('load_quad_points', 101)), int(opt.get('stiff_quad_points', 3)), P,
+             pts.data_ptr(), epochs, float(lr), _MESH_PARAMS[mesh_params], N, coeffs.data_ptr(), sol.data_ptr(), flags.data_ptr(),
+             loss.data_ptr(), g_sol.data_ptr(), gx.data_ptr(), loss_hist.data_ptr() if epochs else None, _ptr(mesh_hist),
+             first_tangled.data_ptr(), min_area.data_ptr(), current_stream(dev))
     if epochs:
         _watch_flags(flags)
     return DescentResult(x=x, coeffs=coeffs if epochs else None, loss_hist=loss_hist, mesh_hist=mesh_hist,

@@ -142,10 +142,8 @@ def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params:
         if min(bt.counts) < 3:
             raise ValueError("poisson_eval_errors: every 1-D mesh needs at least 3 nodes")
         flags = torch.empty(B, dtype=torch.int32, device=dev)
-        _nf.check(lib.gadapt_fem1d_poisson_eval_errors(
-            B, bt.nmax, bt.node_off.data_ptr(), x.data_ptr(), bt.gptr.data_ptr(), bt.gpar.data_ptr(),
-            int(opt.get('load_quad_points', 101)), int(opt.get('stiff_quad_points', 3)), n_eval, lat.data_ptr(), err.data_ptr(),
-            flags.data_ptr(), stream), 'gadapt_fem1d_poisson_eval_errors')
+        _nf.call('gadapt_fem1d_poisson_eval_errors', *bt.head(x), int(opt.get('load_quad_points', 101)),
+                 int(opt.get('stiff_quad_points', 3)), n_eval, lat.data_ptr(), err.data_ptr(), flags.data_ptr(), stream)
         _watch_flags(flags)
     else:
         raise ValueError(f"poisson_eval_errors: x must be [N,2] (2-D) or [N] / [N,1] (1-D), got {tuple(x.shape)}")

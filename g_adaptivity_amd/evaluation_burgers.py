@@ -21,13 +21,10 @@ import time
 import warnings
 from typing import List, Optional, Sequence
 
-import numpy as np
 import torch
 
-from . import _native_fem as _nf
-from ._native import current_stream
 from .evaluation import _as_float, _eval_loader, _eval_mode, _picked, _tables, calculate_error_reduction
-from .fem1d import BURGERS_STIFF_POINTS, _Batch, _burgers_cfg, _require_gpu, _watch_flags, burgers_1d
+from .fem1d import burgers_1d, burgers_project
 from .mmpde5 import mmpde5_batch, warn_unconverged
 from .spline import SPLINE_NOT_FINITE, SPLINE_NOT_INCREASING, SPLINE_OK, cubic_spline_1d
 
@@ -130,29 +127,7 @@ def _row(rows, grid: float, ma: float, ml: float):
 
 
 # ------------------------------------------------------------------------------------------------ the rollout's stages
-def burgers_project(x: torch.Tensor, counts: Sequence[int], params: Sequence[dict], opt, k_proj: Optional[int] = None) -> torch.Tensor:
-    """`get_Burgers_initial_coeffs` for a batch of meshes in one launch: the L2 projection of
-    gauss_amplitude * sum exp(-(x-c)^2/s^2) of each mesh's own Gaussians on its mesh, [N] concatenated.  The mass matrix
-    takes `k_proj` points per interval (eval_quad_points, as for a coarse mesh, unless given; the reference's fine mesh takes
-    10 * eval_quad_points)."""
-    _require_gpu(x, 'burgers_project')
-    dev = x.device
-    x = x.detach().float().contiguous()
-    bt = _Batch(counts, params, dev)
-    cfg = _burgers_cfg(opt, 1, k_proj=k_proj)
-    N = x.shape[0]
-    hist, sol = torch.empty(2 * N, device=dev), torch.empty(bt.B, 1, device=dev)
-    flags, p1 = torch.empty(bt.B, dtype=torch.int32, device=dev), torch.zeros(1, device=dev)
-    _nf.check(_nf.lib().gadapt_fem1d_burgers_forward(
-        bt.B, bt.nmax, bt.node_off.data_ptr(), x.data_ptr(), None, None, bt.gptr.data_ptr(), bt.gpar.data_ptr(), cfg['amp'],
-        cfg['tau'], cfg['taunu'], cfg['k_load'], BURGERS_STIFF_POINTS, cfg['k_proj'], cfg['k_proj_fine'], 1, 0, 1, p1.data_ptr(),
-        hist.data_ptr(), sol.data_ptr(), None, flags.data_ptr(), current_stream(dev)), 'gadapt_fem1d_burgers_forward')
-    _watch_flags(flags)
-    off = np.concatenate([[0], np.cumsum(bt.counts)])
-    idx = np.concatenate([2 * o + np.arange(n) for o, n in zip(off[:-1], bt.counts)])       # u^0 of the (u^0, u^1) history
-    return hist[torch.from_numpy(idx).to(dev, non_blocking=True)]
-
-
+# burgers_project, the initial state of every mesh of a batch in one launch, lives beside get_Burgers_initial_coeffs (fem1d.py)
 def _steps(x, u, counts, opt, pts):
     """num_time_steps FEM steps from u on every mesh: (coefficients [N], solution at pts [B,P]), one launch."""
     un, sol, _ = burgers_1d(x, counts, None, opt, int(opt.get('num_time_steps', 1)), points=pts, u0=u, fine=False)

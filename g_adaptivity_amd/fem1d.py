@@ -9,6 +9,7 @@ mesh, the mesh's state in LDS.
     fem_poisson_1d(x, node_counts, pde_params, opt) -> (coeffs [N], sol [B,P])
     gradient_meshpoints_1D(opt, data, x_phys) -> (loss, x_grads)
     torch_FEM_Burgers_1D, get_Burgers_initial_coeffs, fn_expansion, torch_FEM_1D: the reference's signatures on GPU tensors
+    burgers_project(x, node_counts, pde_params, opt, k_proj=None) -> u^0 [N]: get_Burgers_initial_coeffs for a batch
 
 Gradients are with respect to the node coordinates (and, for `torch_FEM_Burgers_1D`, the incoming coefficients).  The
 Burgers initial projection and the Poisson boundary values are detached, as in the reference.  There is no CPU fallback.
@@ -25,7 +26,7 @@ from . import _native_fem as _nf
 from ._native import NativeError, current_stream
 
 __all__ = ['burgers_1d', 'fem_poisson_1d', 'gradient_meshpoints_1D', 'torch_FEM_Burgers_1D', 'get_Burgers_initial_coeffs',
-           'fn_expansion', 'torch_FEM_1D', 'last_flags', 'GRAD_TYPES']
+           'burgers_project', 'fn_expansion', 'torch_FEM_1D', 'last_flags', 'GRAD_TYPES']
 
 GRAD_TYPES = ('PDE_loss_direct_mse', 'PDE_loss_direct_L2', 'burgers_timestep_loss_direct_mse')
 MAX_NODES = 1024                      # GADAPT_FEM1D_MAX_NODES
@@ -44,7 +45,8 @@ def _ptr(t: Optional[torch.Tensor]):
 
 
 class _Batch:
-    """node_off, the node cap and the packed Gaussians of one call, on the device."""
+    """node_off, the node cap and the packed Gaussians of one call, on the device, and the arguments every 1-D entry point of
+    include/gadapt_fem.h starts with (`head`).  The pointers of its own tensors are taken once, here."""
 
     def __init__(self, node_counts: Sequence[int], pde_params: Optional[Sequence[dict]], device, n_fine: int = 0):
         counts = [int(n) for n in node_counts]
@@ -69,6 +71,13 @@ class _Batch:
                 cnt.append(len(p['centers']))
             self.gptr = torch.tensor(np.cumsum(cnt), dtype=torch.int32, device=device)
             self.gpar = torch.tensor(np.asarray(rows, np.float32).reshape(-1, 2), device=device)
+        self._sizes = (self.B, self.nmax, self.node_off.data_ptr())
+        self.gauss = (_ptr(self.gptr), _ptr(self.gpar))                  # (gptr, gpar), NULL without pde_params
+
+    def head(self, x: torch.Tensor, gauss: bool = True) -> tuple:
+        """n_meshes, max_nodes, node_off and x, then the Gaussians where the entry point takes them right after x
+        (gadapt_fem1d_burgers_forward has u0 and bc in between and appends `gauss` itself)."""
+        return self._sizes + (x.data_ptr(),) + (self.gauss if gauss else ())
 
     def last_index(self, T: int) -> torch.Tensor:
         """Positions of u^T in the step history ((T+1) n_b floats per mesh), built on the host."""
@@ -114,6 +123,13 @@ def _points(opt, device, points=None) -> torch.Tensor:
     return torch.as_tensor(points).detach().to(device=device, dtype=torch.float32).contiguous().view(-1)
 
 
+def _burgers_forward(bt: _Batch, x, u0, bc, cfg: dict, T: int, pts, hist, sol, fine, flags):
+    """gadapt_fem1d_burgers_forward: T steps from u0 (None: from the projection of the batch's Gaussians) into hist and sol."""
+    _nf.call('gadapt_fem1d_burgers_forward', *bt.head(x, gauss=False), _ptr(u0), _ptr(bc), *bt.gauss, cfg['amp'], cfg['tau'],
+             cfg['taunu'], cfg['k_load'], BURGERS_STIFF_POINTS, cfg['k_proj'], cfg['k_proj_fine'], T, bt.n_fine, pts.numel(),
+             pts.data_ptr(), hist.data_ptr(), sol.data_ptr(), _ptr(fine), flags.data_ptr(), current_stream(x.device))
+
+
 class _Burgers(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, u0, bt: _Batch, cfg: dict, pts, bc):
@@ -125,11 +141,7 @@ class _Burgers(torch.autograd.Function):
         fine = torch.empty(B, P, device=dev) if bt.n_fine > 1 else None
         flags = torch.empty(B, dtype=torch.int32, device=dev)
         u0c = None if u0 is None else u0.detach().float().contiguous()
-        _nf.check(_nf.lib().gadapt_fem1d_burgers_forward(
-            B, bt.nmax, bt.node_off.data_ptr(), x.data_ptr(), _ptr(u0c), _ptr(bc), _ptr(bt.gptr), _ptr(bt.gpar), cfg['amp'],
-            cfg['tau'], cfg['taunu'], cfg['k_load'], BURGERS_STIFF_POINTS, cfg['k_proj'], cfg['k_proj_fine'], T, bt.n_fine, P,
-            pts.data_ptr(), hist.data_ptr(), sol.data_ptr(), _ptr(fine), flags.data_ptr(), current_stream(dev)),
-            'gadapt_fem1d_burgers_forward')
+        _burgers_forward(bt, x, u0c, bc, cfg, T, pts, hist, sol, fine, flags)
         _watch_flags(flags)
         ctx.bt, ctx.cfg, ctx.has_u0 = bt, cfg, u0 is not None
         ctx.save_for_backward(x, hist, pts, bc)
@@ -146,10 +158,9 @@ class _Burgers(torch.autograd.Function):
         gu0 = torch.empty_like(x) if ctx.has_u0 and ctx.needs_input_grad[1] else None
         g_last = None if g_last is None else g_last.contiguous().float()
         g_sol = None if g_sol is None else g_sol.contiguous().float()
-        _nf.check(_nf.lib().gadapt_fem1d_burgers_backward(
-            bt.B, bt.nmax, bt.node_off.data_ptr(), x.data_ptr(), _ptr(bc), cfg['tau'], cfg['taunu'], cfg['k_load'],
-            BURGERS_STIFF_POINTS, cfg['T'], pts.numel(), pts.data_ptr(), hist.data_ptr(), _ptr(g_sol), _ptr(g_last),
-            gx.data_ptr(), _ptr(gu0), current_stream(dev)), 'gadapt_fem1d_burgers_backward')
+        _nf.call('gadapt_fem1d_burgers_backward', *bt.head(x, gauss=False), _ptr(bc), cfg['tau'], cfg['taunu'], cfg['k_load'],
+                 BURGERS_STIFF_POINTS, cfg['T'], pts.numel(), pts.data_ptr(), hist.data_ptr(), _ptr(g_sol), _ptr(g_last), gx.data_ptr(),
+                 _ptr(gu0), current_stream(dev))
         return gx, gu0, None, None, None, None
 
 
@@ -190,9 +201,8 @@ class _Poisson(torch.autograd.Function):
         coeffs = torch.empty_like(x)
         sol = torch.empty(B, P, device=dev)
         flags = torch.empty(B, dtype=torch.int32, device=dev)
-        _nf.check(_nf.lib().gadapt_fem1d_poisson_forward(
-            B, bt.nmax, bt.node_off.data_ptr(), x.data_ptr(), bt.gptr.data_ptr(), bt.gpar.data_ptr(), k_load, k_stiff, P,
-            pts.data_ptr(), coeffs.data_ptr(), sol.data_ptr(), flags.data_ptr(), current_stream(dev)), 'gadapt_fem1d_poisson_forward')
+        _nf.call('gadapt_fem1d_poisson_forward', *bt.head(x), k_load, k_stiff, P, pts.data_ptr(), coeffs.data_ptr(), sol.data_ptr(),
+                 flags.data_ptr(), current_stream(dev))
         _watch_flags(flags)
         ctx.bt, ctx.k = bt, (k_load, k_stiff)
         ctx.save_for_backward(x, pts, coeffs)
@@ -205,11 +215,17 @@ class _Poisson(torch.autograd.Function):
         gx = torch.empty_like(x)
         g_coeffs = None if g_coeffs is None else g_coeffs.contiguous().float()
         g_sol = None if g_sol is None else g_sol.contiguous().float()
-        _nf.check(_nf.lib().gadapt_fem1d_poisson_backward(
-            bt.B, bt.nmax, bt.node_off.data_ptr(), x.data_ptr(), bt.gptr.data_ptr(), bt.gpar.data_ptr(), ctx.k[0], ctx.k[1],
-            pts.numel(), pts.data_ptr(), coeffs.data_ptr(), _ptr(g_coeffs), _ptr(g_sol), gx.data_ptr(), current_stream(x.device)),
-            'gadapt_fem1d_poisson_backward')
+        _nf.call('gadapt_fem1d_poisson_backward', *bt.head(x), ctx.k[0], ctx.k[1], pts.numel(), pts.data_ptr(), coeffs.data_ptr(),
+                 _ptr(g_coeffs), _ptr(g_sol), gx.data_ptr(), current_stream(x.device))
         return gx, None, None, None, None
+
+
+def _poisson_on(bt: _Batch, x: torch.Tensor, opt, points=None):
+    """fem_poisson_1d on a built batch (one with Gaussians)."""
+    if min(bt.counts) < 3:
+        raise ValueError("fem_poisson_1d: every mesh needs at least 3 nodes")
+    pts = _points(opt, x.device, points)
+    return _Poisson.apply(x.float(), bt, int(opt.get('load_quad_points', 101)), int(opt.get('stiff_quad_points', 3)), pts)
 
 
 def fem_poisson_1d(x: torch.Tensor, node_counts: Sequence[int], pde_params: Sequence[dict], opt, points=None):
@@ -218,11 +234,7 @@ def fem_poisson_1d(x: torch.Tensor, node_counts: Sequence[int], pde_params: Sequ
     _require_gpu(x, 'fem_poisson_1d')
     if x.dim() != 1:
         raise ValueError(f"fem_poisson_1d: x must be [N] (got {tuple(x.shape)})")
-    bt = _Batch(node_counts, pde_params, x.device)
-    if bt.nmax < 3 or min(int(n) for n in node_counts) < 3:
-        raise ValueError("fem_poisson_1d: every mesh needs at least 3 nodes")
-    pts = _points(opt, x.device, points)
-    return _Poisson.apply(x.float(), bt, int(opt.get('load_quad_points', 101)), int(opt.get('stiff_quad_points', 3)), pts)
+    return _poisson_on(_Batch(node_counts, pde_params, x.device), x, opt, points)
 
 
 # ---------------------------------------------------------------------------------------------- the reference's names
@@ -260,21 +272,36 @@ def get_Burgers_initial_coeffs(fine_mesh_points, num_fine_meshpoints, mesh_point
     o['load_quad_points'] = int(load_quad_points)
     ev = int(opt.get('eval_quad_points', 101))
     out = []
-    for pts, n, kp in ((mesh_points, num_meshpoints, ev), (fine_mesh_points, num_fine_meshpoints, 10 * ev)):
+    for pts, kp in ((mesh_points, ev), (fine_mesh_points, 10 * ev)):
         x = torch.as_tensor(pts, device=mesh_points.device).detach().float().view(-1)
-        bt = _Batch([x.shape[0]], params, x.device)
-        cfg = _burgers_cfg(o, 1, k_proj=kp)
-        hist = torch.empty(2 * x.shape[0], device=x.device)
-        sol = torch.empty(1, 1, device=x.device)
-        flags = torch.empty(1, dtype=torch.int32, device=x.device)
-        p1 = torch.zeros(1, device=x.device)
-        _nf.check(_nf.lib().gadapt_fem1d_burgers_forward(
-            1, bt.nmax, bt.node_off.data_ptr(), x.data_ptr(), None, None, bt.gptr.data_ptr(), bt.gpar.data_ptr(), cfg['amp'],
-            cfg['tau'], cfg['taunu'], cfg['k_load'], BURGERS_STIFF_POINTS, cfg['k_proj'], cfg['k_proj_fine'], 1, 0, 1,
-            p1.data_ptr(), hist.data_ptr(), sol.data_ptr(), None, flags.data_ptr(), current_stream(x.device)),
-            'gadapt_fem1d_burgers_forward')
-        out.append(hist[:x.shape[0]].clone())
+        out.append(_project(x, [x.shape[0]], params, o, kp)[0])
     return out[0], out[1]
+
+
+def _project(x: torch.Tensor, counts: Sequence[int], params: Sequence[dict], opt, k_proj: Optional[int]):
+    """The projection-only call of gadapt_fem1d_burgers_forward: one step on one dummy point, no fine mesh, of which only u^0
+    is kept.  Returns (u^0 [N], flags [B])."""
+    dev = x.device
+    x = x.contiguous()
+    bt = _Batch(counts, params, dev)
+    N = x.shape[0]
+    hist, sol = torch.empty(2 * N, device=dev), torch.empty(bt.B, 1, device=dev)
+    flags, p1 = torch.empty(bt.B, dtype=torch.int32, device=dev), torch.zeros(1, device=dev)
+    _burgers_forward(bt, x, None, None, _burgers_cfg(opt, 1, k_proj=k_proj), 1, p1, hist, sol, None, flags)
+    off = np.concatenate([[0], np.cumsum(bt.counts)])
+    idx = np.concatenate([2 * o + np.arange(n) for o, n in zip(off[:-1], bt.counts)])       # u^0 of the (u^0, u^1) history
+    return hist[torch.from_numpy(idx).to(dev, non_blocking=True)], flags
+
+
+def burgers_project(x: torch.Tensor, counts: Sequence[int], params: Sequence[dict], opt, k_proj: Optional[int] = None) -> torch.Tensor:
+    """`get_Burgers_initial_coeffs` for a batch of meshes in one launch: the L2 projection of
+    gauss_amplitude * sum exp(-(x-c)^2/s^2) of each mesh's own Gaussians on its mesh, [N] concatenated.  The mass matrix
+    takes `k_proj` points per interval (eval_quad_points, as for a coarse mesh, unless given; the reference's fine mesh takes
+    10 * eval_quad_points)."""
+    _require_gpu(x, 'burgers_project')
+    u0, flags = _project(x.detach().float(), counts, params, opt, k_proj)
+    _watch_flags(flags)
+    return u0
 
 
 def fn_expansion(coeffs, mesh, quad_points, num_solpoints=None):
@@ -286,8 +313,8 @@ def fn_expansion(coeffs, mesh, quad_points, num_solpoints=None):
     pts = _points({}, x.device, quad_points)
     bt = _Batch([x.shape[0]], None, x.device)
     sol = torch.empty(pts.numel(), device=x.device)
-    _nf.check(_nf.lib().gadapt_fem1d_expand(1, bt.nmax, bt.node_off.data_ptr(), x.data_ptr(), c.data_ptr(), pts.numel(),
-                                            pts.data_ptr(), sol.data_ptr(), current_stream(x.device)), 'gadapt_fem1d_expand')
+    _nf.call('gadapt_fem1d_expand', *bt.head(x, gauss=False), c.data_ptr(), pts.numel(), pts.data_ptr(), sol.data_ptr(),
+             current_stream(x.device))
     return sol
 
 
@@ -345,8 +372,8 @@ def gradient_meshpoints_1D(opt, data, x_phys):
             _, sol, fine = burgers_1d(x, counts, params, opt, int(opt['num_time_steps']), points=pts)
             per_mesh = ((sol - fine) ** 2).mean(1)
         else:
-            _, sol = fem_poisson_1d(x, counts, params, opt, points=pts)
             bt = _Batch(counts, params, x.device)
+            _, sol = _poisson_on(bt, x, opt, pts)
             err = sol - _gauss_on(pts, bt)
             if gt == 'PDE_loss_direct_mse':
                 per_mesh = (err ** 2).mean(1)

@@ -2,12 +2,13 @@
 // train_step_adjoint, difFEM_2d.py:593-685, and train_step_vec, difFEM_1d.py:241-292), all epochs enqueued by one call.
 //
 // An epoch is the launches the modular loss already has - fem_launch_modular_forward + fem_launch_backward (fem_host.h) in 2-D,
-// gadapt_fem1d_poisson_forward + the L2 seed below + gadapt_fem1d_poisson_backward in 1-D - followed by one step launch that
+// fem1d_launch_poisson_forward + the L2 seed below + fem1d_launch_poisson_backward in 1-D - followed by one step launch that
 // does what torch.optim.SGD does (x - lr * g, the product rounded before the subtraction), keeps the epoch's loss and mesh
 // and watches for tangling.  One workgroup per mesh in the step launches; every reduction runs in a fixed order.
 #include <math.h>
 #include <stdio.h>
 #include "fem_common.h"
+#include "fem1d_common.h"
 #include "fem_host.h"
 
 #pragma clang fp contract(off)
@@ -137,16 +138,7 @@ extern "C" int gadapt_fem_descend(int B, int N, int T, const int32_t* meta, cons
 }
 
 // ---------------------------------------------------------------------------------------------------- 1-D
-// u_true = sum_g exp(-(x-c)^2/s^2), as the 1-D tail evaluates it (fem1d_kernels.hip)
-__device__ inline float gauss_1d(float x, const float* __restrict__ gpar, int g0, int g1) {
-    float sol = 0.0f;
-    for (int g = g0; g < g1; ++g) {
-        const float c = gpar[2 * g], s = gpar[2 * g + 1], r = x - c;
-        sol += expf(-(r * r) / (s * s));
-    }
-    return sol;
-}
-
+// u_true is f1::gauss, the one the 1-D tail evaluates (fem1d_common.h)
 // loss[b] = torch.trapezoid((sol - u_true)^2, pts) = sum_j (e_j+1^2 + e_j^2) (pts_j+1 - pts_j) / 2 (L2norm, difFEM_1d.py:82-83)
 // and g_sol = d loss[b] / d sol.  Lane l adds the intervals l, l + 256, ... in that order; the lanes' sums meet in a binary tree.
 __global__ void __launch_bounds__(DESC_THREADS) fem1d_l2_seed_kernel(const int32_t* __restrict__ gptr, const float* __restrict__ gpar,
@@ -160,11 +152,11 @@ __global__ void __launch_bounds__(DESC_THREADS) fem1d_l2_seed_kernel(const int32
     float acc = 0.0f;
     for (int j = threadIdx.x; j < P; j += DESC_THREADS) {
         const float p = pts[j];
-        const float e = s_row[j] - gauss_1d(p, gpar, g0, g1);
+        const float e = s_row[j] - f1::gauss(p, gpar, g0, g1);
         const float dl = j > 0 ? p - pts[j - 1] : 0.0f, dr = j + 1 < P ? pts[j + 1] - p : 0.0f;
         g_row[j] = 2.0f * e * (0.5f * dl + 0.5f * dr);
         if (j + 1 < P) {
-            const float e1 = s_row[j + 1] - gauss_1d(pts[j + 1], gpar, g0, g1);
+            const float e1 = s_row[j + 1] - f1::gauss(pts[j + 1], gpar, g0, g1);
             acc = acc + (e1 * e1 + e * e) * dr;
         }
     }
@@ -193,7 +185,7 @@ __global__ void __launch_bounds__(GADAPT_FEM1D_MAX_NODES) fem1d_descent_step_ker
     const int32_t* __restrict__ node_off, const float* __restrict__ gx, const float* __restrict__ loss, float lr, int all, int epoch,
     int n_meshes, int n_nodes, float* __restrict__ x, float* __restrict__ loss_hist, float* __restrict__ mesh_hist,
     int32_t* __restrict__ first_tangled, float* __restrict__ min_area) {
-    extern __shared__ float xs[];                                // the mesh's new nodes
+    extern __shared__ float xs[];                                // the mesh's new nodes (f1::Layout::DESCENT_ROWS)
     __shared__ float waves[DESC_MAX_WAVES];
     const int b = blockIdx.x, i = threadIdx.x;
     const int o = node_off[b], n = node_off[b + 1] - o;
@@ -224,34 +216,31 @@ __global__ void __launch_bounds__(GADAPT_FEM1D_MAX_NODES) fem1d_descent_step_ker
     if (i == 0) record_epoch(b, n_meshes, epoch, m, loss, loss_hist, first_tangled, min_area);
 }
 
-extern "C" int gadapt_fem1d_descend(int B, int nmax, const int32_t* node_off, float* x, const int32_t* gptr, const float* gpar, int k_load,
-                                    int k_stiff, int P, const float* pts, int epochs, float lr, int mesh_params, int n_nodes,
+extern "C" int gadapt_fem1d_descend(int n_meshes, int max_nodes, const int32_t* node_off, float* x, const int32_t* gptr, const float* gpar,
+                                    int k_load, int k_stiff, int n_pts, const float* pts, int epochs, float lr, int mesh_params, int n_nodes,
                                     float* coeffs, float* sol, int32_t* flags, float* loss, float* g_sol, float* gx, float* loss_hist,
                                     float* mesh_hist, int32_t* first_tangled, float* min_area, void* stream) {
-    if (B <= 0 || epochs < 0 || n_nodes <= 0 || !node_off || !x || !gptr || !gpar || !pts || P < 2 || !coeffs || !sol || !flags || !loss ||
-        !g_sol || !gx || !first_tangled || !min_area || (epochs > 0 && !loss_hist) ||
+    if (n_meshes <= 0 || epochs < 0 || n_nodes <= 0 || !node_off || !x || !gptr || !gpar || !pts || n_pts < 2 || !coeffs || !sol || !flags ||
+        !loss || !g_sol || !gx || !first_tangled || !min_area || (epochs > 0 && !loss_hist) ||
         (mesh_params != GADAPT_FEM1D_DESCEND_INTERNAL && mesh_params != GADAPT_FEM1D_DESCEND_ALL))
         return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_descend: null pointer, bad size or unknown mesh_params");
-    if (nmax < 3 || nmax > GADAPT_FEM1D_MAX_NODES)
-        return fem_fail(nmax > GADAPT_FEM1D_MAX_NODES ? GADAPT_FEM_E_LDS : GADAPT_FEM_E_BADARG,
+    if (max_nodes < 3 || max_nodes > GADAPT_FEM1D_MAX_NODES)
+        return fem_fail(max_nodes > GADAPT_FEM1D_MAX_NODES ? GADAPT_FEM_E_LDS : GADAPT_FEM_E_BADARG,
                         "gadapt_fem1d_descend: 3..GADAPT_FEM1D_MAX_NODES nodes per mesh (one lane per node)");
+    // the quadrature, as gadapt_fem1d_poisson_forward refuses it in an epoch (and under its name); the Poisson layout fits any
+    // max_nodes that got here (fem1d_common.h)
+    if (epochs > 0 && (k_load < 2 || k_stiff < 1))
+        return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_poisson_forward: need load_quad_points >= 2 and stiff_quad_points >= 1");
+    const Fem1dBatch b = FEM1D_BATCH(gptr, gpar, k_load, k_stiff);
+    const Fem1dPlan solve = fem1d_plan(Fem1dOp::poisson, max_nodes), step = fem1d_plan(Fem1dOp::descent_step, max_nodes);
     hipStream_t s = (hipStream_t)stream;
-    fem1d_descent_init_kernel<<<(B + DESC_THREADS - 1) / DESC_THREADS, DESC_THREADS, 0, s>>>(B, first_tangled, min_area);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
-    const int threads = ((nmax + 63) / 64) * 64;
+    FEM_LAUNCH(fem1d_descent_init_kernel, (n_meshes + DESC_THREADS - 1) / DESC_THREADS, DESC_THREADS, 0, n_meshes, first_tangled, min_area);
     for (int j = 0; j < epochs; ++j) {
-        int rc = gadapt_fem1d_poisson_forward(B, nmax, node_off, x, gptr, gpar, k_load, k_stiff, P, pts, coeffs, sol, flags, stream);
-        if (rc) return rc;
-        fem1d_l2_seed_kernel<<<B, DESC_THREADS, 0, s>>>(gptr, gpar, P, pts, sol, loss, g_sol);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
-        rc = gadapt_fem1d_poisson_backward(B, nmax, node_off, x, gptr, gpar, k_load, k_stiff, P, pts, coeffs, nullptr, g_sol, gx, stream);
-        if (rc) return rc;
-        fem1d_descent_step_kernel<<<B, threads, (size_t)nmax * 4, s>>>(node_off, gx, loss, lr, mesh_params == GADAPT_FEM1D_DESCEND_ALL, j, B,
-                                                                       n_nodes, x, loss_hist, mesh_hist, first_tangled, min_area);
-        e = hipGetLastError();
-        if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
+        if (int rc = fem1d_launch_poisson_forward(b, solve, coeffs, sol, flags, s)) return rc;
+        FEM_LAUNCH(fem1d_l2_seed_kernel, n_meshes, DESC_THREADS, 0, gptr, gpar, n_pts, pts, sol, loss, g_sol);
+        if (int rc = fem1d_launch_poisson_backward(b, solve, coeffs, nullptr, g_sol, gx, s)) return rc;
+        FEM_LAUNCH(fem1d_descent_step_kernel, n_meshes, step.threads, (size_t)step.lds_bytes, node_off, gx, loss, lr,
+                   mesh_params == GADAPT_FEM1D_DESCEND_ALL, j, n_meshes, n_nodes, x, loss_hist, mesh_hist, first_tangled, min_area);
     }
     return GADAPT_FEM_OK;
 }

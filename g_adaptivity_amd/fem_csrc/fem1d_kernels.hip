@@ -8,6 +8,7 @@
 // points must round as in the fp32 reference.
 #include <stdio.h>
 #include "fem_common.h"
+#include "fem1d_common.h"
 #include "fem_host.h"
 
 #pragma clang fp contract(off)
@@ -76,15 +77,7 @@ __device__ inline float dexpand(const float* m, const float* c, int N, int I) {
     return c[J + 1] * dphi - c[J] * dphi;
 }
 
-// sum_g exp(-(x-c)^2/s^2)
-__device__ inline float gauss(float x, const float* __restrict__ gpar, int g0, int g1) {
-    float sol = 0.0f;
-    for (int g = g0; g < g1; ++g) {
-        const float c = gpar[2 * g], s = gpar[2 * g + 1], r = x - c;
-        sol += expf(-(r * r) / (s * s));
-    }
-    return sol;
-}
+// gauss(x, gpar, g0, g1) = sum_g exp(-(x-c)^2/s^2): fem1d_common.h
 // the reference's Poisson forcing f = sum_g -2 exp(-(x-c)^2/s^2) (s^2 - 2 (x-c)^2) / s^4 and its derivative in x
 __device__ inline float forcing(float x, const float* __restrict__ gpar, int g0, int g1, float* dfdx) {
     float sol = 0.0f, ds = 0.0f;
@@ -159,11 +152,7 @@ struct Acc4 {
     }
 };
 
-// One mesh's LDS working set (the arrays a given launch uses).
-struct W1 {
-    float *m, *c, *r, *cp, *Sl, *Sd, *Su, *t0, *t1, *t2, *t3;
-    int n;
-};
+// W1, one mesh's LDS working set, and F1_W1_ROWS, which carves it: fem1d_common.h
 
 __device__ inline void thomas(const float* l, const float* d, const float* u, float* r, float* cp, int lo, int hi) {
     float c = u[lo] / d[lo];
@@ -417,9 +406,8 @@ __global__ void __launch_bounds__(F1_THREADS) burgers_fwd_kernel(
     for (int pass = 0; pass < (n_fine > 1 ? 2 : 1); ++pass) {
         const bool fine = pass == 1;
         const int cap = fine ? n_fine : nmax;
-        float* base = lds + (fine ? 11 * nmax : 0);
-        W1 w{base, base + cap, base + 2 * cap, base + 3 * cap, base + 4 * cap, base + 5 * cap, base + 6 * cap,
-             base + 7 * cap, base + 8 * cap, base + 9 * cap, base + 10 * cap, fine ? n_fine : n};
+        float* base = lds + (fine ? Layout::W1_ROWS * nmax : 0);
+        const W1 w{F1_W1_ROWS(base, cap), fine ? n_fine : n};
         load_mesh(w, x, off, fine ? n_fine : 0);
         if (!fine) {
             const int bad = not_increasing(w);
@@ -493,7 +481,7 @@ __device__ void flux_adjoint(const float* m, const float* c, int n, int i, int k
     trapz_backward(a, d, k, Z, Bk, ga, gb);
 }
 
-// LDS of the backward: m, un, g, gu (also Thomas scratch), Sl, Sd, Su, Ml, Md, Mu, s0..s3, gxs: 15 floats per node
+// LDS of the backward: m, un, g, gu (also Thomas scratch), Sl, Sd, Su, Ml, Md, Mu, s0..s3, gxs: Layout::BWD_ROWS floats per node
 __global__ void __launch_bounds__(F1_THREADS) burgers_bwd_kernel(
     const int32_t* __restrict__ node_off, const float* __restrict__ x, const float* __restrict__ bc, float tau, float taunu,
     int k_load, int k_stiff, int T, int nmax, int P, const float* __restrict__ pts, const float* __restrict__ hist,
@@ -503,9 +491,13 @@ __global__ void __launch_bounds__(F1_THREADS) burgers_bwd_kernel(
     const int b = blockIdx.x, t = threadIdx.x;
     const int off = node_off[b], n = node_off[b + 1] - off;
     float* L = lds;
-    float *m = L, *un = L + nmax, *g = L + 2 * nmax, *gu = L + 3 * nmax, *Sl = L + 4 * nmax, *Sd = L + 5 * nmax, *Su = L + 6 * nmax;
-    float *Ml = L + 7 * nmax, *Md = L + 8 * nmax, *Mu = L + 9 * nmax, *s0 = L + 10 * nmax, *s1 = L + 11 * nmax, *s2 = L + 12 * nmax;
-    float *s3 = L + 13 * nmax, *gxs = L + 14 * nmax;
+    // The rows are formed in increasing order: the compiler strength-reduces them in the order it meets them, and this order
+    // keeps the kernel's machine code what it was when the row numbers were written out here.
+    auto row = [&](int k) { return L + k * nmax; };
+    float *m = row(0), *un = row(1), *g = row(2), *gu = row(3), *Sl = row(Layout::SL), *Sd = row(Layout::SL + 1), *Su = row(Layout::SL + 2);
+    float *Ml = row(Layout::BWD_ML), *Md = row(Layout::BWD_ML + 1), *Mu = row(Layout::BWD_ML + 2);
+    float *s0 = row(Layout::BWD_S0), *s1 = row(Layout::BWD_S0 + 1), *s2 = row(Layout::BWD_S0 + 2), *s3 = row(Layout::BWD_S0 + 3);
+    float* gxs = row(Layout::BWD_GXS);
     // mass_rows / stiff_rows use t0..t3 = s0..s3 as scratch, r / cp are unused there
     W1 w{m, un, g, gu, Sl, Sd, Su, s0, s1, s2, s3, n};
     load_mesh(w, x, off, 0);
@@ -695,17 +687,16 @@ __device__ inline W1 poisson_solve(float* L, int b, const int32_t* __restrict__ 
                                    int32_t* __restrict__ flags) {
     const int t = threadIdx.x;
     const int off = node_off[b], n = node_off[b + 1] - off, g0 = gptr[b], g1 = gptr[b + 1];
-    W1 w{L, L + nmax, L + 2 * nmax, L + 3 * nmax, L + 4 * nmax, L + 5 * nmax, L + 6 * nmax, L + 7 * nmax, L + 8 * nmax,
-         L + 9 * nmax, L + 10 * nmax, n};
+    const W1 w{F1_W1_ROWS(L, nmax), n};
     load_mesh(w, x, off, 0);
     const int bad = not_increasing(w);
     if (t == 0) flags[b] = bad ? GADAPT_FEM1D_F_NOT_INCREASING : 0;
-    double* d64 = reinterpret_cast<double*>(L + 12 * nmax);
+    double* d64 = reinterpret_cast<double*>(L + Layout::POISSON_D64 * nmax);
     const float rhs = load_row(w, k_load, [&](float xq) { return forcing(xq, gpar, g0, g1, nullptr); });   // uses t0, t1
     const float bc1 = gauss(w.m[0], gpar, g0, g1), bc2 = gauss(w.m[n - 1], gpar, g0, g1);
     if (t < n) w.r[t] = rhs;
-    // three fp64 rows over the six fp32 rows Sl..t2 (byte offsets 16, 24, 32 nmax: 8-aligned for any nmax)
-    double *o64 = reinterpret_cast<double*>(L + 4 * nmax), *l64 = o64 + nmax, *r64 = o64 + 2 * nmax;
+    // three fp64 rows over the six fp32 rows Sl..t2 (Layout::POISSON_S64: 8-aligned for any nmax)
+    double *o64 = reinterpret_cast<double*>(L + Layout::POISSON_S64 * nmax), *l64 = o64 + nmax, *r64 = o64 + 2 * nmax;
     stiff_intervals64(w.m, n, k_stiff, o64, l64, r64);
     if (t == 0) {
         thomas64_poisson(o64, l64, r64, w.r, bc1, bc2, d64, d64 + nmax, n);
@@ -766,8 +757,7 @@ __global__ void __launch_bounds__(F1_THREADS) poisson_bwd_kernel(
     const int b = blockIdx.x, t = threadIdx.x;
     const int off = node_off[b], n = node_off[b + 1] - off, g0 = gptr[b], g1 = gptr[b + 1];
     float* L = lds;
-    W1 w{L, L + nmax, L + 2 * nmax, L + 3 * nmax, L + 4 * nmax, L + 5 * nmax, L + 6 * nmax, L + 7 * nmax, L + 8 * nmax,
-         L + 9 * nmax, L + 10 * nmax, n};
+    const W1 w{F1_W1_ROWS(L, nmax), n};
     load_mesh(w, x, off, 0);
     if (t < n) w.c[t] = coeffs[off + t];
     float al, ad, au;
@@ -782,7 +772,7 @@ __global__ void __launch_bounds__(F1_THREADS) poisson_bwd_kernel(
     }
     __syncthreads();
     if (t == 0) {
-        double* d64 = reinterpret_cast<double*>(L + 12 * nmax);
+        double* d64 = reinterpret_cast<double*>(L + Layout::POISSON_D64 * nmax);
         thomas64(w.Sl, w.Sd, w.Su, w.r, d64, d64 + nmax, 1, n - 1, true);
     }
     __syncthreads();
@@ -828,7 +818,7 @@ __global__ void __launch_bounds__(F1_THREADS) expand_kernel(const int32_t* __res
     extern __shared__ float lds[];
     const int b = blockIdx.x, t = threadIdx.x;
     const int off = node_off[b], n = node_off[b + 1] - off;
-    float *m = lds, *cc = lds + nmax;
+    float *m = lds, *cc = lds + nmax;            // Layout::EXPAND_ROWS
     if (t < n) { m[t] = x[off + t]; cc[t] = c[off + t]; }
     __syncthreads();
     for (int p = t; p < P; p += blockDim.x) {
@@ -838,138 +828,136 @@ __global__ void __launch_bounds__(F1_THREADS) expand_kernel(const int32_t* __res
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
-static int threads_for(int n) {
-    int t = ((n + 63) / 64) * 64;
-    return t < 64 ? 64 : t;
-}
-
-static int64_t poisson_lds_bytes(int nmax);
-
+// the largest of the Burgers and Poisson layouts (fem1d_common.h): what a caller that runs any of them has to find in the budget
 extern "C" int64_t gadapt_fem1d_lds_bytes(int max_nodes, int n_fine) {
-    const int64_t fwd = 11 * ((int64_t)max_nodes + (n_fine > 1 ? n_fine : 0)), bwd = 15 * (int64_t)max_nodes;
-    const int64_t burgers = 4 * (fwd > bwd ? fwd : bwd), poisson = poisson_lds_bytes(max_nodes);
+    const int64_t fwd = Layout::burgers_forward_bytes(max_nodes, n_fine), bwd = Layout::burgers_backward_bytes(max_nodes);
+    const int64_t burgers = fwd > bwd ? fwd : bwd, poisson = Layout::poisson_bytes(max_nodes);
     return burgers > poisson ? burgers : poisson;
 }
 
-// the Poisson launches: 12 float arrays, then the fp64 elimination (2 double arrays) at a double-aligned offset
-static int64_t poisson_lds_bytes(int nmax) { return 4 * (12 * (int64_t)nmax) + 16 * (int64_t)nmax; }
+// One lane per node in whole waves; the spline takes one wave per set, four for the larger sets' fill and queries.  The Burgers
+// launches are sized by gadapt_fem1d_lds_bytes, as their callers budget them.
+Fem1dPlan fem1d_plan(Fem1dOp op, int max_nodes, int n_fine) {
+    const int lanes = op == Fem1dOp::burgers_forward && n_fine > max_nodes ? n_fine : max_nodes;
+    const int threads = lanes < 64 ? 64 : ((lanes + 63) / 64) * 64;
+    switch (op) {
+        case Fem1dOp::burgers_forward: return {threads, gadapt_fem1d_lds_bytes(max_nodes, n_fine)};
+        case Fem1dOp::burgers_backward: return {threads, gadapt_fem1d_lds_bytes(max_nodes, 0)};
+        case Fem1dOp::poisson: return {threads, Layout::poisson_bytes(max_nodes)};
+        case Fem1dOp::expand: return {threads, Layout::expand_bytes(max_nodes)};
+        case Fem1dOp::spline: return {max_nodes <= 256 ? 64 : 256, Layout::spline_bytes(max_nodes)};
+        case Fem1dOp::descent_step: return {threads, Layout::descent_step_bytes(max_nodes)};
+    }
+    return {0, 0};
+}
 
-static int check_common(int B, int nmax, int min_nodes, const void* node_off, const void* x, int P, const void* pts, int k_load,
-                        int k_stiff, const char* what) {
+int fem1d_check(const char* who, const Fem1dBatch& b, int min_nodes, bool check_quadrature, bool own_bad, const char* own_msg,
+                int64_t lds_bytes) {
     char msg[200];
-    if (B < 1 || !node_off || !x || (P > 0 && !pts) || P < 0) {
-        snprintf(msg, sizeof msg, "%s: bad batch, pointers or point count", what);
-        return fem_fail(GADAPT_FEM_E_BADARG, msg);
-    }
-    if (nmax < min_nodes || nmax > GADAPT_FEM1D_MAX_NODES) {
-        snprintf(msg, sizeof msg, "%s: %d nodes per mesh; %d..%d supported (one lane per node, state in LDS)", what, nmax, min_nodes,
+    int code = GADAPT_FEM_E_BADARG;
+    if (b.n_meshes < 1 || !b.node_off || !b.x || (b.n_pts > 0 && !b.pts) || b.n_pts < 0) {
+        snprintf(msg, sizeof msg, "%s: bad batch, pointers or point count", who);
+    } else if (b.max_nodes < min_nodes || b.max_nodes > GADAPT_FEM1D_MAX_NODES) {
+        snprintf(msg, sizeof msg, "%s: %d nodes per mesh; %d..%d supported (one lane per node, state in LDS)", who, b.max_nodes, min_nodes,
                  GADAPT_FEM1D_MAX_NODES);
-        return fem_fail(nmax > GADAPT_FEM1D_MAX_NODES ? GADAPT_FEM_E_LDS : GADAPT_FEM_E_BADARG, msg);
+        if (b.max_nodes > GADAPT_FEM1D_MAX_NODES) code = GADAPT_FEM_E_LDS;
+    } else if (check_quadrature && (b.k_load < 2 || b.k_stiff < 1)) {
+        snprintf(msg, sizeof msg, "%s: need load_quad_points >= 2 and stiff_quad_points >= 1", who);
+    } else if (own_bad) {
+        snprintf(msg, sizeof msg, "%s: %s", who, own_msg);
+    } else if (lds_bytes > GADAPT_FEM_LDS_BUDGET) {
+        snprintf(msg, sizeof msg, "%s: needs %lld B of LDS, the budget is %d B", who, (long long)lds_bytes, GADAPT_FEM_LDS_BUDGET);
+        code = GADAPT_FEM_E_LDS;
+    } else {
+        return GADAPT_FEM_OK;
     }
-    if (k_load < 2 || k_stiff < 1) {
-        snprintf(msg, sizeof msg, "%s: need load_quad_points >= 2 and stiff_quad_points >= 1", what);
-        return fem_fail(GADAPT_FEM_E_BADARG, msg);
-    }
+    return fem_fail(code, msg);
+}
+
+int fem1d_launch_poisson_forward(const Fem1dBatch& b, const Fem1dPlan& P, float* coeffs, float* sol, int32_t* flags, hipStream_t s) {
+    FEM_LAUNCH(poisson_fwd_kernel, b.n_meshes, P.threads, (size_t)P.lds_bytes, b.node_off, b.x, b.gptr, b.gpar, b.k_load, b.k_stiff,
+               b.max_nodes, b.n_pts, b.pts, coeffs, sol, flags);
     return GADAPT_FEM_OK;
 }
 
-static int check_lds(int64_t bytes, const char* what) {
-    if (bytes > GADAPT_FEM_LDS_BUDGET) {
-        char msg[160];
-        snprintf(msg, sizeof msg, "%s: needs %lld B of LDS, the budget is %d B", what, (long long)bytes, GADAPT_FEM_LDS_BUDGET);
-        return fem_fail(GADAPT_FEM_E_LDS, msg);
-    }
+int fem1d_launch_poisson_backward(const Fem1dBatch& b, const Fem1dPlan& P, const float* coeffs, const float* g_coeffs, const float* g_sol,
+                                  float* gx, hipStream_t s) {
+    FEM_LAUNCH(poisson_bwd_kernel, b.n_meshes, P.threads, (size_t)P.lds_bytes, b.node_off, b.x, b.gptr, b.gpar, b.k_load, b.k_stiff,
+               b.max_nodes, b.n_pts, b.pts, coeffs, g_coeffs, g_sol, gx);
     return GADAPT_FEM_OK;
 }
 
-extern "C" int gadapt_fem1d_burgers_forward(int B, int nmax, const int32_t* node_off, const float* x, const float* u0, const float* bc,
-                                            const int32_t* gptr, const float* gpar, float amp, float tau, float taunu, int k_load,
-                                            int k_stiff, int k_proj, int k_proj_fine, int T, int n_fine, int P, const float* pts,
-                                            float* hist, float* sol, float* fine_sol, int32_t* flags, void* stream) {
-    int rc = check_common(B, nmax, 2, node_off, x, P, pts, k_load, k_stiff, "gadapt_fem1d_burgers_forward");
-    if (rc) return rc;
-    if (T < 1 || !hist || !sol || !flags || (!u0 && (!gptr || !gpar || k_proj < 2)) ||
-        (n_fine > 1 && (!fine_sol || !gptr || !gpar || k_proj_fine < 2)) || n_fine > GADAPT_FEM1D_MAX_NODES)
-        return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_burgers_forward: bad steps, pointers, projection or fine mesh");
-    const int64_t lds = gadapt_fem1d_lds_bytes(nmax, n_fine);
-    if ((rc = check_lds(lds, "gadapt_fem1d_burgers_forward"))) return rc;
-    const int threads = threads_for(nmax > n_fine ? nmax : n_fine);
-    burgers_fwd_kernel<<<B, threads, (size_t)lds, (hipStream_t)stream>>>(node_off, x, u0, bc, gptr, gpar, amp, tau, taunu, k_load,
-                                                                         k_stiff, k_proj, k_proj_fine, T, nmax, n_fine, P, pts,
-                                                                         hist, sol, fine_sol, flags);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
+// Every entry point: fill the batch (the parameters carry the header's names), its own checks inside fem1d_check, the plan, launch.
+extern "C" int gadapt_fem1d_burgers_forward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const float* u0,
+                                            const float* bc, const int32_t* gptr, const float* gpar, float amp, float tau, float taunu,
+                                            int k_load, int k_stiff, int k_proj, int k_proj_fine, int n_steps, int n_fine, int n_pts,
+                                            const float* pts, float* hist, float* sol, float* fine_sol, int32_t* flags, void* stream) {
+    const Fem1dBatch b = FEM1D_BATCH(gptr, gpar, k_load, k_stiff);
+    const bool own_bad = n_steps < 1 || !hist || !sol || !flags || (!u0 && (!gptr || !gpar || k_proj < 2)) ||
+                         (n_fine > 1 && (!fine_sol || !gptr || !gpar || k_proj_fine < 2)) || n_fine > GADAPT_FEM1D_MAX_NODES;
+    const Fem1dPlan P = fem1d_plan(Fem1dOp::burgers_forward, max_nodes, n_fine);
+    if (int rc = fem1d_check("gadapt_fem1d_burgers_forward", b, 2, true, own_bad, "bad steps, pointers, projection or fine mesh", P.lds_bytes))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    FEM_LAUNCH(burgers_fwd_kernel, n_meshes, P.threads, (size_t)P.lds_bytes, node_off, x, u0, bc, gptr, gpar, amp, tau, taunu, k_load, k_stiff,
+               k_proj, k_proj_fine, n_steps, max_nodes, n_fine, n_pts, pts, hist, sol, fine_sol, flags);
     return GADAPT_FEM_OK;
 }
 
-extern "C" int gadapt_fem1d_burgers_backward(int B, int nmax, const int32_t* node_off, const float* x, const float* bc, float tau,
-                                             float taunu, int k_load, int k_stiff, int T, int P, const float* pts, const float* hist,
-                                             const float* g_sol, const float* g_last, float* gx, float* gu0, void* stream) {
-    int rc = check_common(B, nmax, 2, node_off, x, P, pts, k_load, k_stiff, "gadapt_fem1d_burgers_backward");
-    if (rc) return rc;
-    if (T < 1 || !hist || !gx) return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_burgers_backward: bad steps or pointers");
-    const int64_t lds = gadapt_fem1d_lds_bytes(nmax, 0);
-    if ((rc = check_lds(lds, "gadapt_fem1d_burgers_backward"))) return rc;
-    burgers_bwd_kernel<<<B, threads_for(nmax), (size_t)lds, (hipStream_t)stream>>>(node_off, x, bc, tau, taunu, k_load, k_stiff, T,
-                                                                                   nmax, P, pts, hist, g_sol, g_last, gx, gu0);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
+extern "C" int gadapt_fem1d_burgers_backward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const float* bc, float tau,
+                                             float taunu, int k_load, int k_stiff, int n_steps, int n_pts, const float* pts,
+                                             const float* hist, const float* g_sol, const float* g_last, float* gx, float* gu0,
+                                             void* stream) {
+    const Fem1dBatch b = FEM1D_BATCH(nullptr, nullptr, k_load, k_stiff);
+    const Fem1dPlan P = fem1d_plan(Fem1dOp::burgers_backward, max_nodes);
+    if (int rc = fem1d_check("gadapt_fem1d_burgers_backward", b, 2, true, n_steps < 1 || !hist || !gx, "bad steps or pointers", P.lds_bytes))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    FEM_LAUNCH(burgers_bwd_kernel, n_meshes, P.threads, (size_t)P.lds_bytes, node_off, x, bc, tau, taunu, k_load, k_stiff, n_steps, max_nodes,
+               n_pts, pts, hist, g_sol, g_last, gx, gu0);
     return GADAPT_FEM_OK;
 }
 
-extern "C" int gadapt_fem1d_poisson_forward(int B, int nmax, const int32_t* node_off, const float* x, const int32_t* gptr, const float* gpar,
-                                            int k_load, int k_stiff, int P, const float* pts, float* coeffs, float* sol, int32_t* flags,
-                                            void* stream) {
-    int rc = check_common(B, nmax, 3, node_off, x, P, pts, k_load, k_stiff, "gadapt_fem1d_poisson_forward");
-    if (rc) return rc;
-    if (!gptr || !gpar || !coeffs || !sol || !flags) return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_poisson_forward: null pointer");
-    const int64_t lds = poisson_lds_bytes(nmax);
-    if ((rc = check_lds(lds, "gadapt_fem1d_poisson_forward"))) return rc;
-    poisson_fwd_kernel<<<B, threads_for(nmax), (size_t)lds, (hipStream_t)stream>>>(node_off, x, gptr, gpar, k_load, k_stiff, nmax, P, pts,
-                                                                                   coeffs, sol, flags);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
-    return GADAPT_FEM_OK;
+extern "C" int gadapt_fem1d_poisson_forward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
+                                            const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts, float* coeffs,
+                                            float* sol, int32_t* flags, void* stream) {
+    const Fem1dBatch b = FEM1D_BATCH(gptr, gpar, k_load, k_stiff);
+    const Fem1dPlan P = fem1d_plan(Fem1dOp::poisson, max_nodes);
+    if (int rc = fem1d_check("gadapt_fem1d_poisson_forward", b, 3, true, !gptr || !gpar || !coeffs || !sol || !flags, "null pointer", P.lds_bytes))
+        return rc;
+    return fem1d_launch_poisson_forward(b, P, coeffs, sol, flags, (hipStream_t)stream);
 }
 
-extern "C" int gadapt_fem1d_poisson_eval_errors(int B, int nmax, const int32_t* node_off, const float* x, const int32_t* gptr,
-                                                const float* gpar, int k_load, int k_stiff, int P, const float* pts, float* err,
+extern "C" int gadapt_fem1d_poisson_eval_errors(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
+                                                const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts, float* err,
                                                 int32_t* flags, void* stream) {
-    int rc = check_common(B, nmax, 3, node_off, x, P, pts, k_load, k_stiff, "gadapt_fem1d_poisson_eval_errors");
-    if (rc) return rc;
-    if (!gptr || !gpar || !err || !flags || P < 2)
-        return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_poisson_eval_errors: null pointer or fewer than 2 evaluation points");
-    const int64_t lds = poisson_lds_bytes(nmax);
-    if ((rc = check_lds(lds, "gadapt_fem1d_poisson_eval_errors"))) return rc;
-    poisson_err_kernel<<<B, threads_for(nmax), (size_t)lds, (hipStream_t)stream>>>(node_off, x, gptr, gpar, k_load, k_stiff, nmax, P, pts,
-                                                                                   err, flags);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
+    const Fem1dBatch b = FEM1D_BATCH(gptr, gpar, k_load, k_stiff);
+    const Fem1dPlan P = fem1d_plan(Fem1dOp::poisson, max_nodes);
+    if (int rc = fem1d_check("gadapt_fem1d_poisson_eval_errors", b, 3, true, !gptr || !gpar || !err || !flags || n_pts < 2,
+                             "null pointer or fewer than 2 evaluation points", P.lds_bytes))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    FEM_LAUNCH(poisson_err_kernel, n_meshes, P.threads, (size_t)P.lds_bytes, node_off, x, gptr, gpar, k_load, k_stiff, max_nodes, n_pts, pts, err,
+               flags);
     return GADAPT_FEM_OK;
 }
 
-extern "C" int gadapt_fem1d_poisson_backward(int B, int nmax, const int32_t* node_off, const float* x, const int32_t* gptr,
-                                             const float* gpar, int k_load, int k_stiff, int P, const float* pts, const float* coeffs,
+extern "C" int gadapt_fem1d_poisson_backward(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
+                                             const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts, const float* coeffs,
                                              const float* g_coeffs, const float* g_sol, float* gx, void* stream) {
-    int rc = check_common(B, nmax, 3, node_off, x, P, pts, k_load, k_stiff, "gadapt_fem1d_poisson_backward");
-    if (rc) return rc;
-    if (!gptr || !gpar || !coeffs || !gx) return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_poisson_backward: null pointer");
-    const int64_t lds = poisson_lds_bytes(nmax);
-    if ((rc = check_lds(lds, "gadapt_fem1d_poisson_backward"))) return rc;
-    poisson_bwd_kernel<<<B, threads_for(nmax), (size_t)lds, (hipStream_t)stream>>>(node_off, x, gptr, gpar, k_load, k_stiff, nmax, P, pts,
-                                                                                   coeffs, g_coeffs, g_sol, gx);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
-    return GADAPT_FEM_OK;
+    const Fem1dBatch b = FEM1D_BATCH(gptr, gpar, k_load, k_stiff);
+    const Fem1dPlan P = fem1d_plan(Fem1dOp::poisson, max_nodes);
+    if (int rc = fem1d_check("gadapt_fem1d_poisson_backward", b, 3, true, !gptr || !gpar || !coeffs || !gx, "null pointer", P.lds_bytes))
+        return rc;
+    return fem1d_launch_poisson_backward(b, P, coeffs, g_coeffs, g_sol, gx, (hipStream_t)stream);
 }
 
-extern "C" int gadapt_fem1d_expand(int B, int nmax, const int32_t* node_off, const float* x, const float* c, int P, const float* pts,
-                                   float* sol, void* stream) {
-    int rc = check_common(B, nmax, 2, node_off, x, P, pts, 2, 1, "gadapt_fem1d_expand");
-    if (rc) return rc;
-    if (!c || !sol) return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_expand: null pointer");
-    expand_kernel<<<B, threads_for(nmax), (size_t)8 * nmax, (hipStream_t)stream>>>(node_off, x, c, nmax, P, pts, sol);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
+extern "C" int gadapt_fem1d_expand(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const float* c, int n_pts,
+                                   const float* pts, float* sol, void* stream) {
+    const Fem1dBatch b = FEM1D_BATCH(nullptr, nullptr, 0, 0);
+    const Fem1dPlan P = fem1d_plan(Fem1dOp::expand, max_nodes);
+    if (int rc = fem1d_check("gadapt_fem1d_expand", b, 2, false, !c || !sol, "null pointer", P.lds_bytes)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    FEM_LAUNCH(expand_kernel, n_meshes, P.threads, (size_t)P.lds_bytes, node_off, x, c, max_nodes, n_pts, pts, sol);
     return GADAPT_FEM_OK;
 }

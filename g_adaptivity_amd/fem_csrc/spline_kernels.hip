@@ -19,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
+#include "fem1d_common.h"
 #include "fem_host.h"
 
 #pragma clang fp contract(off)
@@ -28,11 +29,12 @@ namespace {
 __global__ void spline_kernel(const int32_t* __restrict__ set_off, const float* __restrict__ x, const float* __restrict__ y,
                               const float* __restrict__ q, const int32_t* __restrict__ q_off, int Q, int deriv, int nmax,
                               float* __restrict__ out, int32_t* __restrict__ status) {
-    extern __shared__ double lds[];
+    extern __shared__ double lds[];  // f1::Layout::SPLINE_ROWS rows of nmax doubles
     double* sx = lds;                // [nmax] abscissae
     double* sy = sx + nmax;          // [nmax] ordinates
     double* sm = sy + nmax;          // [nmax] second derivatives M (the Thomas right-hand side on the way)
     double* sc = sm + nmax;          // [nmax] the sweep's upper-diagonal ratios
+    static_assert(f1::Layout::SPLINE_ROWS == 4, "sx, sy, sm, sc");
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const int o = set_off[b], n = set_off[b + 1] - o;
     const int64_t q0 = q_off ? (int64_t)q_off[b] : 0, o0 = q_off ? q0 : (int64_t)b * Q;
@@ -117,20 +119,21 @@ __global__ void spline_kernel(const int32_t* __restrict__ set_off, const float* 
 
 }  // namespace
 
-extern "C" int gadapt_fem1d_spline(int B, int nmax, const int32_t* set_off, const float* x, const float* y, int Q, const float* q,
-                                   const int32_t* q_off, int deriv, float* out, int32_t* status, void* stream) {
-    if (B < 1 || !set_off || !x || !y || !q || !out || !status || Q < 0 || (!q_off && Q < 1))
+// Sets and queries where the FEM entry points have meshes and points: its checks are its own, in its order; the plan and the
+// launch are the shared ones (fem_host.h).
+extern "C" int gadapt_fem1d_spline(int n_sets, int max_nodes, const int32_t* set_off, const float* x, const float* y, int n_queries,
+                                   const float* q, const int32_t* q_off, int deriv, float* out, int32_t* status, void* stream) {
+    if (n_sets < 1 || !set_off || !x || !y || !q || !out || !status || n_queries < 0 || (!q_off && n_queries < 1))
         return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_spline: bad batch, pointers or query count");
     if (deriv < 0 || deriv > 2) return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem1d_spline: deriv is 0, 1 or 2");
-    if (nmax < 4 || nmax > GADAPT_FEM1D_MAX_NODES) {
+    if (max_nodes < 4 || max_nodes > GADAPT_FEM1D_MAX_NODES) {
         char msg[160];
-        snprintf(msg, sizeof msg, "gadapt_fem1d_spline: %d points per set; 4..%d supported (the set lives in LDS)", nmax,
+        snprintf(msg, sizeof msg, "gadapt_fem1d_spline: %d points per set; 4..%d supported (the set lives in LDS)", max_nodes,
                  GADAPT_FEM1D_MAX_NODES);
-        return fem_fail(nmax > GADAPT_FEM1D_MAX_NODES ? GADAPT_FEM_E_LDS : GADAPT_FEM_E_BADARG, msg);
+        return fem_fail(max_nodes > GADAPT_FEM1D_MAX_NODES ? GADAPT_FEM_E_LDS : GADAPT_FEM_E_BADARG, msg);
     }
-    const int threads = nmax <= 256 ? 64 : 256;                     // one wave per set; four for the larger sets' fill and queries
-    spline_kernel<<<B, threads, (size_t)32 * nmax, (hipStream_t)stream>>>(set_off, x, y, q, q_off, Q, deriv, nmax, out, status);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fem_fail(GADAPT_FEM_E_LAUNCH, hipGetErrorString(e));
+    const Fem1dPlan P = fem1d_plan(Fem1dOp::spline, max_nodes);
+    hipStream_t s = (hipStream_t)stream;
+    FEM_LAUNCH(spline_kernel, n_sets, P.threads, (size_t)P.lds_bytes, set_off, x, y, q, q_off, n_queries, deriv, max_nodes, out, status);
     return GADAPT_FEM_OK;
 }

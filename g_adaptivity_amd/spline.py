@@ -75,9 +75,9 @@ def cubic_spline_1d(x: torch.Tensor, y: torch.Tensor, counts: Sequence[int], q: 
     status = torch.empty(B, dtype=torch.int32, device=dev)
     off = _offsets(counts, dev)
     with torch.cuda.device(dev):
-        _nf.check(_nf.lib().gadapt_fem1d_spline(B, max(counts), off.data_ptr(), x.data_ptr(), y.data_ptr(), Q, q.data_ptr(),
-                                                None if q_off is None else q_off.data_ptr(), int(deriv), out.data_ptr(),
-                                                status.data_ptr(), current_stream(dev)), 'gadapt_fem1d_spline')
+        # sets and queries, not a mesh batch with Gaussians: the head is spelt here and not by fem1d._Batch
+        _nf.call('gadapt_fem1d_spline', B, max(counts), off.data_ptr(), x.data_ptr(), y.data_ptr(), Q, q.data_ptr(),
+                 None if q_off is None else q_off.data_ptr(), int(deriv), out.data_ptr(), status.data_ptr(), current_stream(dev))
     call_stats['calls'] += 1
     call_stats['sets'] += B
     return out, status
