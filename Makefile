@@ -52,7 +52,7 @@ $(OBJDIR)/fem_topology.o: $(FEM_CSRC)/fem_topology.cpp include/gadapt_fem.h
 
 # the MMPDE5 target-mesh generator (include/gadapt_mesh.h): its own library, without FMA contraction like the FEM tails
 # (the stopping step of the fp32 iteration follows the rounding of its increments)
-MESH_OBJS  := $(OBJDIR)/mmpde5_kernels.o $(OBJDIR)/ma_kernels.o
+MESH_OBJS  := $(OBJDIR)/mmpde5_kernels.o $(OBJDIR)/ma_kernels.o $(OBJDIR)/ma_strided_kernels.o
 $(MESH_LIB): $(MESH_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(MESH_OBJS)
 
@@ -62,6 +62,11 @@ $(OBJDIR)/mmpde5_kernels.o: $(MESH_CSRC)/mmpde5_kernels.hip $(MESH_CSRC)/mesh_co
 
 # the Monge-Ampere target meshes (2-D): the same library and the same flags
 $(OBJDIR)/ma_kernels.o: $(MESH_CSRC)/ma_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+
+# their strided route with an fp64 potential (up to 81 x 81): an object of its own, the same flags
+$(OBJDIR)/ma_strided_kernels.o: $(MESH_CSRC)/ma_strided_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 

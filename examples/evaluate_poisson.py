@@ -10,6 +10,8 @@ error reduction of the last two, with the model's time per sample.
     python examples/evaluate_poisson.py --mesh 64 --band window --mmpde5_route strided --mmpde5_cfl 0.5 --mmpde5_max_steps 40000
                                                                  # ... with real MMPDE5 targets beyond 32 x 32
     python examples/evaluate_poisson.py --target monge_ampere    # the MA columns on Monge-Ampere meshes (2-D, at most 32 x 32)
+    python examples/evaluate_poisson.py --mesh 64 --band window --target monge_ampere --ma_route strided --ma_max_steps 40000
+                                                                 # ... beyond 32 x 32: the fp64-potential route, up to 81 x 81
 """
 import argparse
 import os
@@ -60,7 +62,12 @@ if __name__ == '__main__':
     ap.add_argument('--mmpde5_max_steps', type=int, default=None, help='step cap of MMPDE5 (default: the reference 10000)')
     ap.add_argument('--target', choices=('mmpde5', 'monge_ampere'), default='mmpde5',
                     help="the classical target behind the MA columns: MMPDE5 (default), or the finite-difference Monge-Ampere solve "
-                         "that stands for the reference's default 2-D target (2-D, --mesh <= 32)")
+                         "that stands for the reference's default 2-D target (2-D, --mesh <= 32, or <= 81 with --ma_route strided)")
+    ap.add_argument('--ma_route', choices=('lane', 'strided'), default='lane',
+                    help="Monge-Ampere targets: 'lane' (fp32 potential) stops at 32 a side, 'strided' (fp64 potential) at 81")
+    ap.add_argument('--ma_cfl', type=float, default=None, help='pseudo-time step of Monge-Ampere is cfl h^2 (default 0.2)')
+    ap.add_argument('--ma_max_steps', type=int, default=None,
+                    help='update cap of Monge-Ampere (default 20000; 64 x 64 wanted up to 25 500, 81 x 81 up to 32 000)')
     ap.add_argument('--num_train', type=int, default=32)
     ap.add_argument('--num_test', type=int, default=16)
     ap.add_argument('--epochs', type=int, default=20)
@@ -70,15 +77,17 @@ if __name__ == '__main__':
     dims = [a.mesh] * a.dim
     opt = hot_path_opt(mesh_dims=dims, hidden_dim=8, num_layers=4, batch_size=8, device='cuda:0', lr=1e-2, loss_type='mesh_loss',
                        solver='torch_FEM', evaler='analytical', eval_quad_points=101, load_quad_points=101,
-                       fem_band=a.band, mmpde5_route=a.mmpde5_route)
+                       fem_band=a.band, mmpde5_route=a.mmpde5_route, ma_route=a.ma_route)
     # the default route of the batched MMPDE5 generator stops at 32 nodes a side in 2-D: beyond it the "MA" columns are those of
     # the stand-in target unless --mmpde5_route strided is given (81 a side)
     target = 'mmpde5' if a.dim == 1 or a.mesh <= (81 if opt['mmpde5_route'] == 'strided' else 32) else 'noise'
     solver = {'route': opt['mmpde5_route']}
     solver.update({k: v for k, v in (('cfl', a.mmpde5_cfl), ('max_steps', a.mmpde5_max_steps)) if v is not None})
     target_params = {'solver': solver} if target == 'mmpde5' else None
-    if a.target == 'monge_ampere':                 # the reference's own 2-D configuration: 2-D, at most 32 a side, its own defaults
-        target, target_params = 'monge_ampere', None
+    if a.target == 'monge_ampere':                 # the reference's own 2-D configuration: 2-D, its own monitor defaults
+        solver = {'route': opt['ma_route']}
+        solver.update({k: v for k, v in (('cfl', a.ma_cfl), ('max_steps', a.ma_max_steps)) if v is not None})
+        target, target_params = 'monge_ampere', {'solver': solver}
     test = MeshDataset(dims, a.num_test, seed=1, target=target, target_params=target_params)
     torch.manual_seed(0)
     model = GNN(test, opt).to(opt['device'])

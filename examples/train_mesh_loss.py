@@ -89,19 +89,28 @@ if __name__ == '__main__':
     ap.add_argument('--target', choices=('noise', 'mmpde5', 'monge_ampere'), default='noise',
                     help="x_phys of the samples: the noise stand-in, the reference's MMPDE5 meshes (one batched GPU call; --mesh <= 32, "
                          "or <= 81 with --mmpde5_route strided), or Monge-Ampere meshes, the reference's default 2-D target "
-                         "(finite differences, one batched GPU call; --mesh <= 32)")
+                         "(finite differences, one batched GPU call; --mesh <= 32, or <= 81 with --ma_route strided)")
     ap.add_argument('--mmpde5_route', choices=('lane', 'strided'), default='lane', help="route of the MMPDE5 generator (--target mmpde5)")
     ap.add_argument('--mmpde5_cfl', type=float, default=None, help='RK4 step of MMPDE5 is cfl / N^3 (default: the reference 0.05)')
     ap.add_argument('--mmpde5_max_steps', type=int, default=None, help='step cap of MMPDE5 (default: the reference 10000)')
+    ap.add_argument('--ma_route', choices=('lane', 'strided'), default='lane',
+                    help="route of the Monge-Ampere generator (--target monge_ampere): 'lane' to 32 a side, 'strided' (fp64 potential) to 81")
+    ap.add_argument('--ma_cfl', type=float, default=None, help='pseudo-time step of Monge-Ampere is cfl h^2 (default 0.2)')
+    ap.add_argument('--ma_max_steps', type=int, default=None,
+                    help='update cap of Monge-Ampere (default 20000; 64 x 64 wanted up to 25 500, 81 x 81 up to 32 000)')
     a = ap.parse_args()
     opt = hot_path_opt(mesh_dims=[a.mesh, a.mesh], hidden_dim=a.hidden_dim, num_layers=a.num_layers, batch_size=a.batch_size,
                        epochs=a.epochs, device='cuda:0', loss_fn='mse', lr=1e-3, show_mesh_evol_plots='False',
                        device_loader=not a.cpu_loader, native_loss=not a.torch_loss, graphed=not a.eager,
-                       mmpde5_route=a.mmpde5_route)
-    solver = {'route': opt['mmpde5_route']}
-    solver.update({k: v for k, v in (('cfl', a.mmpde5_cfl), ('max_steps', a.mmpde5_max_steps)) if v is not None})
+                       mmpde5_route=a.mmpde5_route, ma_route=a.ma_route)
+    if a.target == 'monge_ampere':
+        solver = {'route': opt['ma_route']}
+        solver.update({k: v for k, v in (('cfl', a.ma_cfl), ('max_steps', a.ma_max_steps)) if v is not None})
+    else:
+        solver = {'route': opt['mmpde5_route']}
+        solver.update({k: v for k, v in (('cfl', a.mmpde5_cfl), ('max_steps', a.mmpde5_max_steps)) if v is not None})
     ds = MeshDataset(opt['mesh_dims'], a.num_train, seed=0, target=a.target,
-                     target_params={'solver': solver} if a.target == 'mmpde5' else None)
+                     target_params={'solver': solver} if a.target != 'noise' else None)
     t0 = time.time()
     model, losses, rate = main(opt, ds)
     torch.cuda.synchronize()

@@ -292,7 +292,8 @@ class MeshDataset:
         need `target_params={'solver': {'route': 'strided', ...}}`, and want `cfl` or `max_steps` raised there (`mmpde5.py`).
         'monge_ampere': the reference's default 2-D target (`mesh_type = 'ma'`), a finite-difference Monge-Ampere solve of the
         sample's own Gaussians (`monge_ampere.attach_ma_targets`; 2-D only, N <= 32; `target_params`: `mon_reg` / `mon_power` and
-        keyword arguments of `ma_batch` under 'solver')."""
+        keyword arguments of `ma_batch` under 'solver').  33..81 a side need `target_params={'solver': {'route': 'strided',
+        'max_steps': 40000}}`: the fp64-potential route, which wants more updates than the default cap (`monge_ampere.py`)."""
         self.mesh_dims = list(mesh_dims)
         self.dim = len(self.mesh_dims)
         if self.dim == 1:

@@ -16,7 +16,17 @@ fp64 restatement (`tests/ma_restatement.py`) and the equidistribution it has to 
 `MA2d` and `deform_mesh_ma2d` keep the reference's names, argument lists and return tuples.  2-D only (the reference has no
 1-D MA), 3 <= N <= 32 a side, at most 8 Gaussians; anything else raises `ValueError`.  The iteration runs on the GPU only:
 `NativeError` without one.  The `M2N` monitors of `MA2d` are not built: they need a maximum over the moving nodes at every
-step and FEM solves.  Sides above 32 are not built either: the fp32 residual floor reaches `tol` near 64 x 64.
+step and FEM solves.
+
+Two routes (`ROUTES`).  `route='lane'`, the default, holds one node per lane and phi in fp32: 3 <= N <= 32.  Its residual floor
+reaches `tol` near 64 x 64 (at 81 x 81 the fp32 restatement stops 12 % late), so sides above 32 are not the same kernel with
+more nodes: `route='strided'` (`ma_batch`, `attach_ma_targets` and through it the datasets' `target_params['solver']`) holds
+K = ceil(N^2 / 1024) <= 7 nodes per lane and phi in fp64, 3 <= N <= 81, everything after the five stencil expressions in the
+lane route's fp32.  THE TWO ROUTES DO NOT SHARE BITS at N <= 32: phi is fp64 on one and fp32 on the other; each is within its
+own noise bar of the fp64 restatement.  Nothing changes its route unasked; `MA2d` and `deform_mesh_ma2d` stay on 'lane'.
+The defaults `cfl=0.2, tol=1e-4, max_steps=20000` hold on both routes: 64 x 64 wanted 17 500 to 25 500 updates in the cases
+tried and 81 x 81 28 000 to 32 000, so large meshes need `max_steps` raised (40 000 covered both), and the default call can
+return CAP there.
 """
 from __future__ import annotations
 
@@ -35,6 +45,8 @@ from .mmpde5 import _gauss_dd, unit_grid, warn_unconverged, write_back_to_nodes
 CONVERGED, CAP, NONCONVEX = _native_mesh.MA_CONVERGED, _native_mesh.MA_CAP, _native_mesh.MA_NONCONVEX
 STATUS_NAMES = {CONVERGED: 'converged', CAP: 'cap reached', NONCONVEX: 'convexity lost'}
 MAX_SIDE, MAX_GAUSS = _native_mesh.MA_MAX_SIDE, _native_mesh.MA_MAX_GAUSS
+STRIDED_MAX_SIDE = _native_mesh.MA_STRIDED_MAX_SIDE
+ROUTES = ('lane', 'strided')
 
 MAResult = namedtuple('MAResult', 'coords steps residual status')
 
@@ -62,7 +74,7 @@ def monitor_ma(x: torch.Tensor, y: torch.Tensor, params) -> torch.Tensor:
     return (reg + torch.sqrt(uxx ** 2 + uyy ** 2)) ** power
 
 
-def _side(b: int, size) -> int:
+def _side(b: int, size, route: str = 'lane') -> int:
     if isinstance(size, (tuple, list)):
         if len(size) != 2 or int(size[0]) != int(size[1]):
             raise ValueError(f"mesh {b}: size {tuple(size)}; square grids only")
@@ -70,8 +82,12 @@ def _side(b: int, size) -> int:
     n = int(size)
     if n < 3:
         raise ValueError(f"mesh {b}: N = {n}; at least 3 nodes a side")
-    if n > MAX_SIDE:
-        raise ValueError(f"mesh {b}: N = {n}; Monge-Ampere meshes go up to {MAX_SIDE} a side (one lane per node, one workgroup per mesh)")
+    if route == 'strided':
+        if n > STRIDED_MAX_SIDE:
+            raise ValueError(f"mesh {b}: N = {n}; route='strided' goes up to {STRIDED_MAX_SIDE} a side (one workgroup per mesh)")
+    elif n > MAX_SIDE:
+        raise ValueError(f"mesh {b}: N = {n}; Monge-Ampere meshes go up to {MAX_SIDE} a side (one lane per node, one workgroup per mesh); "
+                         f"route='strided' goes up to {STRIDED_MAX_SIDE}")
     return n
 
 
@@ -89,16 +105,19 @@ def _gaussians(b: int, params):
     return rows
 
 
-def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000, device=None):
+def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000, device=None,
+             route: str = 'lane'):
     """The host side of `ma_batch`: checks, the batch's descriptors and Gaussians on the GPU, the argument list.  Returns
     (launch, collect): `launch()` issues the one kernel (it may be issued again), `collect()` gives the MAResult."""
+    if route not in ROUTES:
+        raise ValueError(f"route = {route!r}; one of {ROUTES}")
     if len(sizes) == 0 or len(sizes) != len(pde_params):
         raise ValueError(f"{len(sizes)} mesh sizes and {len(pde_params)} parameter sets")
     if not (0 <= int(max_steps) <= _native_mesh.MAX_STEPS):
         raise ValueError(f"max_steps = {max_steps}; 0..{_native_mesh.MAX_STEPS} (the loop has to end)")
     if not (0 < cfl < float('inf') and 0 <= tol < float('inf')):
         raise ValueError(f"cfl = {cfl}, tol = {tol}; cfl > 0 and tol >= 0 expected")
-    ns = [_side(b, s) for b, s in enumerate(sizes)]
+    ns = [_side(b, s, route) for b, s in enumerate(sizes)]
     gauss = [_gaussians(b, p) for b, p in enumerate(pde_params)]
     mon = [monitor_constants(p) for p in pde_params]
     B = len(ns)
@@ -128,9 +147,11 @@ def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
             int(max_steps), x.data_ptr(), y.data_ptr(), steps.data_ptr(), residual.data_ptr(), status.data_ptr())
     keep = (desc_host, desc_dev, gauss_dev, mon_dev)                     # what the argument list points into
 
+    entry = 'gadapt_ma_batch_strided' if route == 'strided' else 'gadapt_ma_batch'
+
     def launch(_keep=keep):                                              # the closure keeps the inputs alive
         with torch.cuda.device(dev):
-            _native_mesh.check(_native_mesh.lib().gadapt_ma_batch(*args, current_stream(dev)), 'gadapt_ma_batch')
+            _native_mesh.check(getattr(_native_mesh.lib(), entry)(*args, current_stream(dev)), entry)
 
     def collect():
         out, o = [], 0
@@ -143,7 +164,7 @@ def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
 
 
 def ma_batch(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000,
-             device=None) -> MAResult:
+             device=None, route: str = 'lane') -> MAResult:
     """Monge-Ampere meshes of many samples, mixed sizes in one launch.
 
     sizes[b]       N (or a pair (N, N)): the mesh is the N x N grid on the unit square, node (i, j) of meshgrid(..., indexing='ij')
@@ -152,12 +173,15 @@ def ma_batch(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
     cfl            the pseudo-time step is cfl h^2 min(1, lambda_min); 0.2 converged in every case tried up to 32 x 32, 0.5
                    oscillates into the cap, 1 loses convexity at once
     tol            stop when max |r - mean r| <= tol; 0 runs exactly `max_steps` updates
-    max_steps      the cap (32 x 32 needed up to 8 200 residual evaluations)
+    max_steps      the cap (32 x 32 needed up to 8 200 residual evaluations; 64 x 64 wanted 17 500 to 25 500 updates and
+                   81 x 81 28 000 to 32 000: raise it there, the default can return CAP)
+    route          'lane' (3 <= N <= 32, phi in fp32) or 'strided' (3 <= N <= 81, phi in fp64, K = ceil(N^2 / 1024) nodes per
+                   lane).  The two do not give the same bits at N <= 32; any other value is a `ValueError`
 
     Returns MAResult(coords, steps, residual, status) on the GPU: coords[b] is [2, N, N], and per-mesh tensors of the number of
     updates (int32), the last residual and CONVERGED / CAP / NONCONVEX.  A mesh's result does not depend on its batch.
     """
-    launch, collect = _prepare(sizes, pde_params, cfl=cfl, tol=tol, max_steps=max_steps, device=device)
+    launch, collect = _prepare(sizes, pde_params, cfl=cfl, tol=tol, max_steps=max_steps, device=device, route=route)
     launch()
     return collect()
 
@@ -171,11 +195,16 @@ def warn_status(status, what: str = 'Monge-Ampere'):
     warn_unconverged([_native_mesh.CAP if s == CAP else _native_mesh.CONVERGED for s in st], what)
 
 
-def _solver_kwargs(solver: dict) -> dict:
-    extra = set(solver) - {'cfl', 'max_steps', 'tol', 'device'}
+def _solver_kwargs(solver: dict, allowed=('cfl', 'tol', 'max_steps', 'device')) -> dict:
+    extra = set(solver) - set(allowed)
     if extra:
-        raise TypeError(f"unexpected keyword arguments {sorted(extra)}; cfl, tol, max_steps and device go to ma_batch")
+        raise TypeError(f"unexpected keyword arguments {sorted(extra)}; {', '.join(allowed[:-1])} and {allowed[-1]} go to ma_batch")
     return solver
+
+
+def _dataset_solver_kwargs(solver: dict) -> dict:
+    """The dataset path also takes `route`; `MA2d` and `deform_mesh_ma2d` keep the reference-shaped keyword set."""
+    return _solver_kwargs(solver, ('cfl', 'tol', 'max_steps', 'route', 'device'))
 
 
 # --------------------------------------------------------------------------
@@ -220,8 +249,9 @@ def attach_ma_targets(samples, monitor_params: Optional[dict] = None, **solver):
     """`x_phys` of every sample := its Monge-Ampere mesh, all samples in ONE batched call; `ma_its` = updates + 1 and
     `build_time` (the batched call's wall time shared out evenly) as `attach_mmpde5_targets` sets them.  The monitor of a
     sample is `monitor_ma` of its own `pde_params` with `monitor_params` (`mon_reg`, `mon_power`) added.  The samples' meshes
-    must be square grids in grid order (`square_mesh`).  A sample that lost convexity gets zeros and `ma_its` = 1."""
-    _solver_kwargs(solver)
+    must be square grids in grid order (`square_mesh`).  A sample that lost convexity gets zeros and `ma_its` = 1.
+    Keyword-only `cfl`, `tol`, `max_steps`, `route` and `device` go to `ma_batch` (`route='strided'` for 33..81 a side)."""
+    _dataset_solver_kwargs(solver)
     sizes, params = [], []
     for d in samples:
         if d.x_comp.dim() != 2 or d.x_comp.shape[1] != 2:

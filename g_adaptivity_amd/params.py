@@ -44,6 +44,9 @@ def hot_path_opt(**overrides) -> dict:
         # not a reference key: the route of the MMPDE5 target meshes that the examples build (`target_params={'solver':
         # {'route': ...}}` of the datasets).  'lane': one node per lane, 2-D meshes up to 32 x 32; 'strided': up to 81 x 81
         'mmpde5_route': 'lane',
+        # not a reference key: the route of the Monge-Ampere target meshes that the examples build, passed on in the same way.
+        # 'lane': one node per lane and an fp32 potential, up to 32 x 32; 'strided': an fp64 potential, up to 81 x 81
+        'ma_route': 'lane',
         # features
         'gnn_inc_feat_f': True,             # params.py:114
         'gnn_inc_feat_uu': True,            # params.py:115

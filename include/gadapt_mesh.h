@@ -1,6 +1,6 @@
 /*
  * gadapt_mesh.h - C-ABI of the classical target-mesh generators: batched MMPDE5 and, further down, batched Monge-Ampere
- * (libgadapt_mesh.so).
+ * (libgadapt_mesh.so; one node per lane up to 32 x 32, and a strided route with an fp64 potential up to 81 x 81).
  *
  * The reference builds the target mesh `x_phys` of loss_type='mesh_loss' with the moving-mesh PDE "MMPDE5"
  * (classical_meshing/ma_mesh_1d.py:7-134, ma_mesh_2d.py:11-103, called from src/data.py:394-416): classical RK4 in
@@ -150,6 +150,40 @@ int64_t gadapt_ma_lds_bytes(int nodes);
  * GADAPT_MESH_E_SIZE for N > 32, more than 8 Gaussians or max_steps beyond the cap; neither allocates nor synchronises. */
 int gadapt_ma_batch(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* gauss, const float* mon, double cfl,
                     double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual, int32_t* status, void* stream);
+
+/*
+ * The strided route: Monge-Ampere meshes up to gadapt_ma_strided_max_side() (81) a side, with an fp64 potential.  The fp32
+ * iteration above stalls against its rounding floor as the mesh grows (its residual floor reaches tol near 64 x 64), so this
+ * route is not the same arithmetic on more nodes: it is the iteration above with these changes and no others.
+ *   phi [N, N] is fp64 (it starts at 0 and is reflected as above).
+ *   The five stencil expressions are formed in fp64 from the fp64 phi, with the association and the exact constants above,
+ *   and each is rounded once to fp32:
+ *       px = (float)((phi[i+1,j] - phi[i-1,j]) * (n1 / 2))                                      py likewise in j
+ *       a  = (float)(1 + ((phi[i+1,j] - 2 phi[i,j]) + phi[i-1,j]) * n1^2)                       b likewise in j
+ *       c  = (float)((((phi[i+1,j+1] - phi[i+1,j-1]) - phi[i-1,j+1]) + phi[i-1,j-1]) * (n1^2 / 4))
+ *   Everything after that is the fp32 above, operation for operation: x = xi_i + px, det, lambda, the Gaussians, m,
+ *   r = logf(m det).
+ *   One workgroup per mesh, T = min(nodes rounded up to whole waves, 1024) lanes, K = ceil(nodes / T) <= 7 nodes per lane, lane t
+ *   owning nodes t + k T (the ownership of gadapt_mmpde5_batch_strided).  Reductions: a lane starts from 0, -inf, +inf, +inf and,
+ *   over its own slots in increasing k, adds w r, takes the max and the min of r and the min of lambda; then the 64 lanes of a
+ *   wave as above; then the waves in increasing order, read back from LDS by every lane alike, so that no lane decides an
+ *   exit from a value it computed alone.  Lanes and slots without a node contribute 0, -inf, +inf, +inf.
+ *   The exit tests are those above, in that order: NONCONVEX, then CONVERGED, then CAP.
+ *   Update: phi += (double)(((float)(cfl / n1^2) * fminf(1, lmin)) * (r - rbar)): the increment is formed in fp32 and added in fp64.
+ * T, K and the order of the reductions follow from the mesh's own node count only: a mesh gives the same bits alone and in any
+ * batch.  The two routes do NOT give the same bits at N <= 32: phi is fp64 here and fp32 there.
+ * With the default cfl = 0.2 and tol = 1e-4, 64 x 64 wanted 17 500 to 25 500 updates in the cases tried and 81 x 81
+ * 28 000 to 32 000: the default max_steps of the Python callers (20 000) can return CAP there.
+ * Arguments, descriptor, outputs, status words and error codes are those of gadapt_ma_batch; GADAPT_MESH_E_SIZE for N > 81, more
+ * than 8 Gaussians or max_steps beyond the cap; neither allocates nor synchronises.  The launch's dynamic LDS (one fp64 image of
+ * phi, the wave partials and the Gaussians' constants: 53 000 bytes at 81 x 81) stays below the 64 KB that need no raised limit.
+ */
+int gadapt_ma_strided_max_side(void);   /* 81 */
+/* Dynamic LDS of a strided launch whose largest mesh has `nodes` nodes (9..6561). */
+int64_t gadapt_ma_strided_lds_bytes(int nodes);
+int gadapt_ma_batch_strided(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* gauss, const float* mon,
+                            double cfl, double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual,
+                            int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
