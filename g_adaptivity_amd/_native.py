@@ -120,6 +120,7 @@ PROTOTYPES = {
     'gadapt_debug_set_narrow_tail_spread': (_I, [_I]),
     'gadapt_debug_occupancy': (_I, [_I, C.POINTER(C.c_int)]),
     'gadapt_debug_wave_sum_desc': (_I, [_P, _P, _P, _I, _I, _P]),
+    'gadapt_debug_wave_sum_scatter': (_I, [_P, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

@@ -1008,6 +1008,57 @@ template <int N> __device__ __forceinline__ void wave_sum_desc(float (&v)[N]) {
 #pragma unroll
     for (int k = 0; k < N; ++k) v[k] = dpp_add<0xB1>(v[k]);     // quad_perm [1,0,3,2]
 }
+// The same sums for the 20 slab partials with each total in ONE lane: the partner of every level (32, 16, 8, 4, 2, 1) and the addition
+// tree of every value are wave_sum_desc's, so the bits are (fp32 addition commutes; a NaN's payload is not pinned), but an exchange hands
+// over half of the values instead of all of them - the lane and its partner each keep the sum of one value and drop the other's:
+//     xor 32  v_permlane32_swap_b32 on the pair (e, e + 10): lanes 0..31 go on with entries 0..9, lanes 32..63 with 10..19   20 -> 10
+//     xor 16  v_permlane16_swap_b32 on the pair (e, e + 5): even rows go on with the lower five, odd rows with the upper     10 -> 5
+//     xor 8   two row_ror:8 adds into one register, banks 0, 1 from the first of a pair and banks 2, 3 from the second; the
+//             fifth register is summed whole (both halves of the row then hold its sum)                                       5 -> 3
+//     xor 4   row_shl:4 into banks 0, 2 and row_shr:4 into banks 1, 3 (lane i ^ 4 itself: the halves of a row now differ);
+//             the fifth register still takes row_ror:4 whole, as in wave_sum_desc                                             3 -> 2
+//     xor 2, xor 1  quad_perm on both registers (a quad has no write mask of its own: halving would cost a select per value)
+// 42 vector instructions where wave_sum_desc on 20 values is 240.  lane: the lane's index in the wave.  Returns the total of entry wave_sum_scatter_entry(lane) in the
+// lanes for which that is >= 0 (20 lanes, each entry once) and something else in the other 44.
+// CONTRACT: wave_sum_desc's - every lane of the wave is active.  The masked DPP adds are inline assembly like the swaps: the wait
+// states of a DPP or swap operand written by the instruction before are in the strings (s_nop 1), also behind the last string, whose
+// results the compiler's own DPP adds read next.
+__device__ __forceinline__ int wave_sum_scatter_entry(int lane) {
+    const int base = 10 * (lane >> 5) + 5 * ((lane >> 4) & 1), c = lane & 15, b = c >> 2;
+    if (c == 1) return base + 4;                                 // the fifth register: every lane of the row has it, lane 1 of the row hands it in
+    if (c & 3) return -1;
+    return base + 2 * (b & 1) + (b >> 1);                        // banks 0, 1, 2, 3 of the row: entries 0, 2, 1, 3 of its five
+}
+__device__ __forceinline__ float wave_sum_scatter(float (&v)[20], int lane) {
+#pragma unroll
+    for (int g = 0; g < 10; g += 5) {
+        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %5\n\tv_permlane32_swap_b32 %1, %6\n\tv_permlane32_swap_b32 %2, %7\n\t"
+                     "v_permlane32_swap_b32 %3, %8\n\tv_permlane32_swap_b32 %4, %9"
+                     : "+v"(v[g]), "+v"(v[g + 1]), "+v"(v[g + 2]), "+v"(v[g + 3]), "+v"(v[g + 4]),
+                       "+v"(v[g + 10]), "+v"(v[g + 11]), "+v"(v[g + 12]), "+v"(v[g + 13]), "+v"(v[g + 14]));   // xor 32
+#pragma unroll
+        for (int e = g; e < g + 5; ++e) v[e] = v[e] + v[e + 10];
+    }
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %5\n\tv_permlane16_swap_b32 %1, %6\n\tv_permlane16_swap_b32 %2, %7\n\t"
+                 "v_permlane16_swap_b32 %3, %8\n\tv_permlane16_swap_b32 %4, %9"
+                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]));   // xor 16
+#pragma unroll
+    for (int e = 0; e < 5; ++e) v[e] = v[e] + v[e + 5];
+    float s0, s1, t0;
+    asm volatile("s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\tv_add_f32_dpp %0, %3, %3 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"
+                 "v_add_f32_dpp %1, %4, %4 row_ror:8 row_mask:0xf bank_mask:0x3\n\tv_add_f32_dpp %1, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc"
+                 : "=&v"(s0), "=&v"(s1) : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));                                          // xor 8
+    float t1 = dpp_add<0x128>(v[4]);
+    asm volatile("s_nop 1\n\t"
+                 "v_add_f32_dpp %0, %1, %1 row_shl:4 row_mask:0xf bank_mask:0x5\n\tv_add_f32_dpp %0, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+                 "s_nop 1"
+                 : "=&v"(t0) : "v"(s0), "v"(s1));                                                                                  // xor 4
+    t1 = dpp_add<0x124>(t1);
+    t0 = dpp_add<0x4E>(t0); t1 = dpp_add<0x4E>(t1);             // xor 2
+    t0 = dpp_add<0xB1>(t0); t1 = dpp_add<0xB1>(t1);             // xor 1
+    return (lane & 15) == 1 ? t1 : t0;
+}
 template <int NW> __device__ __forceinline__ void loss_wave_partial(const LossArgs& L, float lv, int tid) {
     const float t = wave_sum(lv);
     if ((tid & 63) == 0) L.partials[blockIdx.x * NW + (tid >> 6)] = t;

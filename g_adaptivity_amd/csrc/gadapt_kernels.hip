@@ -233,6 +233,29 @@ extern "C" int gadapt_debug_wave_sum_desc(const float* in, float* out_shfl, floa
     return check_launch("wave_sum_desc_debug_kernel");
 }
 
+// Diagnostic: wave_sum_scatter (gadapt_common.inc) beside wave_sum_desc on the same 20 values per lane.  Thread t writes what
+// wave_sum_desc leaves it with (out_desc[t][0..20)), what wave_sum_scatter returns to it (out_scatter[t]) and the entry the helper says
+// that is the total of (out_entry[t], -1: none).
+__global__ void wave_sum_scatter_debug_kernel(const float* __restrict__ in, float* __restrict__ out_desc, float* __restrict__ out_scatter,
+                                              int* __restrict__ out_entry) {
+    const size_t at = (size_t)threadIdx.x * 20;
+    float a[20], b[20];
+#pragma unroll
+    for (int k = 0; k < 20; ++k) a[k] = b[k] = in[at + k];
+    wave_sum_desc(a);
+    const float tot = wave_sum_scatter(b, threadIdx.x & 63);
+#pragma unroll
+    for (int k = 0; k < 20; ++k) out_desc[at + k] = a[k];
+    out_scatter[threadIdx.x] = tot;
+    out_entry[threadIdx.x] = wave_sum_scatter_entry(threadIdx.x & 63);
+}
+extern "C" int gadapt_debug_wave_sum_scatter(const float* in, float* out_desc, float* out_scatter, int* out_entry, int n_waves, void* stream) {
+    if (!in || !out_desc || !out_scatter || !out_entry || n_waves < 1 || n_waves > 16)
+        return fail(GADAPT_E_BADARG, "wave_sum_scatter: null pointer, or not 1..16 waves");
+    hipLaunchKernelGGL(wave_sum_scatter_debug_kernel, dim3(1), dim3(64 * n_waves), 0, static_cast<hipStream_t>(stream), in, out_desc, out_scatter, out_entry);
+    return check_launch("wave_sum_scatter_debug_kernel");
+}
+
 extern "C" int gadapt_layer_forward(const gadapt_graph* g, const float* x_in, float* x_out, const float* a, const float* p0,
                                     const float* layer_params, float* alpha_out, int residual_only, int c, void* stream) {
     if (int rc = check_graph(g, c)) return rc;

@@ -35,9 +35,9 @@
 // where the fused kernel reads row 0 of the global buffer: weight 0 on a finite value either way.  Eligibility (narrow_bwd_block_eligible)
 // refuses rows longer than 8 in either table.
 //
-// Slab rows.  Only owned nodes contribute.  The wave of an owned block runs wave_sum_desc on its 20 partials after each stage (the whole
-// wave: the branch is on the wave index) and parks them in tred; at the end 64 threads form, per stage, (b0 + b1) + (b2 + b3) for rows 2 t
-// and 2 t + 1 and add them to the row read at the top of the launch in launch order, ((row_old + v0) + v1) + v2 - the sequence of
+// Slab rows.  Only owned nodes contribute.  The wave of an owned block runs wave_sum_scatter on its 20 partials after each stage (the whole
+// wave: the branch is on the wave index; wave_sum_desc's additions, each total ending in one lane) and parks them in tred with one store
+// from those 20 lanes; at the end 64 threads form, per stage, (b0 + b1) + (b2 + b3) for rows 2 t and 2 t + 1 and add them to the row read at the top of the launch in launch order, ((row_old + v0) + v1) + v2 - the sequence of
 // accumulating launches this replaces, whose workgroup r sums nodes 256 r .. 256 r + 255 the same way (N <= 256 rows: one node per lane).
 // Rows from 2 n_tiles on are not touched: no node maps to them, T_{L-1} wrote +0 there and each launch this replaces adds
 // (+0 + +0) + (+0 + +0) = +0 to it, which leaves +0 (tests/test_gpu_narrow_block_backward.py compares all 32 entries of every row).
@@ -98,6 +98,8 @@ __global__ __launch_bounds__(NBB_NT) void grand_bwd_narrow_block_kernel(BwdBlock
 #pragma unroll
         for (int s = 0; s < GADAPT_NARROW_BWD_BLOCK_STAGES; ++s) tred[(s * 8 + ob) * 20 + lane] = 0.f;
     }
+
+    const int pe = wave_sum_scatter_entry(lane), park = pe < 0 ? -1 : ob * 20 + pe;   // where this lane parks the total it ends with, in a stage's [8][20]
 
     float4 dreg[2] = {f4zero(), f4zero()};                       // dxd of this lane's two nodes, from stage to stage
     int wb = 0, wlast = 0;                                      // this stage's pair window in LDS: first position in source order, last index
@@ -239,11 +241,8 @@ __global__ __launch_bounds__(NBB_NT) void grand_bwd_narrow_block_kernel(BwdBlock
                 for (int c = 0; c < 4; ++c) part[4 * o + c] = valid ? fmaf(dp[o], xv[c], zero) : 0.f;
                 part[16 + o] = valid ? zero + dp[o] : 0.f;
             }
-            wave_sum_desc(part);                                 // every lane of the owned block's wave is here
-            if (lane == 0) {
-#pragma unroll
-                for (int e = 0; e < 20; ++e) tred[(s * 8 + ob) * 20 + e] = part[e];
-            }
+            const float tot = wave_sum_scatter(part, lane);            // every lane of the owned block's wave is here
+            if (park >= 0) tred[s * 160 + park] = tot;           // each total from the lane it ended in: one LDS store
         }
         wb = wb_n; wlast = max(wn_n - 1, 0);
         if (!fin) __syncthreads();                               // stage s is in LDS

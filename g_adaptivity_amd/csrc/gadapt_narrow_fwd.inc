@@ -565,13 +565,12 @@ __global__ __launch_bounds__(NRB_NT) void fwd_narrow_block_kernel(BlockArgs q) {
                     narrow_top_target(part, g4, own, xv, w, deg, dt, sc, a4, tp, i < N, i, q.edge_out, q.dxd);
                     const int ob = gadapt_block_owned_block(margin, wave);
                     // the wave sum of bwd_target_compact_body, butterfly 32, 16, .., 1 - the same additions on DPP / lane swaps, stage by
-                    // stage over the 20 independent values (wave_sum_desc; every lane of the owned block's wave is here: halo waves left
-                    // at the `continue` above as a whole, lanes past N carry zeros)
-                    wave_sum_desc(part);
-                    if (lane == 0) {
-#pragma unroll
-                        for (int e = 0; e < 20; ++e) tred[ob][e] = part[e];
-                    }
+                    // stage over the 20 independent values, each total in the one lane that parks it (wave_sum_scatter: wave_sum_desc's
+                    // additions; every lane of the owned block's wave is here: halo waves left at the `continue` above as a whole, lanes
+                    // past N carry zeros)
+                    const float tot = wave_sum_scatter(part, lane);
+                    const int pe = wave_sum_scatter_entry(lane);
+                    if (pe >= 0) tred[ob][pe] = tot;
                 }
             }
         }

@@ -659,6 +659,14 @@ int gadapt_debug_occupancy(int c, int* out3);
  * in[w][l][0..n_values); out_shfl / out_desc, same shape: both sums as that lane sees them.  n_values = 1, 20 or 22.  The two must
  * agree bit for bit in every lane (tests/test_gpu_wave_sum_desc.py). */
 int gadapt_debug_wave_sum_desc(const float* in, float* out_shfl, float* out_desc, int n_waves, int n_values, void* stream);
+/* Diagnostic: wave_sum_scatter, the wave sum the block kernels use for their 20 slab partials (every exchange hands over half of the
+ * values; each total ends in one lane), beside wave_sum_desc.  in [n_waves][64][20] (device), laid out as above; out_desc, same shape:
+ * wave_sum_desc's sums as every lane sees them; out_scatter [n_waves][64]: what the helper returns to each lane; out_entry [n_waves][64]
+ * int32: the entry that value is the total of, or -1.  Documented lanes: with base = 10 (lane >> 5) + 5 ((lane >> 4) & 1) and
+ * c = lane & 15, lane c = 0, 4, 8, 12 of a row of 16 holds entry base + 0, 2, 1, 3 and lane c = 1 holds entry base + 4; the other 44
+ * lanes hold no total.  out_scatter at those lanes must equal out_desc's lane-0 value of the entry bit for bit
+ * (tests/test_gpu_wave_sum_scatter.py). */
+int gadapt_debug_wave_sum_scatter(const float* in, float* out_desc, float* out_scatter, int* out_entry, int n_waves, void* stream);
 
 #ifdef __cplusplus
 }
