@@ -11,6 +11,7 @@ error reduction of the last two, with the model's time per sample.
                                                                  # ... with real MMPDE5 targets beyond 32 x 32
     python examples/evaluate_poisson.py --target monge_ampere    # the MA columns on Monge-Ampere meshes (2-D, at most 32 x 32)
     python examples/evaluate_poisson.py --mesh 64 --band window --target monge_ampere --ma_route strided --ma_max_steps 40000
+    python examples/evaluate_poisson.py --target monge_ampere --ma_monitor M2N --ma_mon_reg 0.1 --m2n_beta 1.5   # the M2N 'fast' monitor
                                                                  # ... beyond 32 x 32: the fp64-potential route, up to 81 x 81
 """
 import argparse
@@ -68,6 +69,13 @@ if __name__ == '__main__':
     ap.add_argument('--ma_cfl', type=float, default=None, help='pseudo-time step of Monge-Ampere is cfl h^2 (default 0.2)')
     ap.add_argument('--ma_max_steps', type=int, default=None,
                     help='update cap of Monge-Ampere (default 20000; 64 x 64 wanted up to 25 500, 81 x 81 up to 32 000)')
+    ap.add_argument('--ma_monitor', choices=('ma', 'M2N'), default='ma',
+                    help="monitor of the Monge-Ampere targets: the reference's mesh_type 'ma', or 'M2N' with fast_M2N_monitor = 'fast' "
+                         "(mon_reg + beta F / max F over the moving nodes; 'slow' and 'superslow' are not built)")
+    ap.add_argument('--ma_mon_reg', type=float, default=None,
+                    help="mon_reg of the Monge-Ampere monitor: 'ma' then uses (mon_reg + |H|)^0.2 in place of (1 + |H|)^0.2; "
+                         "'M2N' needs it (default 0.1, the reference's run parameters)")
+    ap.add_argument('--m2n_beta', type=float, default=1.5, help="beta of the M2N monitor (the reference's default 1.5)")
     ap.add_argument('--num_train', type=int, default=32)
     ap.add_argument('--num_test', type=int, default=16)
     ap.add_argument('--epochs', type=int, default=20)
@@ -87,7 +95,12 @@ if __name__ == '__main__':
     if a.target == 'monge_ampere':                 # the reference's own 2-D configuration: 2-D, its own monitor defaults
         solver = {'route': opt['ma_route']}
         solver.update({k: v for k, v in (('cfl', a.ma_cfl), ('max_steps', a.ma_max_steps)) if v is not None})
-        target, target_params = 'monge_ampere', {'solver': solver}
+        if a.ma_monitor == 'M2N':                  # the monitor travels in target_params, next to the solver's keywords
+            monitor = {'mesh_type': 'M2N', 'fast_M2N_monitor': 'fast', 'mon_reg': 0.1 if a.ma_mon_reg is None else a.ma_mon_reg,
+                       'M2N_beta': a.m2n_beta}
+        else:
+            monitor = {} if a.ma_mon_reg is None else {'mon_reg': a.ma_mon_reg, 'mon_power': 0.2}
+        target, target_params = 'monge_ampere', dict(monitor, solver=solver)
     test = MeshDataset(dims, a.num_test, seed=1, target=target, target_params=target_params)
     torch.manual_seed(0)
     model = GNN(test, opt).to(opt['device'])

@@ -98,6 +98,13 @@ if __name__ == '__main__':
     ap.add_argument('--ma_cfl', type=float, default=None, help='pseudo-time step of Monge-Ampere is cfl h^2 (default 0.2)')
     ap.add_argument('--ma_max_steps', type=int, default=None,
                     help='update cap of Monge-Ampere (default 20000; 64 x 64 wanted up to 25 500, 81 x 81 up to 32 000)')
+    ap.add_argument('--ma_monitor', choices=('ma', 'M2N'), default='ma',
+                    help="monitor of the Monge-Ampere targets: the reference's mesh_type 'ma', or 'M2N' with fast_M2N_monitor = 'fast' "
+                         "(mon_reg + beta F / max F over the moving nodes; 'slow' and 'superslow' are not built)")
+    ap.add_argument('--ma_mon_reg', type=float, default=None,
+                    help="mon_reg of the Monge-Ampere monitor: 'ma' then uses (mon_reg + |H|)^0.2 in place of (1 + |H|)^0.2; "
+                         "'M2N' needs it (default 0.1, the reference's run parameters)")
+    ap.add_argument('--m2n_beta', type=float, default=1.5, help="beta of the M2N monitor (the reference's default 1.5)")
     a = ap.parse_args()
     opt = hot_path_opt(mesh_dims=[a.mesh, a.mesh], hidden_dim=a.hidden_dim, num_layers=a.num_layers, batch_size=a.batch_size,
                        epochs=a.epochs, device='cuda:0', loss_fn='mse', lr=1e-3, show_mesh_evol_plots='False',
@@ -106,11 +113,17 @@ if __name__ == '__main__':
     if a.target == 'monge_ampere':
         solver = {'route': opt['ma_route']}
         solver.update({k: v for k, v in (('cfl', a.ma_cfl), ('max_steps', a.ma_max_steps)) if v is not None})
+        if a.ma_monitor == 'M2N':                  # the monitor travels in target_params, next to the solver's keywords
+            monitor = {'mesh_type': 'M2N', 'fast_M2N_monitor': 'fast', 'mon_reg': 0.1 if a.ma_mon_reg is None else a.ma_mon_reg,
+                       'M2N_beta': a.m2n_beta}
+        else:
+            monitor = {} if a.ma_mon_reg is None else {'mon_reg': a.ma_mon_reg, 'mon_power': 0.2}
     else:
+        monitor = {}
         solver = {'route': opt['mmpde5_route']}
         solver.update({k: v for k, v in (('cfl', a.mmpde5_cfl), ('max_steps', a.mmpde5_max_steps)) if v is not None})
     ds = MeshDataset(opt['mesh_dims'], a.num_train, seed=0, target=a.target,
-                     target_params={'solver': solver} if a.target != 'noise' else None)
+                     target_params=dict(monitor, solver=solver) if a.target != 'noise' else None)
     t0 = time.time()
     model, losses, rate = main(opt, ds)
     torch.cuda.synchronize()

@@ -46,6 +46,10 @@ PROTOTYPES = {
     'gadapt_ma_strided_max_side': (_I, []),
     'gadapt_ma_strided_lds_bytes': (_L, [_I]),
     'gadapt_ma_batch_strided': (_I, [_I] + [_P] * 4 + [_D, _D, _I] + [_P] * 6),
+    'gadapt_ma_m2n_lds_bytes': (_L, [_I]),
+    'gadapt_ma_m2n_strided_lds_bytes': (_L, [_I]),
+    'gadapt_ma_m2n_batch': (_I, [_I] + [_P] * 4 + [_D, _D, _I] + [_P] * 6),
+    'gadapt_ma_m2n_batch_strided': (_I, [_I] + [_P] * 4 + [_D, _D, _I] + [_P] * 6),
 }
 
 _lib = None

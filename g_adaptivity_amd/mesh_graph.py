@@ -293,7 +293,9 @@ class MeshDataset:
         'monge_ampere': the reference's default 2-D target (`mesh_type = 'ma'`), a finite-difference Monge-Ampere solve of the
         sample's own Gaussians (`monge_ampere.attach_ma_targets`; 2-D only, N <= 32; `target_params`: `mon_reg` / `mon_power` and
         keyword arguments of `ma_batch` under 'solver').  33..81 a side need `target_params={'solver': {'route': 'strided',
-        'max_steps': 40000}}`: the fp64-potential route, which wants more updates than the default cap (`monge_ampere.py`)."""
+        'max_steps': 40000}}`: the fp64-potential route, which wants more updates than the default cap (`monge_ampere.py`).
+        `target_params={'mesh_type': 'M2N', 'fast_M2N_monitor': 'fast', 'mon_reg': 0.1, 'M2N_beta': 1.5, ...}` selects the
+        reference's M2N 'fast' monitor for every sample (`monge_ampere.monitor_m2n`)."""
         self.mesh_dims = list(mesh_dims)
         self.dim = len(self.mesh_dims)
         if self.dim == 1:

@@ -15,8 +15,20 @@ fp64 restatement (`tests/ma_restatement.py`) and the equidistribution it has to 
 `ma_batch` is the batched form: one launch of `libgadapt_mesh.so`, one workgroup per mesh, each to its own stopping step.
 `MA2d` and `deform_mesh_ma2d` keep the reference's names, argument lists and return tuples.  2-D only (the reference has no
 1-D MA), 3 <= N <= 32 a side, at most 8 Gaussians; anything else raises `ValueError`.  The iteration runs on the GPU only:
-`NativeError` without one.  The `M2N` monitors of `MA2d` are not built: they need a maximum over the moving nodes at every
-step and FEM solves.
+`NativeError` without one.
+
+Two monitors, chosen per call from `pde_params[b].get('mesh_type', 'ma')`; all meshes of one call share one (one launch per call).
+`'ma'` is `monitor_ma`.  `'M2N'` is the reference's M2N branch of `MA2d` (`ma_mesh_2d.py:178-278`) with `fast_M2N_monitor =
+'fast'`, the value the reference's run parameters select for M2N: `monitor_m2n`, mon_reg + beta F / max F with
+F = sqrt(u_xx^2 + 2 u_xy^2 + u_yy^2) and the maximum over the mesh's CURRENT nodes, reduced inside the kernel at every update
+(`ma_m2n_kernel`, `ma_m2n_strided_kernel`).  u_xy IS THE LAST GAUSSIAN'S ONLY: the reference assigns it with `=` inside its loop
+(`ma_mesh_2d.py:133,151`), and that is kept.  `mon_reg` is required and > 0, `M2N_beta` defaults to 1.5 and is >= 0; `mon_power`
+and `M2N_alpha` are accepted and ignored, as that branch of the reference does not read them.  'fast' is built; 'slow' and
+'superslow' ARE NOT BUILT (`NotImplementedError`): they add |u_h - u|^2 from a P1 Poisson solve on the moving mesh at every
+monitor evaluation.  Parity with `movement` is unpinned for M2N as for 'ma'; the yardstick is `tests/ma_m2n_restatement.py`.
+A contrast of mon_reg against beta that is too strong for the mesh loses convexity at the first update and comes back as
+NONCONVEX, which means "lower `cfl`": two Gaussians drawn with seed 15 on 15 x 15 with mon_reg = 0.01, beta = 1.0 and
+cfl = 0.2 do (min lambda -0.18, in fp32 and fp64 alike).
 
 Two routes (`ROUTES`).  `route='lane'`, the default, holds one node per lane and phi in fp32: 3 <= N <= 32.  Its residual floor
 reaches `tol` near 64 x 64 (at 81 x 81 the fp32 restatement stops 12 % late), so sides above 32 are not the same kernel with
@@ -74,6 +86,54 @@ def monitor_ma(x: torch.Tensor, y: torch.Tensor, params) -> torch.Tensor:
     return (reg + torch.sqrt(uxx ** 2 + uyy ** 2)) ** power
 
 
+MONITORS = ('ma', 'M2N')
+
+
+def monitor_kind(b: int, params) -> str:
+    """'ma' or 'M2N' from `params.get('mesh_type', 'ma')`, with the checks of the M2N branch of the reference's `MA2d`."""
+    kind = params.get('mesh_type', 'ma')
+    if kind not in MONITORS:
+        raise ValueError(f"mesh {b}: mesh_type = {kind!r}; one of {MONITORS}")
+    if kind == 'M2N':
+        fast = params.get('fast_M2N_monitor')
+        if fast in ('slow', 'superslow'):
+            raise NotImplementedError(f"mesh {b}: fast_M2N_monitor = {fast!r} adds |u_h - u|^2 from a P1 FEM Poisson solve on the moving "
+                                      "mesh at every monitor evaluation, which is not built; 'fast' is")
+        if fast != 'fast':
+            raise ValueError(f"mesh {b}: Please specify fast_M2N_monitor in params (got {fast!r}; 'fast' is built)")
+    return kind
+
+
+def m2n_constants(params):
+    """(mon_reg, beta) of the M2N 'fast' monitor (`ma_mesh_2d.py:263-272`): 'mon_reg' is read unconditionally there, so it is
+    required here, and > 0 (the monitor is mon_reg where F vanishes); 'M2N_beta' defaults to 1.5 and is >= 0."""
+    if 'mon_reg' not in params:
+        raise ValueError("the M2N monitor reads 'mon_reg': pass it (the reference's run parameters use 0.1)")
+    reg, beta = float(params['mon_reg']), float(params.get('M2N_beta', 1.5))
+    if not (0 < reg < float('inf')):
+        raise ValueError(f"mon_reg = {reg}; the M2N monitor needs mon_reg > 0")
+    if not (0 <= beta < float('inf')):
+        raise ValueError(f"M2N_beta = {beta}; >= 0 expected")
+    return reg, beta
+
+
+def monitor_m2n(x: torch.Tensor, y: torch.Tensor, params) -> torch.Tensor:
+    """`MA2d`'s M2N 'fast' monitor on the points given: mon_reg + beta F / max(F) with F = sqrt(u_xx^2 + 2 u_xy^2 + u_yy^2), the
+    maximum over THE POINTS GIVEN (the reference takes it over the mesh's current nodes).  u_xx and u_yy are the signed sums of
+    `monitor_ma`; u_xy is the last Gaussian's only, as in the reference.  Points where no F is positive get mon_reg."""
+    reg, beta = m2n_constants(params)
+    uxx, uyy, uxy = torch.zeros_like(x), torch.zeros_like(x), torch.zeros_like(x)
+    for c, s in zip(params['centers'], params['scales']):
+        c0, c1, s0, s1 = float(c[0]), float(c[1]), float(s[0]), float(s[1])
+        g = torch.exp(-(x - c0) ** 2 / s0 ** 2 - (y - c1) ** 2 / s1 ** 2)
+        uxx = uxx + _gauss_dd(x, c0, s0) * g
+        uyy = uyy + _gauss_dd(y, c1, s1) * g
+        uxy = 16 * ((x - c0) * (y - c1)) / s0 ** 2 / s1 ** 2 * g          # `=`, not `+=`: ma_mesh_2d.py:133
+    F = torch.sqrt(uxx ** 2 + 2 * uxy ** 2 + uyy ** 2)
+    top = F.max() if F.numel() else F.new_zeros(())
+    return reg + beta * F / top if top > 0 else reg + torch.zeros_like(F)
+
+
 def _side(b: int, size, route: str = 'lane') -> int:
     if isinstance(size, (tuple, list)):
         if len(size) != 2 or int(size[0]) != int(size[1]):
@@ -119,7 +179,12 @@ def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
         raise ValueError(f"cfl = {cfl}, tol = {tol}; cfl > 0 and tol >= 0 expected")
     ns = [_side(b, s, route) for b, s in enumerate(sizes)]
     gauss = [_gaussians(b, p) for b, p in enumerate(pde_params)]
-    mon = [monitor_constants(p) for p in pde_params]
+    kinds = [monitor_kind(b, p) for b, p in enumerate(pde_params)]
+    if len(set(kinds)) != 1:
+        raise ValueError(f"mesh_type 'ma' for {kinds.count('ma')} meshes and 'M2N' for {kinds.count('M2N')}: all meshes of one call share "
+                         "one monitor (one launch per call); split the batch")
+    m2n = kinds[0] == 'M2N'
+    mon = [(m2n_constants if m2n else monitor_constants)(p) for p in pde_params]
     B = len(ns)
 
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device() if torch.cuda.is_available() else 0)
@@ -147,7 +212,7 @@ def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
             int(max_steps), x.data_ptr(), y.data_ptr(), steps.data_ptr(), residual.data_ptr(), status.data_ptr())
     keep = (desc_host, desc_dev, gauss_dev, mon_dev)                     # what the argument list points into
 
-    entry = 'gadapt_ma_batch_strided' if route == 'strided' else 'gadapt_ma_batch'
+    entry = ('gadapt_ma_m2n_batch' if m2n else 'gadapt_ma_batch') + ('_strided' if route == 'strided' else '')
 
     def launch(_keep=keep):                                              # the closure keeps the inputs alive
         with torch.cuda.device(dev):
@@ -169,7 +234,10 @@ def ma_batch(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
 
     sizes[b]       N (or a pair (N, N)): the mesh is the N x N grid on the unit square, node (i, j) of meshgrid(..., indexing='ij')
     pde_params[b]  'centers' and 'scales' of the sample's Gaussians (at most 8; none gives a constant monitor and the grid itself),
-                   optionally 'mon_reg' and 'mon_power' (`monitor_ma`)
+                   optionally 'mon_reg' and 'mon_power' (`monitor_ma`).  With 'mesh_type': 'M2N' (and 'fast_M2N_monitor': 'fast',
+                   'mon_reg' > 0, optionally 'M2N_beta', default 1.5) the monitor is `monitor_m2n` with its maximum over the
+                   mesh's current nodes at every update; 'mon_power' and 'M2N_alpha' are accepted and ignored there.  All
+                   meshes of a call share one 'mesh_type' ('ma' when absent); a mixed batch is a `ValueError`
     cfl            the pseudo-time step is cfl h^2 min(1, lambda_min); 0.2 converged in every case tried up to 32 x 32, 0.5
                    oscillates into the cap, 1 loses convexity at once
     tol            stop when max |r - mean r| <= tol; 0 runs exactly `max_steps` updates
@@ -214,7 +282,8 @@ def _dataset_solver_kwargs(solver: dict) -> dict:
 def MA2d(x_comp: torch.Tensor, N: int, params, **solver):
     """`MA2d(x_comp, N, params)` -> (x_phys, j, build_time): the Monge-Ampere mesh of the N x N grid written back in the node
     order of `x_comp` [N*N, 2] (`mmpde5.write_back_to_nodes`), j the number of updates.  Lost convexity warns and gives zeros
-    and j = 0, as the reference's `except` branch does; a reached cap warns.  Keyword-only `cfl`, `tol`, `max_steps` go to `ma_batch`."""
+    and j = 0, as the reference's `except` branch does; a reached cap warns.  Keyword-only `cfl`, `tol`, `max_steps` go to `ma_batch`.
+    `params['mesh_type'] == 'M2N'` selects the M2N 'fast' monitor (`monitor_m2n`), as in the reference; absent, it is 'ma'."""
     _solver_kwargs(solver)
     if x_comp.dim() != 2 or tuple(x_comp.shape) != (N * N, 2):
         raise ValueError(f"MA2d: x_comp of shape {tuple(x_comp.shape)}; [{N * N}, 2] expected (square grids only)")
@@ -248,7 +317,8 @@ def deform_mesh_ma2d(x_comp: torch.Tensor, n: int, m: int, pde_params, **solver)
 def attach_ma_targets(samples, monitor_params: Optional[dict] = None, **solver):
     """`x_phys` of every sample := its Monge-Ampere mesh, all samples in ONE batched call; `ma_its` = updates + 1 and
     `build_time` (the batched call's wall time shared out evenly) as `attach_mmpde5_targets` sets them.  The monitor of a
-    sample is `monitor_ma` of its own `pde_params` with `monitor_params` (`mon_reg`, `mon_power`) added.  The samples' meshes
+    sample is `monitor_ma` of its own `pde_params` with `monitor_params` (`mon_reg`, `mon_power`) added, or `monitor_m2n` where
+    `monitor_params` carries `mesh_type: 'M2N'` (`fast_M2N_monitor`, `mon_reg`, `M2N_beta`).  The samples' meshes
     must be square grids in grid order (`square_mesh`).  A sample that lost convexity gets zeros and `ma_its` = 1.
     Keyword-only `cfl`, `tol`, `max_steps`, `route` and `device` go to `ma_batch` (`route='strided'` for 33..81 a side)."""
     _dataset_solver_kwargs(solver)

@@ -185,6 +185,44 @@ int gadapt_ma_batch_strided(int n_mesh, const int32_t* desc_host, const int32_t*
                             double cfl, double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual,
                             int32_t* status, void* stream);
 
+/*
+ * The M2N 'fast' monitor: the reference's MA2d with mesh_type = 'M2N' and fast_M2N_monitor = 'fast'
+ * (classical_meshing/ma_mesh_2d.py:263-272), the value its run parameters select for M2N.  The monitor of a node is scaled by a
+ * maximum over the mesh's current nodes, so it moves with the mesh:
+ *   m(x, y) = mon_reg + beta F(x, y) / max over the nodes of F,   F = sqrt(u_xx^2 + 2 u_xy^2 + u_yy^2).
+ * The 'slow' and 'superslow' monitors (a P1 Poisson solve on the moving mesh per evaluation) are not built.  gadapt_ma_m2n_batch
+ * is the iteration of gadapt_ma_batch above with these changes and no others:
+ *   Per mesh, once: the Gaussians' constants above, and Cxy = (16 * (1 / q0)) * (1 / q1) of the LAST Gaussian of the mesh.  The
+ *   reference assigns u_xy with `=` inside its loop over the Gaussians (ma_mesh_2d.py:133,151), so only the last Gaussian's u_xy
+ *   survives; that is kept.
+ *   Per node, fp32 without FMA contraction, after u_xx and u_yy (the signed sums above):
+ *       u_xy = (Cxy * (dx * dy)) * g        with dx = x - c0, dy = y - c1 and g of the last Gaussian (0 without Gaussians)
+ *       F    = sqrtf((u_xx*u_xx + 2.0f*(u_xy*u_xy)) + u_yy*u_yy)
+ *   Per step: Fmax = max of F over the mesh's nodes, reduced like the other extremes: lanes without a node give -inf, then the
+ *   64 lanes of a wave, then the waves in increasing order, read back from LDS by every lane alike.  Then per node
+ *       m = mon[b][0] + (Fmax > 0 ? mon[b][1] * (F / Fmax) : 0)            (mon[b] = (mon_reg, beta); there is no powf)
+ *       r = logf(m det)
+ *   A mesh without Gaussians, or whose F underflows to 0 at every node, has the constant monitor mon_reg: 0 updates and the grid
+ *   itself.  That choice is made on Fmax as read from LDS, never by a lane from its own F.
+ *   rbar, res, lmin, the three exit tests and their order, the update, the status words, the descriptor, cfl, tol and
+ *   max_steps are unchanged.  Three barriers a step instead of two (F, then Fmax and r, then the combine), and a fifth row of
+ *   wave partials for Fmax.
+ * gadapt_ma_m2n_batch_strided is gadapt_ma_batch_strided with the same changes: fp64 phi, the five stencil expressions rounded
+ * once, the rest in fp32.  A lane folds F over its own slots in increasing k, starting from -inf, before the wave step; F and
+ * det of a slot (det itself, not its logarithm) are what a lane keeps until Fmax is known.
+ * Arguments, outputs, limits (32 and 81 a side, 8 Gaussians) and error codes are those of the two entry points above.
+ * Dynamic LDS: 4 * (5*16 + 8*8 + 4 + 2 * nodes) bytes on the lane route (the 4 floats hold Cxy), 592 + 8 * nodes on the strided
+ * route (53 080 bytes at 81 x 81).
+ */
+int64_t gadapt_ma_m2n_lds_bytes(int nodes);           /* 9..1024 nodes */
+int64_t gadapt_ma_m2n_strided_lds_bytes(int nodes);   /* 9..6561 nodes */
+int gadapt_ma_m2n_batch(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* gauss, const float* mon, double cfl,
+                        double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual, int32_t* status,
+                        void* stream);
+int gadapt_ma_m2n_batch_strided(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* gauss, const float* mon,
+                                double cfl, double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual,
+                                int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
