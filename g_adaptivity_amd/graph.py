@@ -158,6 +158,8 @@ class MeshGraph:
         rowptr_s = torch.empty(n + 1, dtype=torch.int32)
         col_t, eid_t, col_s, perm_s, tpos_s = (torch.empty(max(e, 1), dtype=torch.int32) for _ in range(5))
         src, dst = ei[0].contiguous(), ei[1].contiguous()
+        if e == 0:                                          # an empty tensor has no address; the build reads no entry of either
+            src = dst = torch.zeros(1, dtype=torch.int64)
         rc = _native.lib().gadapt_csr_build_host(src.data_ptr(), dst.data_ptr(), e, n,
                                                  rowptr_t.data_ptr(), col_t.data_ptr(), eid_t.data_ptr(),
                                                  rowptr_s.data_ptr(), col_s.data_ptr(), perm_s.data_ptr(), tpos_s.data_ptr())

@@ -1,5 +1,5 @@
 """Differentiable message-passing primitives over a `MeshGraph` (C-ABI: `gadapt_spmm`, `gadapt_sddmm`,
-`gadapt_edge_softmax_*`, `gadapt_edge_combine`, `gadapt_edge_rowsum`; include/gadapt_hip.h).
+`gadapt_edge_softmax_*`, `gadapt_edge_combine`, `gadapt_edge_rowsum`, `gadapt_edge_vector_op`; include/gadapt_hip.h).
 
 They are what PyG's `MessagePassing.propagate` + `utils.softmax` are to the reference's conv variants
 (`get_conv`, `src/GNN.py:108-124`): gather by `edge_index[0]`, combine per edge, softmax grouped by
@@ -35,6 +35,14 @@ def _pad4(x: torch.Tensor):
     if c % 4 == 0:
         return x, c
     return torch.nn.functional.pad(x, (0, 4 - c % 4)), c
+
+
+def _per_edge(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A per-edge array as the C-ABI takes it: on a graph without edges, one element that no kernel reads (an empty tensor has no
+    address, and the entry points refuse NULL)."""
+    if t is None or t.numel():
+        return t
+    return t.new_zeros((1,) + tuple(t.shape[1:]))
 
 
 def _spmm_raw(graph: MeshGraph, w: Optional[torch.Tensor], x: torch.Tensor, transpose: bool, self_scale: float = 0.0) -> torch.Tensor:
@@ -108,7 +116,7 @@ class _EdgeSoftmax(torch.autograd.Function):
         if s.numel() != graph.num_edges:
             raise ValueError(f"edge_softmax: {s.numel()} scores for {graph.num_edges} edges")
         alpha = torch.empty(max(graph.num_edges, 1), device=s.device, dtype=torch.float32)
-        check(lib().gadapt_edge_softmax_forward(graph.c_ref, ptr(s.reshape(-1)), ptr(alpha), current_stream(s.device)),
+        check(lib().gadapt_edge_softmax_forward(graph.c_ref, ptr(_per_edge(s.reshape(-1))), ptr(alpha), current_stream(s.device)),
               'gadapt_edge_softmax_forward')
         alpha = alpha[:graph.num_edges]
         ctx.graph = graph
@@ -119,14 +127,14 @@ class _EdgeSoftmax(torch.autograd.Function):
     def backward(ctx, d_alpha):
         (alpha,) = ctx.saved_tensors
         ds = torch.empty(max(ctx.graph.num_edges, 1), device=alpha.device, dtype=torch.float32)
-        check(lib().gadapt_edge_softmax_backward(ctx.graph.c_ref, ptr(alpha.contiguous()), ptr(d_alpha.contiguous()), ptr(ds),
+        check(lib().gadapt_edge_softmax_backward(ctx.graph.c_ref, ptr(_per_edge(alpha.contiguous())), ptr(_per_edge(d_alpha.contiguous())), ptr(ds),
                                                  current_stream(alpha.device)), 'gadapt_edge_softmax_backward')
         return ds[:ctx.graph.num_edges], None
 
 
 def _rowsum(graph: MeshGraph, vals: torch.Tensor, by_source: bool) -> torch.Tensor:
     out = torch.empty(graph.num_nodes, device=vals.device, dtype=torch.float32)
-    check(lib().gadapt_edge_rowsum(graph.c_ref, int(by_source), ptr(vals.contiguous()), ptr(out), current_stream(vals.device)),
+    check(lib().gadapt_edge_rowsum(graph.c_ref, int(by_source), ptr(_per_edge(vals.contiguous())), ptr(out), current_stream(vals.device)),
           'gadapt_edge_rowsum')
     return out
 
@@ -163,7 +171,7 @@ def _edge_vec_raw(graph: MeshGraph, mode: int, w, a, b, c: int) -> torch.Tensor:
     dev = (b if b is not None else a).device
     e = max(graph.num_edges, 1)
     out = torch.empty((e,) if mode == 0 else ((graph.num_nodes, c) if mode == 1 else (e, c)), device=dev, dtype=torch.float32)
-    check(lib().gadapt_edge_vector_op(graph.c_ref, mode, ptr(w), ptr(a), ptr(b), ptr(out), c, current_stream(dev)), 'gadapt_edge_vector_op')
+    check(lib().gadapt_edge_vector_op(graph.c_ref, mode, ptr(_per_edge(w)), ptr(a), ptr(_per_edge(b)), ptr(out), c, current_stream(dev)), 'gadapt_edge_vector_op')
     return out[:graph.num_edges] if mode != 1 else out
 
 
