@@ -100,7 +100,11 @@ if __name__ == '__main__':
                     help='update cap of Monge-Ampere (default 20000; 64 x 64 wanted up to 25 500, 81 x 81 up to 32 000)')
     ap.add_argument('--ma_monitor', choices=('ma', 'M2N'), default='ma',
                     help="monitor of the Monge-Ampere targets: the reference's mesh_type 'ma', or 'M2N' with fast_M2N_monitor = 'fast' "
-                         "(mon_reg + beta F / max F over the moving nodes; 'slow' and 'superslow' are not built)")
+                         "(mon_reg + beta F / max F over the moving nodes) or, with --m2n_monitor slow, 'slow'")
+    ap.add_argument('--m2n_monitor', choices=('fast', 'slow'), default='fast',
+                    help="fast_M2N_monitor of --ma_monitor M2N.  'slow' adds alpha (u_h - u)^2 / max from a P1 Poisson solve on the moving "
+                         "mesh inside every update (m2n_solve='p1': lane route, up to 24 a side); 'superslow' is not built")
+    ap.add_argument('--m2n_alpha', type=float, default=1.0, help="alpha of the M2N 'slow' monitor (the reference's default 1.0)")
     ap.add_argument('--ma_mon_reg', type=float, default=None,
                     help="mon_reg of the Monge-Ampere monitor: 'ma' then uses (mon_reg + |H|)^0.2 in place of (1 + |H|)^0.2; "
                          "'M2N' needs it (default 0.1, the reference's run parameters)")
@@ -114,8 +118,11 @@ if __name__ == '__main__':
         solver = {'route': opt['ma_route']}
         solver.update({k: v for k, v in (('cfl', a.ma_cfl), ('max_steps', a.ma_max_steps)) if v is not None})
         if a.ma_monitor == 'M2N':                  # the monitor travels in target_params, next to the solver's keywords
-            monitor = {'mesh_type': 'M2N', 'fast_M2N_monitor': 'fast', 'mon_reg': 0.1 if a.ma_mon_reg is None else a.ma_mon_reg,
+            monitor = {'mesh_type': 'M2N', 'fast_M2N_monitor': a.m2n_monitor, 'mon_reg': 0.1 if a.ma_mon_reg is None else a.ma_mon_reg,
                        'M2N_beta': a.m2n_beta}
+            if a.m2n_monitor == 'slow':            # opt-in: the P1 solve inside the kernel
+                monitor['M2N_alpha'] = a.m2n_alpha
+                solver['m2n_solve'] = 'p1'
         else:
             monitor = {} if a.ma_mon_reg is None else {'mon_reg': a.ma_mon_reg, 'mon_power': 0.2}
     else:

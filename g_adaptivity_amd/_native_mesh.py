@@ -21,6 +21,7 @@ E_SIZE = -3                                            # GADAPT_MESH_E_SIZE
 CONVERGED, CAP, STIFF = 0, 1, 2                        # GADAPT_MMPDE5_CONVERGED / _CAP / _STIFF
 MA_MAX_SIDE = 32                                       # gadapt_ma_max_side(): Monge-Ampere meshes are 2-D, N <= 32 a side
 MA_STRIDED_MAX_SIDE = 81                               # gadapt_ma_strided_max_side(): route='strided', fp64 potential
+MA_M2N_SLOW_MAX_SIDE = 24                              # gadapt_ma_m2n_slow_max_side(): the band of the P1 solve stays in LDS
 MA_MAX_GAUSS = 8                                       # gadapt_ma_max_gauss()
 MA_DESC = 4                                            # GADAPT_MA_DESC: N, node offset, Gaussian offset, Gaussian count
 MA_CONVERGED, MA_CAP, MA_NONCONVEX = 0, 1, 2           # GADAPT_MA_CONVERGED / _CAP / _NONCONVEX
@@ -50,6 +51,9 @@ PROTOTYPES = {
     'gadapt_ma_m2n_strided_lds_bytes': (_L, [_I]),
     'gadapt_ma_m2n_batch': (_I, [_I] + [_P] * 4 + [_D, _D, _I] + [_P] * 6),
     'gadapt_ma_m2n_batch_strided': (_I, [_I] + [_P] * 4 + [_D, _D, _I] + [_P] * 6),
+    'gadapt_ma_m2n_slow_max_side': (_I, []),
+    'gadapt_ma_m2n_slow_lds_bytes': (_L, [_I]),
+    'gadapt_ma_m2n_slow_batch': (_I, [_I] + [_P] * 4 + [_D, _D, _I] + [_P] * 7),
 }
 
 _lib = None
@@ -78,6 +82,9 @@ def lib():
         if handle.gadapt_ma_strided_max_side() != MA_STRIDED_MAX_SIDE:
             raise NativeError(f"{LIB_PATH}: strided Monge-Ampere route up to {handle.gadapt_ma_strided_max_side()} a side, expected "
                               f"{MA_STRIDED_MAX_SIDE}; rebuild it with `make`")
+        if handle.gadapt_ma_m2n_slow_max_side() != MA_M2N_SLOW_MAX_SIDE:
+            raise NativeError(f"{LIB_PATH}: M2N 'slow' monitor up to {handle.gadapt_ma_m2n_slow_max_side()} a side, expected "
+                              f"{MA_M2N_SLOW_MAX_SIDE}; rebuild it with `make`")
         _lib = handle
     return _lib
 

@@ -295,7 +295,9 @@ class MeshDataset:
         keyword arguments of `ma_batch` under 'solver').  33..81 a side need `target_params={'solver': {'route': 'strided',
         'max_steps': 40000}}`: the fp64-potential route, which wants more updates than the default cap (`monge_ampere.py`).
         `target_params={'mesh_type': 'M2N', 'fast_M2N_monitor': 'fast', 'mon_reg': 0.1, 'M2N_beta': 1.5, ...}` selects the
-        reference's M2N 'fast' monitor for every sample (`monge_ampere.monitor_m2n`)."""
+        reference's M2N 'fast' monitor for every sample (`monge_ampere.monitor_m2n`); `'fast_M2N_monitor': 'slow'` with
+        `'solver': {'m2n_solve': 'p1'}` (and optionally `'M2N_alpha'`) its 'slow' one, a P1 Poisson solve on the moving mesh inside
+        every update (`monge_ampere.monitor_m2n_slow`; lane route, N <= 24).  Without that keyword 'slow' is refused."""
         self.mesh_dims = list(mesh_dims)
         self.dim = len(self.mesh_dims)
         if self.dim == 1:

@@ -23,9 +23,14 @@ Two monitors, chosen per call from `pde_params[b].get('mesh_type', 'ma')`; all m
 F = sqrt(u_xx^2 + 2 u_xy^2 + u_yy^2) and the maximum over the mesh's CURRENT nodes, reduced inside the kernel at every update
 (`ma_m2n_kernel`, `ma_m2n_strided_kernel`).  u_xy IS THE LAST GAUSSIAN'S ONLY: the reference assigns it with `=` inside its loop
 (`ma_mesh_2d.py:133,151`), and that is kept.  `mon_reg` is required and > 0, `M2N_beta` defaults to 1.5 and is >= 0; `mon_power`
-and `M2N_alpha` are accepted and ignored, as that branch of the reference does not read them.  'fast' is built; 'slow' and
-'superslow' ARE NOT BUILT (`NotImplementedError`): they add |u_h - u|^2 from a P1 Poisson solve on the moving mesh at every
-monitor evaluation.  Parity with `movement` is unpinned for M2N as for 'ma'; the yardstick is `tests/ma_m2n_restatement.py`.
+and `M2N_alpha` are accepted and ignored, as that branch of the reference does not read them.  'slow' and 'superslow' add
+alpha |u_h - u|^2 / max from a Poisson solve on the moving mesh at every monitor evaluation.  'slow' IS OPT-IN: it raises
+`NotImplementedError` unless the call passes `m2n_solve='p1'`, which runs `ma_m2n_slow_kernel` (`monitor_m2n_slow` is its readable
+statement): the P1 solve with nodal forcing and nodal boundary values inside the update loop, a banded Cholesky in LDS, lane
+route only, 3 <= N <= 24 (`SLOW_MAX_SIDE`), `M2N_alpha` and `M2N_beta` both defaulting to 1.0, result `MASlowResult` with the
+last monitor.  The reference L2-projects f and u into P1 and solves with Firedrake; that is not reproduced.  'superslow'
+(it differentiates a high-order solution) IS NOT BUILT.  Parity with `movement` is unpinned for M2N as for 'ma'; the yardsticks
+are `tests/ma_m2n_restatement.py` and `tests/ma_m2n_slow_restatement.py`.
 A contrast of mon_reg against beta that is too strong for the mesh loses convexity at the first update and comes back as
 NONCONVEX, which means "lower `cfl`": two Gaussians drawn with seed 15 on 15 x 15 with mon_reg = 0.01, beta = 1.0 and
 cfl = 0.2 do (min lambda -0.18, in fp32 and fp64 alike).
@@ -58,9 +63,12 @@ CONVERGED, CAP, NONCONVEX = _native_mesh.MA_CONVERGED, _native_mesh.MA_CAP, _nat
 STATUS_NAMES = {CONVERGED: 'converged', CAP: 'cap reached', NONCONVEX: 'convexity lost'}
 MAX_SIDE, MAX_GAUSS = _native_mesh.MA_MAX_SIDE, _native_mesh.MA_MAX_GAUSS
 STRIDED_MAX_SIDE = _native_mesh.MA_STRIDED_MAX_SIDE
+SLOW_MAX_SIDE = _native_mesh.MA_M2N_SLOW_MAX_SIDE
 ROUTES = ('lane', 'strided')
+M2N_SOLVES = ('p1',)
 
 MAResult = namedtuple('MAResult', 'coords steps residual status')
+MASlowResult = namedtuple('MASlowResult', 'coords steps residual status monitor')
 
 
 def monitor_constants(params):
@@ -89,16 +97,25 @@ def monitor_ma(x: torch.Tensor, y: torch.Tensor, params) -> torch.Tensor:
 MONITORS = ('ma', 'M2N')
 
 
-def monitor_kind(b: int, params) -> str:
-    """'ma' or 'M2N' from `params.get('mesh_type', 'ma')`, with the checks of the M2N branch of the reference's `MA2d`."""
+def monitor_kind(b: int, params, m2n_solve: Optional[str] = None) -> str:
+    """'ma', 'M2N' or 'M2N slow' from `params.get('mesh_type', 'ma')`, with the checks of the M2N branch of the reference's `MA2d`.
+    'M2N slow' is `fast_M2N_monitor = 'slow'` under `m2n_solve='p1'`; without that keyword 'slow' is refused as before."""
+    if m2n_solve is not None and m2n_solve not in M2N_SOLVES:
+        raise ValueError(f"m2n_solve = {m2n_solve!r}; None or one of {M2N_SOLVES}")
     kind = params.get('mesh_type', 'ma')
     if kind not in MONITORS:
         raise ValueError(f"mesh {b}: mesh_type = {kind!r}; one of {MONITORS}")
     if kind == 'M2N':
         fast = params.get('fast_M2N_monitor')
-        if fast in ('slow', 'superslow'):
-            raise NotImplementedError(f"mesh {b}: fast_M2N_monitor = {fast!r} adds |u_h - u|^2 from a P1 FEM Poisson solve on the moving "
-                                      "mesh at every monitor evaluation, which is not built; 'fast' is")
+        if fast == 'slow' and m2n_solve == 'p1':
+            return 'M2N slow'
+        if fast == 'superslow':
+            raise NotImplementedError(f"mesh {b}: fast_M2N_monitor = 'superslow' differentiates a high-order FEM solution on the moving "
+                                      "mesh at every monitor evaluation, which is not built; 'fast' is, and 'slow' with m2n_solve='p1'")
+        if fast == 'slow':
+            raise NotImplementedError(f"mesh {b}: fast_M2N_monitor = 'slow' adds |u_h - u|^2 from a P1 FEM Poisson solve on the moving "
+                                      "mesh at every monitor evaluation, which runs only when asked for: pass m2n_solve='p1' "
+                                      f"(nodal forcing, up to {SLOW_MAX_SIDE} a side); 'fast' needs nothing")
         if fast != 'fast':
             raise ValueError(f"mesh {b}: Please specify fast_M2N_monitor in params (got {fast!r}; 'fast' is built)")
     return kind
@@ -134,6 +151,72 @@ def monitor_m2n(x: torch.Tensor, y: torch.Tensor, params) -> torch.Tensor:
     return reg + beta * F / top if top > 0 else reg + torch.zeros_like(F)
 
 
+def m2n_slow_constants(params):
+    """(mon_reg, alpha, beta) of the M2N 'slow' monitor (`ma_mesh_2d.py:227-261`): 'mon_reg' is required and > 0; 'M2N_alpha' and
+    'M2N_beta' both default to 1.0 there and are >= 0."""
+    if 'mon_reg' not in params:
+        raise ValueError("the M2N monitor reads 'mon_reg': pass it (the reference's run parameters use 0.1)")
+    reg, alpha, beta = float(params['mon_reg']), float(params.get('M2N_alpha', 1.0)), float(params.get('M2N_beta', 1.0))
+    if not (0 < reg < float('inf')):
+        raise ValueError(f"mon_reg = {reg}; the M2N monitor needs mon_reg > 0")
+    if not (0 <= alpha < float('inf')):
+        raise ValueError(f"M2N_alpha = {alpha}; >= 0 expected")
+    if not (0 <= beta < float('inf')):
+        raise ValueError(f"M2N_beta = {beta}; >= 0 expected")
+    return reg, alpha, beta
+
+
+def p1_error(x: torch.Tensor, y: torch.Tensor, u: torch.Tensor, f: torch.Tensor) -> torch.Tensor:
+    """u_h - u on the N x N node set (x, y), node (i, j) of `square_mesh(N)`: u_h is the P1 solution of -Laplace(u_h) = f with
+    u_h = u on the boundary, the load being the consistent mass matrix applied to the nodal f.  Dense, in the dtype given;
+    exactly 0 on the boundary."""
+    from .mesh_graph import square_mesh
+    N = x.shape[0]
+    cells = square_mesh(N).cells.to(x.device)
+    px, py = x.reshape(-1)[cells], y.reshape(-1)[cells]                  # [T, 3]
+    rx = torch.stack([py[:, 1] - py[:, 2], py[:, 2] - py[:, 0], py[:, 0] - py[:, 1]], 1)   # tri_geometry of fem_kernels.hip
+    ry = torch.stack([px[:, 2] - px[:, 1], px[:, 0] - px[:, 2], px[:, 1] - px[:, 0]], 1)
+    D = (px * rx).sum(1).abs()                                           # twice the area
+    Pe = (rx[:, :, None] * rx[:, None, :] + ry[:, :, None] * ry[:, None, :]) / (2 * D)[:, None, None]
+    K = x.new_zeros(N * N, N * N)
+    K.index_put_((cells[:, :, None].expand(-1, 3, 3), cells[:, None, :].expand(-1, 3, 3)), Pe, accumulate=True)
+    ff = f.reshape(-1)[cells]
+    b = x.new_zeros(N * N).index_add_(0, cells.reshape(-1), ((D / 24)[:, None] * (ff + ff.sum(1, keepdim=True))).reshape(-1))
+    i, j = torch.meshgrid(torch.arange(N, device=x.device), torch.arange(N, device=x.device), indexing='ij')
+    inner = ((i > 0) & (i < N - 1) & (j > 0) & (j < N - 1)).reshape(-1)
+    uf = u.reshape(-1)
+    c = torch.linalg.solve(K[inner][:, inner], b[inner] - K[inner][:, ~inner] @ uf[~inner])
+    e = x.new_zeros(N * N)
+    e[inner] = c - uf[inner]
+    return e.reshape(N, N)
+
+
+def monitor_m2n_slow(x: torch.Tensor, y: torch.Tensor, params) -> torch.Tensor:
+    """`MA2d`'s M2N 'slow' monitor on the N x N node set given, which is its own mesh (`square_mesh(N)`'s triangles on these
+    nodes): mon_reg + alpha E / max(E) + beta F / max(F) with E = (u_h - u)^2 from `p1_error`, u the sum of the Gaussians,
+    f = -(u_xx + u_yy), and F as in `monitor_m2n`; both maxima over the nodes given, a term whose maximum is not positive being 0.
+    What `ma_m2n_slow_kernel` computes at every update, in torch, with a dense solve, in any dtype."""
+    if x.dim() != 2 or x.shape[0] != x.shape[1] or x.shape != y.shape or x.shape[0] < 3:
+        raise ValueError(f"monitor_m2n_slow: x of shape {tuple(x.shape)} and y of {tuple(y.shape)}; two [N, N] node arrays, N >= 3")
+    reg, alpha, beta = m2n_slow_constants(params)
+    uxx, uyy, uxy, u = torch.zeros_like(x), torch.zeros_like(x), torch.zeros_like(x), torch.zeros_like(x)
+    for c, s in zip(params['centers'], params['scales']):
+        c0, c1, s0, s1 = float(c[0]), float(c[1]), float(s[0]), float(s[1])
+        g = torch.exp(-(x - c0) ** 2 / s0 ** 2 - (y - c1) ** 2 / s1 ** 2)
+        u = u + g
+        uxx = uxx + _gauss_dd(x, c0, s0) * g
+        uyy = uyy + _gauss_dd(y, c1, s1) * g
+        uxy = 16 * ((x - c0) * (y - c1)) / s0 ** 2 / s1 ** 2 * g          # `=`, not `+=`: ma_mesh_2d.py:133
+    F = torch.sqrt(uxx ** 2 + 2 * uxy ** 2 + uyy ** 2)
+    E = p1_error(x, y, u, -(uxx + uyy)) ** 2
+    m = reg + torch.zeros_like(F)
+    if E.max() > 0:
+        m = m + alpha * E / E.max()
+    if F.max() > 0:
+        m = m + beta * F / F.max()
+    return m
+
+
 def _side(b: int, size, route: str = 'lane') -> int:
     if isinstance(size, (tuple, list)):
         if len(size) != 2 or int(size[0]) != int(size[1]):
@@ -166,9 +249,10 @@ def _gaussians(b: int, params):
 
 
 def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000, device=None,
-             route: str = 'lane'):
+             route: str = 'lane', m2n_solve: Optional[str] = None):
     """The host side of `ma_batch`: checks, the batch's descriptors and Gaussians on the GPU, the argument list.  Returns
-    (launch, collect): `launch()` issues the one kernel (it may be issued again), `collect()` gives the MAResult."""
+    (launch, collect): `launch()` issues the one kernel (it may be issued again), `collect()` gives the MAResult (the
+    MASlowResult under the 'slow' monitor)."""
     if route not in ROUTES:
         raise ValueError(f"route = {route!r}; one of {ROUTES}")
     if len(sizes) == 0 or len(sizes) != len(pde_params):
@@ -179,12 +263,22 @@ def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
         raise ValueError(f"cfl = {cfl}, tol = {tol}; cfl > 0 and tol >= 0 expected")
     ns = [_side(b, s, route) for b, s in enumerate(sizes)]
     gauss = [_gaussians(b, p) for b, p in enumerate(pde_params)]
-    kinds = [monitor_kind(b, p) for b, p in enumerate(pde_params)]
+    kinds = [monitor_kind(b, p, m2n_solve) for b, p in enumerate(pde_params)]
     if len(set(kinds)) != 1:
-        raise ValueError(f"mesh_type 'ma' for {kinds.count('ma')} meshes and 'M2N' for {kinds.count('M2N')}: all meshes of one call share "
-                         "one monitor (one launch per call); split the batch")
-    m2n = kinds[0] == 'M2N'
-    mon = [(m2n_constants if m2n else monitor_constants)(p) for p in pde_params]
+        if 'M2N slow' not in kinds:
+            raise ValueError(f"mesh_type 'ma' for {kinds.count('ma')} meshes and 'M2N' for {kinds.count('M2N')}: all meshes of one call "
+                             "share one monitor (one launch per call); split the batch")
+        raise ValueError("monitors " + ', '.join(f"{k!r} for {kinds.count(k)}" for k in sorted(set(kinds))) + " meshes: all meshes of one "
+                         "call share one monitor (one launch per call); split the batch")
+    m2n, slow = kinds[0] == 'M2N', kinds[0] == 'M2N slow'
+    if slow:
+        if route != 'lane':
+            raise ValueError(f"route = {route!r}: the M2N 'slow' monitor runs on route='lane' only (its band solve lives in LDS)")
+        for b, n in enumerate(ns):
+            if n > SLOW_MAX_SIDE:
+                raise ValueError(f"mesh {b}: N = {n}; the M2N 'slow' monitor goes up to {SLOW_MAX_SIDE} a side (the band of the P1 solve "
+                                 "stays in LDS)")
+    mon = [(m2n_slow_constants if slow else m2n_constants if m2n else monitor_constants)(p) for p in pde_params]
     B = len(ns)
 
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device() if torch.cuda.is_available() else 0)
@@ -208,28 +302,34 @@ def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
     steps = torch.empty(B, dtype=torch.int32, device=dev)
     residual = torch.empty(B, dtype=torch.float32, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
+    monitor = torch.empty_like(x) if slow else None
     args = (B, C.cast(desc_host, C.c_void_p), desc_dev.data_ptr(), gauss_dev.data_ptr(), mon_dev.data_ptr(), float(cfl), float(tol),
             int(max_steps), x.data_ptr(), y.data_ptr(), steps.data_ptr(), residual.data_ptr(), status.data_ptr())
     keep = (desc_host, desc_dev, gauss_dev, mon_dev)                     # what the argument list points into
 
-    entry = ('gadapt_ma_m2n_batch' if m2n else 'gadapt_ma_batch') + ('_strided' if route == 'strided' else '')
+    if slow:
+        args, entry = args + (monitor.data_ptr(),), 'gadapt_ma_m2n_slow_batch'
+    else:
+        entry = ('gadapt_ma_m2n_batch' if m2n else 'gadapt_ma_batch') + ('_strided' if route == 'strided' else '')
 
     def launch(_keep=keep):                                              # the closure keeps the inputs alive
         with torch.cuda.device(dev):
             _native_mesh.check(getattr(_native_mesh.lib(), entry)(*args, current_stream(dev)), entry)
 
     def collect():
-        out, o = [], 0
+        out, mons, o = [], [], 0
         for n in ns:
             out.append(torch.stack([x[o:o + n * n].view(n, n), y[o:o + n * n].view(n, n)]))
+            if slow:
+                mons.append(monitor[o:o + n * n].view(n, n))
             o += n * n
-        return MAResult(out, steps, residual, status)
+        return MASlowResult(out, steps, residual, status, mons) if slow else MAResult(out, steps, residual, status)
 
     return launch, collect
 
 
 def ma_batch(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000,
-             device=None, route: str = 'lane') -> MAResult:
+             device=None, route: str = 'lane', m2n_solve: Optional[str] = None) -> MAResult:
     """Monge-Ampere meshes of many samples, mixed sizes in one launch.
 
     sizes[b]       N (or a pair (N, N)): the mesh is the N x N grid on the unit square, node (i, j) of meshgrid(..., indexing='ij')
@@ -245,11 +345,17 @@ def ma_batch(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
                    81 x 81 28 000 to 32 000: raise it there, the default can return CAP)
     route          'lane' (3 <= N <= 32, phi in fp32) or 'strided' (3 <= N <= 81, phi in fp64, K = ceil(N^2 / 1024) nodes per
                    lane).  The two do not give the same bits at N <= 32; any other value is a `ValueError`
+    m2n_solve      None (the default: 'fast_M2N_monitor': 'slow' is a `NotImplementedError`, as ever) or 'p1': 'slow' then runs
+                   `monitor_m2n_slow` inside the kernel ('mon_reg' > 0, 'M2N_alpha' and 'M2N_beta' >= 0, both 1.0 by default;
+                   route 'lane' only, N <= 24, else `ValueError`).  'ma' and 'fast' ignore it; 'superslow' stays unbuilt
 
     Returns MAResult(coords, steps, residual, status) on the GPU: coords[b] is [2, N, N], and per-mesh tensors of the number of
-    updates (int32), the last residual and CONVERGED / CAP / NONCONVEX.  A mesh's result does not depend on its batch.
+    updates (int32), the last residual and CONVERGED / CAP / NONCONVEX.  A mesh's result does not depend on its batch.  Under
+    the 'slow' monitor it is MASlowResult(coords, steps, residual, status, monitor), monitor[b] [N, N] being m of the last
+    evaluation (with `max_steps=0, tol=0`: the monitor of the uniform grid).
     """
-    launch, collect = _prepare(sizes, pde_params, cfl=cfl, tol=tol, max_steps=max_steps, device=device, route=route)
+    launch, collect = _prepare(sizes, pde_params, cfl=cfl, tol=tol, max_steps=max_steps, device=device, route=route,
+                               m2n_solve=m2n_solve)
     launch()
     return collect()
 
@@ -263,7 +369,7 @@ def warn_status(status, what: str = 'Monge-Ampere'):
     warn_unconverged([_native_mesh.CAP if s == CAP else _native_mesh.CONVERGED for s in st], what)
 
 
-def _solver_kwargs(solver: dict, allowed=('cfl', 'tol', 'max_steps', 'device')) -> dict:
+def _solver_kwargs(solver: dict, allowed=('cfl', 'tol', 'max_steps', 'm2n_solve', 'device')) -> dict:
     extra = set(solver) - set(allowed)
     if extra:
         raise TypeError(f"unexpected keyword arguments {sorted(extra)}; {', '.join(allowed[:-1])} and {allowed[-1]} go to ma_batch")
@@ -272,7 +378,7 @@ def _solver_kwargs(solver: dict, allowed=('cfl', 'tol', 'max_steps', 'device')) 
 
 def _dataset_solver_kwargs(solver: dict) -> dict:
     """The dataset path also takes `route`; `MA2d` and `deform_mesh_ma2d` keep the reference-shaped keyword set."""
-    return _solver_kwargs(solver, ('cfl', 'tol', 'max_steps', 'route', 'device'))
+    return _solver_kwargs(solver, ('cfl', 'tol', 'max_steps', 'route', 'm2n_solve', 'device'))
 
 
 # --------------------------------------------------------------------------
@@ -282,8 +388,9 @@ def _dataset_solver_kwargs(solver: dict) -> dict:
 def MA2d(x_comp: torch.Tensor, N: int, params, **solver):
     """`MA2d(x_comp, N, params)` -> (x_phys, j, build_time): the Monge-Ampere mesh of the N x N grid written back in the node
     order of `x_comp` [N*N, 2] (`mmpde5.write_back_to_nodes`), j the number of updates.  Lost convexity warns and gives zeros
-    and j = 0, as the reference's `except` branch does; a reached cap warns.  Keyword-only `cfl`, `tol`, `max_steps` go to `ma_batch`.
-    `params['mesh_type'] == 'M2N'` selects the M2N 'fast' monitor (`monitor_m2n`), as in the reference; absent, it is 'ma'."""
+    and j = 0, as the reference's `except` branch does; a reached cap warns.  Keyword-only `cfl`, `tol`, `max_steps` and `m2n_solve`
+    go to `ma_batch`.  `params['mesh_type'] == 'M2N'` selects the M2N 'fast' monitor (`monitor_m2n`), as in the reference, or, with
+    `fast_M2N_monitor = 'slow'` and `m2n_solve='p1'`, the 'slow' one (`monitor_m2n_slow`); absent, it is 'ma'."""
     _solver_kwargs(solver)
     if x_comp.dim() != 2 or tuple(x_comp.shape) != (N * N, 2):
         raise ValueError(f"MA2d: x_comp of shape {tuple(x_comp.shape)}; [{N * N}, 2] expected (square grids only)")
@@ -320,7 +427,8 @@ def attach_ma_targets(samples, monitor_params: Optional[dict] = None, **solver):
     sample is `monitor_ma` of its own `pde_params` with `monitor_params` (`mon_reg`, `mon_power`) added, or `monitor_m2n` where
     `monitor_params` carries `mesh_type: 'M2N'` (`fast_M2N_monitor`, `mon_reg`, `M2N_beta`).  The samples' meshes
     must be square grids in grid order (`square_mesh`).  A sample that lost convexity gets zeros and `ma_its` = 1.
-    Keyword-only `cfl`, `tol`, `max_steps`, `route` and `device` go to `ma_batch` (`route='strided'` for 33..81 a side)."""
+    Keyword-only `cfl`, `tol`, `max_steps`, `route`, `m2n_solve` and `device` go to `ma_batch` (`route='strided'` for 33..81 a side;
+    `m2n_solve='p1'` for `fast_M2N_monitor: 'slow'`)."""
     _dataset_solver_kwargs(solver)
     sizes, params = [], []
     for d in samples:

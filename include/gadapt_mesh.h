@@ -190,7 +190,8 @@ int gadapt_ma_batch_strided(int n_mesh, const int32_t* desc_host, const int32_t*
  * (classical_meshing/ma_mesh_2d.py:263-272), the value its run parameters select for M2N.  The monitor of a node is scaled by a
  * maximum over the mesh's current nodes, so it moves with the mesh:
  *   m(x, y) = mon_reg + beta F(x, y) / max over the nodes of F,   F = sqrt(u_xx^2 + 2 u_xy^2 + u_yy^2).
- * The 'slow' and 'superslow' monitors (a P1 Poisson solve on the moving mesh per evaluation) are not built.  gadapt_ma_m2n_batch
+ * The 'slow' and 'superslow' monitors add a Poisson solve on the moving mesh per evaluation: 'slow' is gadapt_ma_m2n_slow_batch
+ * further down, 'superslow' is not built.  gadapt_ma_m2n_batch
  * is the iteration of gadapt_ma_batch above with these changes and no others:
  *   Per mesh, once: the Gaussians' constants above, and Cxy = (16 * (1 / q0)) * (1 / q1) of the LAST Gaussian of the mesh.  The
  *   reference assigns u_xy with `=` inside its loop over the Gaussians (ma_mesh_2d.py:133,151), so only the last Gaussian's u_xy
@@ -222,6 +223,51 @@ int gadapt_ma_m2n_batch(int n_mesh, const int32_t* desc_host, const int32_t* des
 int gadapt_ma_m2n_batch_strided(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* gauss, const float* mon,
                                 double cfl, double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual,
                                 int32_t* status, void* stream);
+
+/*
+ * The M2N 'slow' monitor (classical_meshing/ma_mesh_2d.py:227-261; the reference's argparse default for fast_M2N_monitor):
+ *   m = mon_reg + alpha (u_h - u)^2 / max + beta F / max,
+ * u = the sum of the Gaussians, u_h the P1 finite-element solution of -Laplace(u_h) = f = -(u_xx + u_yy), u_h = u on the boundary,
+ * ON THE MOVING MESH, solved again at every monitor evaluation; both maxima over the mesh's current nodes.  'superslow'
+ * (it differentiates a high-order solution) is not built.  Stated deviations, parity being unpinned as above: the reference
+ * L2-projects f and u into P1 and solves with Firedrake, here both are nodal values; u_xy is still the last Gaussian's only.
+ * gadapt_ma_m2n_slow_batch is the iteration of gadapt_ma_m2n_batch on the lane route (one workgroup per mesh, one lane per node,
+ * fp32, no FMA contraction) with these changes and no others:
+ *   In the loop over the Gaussians each node also forms u = u + g (from 0); after the loop f = -(u_xx + u_yy).
+ *   The mesh is square_mesh(N)'s: node (i, j) = i N + j; quad (ix, iy) has v0 = (ix, iy), v1 = (ix, iy+1), v2 = (ix+1, iy+1),
+ *   v3 = (ix+1, iy) and is cut into the triangles (v0, v1, v3) ("lower") and (v1, v2, v3) ("upper").
+ *   The solve: x, y, u, f of all nodes go to LDS.  Interior node (i, j), 1 <= i, j <= N - 2, is row r = (i-1)(N-2) + (j-1);
+ *   w = N - 2 is the half-bandwidth, n_int = w^2.   K_II c = b_I - K_IB u_B,  with per triangle (p0, p1, p2), as in fem_factor_kernel:
+ *       r0 = (p1.y - p2.y, p2.x - p1.x), r1 = (p2.y - p0.y, p0.x - p2.x), r2 = (p0.y - p1.y, p1.x - p0.x)
+ *       D  = p0.x (p1.y - p2.y) + p1.x (p2.y - p0.y) + p2.x (p0.y - p1.y),   inv = 1 / (2 |D|),   p_lk = (r_l . r_k) * inv
+ *   and the consistent P1 mass matrix applied to the nodal f as the load: (|D| / 24) * (f_l + ((f_0 + f_1) + f_2)).
+ *   The lane of node (i, j) owns band row r (K[r][r-d] at r (w+1) + d) and b[r].  From zeros it gathers its six triangles in the
+ *   order of their cell numbers: lower of quad (i-1, j) (the node is vertex l = 2), lower of (i, j-1) (l = 1), lower of (i, j)
+ *   (l = 0), upper of (i-1, j-1) (l = 1), upper of (i-1, j) (l = 2), upper of (i, j-1) (l = 0).  Per triangle: b += load; then for
+ *   k = 0, 1, 2: a boundary vertex gives b -= p_lk u_k, an interior vertex of row r' <= r gives K[r][r'] += p_lk.
+ *   Banded Cholesky in fp32, in LDS, right-looking: per column k, d = sqrtf(K[k][k]) if K[k][k] > 0 else NaN;
+ *   L[k+i][k] = K[k+i][k] / d and b[k] = b[k] / d; then K[k+i][k+j] -= L[k+i][k] L[k+j][k] for 1 <= j <= i <= w (rows below
+ *   n_int skipped) and b[k+i] -= L[k+i][k] b[k].  Backwards, k = n_int - 1 .. 0: y = b[k] / d_k, b[k-j] -= L[k][k-j] y; c_r = b[r] / d_r.
+ *   e = c - u at interior nodes and exactly 0 on the boundary.
+ *   The monitor: E = e*e; Emax is reduced exactly like Fmax (lanes without a node give -inf, then the 64 lanes of a wave, then the
+ *   waves in increasing order, read back from LDS by every lane alike), in a partial row of its own.  Then per node
+ *       m = (mon[b][0] + (Emax > 0 ? mon[b][1] * (E / Emax) : 0)) + (Fmax > 0 ? mon[b][2] * (F / Fmax) : 0)
+ *   with mon[b] = (mon_reg, alpha, beta), so mon is [B, 3]; both choices are made on the LDS values.  A pivot that is not
+ *   positive makes m NaN at every node (every lane reads every pivot from LDS), so it arrives as NaN in res and ends the loop
+ *   as NONCONVEX.  alpha = 0 gives the bits of gadapt_ma_m2n_batch with the same mon_reg and beta: reg + 0 is exact.
+ *   rbar, res, lmin, the three exit tests and their order, the update, the status words, the descriptor, cfl, tol and max_steps
+ *   are unchanged.  3 n_int + 5 barriers an update, each reached by every lane of the workgroup: all trip counts follow from N.
+ * Limits: N <= gadapt_ma_m2n_slow_max_side() (24; the band has to stay in LDS), 8 Gaussians.  Dynamic LDS of a launch whose largest
+ * mesh has N x N nodes: 4 * (6*16 + 8*8 + 4 + 6 N^2 + (N-2)^2 (N-1) + (N-2)^2) bytes, 60 944 at 24 x 24, below the 64 KB that need no
+ * raised limit.  Arguments, checks and error codes are those of gadapt_ma_m2n_batch, with mon3 [B, 3] and one more output:
+ * monitor_out [total nodes] (device, fp32; may be null) receives m of the last evaluation, so max_steps = 0 with tol = 0 gives the
+ * monitor of the uniform grid: the solve alone.
+ */
+int gadapt_ma_m2n_slow_max_side(void);                /* 24 */
+int64_t gadapt_ma_m2n_slow_lds_bytes(int nodes);      /* N x N nodes, 3 <= N <= 24 */
+int gadapt_ma_m2n_slow_batch(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* gauss, const float* mon3,
+                             double cfl, double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual,
+                             int32_t* status, float* monitor_out, void* stream);
 
 #ifdef __cplusplus
 }
