@@ -52,7 +52,8 @@ $(OBJDIR)/fem_topology.o: $(FEM_CSRC)/fem_topology.cpp include/gadapt_fem.h
 
 # the MMPDE5 target-mesh generator (include/gadapt_mesh.h): its own library, without FMA contraction like the FEM tails
 # (the stopping step of the fp32 iteration follows the rounding of its increments)
-MESH_OBJS  := $(OBJDIR)/mmpde5_kernels.o $(OBJDIR)/ma_kernels.o $(OBJDIR)/ma_strided_kernels.o $(OBJDIR)/ma_m2n_slow_kernels.o
+MESH_OBJS  := $(OBJDIR)/mmpde5_kernels.o $(OBJDIR)/ma_kernels.o $(OBJDIR)/ma_strided_kernels.o $(OBJDIR)/ma_m2n_slow_kernels.o \
+              $(OBJDIR)/ma_table_kernels.o
 $(MESH_LIB): $(MESH_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(MESH_OBJS)
 
@@ -72,6 +73,11 @@ $(OBJDIR)/ma_strided_kernels.o: $(MESH_CSRC)/ma_strided_kernels.hip $(MESH_CSRC)
 
 # the M2N 'slow' monitor (a P1 Poisson solve on the moving mesh inside the update loop, up to 24 x 24): the same flags
 $(OBJDIR)/ma_m2n_slow_kernels.o: $(MESH_CSRC)/ma_m2n_slow_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
+
+# Monge-Ampere meshes from a tabulated monitor, both routes: the same flags
+$(OBJDIR)/ma_table_kernels.o: $(MESH_CSRC)/ma_table_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 

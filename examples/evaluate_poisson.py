@@ -14,6 +14,8 @@ error reduction of the last two, with the model's time per sample.
     python examples/evaluate_poisson.py --target monge_ampere --ma_monitor M2N --ma_mon_reg 0.1 --m2n_beta 1.5   # the M2N 'fast' monitor
     python examples/evaluate_poisson.py --target monge_ampere --ma_monitor M2N --m2n_monitor slow --m2n_alpha 1.0   # the 'slow' one
                                                                  # ... beyond 32 x 32: the fp64-potential route, up to 81 x 81
+    python examples/evaluate_poisson.py --mesh 11 --target monge_ampere --uu fem --ma_monitor_source uu
+                                                                 # the MA columns of a mover that knows only the coarse P1 solution
 """
 import argparse
 import os
@@ -81,6 +83,12 @@ if __name__ == '__main__':
                     help="mon_reg of the Monge-Ampere monitor: 'ma' then uses (mon_reg + |H|)^0.2 in place of (1 + |H|)^0.2; "
                          "'M2N' needs it (default 0.1, the reference's run parameters)")
     ap.add_argument('--m2n_beta', type=float, default=1.5, help="beta of the M2N monitor (the reference's default 1.5)")
+    ap.add_argument('--ma_monitor_source', choices=('analytic', 'uu'), default='analytic',
+                    help="what drives the Monge-Ampere monitor: the Gaussians' analytic Hessian (default), or second differences of "
+                         "each sample's own uu_tensor, read from a table (monitor_from_nodal, ma_table_batch; --ma_monitor ma only)")
+    ap.add_argument('--uu', choices=('exact', 'fem'), default='exact',
+                    help="uu_tensor of the samples: u_true at the nodes (default), or the coarse P1 Poisson solve the reference stores "
+                         "(sides above 26 take --band window)")
     ap.add_argument('--num_train', type=int, default=32)
     ap.add_argument('--num_test', type=int, default=16)
     ap.add_argument('--epochs', type=int, default=20)
@@ -108,14 +116,17 @@ if __name__ == '__main__':
                 solver['m2n_solve'] = 'p1'
         else:
             monitor = {} if a.ma_mon_reg is None else {'mon_reg': a.ma_mon_reg, 'mon_power': 0.2}
+        if a.ma_monitor_source != 'analytic':      # absent, the datasets take today's path
+            monitor['monitor_source'] = a.ma_monitor_source
         target, target_params = 'monge_ampere', dict(monitor, solver=solver)
-    test = MeshDataset(dims, a.num_test, seed=1, target=target, target_params=target_params)
+    uu = {} if a.uu == 'exact' else {'uu': a.uu, 'uu_params': {'fem_band': a.band}}
+    test = MeshDataset(dims, a.num_test, seed=1, target=target, target_params=target_params, **uu)
     torch.manual_seed(0)
     model = GNN(test, opt).to(opt['device'])
     if a.state:
         model.load_state_dict(torch.load(a.state, map_location=opt['device']))
     else:
-        train_briefly(model, MeshDataset(dims, a.num_train, seed=0, target=target, target_params=target_params), opt, a.epochs)
+        train_briefly(model, MeshDataset(dims, a.num_train, seed=0, target=target, target_params=target_params, **uu), opt, a.epochs)
     eval_grid_MMPDE_MA(test, opt)                  # grid and target errors once; further checkpoints reuse them
     df, df_time = evaluate_model_fine(model, test, opt, batch_size=a.batch_size)
     print(describe(df))

@@ -109,6 +109,12 @@ if __name__ == '__main__':
                     help="mon_reg of the Monge-Ampere monitor: 'ma' then uses (mon_reg + |H|)^0.2 in place of (1 + |H|)^0.2; "
                          "'M2N' needs it (default 0.1, the reference's run parameters)")
     ap.add_argument('--m2n_beta', type=float, default=1.5, help="beta of the M2N monitor (the reference's default 1.5)")
+    ap.add_argument('--ma_monitor_source', choices=('analytic', 'uu'), default='analytic',
+                    help="what drives the Monge-Ampere monitor: the Gaussians' analytic Hessian (default), or second differences of "
+                         "each sample's own uu_tensor, read from a table (monitor_from_nodal, ma_table_batch; --ma_monitor ma only)")
+    ap.add_argument('--uu', choices=('exact', 'fem'), default='exact',
+                    help="uu_tensor of the samples: u_true at the nodes (default), or the coarse P1 Poisson solve the reference stores "
+                         "(windowed band solve above 26 a side)")
     a = ap.parse_args()
     opt = hot_path_opt(mesh_dims=[a.mesh, a.mesh], hidden_dim=a.hidden_dim, num_layers=a.num_layers, batch_size=a.batch_size,
                        epochs=a.epochs, device='cuda:0', loss_fn='mse', lr=1e-3, show_mesh_evol_plots='False',
@@ -125,12 +131,15 @@ if __name__ == '__main__':
                 solver['m2n_solve'] = 'p1'
         else:
             monitor = {} if a.ma_mon_reg is None else {'mon_reg': a.ma_mon_reg, 'mon_power': 0.2}
+        if a.ma_monitor_source != 'analytic':      # absent, the dataset takes today's path
+            monitor['monitor_source'] = a.ma_monitor_source
     else:
         monitor = {}
         solver = {'route': opt['mmpde5_route']}
         solver.update({k: v for k, v in (('cfl', a.mmpde5_cfl), ('max_steps', a.mmpde5_max_steps)) if v is not None})
     ds = MeshDataset(opt['mesh_dims'], a.num_train, seed=0, target=a.target,
-                     target_params=dict(monitor, solver=solver) if a.target != 'noise' else None)
+                     target_params=dict(monitor, solver=solver) if a.target != 'noise' else None,
+                     **({} if a.uu == 'exact' else {'uu': a.uu, 'uu_params': {'fem_band': 'window' if a.mesh > 26 else 'lds'}}))
     t0 = time.time()
     model, losses, rate = main(opt, ds)
     torch.cuda.synchronize()

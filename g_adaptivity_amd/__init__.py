@@ -32,7 +32,8 @@ from .mesh_graph import (DeviceMeshLoader, MeshData, MeshDataset, MeshLoader, Mi
                          square_mesh, synthetic_batch)
 from .mmpde5 import (MMPDE5_1d, MMPDE5_1d_burgers, MMPDE5_2d, deform_mesh_mmpde1d, deform_mesh_mmpde2d, mmpde5_batch, monitor_1d,
                      monitor_2d)
-from .monge_ampere import MA2d, MAResult, MASlowResult, attach_ma_targets, deform_mesh_ma2d, ma_batch, monitor_m2n, monitor_m2n_slow, monitor_ma
+from .monge_ampere import (MA2d, MAResult, MASlowResult, attach_ma_targets, deform_mesh_ma2d, ma_batch, ma_table_batch, monitor_from_nodal,
+                           monitor_m2n, monitor_m2n_slow, monitor_ma, monitor_table)
 from .params import hot_path_opt, model_defaults
 from .spline import cubic_spline_1d
 from .training import GraphedTrainStep
@@ -44,7 +45,7 @@ __all__ = ['GNN', 'MLP', 'get_conv', 'build_conv_list', 'get_enc', 'get_dec', 'g
            'fem_poisson', 'torch_FEM_2D', 'burgers_1d', 'fem_poisson_1d', 'gradient_meshpoints_1D', 'torch_FEM_Burgers_1D',
            'get_Burgers_initial_coeffs', 'fn_expansion', 'torch_FEM_1D', 'gradient_meshpoints_2D',
            'mmpde5_batch', 'monitor_1d', 'monitor_2d', 'MMPDE5_1d', 'MMPDE5_2d', 'MMPDE5_1d_burgers', 'deform_mesh_mmpde1d',
-           'deform_mesh_mmpde2d', 'ma_batch', 'monitor_ma', 'monitor_m2n', 'monitor_m2n_slow', 'MA2d', 'MAResult', 'MASlowResult', 'deform_mesh_ma2d', 'attach_ma_targets', 'poisson_eval_errors', 'eval_grid_MMPDE_MA', 'evaluate_model_fine', 'evaluate_error_np',
+           'deform_mesh_mmpde2d', 'ma_batch', 'ma_table_batch', 'monitor_table', 'monitor_from_nodal', 'monitor_ma', 'monitor_m2n', 'monitor_m2n_slow', 'MA2d', 'MAResult', 'MASlowResult', 'deform_mesh_ma2d', 'attach_ma_targets', 'poisson_eval_errors', 'eval_grid_MMPDE_MA', 'evaluate_model_fine', 'evaluate_error_np',
            'evaluate_error_np_2d', 'calculate_error_reduction', 'cubic_spline_1d', 'evaluate_model_fine_burgers',
            'evaluate_model_fine_burgers_time_step', 'burgers_project', 'backFEM_2D', 'backFEM_1D', 'Fixed_Mesh_2D', 'Fixed_Mesh_1D',
            'get_model', 'mesh_descent_2d', 'mesh_descent_1d', 'DescentResult', 'model_defaults']

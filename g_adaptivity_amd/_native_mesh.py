@@ -24,6 +24,7 @@ MA_STRIDED_MAX_SIDE = 81                               # gadapt_ma_strided_max_s
 MA_M2N_SLOW_MAX_SIDE = 24                              # gadapt_ma_m2n_slow_max_side(): the band of the P1 solve stays in LDS
 MA_MAX_GAUSS = 8                                       # gadapt_ma_max_gauss()
 MA_DESC = 4                                            # GADAPT_MA_DESC: N, node offset, Gaussian offset, Gaussian count
+MA_TABLE_MAX_SIDE = 1024                               # gadapt_ma_table_max_side(): 2 <= T <= 1024 a side of a tabulated monitor
 MA_CONVERGED, MA_CAP, MA_NONCONVEX = 0, 1, 2           # GADAPT_MA_CONVERGED / _CAP / _NONCONVEX
 
 _P, _I, _L, _D = C.c_void_p, C.c_int, C.c_int64, C.c_double
@@ -54,6 +55,9 @@ PROTOTYPES = {
     'gadapt_ma_m2n_slow_max_side': (_I, []),
     'gadapt_ma_m2n_slow_lds_bytes': (_L, [_I]),
     'gadapt_ma_m2n_slow_batch': (_I, [_I] + [_P] * 4 + [_D, _D, _I] + [_P] * 7),
+    'gadapt_ma_table_max_side': (_I, []),
+    'gadapt_ma_table_batch': (_I, [_I] + [_P] * 3 + [_D, _D, _I] + [_P] * 6),
+    'gadapt_ma_table_batch_strided': (_I, [_I] + [_P] * 3 + [_D, _D, _I] + [_P] * 6),
 }
 
 _lib = None
@@ -85,6 +89,9 @@ def lib():
         if handle.gadapt_ma_m2n_slow_max_side() != MA_M2N_SLOW_MAX_SIDE:
             raise NativeError(f"{LIB_PATH}: M2N 'slow' monitor up to {handle.gadapt_ma_m2n_slow_max_side()} a side, expected "
                               f"{MA_M2N_SLOW_MAX_SIDE}; rebuild it with `make`")
+        if handle.gadapt_ma_table_max_side() != MA_TABLE_MAX_SIDE:
+            raise NativeError(f"{LIB_PATH}: tabulated monitors up to {handle.gadapt_ma_table_max_side()} a side, expected "
+                              f"{MA_TABLE_MAX_SIDE}; rebuild it with `make`")
         _lib = handle
     return _lib
 

@@ -1,5 +1,6 @@
 // mesh_common.h - what the translation units of libgadapt_mesh.so share: the error string behind gadapt_mesh_last_error()
-// and the wave reductions on DPP (mmpde5_kernels.hip, ma_kernels.hip, ma_strided_kernels.hip, ma_m2n_slow_kernels.hip).
+// and the wave reductions on DPP (mmpde5_kernels.hip, ma_kernels.hip, ma_strided_kernels.hip, ma_m2n_slow_kernels.hip,
+// ma_table_kernels.hip).
 #ifndef GADAPT_MESH_COMMON_H
 #define GADAPT_MESH_COMMON_H
 

@@ -188,8 +188,9 @@ def attach_random_fields(mesh: MeshData, rng: np.random.Generator, num_gauss: in
                          target_noise: float = 0.01, burgers: Optional[Tuple[float, float]] = None) -> MeshData:
     """One dataset sample: the shared mesh + its own Gaussians (`src/data.py:147-158`).
 
-    `uu` stands in for the coarse FEM solve (= u_true at the nodes); the target
-    `x_phys` stands in for the MA/MMPDE5 mesh (x_comp + small interior noise).
+    `uu` is u_true at the nodes here; the datasets' `uu='fem'` replaces it with what the reference stores, the coarse P1
+    solve on the sample's own mesh (`src/data.py:216-236`; `attach_fem_uu`).  The target `x_phys` stands in for the
+    MA/MMPDE5 mesh (x_comp + small interior noise) until the datasets' `target` replaces it.
     """
     d = mesh.clone()
     x = d.x_comp.double().numpy()
@@ -284,7 +285,7 @@ class MeshDataset:
 
     def __init__(self, mesh_dims: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2, pde_loss_fields: bool = False,
                  eval_quad_points: int = 101, burgers: bool = False, scale: float = 0.1, burgers_limits: float = 3.0,
-                 target: str = 'noise', target_params: Optional[dict] = None):
+                 target: str = 'noise', target_params: Optional[dict] = None, uu: str = 'exact', uu_params: Optional[dict] = None):
         """`target`: what `x_phys` of a sample is.  'noise' (default): x_comp + small interior noise, a stand-in.  'mmpde5': the
         reference's classical target (`src/data.py:206-212`), the MMPDE5 mesh of the sample's own Gaussians, all samples in one
         batched GPU call at construction (`mmpde5.attach_mmpde5_targets`; `ma_its` per sample).  `target_params`: `mon_power` /
@@ -297,7 +298,13 @@ class MeshDataset:
         `target_params={'mesh_type': 'M2N', 'fast_M2N_monitor': 'fast', 'mon_reg': 0.1, 'M2N_beta': 1.5, ...}` selects the
         reference's M2N 'fast' monitor for every sample (`monge_ampere.monitor_m2n`); `'fast_M2N_monitor': 'slow'` with
         `'solver': {'m2n_solve': 'p1'}` (and optionally `'M2N_alpha'`) its 'slow' one, a P1 Poisson solve on the moving mesh inside
-        every update (`monge_ampere.monitor_m2n_slow`; lane route, N <= 24).  Without that keyword 'slow' is refused."""
+        every update (`monge_ampere.monitor_m2n_slow`; lane route, N <= 24).  Without that keyword 'slow' is refused.
+        `target_params={'monitor_source': 'uu', ...}` drives the Monge-Ampere mesh by a monitor tabulated from the sample's own
+        `uu_tensor` (`monge_ampere.monitor_from_nodal`, `ma_table_batch`) instead of the Gaussians' analytic Hessian.
+        `uu`: what `uu_tensor` of a sample is.  'exact' (default): u_true at the nodes.  'fem': the nodal coefficients of the P1
+        Poisson solve on the sample's own uniform mesh, as the reference stores them, all samples in one batched GPU call at
+        construction, before the targets are set (`attach_fem_uu`; the limits of the FEM route: 2-D sides up to 26, or up to 81
+        with `uu_params={'fem_band': 'window'}`)."""
         self.mesh_dims = list(mesh_dims)
         self.dim = len(self.mesh_dims)
         if self.dim == 1:
@@ -316,6 +323,7 @@ class MeshDataset:
         self.mesh = MeshTopology(base.cells.numpy()) if self.dim == 2 else None
         if pde_loss_fields:                                  # loss_type='pde_loss': only when asked, samples are unchanged otherwise
             _add_pde_loss_fields(self, eval_quad_points)
+        _set_uu(self, uu, uu_params)
         _set_targets(self, target, target_params)
 
     def __len__(self):
@@ -336,7 +344,8 @@ class MixedMeshDataset(MeshDataset):
     (`{'solver': {'route': 'strided'}}` for sizes of 33..81 a side)."""
 
     def __init__(self, mesh_sizes: Sequence[int], num_data: int, seed: int = 0, num_gauss: int = 2, pde_loss_fields: bool = False,
-                 eval_quad_points: int = 101, target: str = 'noise', target_params: Optional[dict] = None):
+                 eval_quad_points: int = 101, target: str = 'noise', target_params: Optional[dict] = None, uu: str = 'exact',
+                 uu_params: Optional[dict] = None):
         self.mesh_sizes = list(mesh_sizes)
         self.mesh_dims = [self.mesh_sizes[0], self.mesh_sizes[0]]
         self.dim = 2
@@ -355,7 +364,53 @@ class MixedMeshDataset(MeshDataset):
         self.mesh = MeshTopology(self.base.cells.numpy())
         if pde_loss_fields:
             _add_pde_loss_fields(self, eval_quad_points)
+        _set_uu(self, uu, uu_params)
         _set_targets(self, target, target_params)
+
+
+UU_SOURCES = ('exact', 'fem')
+
+
+def _set_uu(ds, uu: str, uu_params: Optional[dict]):
+    """`uu='exact'` leaves every sample as it is; `uu='fem'` is `attach_fem_uu` on all of them."""
+    if uu not in UU_SOURCES:
+        raise ValueError(f"uu = {uu!r}; one of {UU_SOURCES}")
+    extra = set(uu_params or {}) - {'fem_band', 'device'}
+    if extra:
+        raise TypeError(f"unexpected uu_params {sorted(extra)}; 'fem_band' and 'device'")
+    if uu == 'fem':
+        attach_fem_uu(ds.samples, **(uu_params or {}))
+
+
+def attach_fem_uu(samples, fem_band: str = 'lds', device=None):
+    """`uu_tensor` of every sample := the nodal coefficients of the P1 Poisson solve of its own Gaussians on its own uniform
+    mesh (`x_comp`), what the reference's dataset builder stores (`src/data.py:216-236`): one batched call of `fem_poisson`
+    (2-D; `fem_band='window'` for sides above 26) or `fem_poisson_1d`, mixed mesh sizes sharing it.  GPU only."""
+    from ._native import NativeError
+    if not torch.cuda.is_available():
+        raise NativeError("uu='fem' solves on the GPU only (libgadapt_fem.so): no CUDA/HIP device is visible; there is no CPU fallback")
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    counts = [d.num_nodes for d in samples]
+    params = [d.pde_params for d in samples]
+    x = torch.cat([d.x_comp for d in samples]).to(dev)
+    with torch.no_grad():
+        if x.dim() == 1:
+            from .fem1d import fem_poisson_1d
+            if fem_band != 'lds':
+                raise ValueError(f"fem_band = {fem_band!r}: the 1-D solve has one route")
+            coeffs, _ = fem_poisson_1d(x, counts, params, {})
+        else:
+            from .fem import fem_poisson
+            offs = np.cumsum([0] + counts)
+            cells = torch.cat([d.cells + int(o) for d, o in zip(samples, offs[:-1])])
+            boundary = torch.cat([d.boundary_nodes for d in samples])
+            axis = torch.linspace(0, 1, 2)                   # the lattice is not read here: its smallest form
+            coeffs, _ = fem_poisson(x, cells, boundary, counts, params, (axis, axis), tri_counts=[d.cells.shape[0] for d in samples],
+                                    band=fem_band)
+    coeffs = coeffs.reshape(-1).cpu()
+    for d, o, n in zip(samples, np.cumsum([0] + counts)[:-1], counts):
+        d.uu_tensor = coeffs[int(o):int(o) + n].clone().to(d.u_true_tensor.dtype)
+    return coeffs
 
 
 def _set_targets(ds, target: str, target_params: Optional[dict]):

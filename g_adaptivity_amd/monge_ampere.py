@@ -44,6 +44,16 @@ own noise bar of the fp64 restatement.  Nothing changes its route unasked; `MA2d
 The defaults `cfl=0.2, tol=1e-4, max_steps=20000` hold on both routes: 64 x 64 wanted 17 500 to 25 500 updates in the cases
 tried and 81 x 81 28 000 to 32 000, so large meshes need `max_steps` raised (40 000 covered both), and the default call can
 return CAP there.
+
+A TABULATED MONITOR (`ma_table_batch`, `ma_table_kernel` and `ma_table_strided_kernel`): the same iteration on both routes with
+the monitor read bilinearly from a table M [T, T] on a lattice of the physical unit square, M[i, j] at (i / (T-1), j / (T-1)),
+2 <= T <= 1024, each mesh its own T, instead of from the Gaussians.  `monitor_table` tabulates a closed-form monitor,
+`monitor_from_nodal` builds the `diag_hessian_ma` monitor from the second differences of ANY nodal field on a uniform lattice,
+and `attach_ma_targets(..., {'monitor_source': 'uu'})` (the datasets' `target_params`) drives every sample's mesh by its own
+`uu_tensor`: the classical competitor that knows the computed coarse solution, not the exact one.  The reference approximates
+that with a high-order Firedrake solve ('superslow', `ma_mesh_2d.py:182-225`), which is not built; a second difference of the
+coarse P1 solution is the STATED DEVIATION, and parity with `movement` is unpinned here as for the other monitors.  The table
+does not move with the mesh, so `mesh_type: 'M2N'` (whose maximum does) is refused under `monitor_source: 'uu'`.
 """
 from __future__ import annotations
 
@@ -64,7 +74,9 @@ STATUS_NAMES = {CONVERGED: 'converged', CAP: 'cap reached', NONCONVEX: 'convexit
 MAX_SIDE, MAX_GAUSS = _native_mesh.MA_MAX_SIDE, _native_mesh.MA_MAX_GAUSS
 STRIDED_MAX_SIDE = _native_mesh.MA_STRIDED_MAX_SIDE
 SLOW_MAX_SIDE = _native_mesh.MA_M2N_SLOW_MAX_SIDE
+TABLE_MAX_SIDE = _native_mesh.MA_TABLE_MAX_SIDE
 ROUTES = ('lane', 'strided')
+MONITOR_SOURCES = ('analytic', 'uu')
 M2N_SOLVES = ('p1',)
 
 MAResult = namedtuple('MAResult', 'coords steps residual status')
@@ -360,6 +372,120 @@ def ma_batch(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
     return collect()
 
 
+# --------------------------------------------------------------------------
+# a tabulated monitor
+# --------------------------------------------------------------------------
+
+def monitor_table(params, T: int, dtype=torch.float64) -> torch.Tensor:
+    """The closed-form monitor of `params` on the T x T lattice of the unit square, [T, T] with entry (i, j) at
+    (i / (T-1), j / (T-1)): `monitor_ma`, or `monitor_m2n` for `mesh_type: 'M2N'` with `fast_M2N_monitor: 'fast'`, its maximum
+    taken over the lattice (a table does not move with the mesh).  What `ma_table_batch` takes for a monitor that is known."""
+    T = int(T)
+    if not (2 <= T <= TABLE_MAX_SIDE):
+        raise ValueError(f"T = {T}; a monitor table has 2..{TABLE_MAX_SIDE} points a side")
+    kind = monitor_kind(0, params)
+    lin = torch.arange(T, dtype=dtype) / (T - 1)
+    gx, gy = torch.meshgrid(lin, lin, indexing='ij')
+    return (monitor_m2n if kind == 'M2N' else monitor_ma)(gx, gy, params)
+
+
+def monitor_from_nodal(u: torch.Tensor, *, mon_reg: float = 1.0, mon_power: float = 0.2) -> torch.Tensor:
+    """The `diag_hessian_ma` monitor (mon_reg + sqrt(u_xx^2 + u_yy^2)) ** mon_power of a nodal field u [T, T] on the uniform
+    lattice of the unit square (entry (i, j) at (i / (T-1), j / (T-1))), T >= 3.  u_xx and u_yy are second differences with spacing
+    1 / (T-1); a boundary row or column takes the value of its interior neighbour, so a quadratic u gives the exact monitor
+    everywhere.  Plain torch, in the dtype and on the device of u."""
+    if not torch.is_tensor(u) or u.dim() != 2 or u.shape[0] != u.shape[1] or u.shape[0] < 3 or not u.is_floating_point():
+        raise ValueError(f"monitor_from_nodal: u of shape {tuple(u.shape) if torch.is_tensor(u) else type(u)}; a floating [T, T] "
+                         "lattice, T >= 3")
+    inv_h2 = float((u.shape[0] - 1) ** 2)
+    dxx = ((u[2:, :] - 2.0 * u[1:-1, :]) + u[:-2, :]) * inv_h2
+    dyy = ((u[:, 2:] - 2.0 * u[:, 1:-1]) + u[:, :-2]) * inv_h2
+    uxx = torch.cat([dxx[:1], dxx, dxx[-1:]], 0)
+    uyy = torch.cat([dyy[:, :1], dyy, dyy[:, -1:]], 1)
+    return (mon_reg + torch.sqrt(uxx * uxx + uyy * uyy)) ** mon_power
+
+
+def _table_side(b: int, table) -> int:
+    if not torch.is_tensor(table) or table.dim() != 2 or table.shape[0] != table.shape[1] or not table.is_floating_point():
+        what = tuple(table.shape) if torch.is_tensor(table) else type(table).__name__
+        raise ValueError(f"mesh {b}: monitor table {what}; a square [T, T] floating-point tensor")
+    T = int(table.shape[0])
+    if not (2 <= T <= TABLE_MAX_SIDE):
+        raise ValueError(f"mesh {b}: T = {T}; a monitor table has 2..{TABLE_MAX_SIDE} points a side")
+    return T
+
+
+def _prepare_table(sizes: Sequence, tables: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000, device=None,
+                   route: str = 'lane'):
+    """The host side of `ma_table_batch`, split like `_prepare`: checks, the batch's descriptors and tables on the GPU, the
+    argument list.  Returns (launch, collect)."""
+    if route not in ROUTES:
+        raise ValueError(f"route = {route!r}; one of {ROUTES}")
+    if len(sizes) == 0 or len(sizes) != len(tables):
+        raise ValueError(f"{len(sizes)} mesh sizes and {len(tables)} monitor tables")
+    if not (0 <= int(max_steps) <= _native_mesh.MAX_STEPS):
+        raise ValueError(f"max_steps = {max_steps}; 0..{_native_mesh.MAX_STEPS} (the loop has to end)")
+    if not (0 < cfl < float('inf') and 0 <= tol < float('inf')):
+        raise ValueError(f"cfl = {cfl}, tol = {tol}; cfl > 0 and tol >= 0 expected")
+    ns = [_side(b, s, route) for b, s in enumerate(sizes)]
+    ts = [_table_side(b, t) for b, t in enumerate(tables)]
+    B = len(ns)
+
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device() if torch.cuda.is_available() else 0)
+    if dev.type != 'cuda' or not torch.cuda.is_available():
+        raise NativeError("Monge-Ampere meshes are built on the GPU only (libgadapt_mesh.so): no CUDA/HIP device is visible; "
+                          "there is no CPU fallback")
+
+    desc, noff, toff = [], 0, 0
+    for n, t in zip(ns, ts):
+        desc += [n, noff, toff, t]
+        noff, toff = noff + n * n, toff + t * t
+    if noff >= 2 ** 31 or toff >= 2 ** 31:
+        raise ValueError("more than 2^31 nodes or table entries in one batch")
+    desc_host = (C.c_int32 * len(desc))(*desc)
+    desc_dev = torch.tensor(desc, dtype=torch.int32).to(dev)
+    tables_dev = torch.cat([t.detach().to(device=dev, dtype=torch.float32).reshape(-1) for t in tables]).contiguous()
+    x = torch.empty(noff, dtype=torch.float32, device=dev)
+    y = torch.empty_like(x)
+    steps = torch.empty(B, dtype=torch.int32, device=dev)
+    residual = torch.empty(B, dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    args = (B, C.cast(desc_host, C.c_void_p), desc_dev.data_ptr(), tables_dev.data_ptr(), float(cfl), float(tol), int(max_steps),
+            x.data_ptr(), y.data_ptr(), steps.data_ptr(), residual.data_ptr(), status.data_ptr())
+    keep = (desc_host, desc_dev, tables_dev)                             # what the argument list points into
+    entry = 'gadapt_ma_table_batch' + ('_strided' if route == 'strided' else '')
+
+    def launch(_keep=keep):                                              # the closure keeps the inputs alive
+        with torch.cuda.device(dev):
+            _native_mesh.check(getattr(_native_mesh.lib(), entry)(*args, current_stream(dev)), entry)
+
+    def collect():
+        out, o = [], 0
+        for n in ns:
+            out.append(torch.stack([x[o:o + n * n].view(n, n), y[o:o + n * n].view(n, n)]))
+            o += n * n
+        return MAResult(out, steps, residual, status)
+
+    return launch, collect
+
+
+def ma_table_batch(sizes: Sequence, tables: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000,
+                   route: str = 'lane', device=None) -> MAResult:
+    """Monge-Ampere meshes of many samples from TABULATED monitors, mixed mesh sizes and mixed table sizes in one launch.
+
+    sizes[b]    N (or a pair (N, N)), as in `ma_batch`
+    tables[b]   [T, T], any float dtype, any device (copied to fp32 on the GPU): the monitor at the physical points
+                (i / (T-1), j / (T-1)), 2 <= T <= 1024, read bilinearly at the moving nodes (`include/gadapt_mesh.h`).  The entries
+                have to be positive and finite: one that is not comes back as NONCONVEX, never as a fault
+    cfl, tol, max_steps, route   as in `ma_batch`: 'lane' for 3 <= N <= 32, 'strided' for 3 <= N <= 81
+
+    Returns `ma_batch`'s MAResult.  A mesh's result does not depend on its batch; a constant table gives 0 updates and the grid.
+    """
+    launch, collect = _prepare_table(sizes, tables, cfl=cfl, tol=tol, max_steps=max_steps, device=device, route=route)
+    launch()
+    return collect()
+
+
 def warn_status(status, what: str = 'Monge-Ampere'):
     """NONCONVEX and CAP as warnings (the reference swallows the mover's exception and prints nothing)."""
     st = status.tolist() if torch.is_tensor(status) else list(status)
@@ -421,6 +547,16 @@ def deform_mesh_ma2d(x_comp: torch.Tensor, n: int, m: int, pde_params, **solver)
 # dataset targets
 # --------------------------------------------------------------------------
 
+def nodal_grid(x_comp: torch.Tensor, values: torch.Tensor, n: int) -> torch.Tensor:
+    """A nodal field [n*n] in the node order of `x_comp` [n*n, 2] laid out as [n, n] on `unit_grid(n)`: entry (i, j) is the value
+    at the node nearest to the grid point (i, j), the mapping of `write_back_to_nodes` read the other way."""
+    gx, gy = unit_grid(n, x_comp.device)
+    lo, hi = x_comp.min(0).values, x_comp.max(0).values
+    scaled = ((x_comp - lo) / (hi - lo)).to(torch.float32)
+    node = torch.cdist(torch.stack([gx.reshape(-1), gy.reshape(-1)], 1), scaled).argmin(1)
+    return values.reshape(-1)[node].reshape(n, n)
+
+
 def attach_ma_targets(samples, monitor_params: Optional[dict] = None, **solver):
     """`x_phys` of every sample := its Monge-Ampere mesh, all samples in ONE batched call; `ma_its` = updates + 1 and
     `build_time` (the batched call's wall time shared out evenly) as `attach_mmpde5_targets` sets them.  The monitor of a
@@ -428,8 +564,24 @@ def attach_ma_targets(samples, monitor_params: Optional[dict] = None, **solver):
     `monitor_params` carries `mesh_type: 'M2N'` (`fast_M2N_monitor`, `mon_reg`, `M2N_beta`).  The samples' meshes
     must be square grids in grid order (`square_mesh`).  A sample that lost convexity gets zeros and `ma_its` = 1.
     Keyword-only `cfl`, `tol`, `max_steps`, `route`, `m2n_solve` and `device` go to `ma_batch` (`route='strided'` for 33..81 a side;
-    `m2n_solve='p1'` for `fast_M2N_monitor: 'slow'`)."""
+    `m2n_solve='p1'` for `fast_M2N_monitor: 'slow'`).
+    `monitor_params['monitor_source']`: 'analytic' (the default: the path above) or 'uu': each sample's monitor is then
+    `monitor_from_nodal` of its own `uu_tensor` laid out on its N x N grid (`nodal_grid`), with `mon_reg` / `mon_power` from
+    `monitor_params`, as a table of T = N for `ma_table_batch`; `route`, `cfl`, `tol` and `max_steps` work as above.  'uu' with
+    `mesh_type: 'M2N'` is a `ValueError`: that monitor's maximum moves with the mesh, a table does not."""
     _dataset_solver_kwargs(solver)
+    monitor_params = dict(monitor_params or {})
+    source = monitor_params.pop('monitor_source', 'analytic')
+    if source not in MONITOR_SOURCES:
+        raise ValueError(f"monitor_source = {source!r}; one of {MONITOR_SOURCES}")
+    if source == 'uu':
+        if monitor_params.get('mesh_type', 'ma') != 'ma':
+            raise ValueError(f"monitor_source = 'uu' with mesh_type = {monitor_params['mesh_type']!r}: the M2N monitor's maximum moves "
+                             "with the mesh, a tabulated monitor does not; use mesh_type 'ma' (mon_reg, mon_power)")
+        if solver.get('m2n_solve') is not None:
+            raise ValueError("monitor_source = 'uu' has no M2N solve: leave m2n_solve out")
+        solver = {k: v for k, v in solver.items() if k != 'm2n_solve'}
+        reg, power = monitor_constants(monitor_params)
     sizes, params = [], []
     for d in samples:
         if d.x_comp.dim() != 2 or d.x_comp.shape[1] != 2:
@@ -440,7 +592,12 @@ def attach_ma_targets(samples, monitor_params: Optional[dict] = None, **solver):
         sizes.append(n)
         params.append(dict(d.pde_params, **(monitor_params or {})))
     t0 = time.time()
-    res = ma_batch(sizes, params, **solver)
+    if source == 'uu':
+        tables = [monitor_from_nodal(nodal_grid(d.x_comp, d.uu_tensor, n).double(), mon_reg=reg, mon_power=power)
+                  for d, n in zip(samples, sizes)]
+        res = ma_table_batch(sizes, tables, **solver)
+    else:
+        res = ma_batch(sizes, params, **solver)
     steps, status = res.steps.tolist(), res.status.tolist()   # waits for the device: the batched call is done
     build_time = (time.time() - t0) / max(len(samples), 1)
     warn_status(status, 'Monge-Ampere (dataset targets)')

@@ -269,6 +269,46 @@ int gadapt_ma_m2n_slow_batch(int n_mesh, const int32_t* desc_host, const int32_t
                              double cfl, double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual,
                              int32_t* status, float* monitor_out, void* stream);
 
+/*
+ * Monge-Ampere meshes from a TABULATED monitor: the monitor is not a closed form of the sample's Gaussians but a table on a
+ * lattice of the physical unit square, so a mesh can be adapted to any nodal field (a computed coarse solution, say).
+ * gadapt_ma_table_batch is the iteration of gadapt_ma_batch and gadapt_ma_table_batch_strided that of gadapt_ma_batch_strided,
+ * each with this change and no other: the lines "per Gaussian k" and "m = powf(...)" are replaced by a bilinear read of the
+ * mesh's own table M [T, T] (fp32, row-major), M[i, j] being the monitor at the physical point (i / (T-1), j / (T-1)), the
+ * 'ij' convention of the coordinates.  Per node, fp32 without FMA contraction:
+ *   xc = x > 0 ? (x < 1 ? x : 1) : 0            (a NaN maps to 0: no index is ever formed from a NaN)     yc likewise
+ *   fx = xc * (float)(T-1),  i0 = min((int)fx, T-2),  ax = fx - (float)i0                                 fy, j0, ay likewise
+ *   m0 = M[i0,j0]   + ax * (M[i0+1,j0]   - M[i0,j0])
+ *   m1 = M[i0,j0+1] + ax * (M[i0+1,j0+1] - M[i0,j0+1])
+ *   m  = m0 + ay * (m1 - m0)
+ *   r  = logf(m det)
+ * The form is continuous across table cells (a node whose i0 differs between two arithmetics costs rounding only) and exact for
+ * tables linear in x and y.  Nodes with x == 1 exactly (every mesh has them: boundary nodes keep their normal coordinate) give
+ * i0 = T-2, ax = 1: the last row and column are read, in bounds.  A table entry that is <= 0 or not finite has no check of its
+ * own: it makes r not finite, which is the NONCONVEX exit.  A constant table gives 0 updates and the grid itself.
+ * px, py, a, b, c, x, y, det, lambda, rbar, res, lmin, the reductions and their order, the three exit tests and their order, the
+ * update, the status words, cfl, tol and max_steps are unchanged; on the strided route so are the fp64 phi, the five stencil
+ * expressions rounded once to fp32, the ownership t + k T and the fp32 increment added in fp64.  The two routes do not give the
+ * same bits at N <= 32, as above.
+ * `desc` is int32 [B, GADAPT_MA_DESC] with GADAPT_MA_D_N and GADAPT_MA_D_NODE_OFF as above, GADAPT_MA_D_TABLE_OFF the offset of
+ * the mesh's table in `tables`, in floats, and GADAPT_MA_D_TABLE_T its side.  `tables` is one device buffer [sum of T_b^2], fp32;
+ * every mesh has its own T, 2 <= T <= gadapt_ma_table_max_side() (1024).  The table is read from global memory on both routes;
+ * the launch's dynamic LDS is 256 + 8 N^2 bytes (two fp32 images on the lane route, one fp64 image on the strided one), 52 744
+ * at 81 x 81.
+ * Arguments are those of gadapt_ma_batch with `tables` in the place of `gauss` and without `mon`; outputs and error codes are
+ * the same: GADAPT_MESH_E_SIZE for N above the route's side (32, 81), T outside 2..1024 or max_steps beyond the cap; neither
+ * allocates nor synchronises.
+ */
+#define GADAPT_MA_D_TABLE_OFF 2   /* the word of GADAPT_MA_D_GAUSS_OFF */
+#define GADAPT_MA_D_TABLE_T   3   /* the word of GADAPT_MA_D_GAUSS_N */
+
+int gadapt_ma_table_max_side(void);                   /* 1024 */
+int gadapt_ma_table_batch(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* tables, double cfl, double tol,
+                          int max_steps, float* x, float* y, int32_t* steps, float* residual, int32_t* status, void* stream);
+int gadapt_ma_table_batch_strided(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* tables, double cfl,
+                                  double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual, int32_t* status,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
