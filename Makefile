@@ -18,7 +18,7 @@ HIPFLAGS   := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -I$(CSRC) -W
 ifdef DEV_C
 HIPFLAGS   += -DGADAPT_DEV_C=$(DEV_C)
 endif
-UNITS      := gadapt_kernels gadapt_tu_fwd gadapt_tu_bwd_target gadapt_tu_bwd_source gadapt_tu_smallmesh gadapt_tu_sparse gadapt_tu_gat
+UNITS      := gadapt_kernels gadapt_tu_fwd gadapt_tu_bwd_target gadapt_tu_bwd_source gadapt_tu_smallmesh gadapt_tu_sparse gadapt_tu_gat gadapt_tu_cnn
 OBJS       := $(UNITS:%=$(OBJDIR)/%.o) $(OBJDIR)/csr_build.o
 SHARED     := $(CSRC)/gadapt_internal.h $(CSRC)/gadapt_common.inc $(CSRC)/gadapt_block_plan.h $(CSRC)/gadapt_narrow_plan.h include/gadapt_hip.h
 TAIL_PLAN  := $(CSRC)/gadapt_tail_plan.h
@@ -91,6 +91,7 @@ $(OBJDIR)/gadapt_tu_bwd_source.o: $(CSRC)/gadapt_bwd_source.inc
 $(OBJDIR)/gadapt_tu_smallmesh.o: $(CSRC)/gadapt_smallmesh.inc
 $(OBJDIR)/gadapt_tu_sparse.o: $(CSRC)/gadapt_sparse.inc
 $(OBJDIR)/gadapt_tu_gat.o: $(CSRC)/gadapt_gat.inc
+$(OBJDIR)/gadapt_tu_cnn.o: $(CSRC)/gadapt_cnn.inc $(CSRC)/gadapt_cnn_plan.h
 
 # FLAGS_<unit>="-D..." adds flags to ONE translation unit (A/B builds of a kernel family: tools/ab_units.sh)
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(SHARED)

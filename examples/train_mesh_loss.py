@@ -115,8 +115,14 @@ if __name__ == '__main__':
     ap.add_argument('--uu', choices=('exact', 'fem'), default='exact',
                     help="uu_tensor of the samples: u_true at the nodes (default), or the coarse P1 Poisson solve the reference stores "
                          "(windowed band solve above 26 a side)")
+    ap.add_argument('--glob_feat', action='store_true',
+                    help="per-mesh CNN features of f and uu on every node (gnn_inc_glob_feat_f / _uu, the reference's argparse default)")
+    ap.add_argument('--glob_feat_kernel', choices=('torch', 'hip', 'auto'), default='torch',
+                    help="what computes them: the Conv modules, the one-launch HIP kernels (2-D images up to 23 x 23 at hidden 8, 16 x 16 at 16, "
+                         "11 x 11 at 32, 7 x 7 at 64; an error beyond), or HIP where it fits")
     a = ap.parse_args()
     opt = hot_path_opt(mesh_dims=[a.mesh, a.mesh], hidden_dim=a.hidden_dim, num_layers=a.num_layers, batch_size=a.batch_size,
+                       gnn_inc_glob_feat_f=a.glob_feat, gnn_inc_glob_feat_uu=a.glob_feat, glob_feat_kernel=a.glob_feat_kernel,
                        epochs=a.epochs, device='cuda:0', loss_fn='mse', lr=1e-3, show_mesh_evol_plots='False',
                        device_loader=not a.cpu_loader, native_loss=not a.torch_loss, graphed=not a.eager,
                        mmpde5_route=a.mmpde5_route, ma_route=a.ma_route)

@@ -102,6 +102,12 @@ PROTOTYPES = {
     'gadapt_adam_step': (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _F, _P]),
     'gadapt_adam_step_dev': (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _P, _F, _P]),
     'gadapt_allreduce_flat': (_I, [_P, _P, _L, _I, _P]),
+    'gadapt_cnn_forward_lds_bytes': (_L, [_I, _I, _I, _I, _I]),
+    'gadapt_cnn_backward_lds_bytes': (_L, [_I, _I, _I, _I, _I]),
+    'gadapt_cnn_workspace_floats': (_L, [_I, _I, _I, _I, _I, _I]),
+    'gadapt_cnn_param_floats': (_I, [_I, _I, _I]),
+    'gadapt_cnn_forward': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'gadapt_cnn_backward': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'gadapt_gat_plus_block_forward': (_I, [_G, _P, _I, _P, _P, _L, _F, _I, _I, _I, _P, _P, _I, _P]),
     'gadapt_gat_plus_block_backward': (_I, [_G, _P, _P, _P, _P, _I, _P, _P, _L, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     'gadapt_gat_plus_partial_rows': (_I, [_L, _I]),

@@ -16,6 +16,7 @@
 //   gadapt_tu_smallmesh.hip    one-launch small-mesh pair (gadapt_smallmesh.inc)
 //   gadapt_tu_sparse.hip       generic CSR primitives (gadapt_sparse.inc)
 //   gadapt_tu_gat.hip          fused GAT_plus block (gadapt_gat.inc)
+//   gadapt_tu_cnn.hip          global CNN features of a field, one launch forward and one backward (gadapt_cnn.inc, gadapt_cnn_plan.h)
 // Device code is never shared across units (no relocatable device code): every unit includes gadapt_common.inc itself.
 #ifndef GADAPT_INTERNAL_H
 #define GADAPT_INTERNAL_H

@@ -146,10 +146,12 @@ class GNN(nn.Module):
         self.dec = get_dec(opt, hid, self.dim, nonlin_type=opt['non_lin'])
         if opt.get('gnn_inc_glob_feat_f'):                                # GNN.py:170-175
             self.global_out_dim = opt['global_feat_dim']
-            self.global_feature_extractor_cnn_f = GlobalFeatureExtractorCNN(1, hid, self.global_out_dim, dim=self.dim)
+            self.global_feature_extractor_cnn_f = GlobalFeatureExtractorCNN(1, hid, self.global_out_dim, dim=self.dim,
+                                                                            kernel=opt.get('glob_feat_kernel', 'torch'))
         if opt.get('gnn_inc_glob_feat_uu'):
             self.global_out_dim = opt['global_feat_dim']
-            self.global_feature_extractor_cnn_uu = GlobalFeatureExtractorCNN(1, hid, self.global_out_dim, dim=self.dim)
+            self.global_feature_extractor_cnn_uu = GlobalFeatureExtractorCNN(1, hid, self.global_out_dim, dim=self.dim,
+                                                                             kernel=opt.get('glob_feat_kernel', 'torch'))
         if opt.get('learn_step'):
             self.steps = nn.ParameterList([nn.Parameter(torch.tensor([opt['time_step']]))
                                            for _ in range(opt['num_layers'])])       # GNN.py:179-180
@@ -374,7 +376,8 @@ class GNN(nn.Module):
                         side = int(np.sqrt(x_comp.shape[0]))               # GNN.py:247,261: one mesh per batch for this data type
                         dims = [side, side]
                     grid = field_to_grid(field, mapping, dims, n_meshes, self.dim)
-                    glob.append(expand_to_nodes(getattr(self, extractor)(grid.unsqueeze(1)), batch))
+                    cnn = getattr(self, extractor)
+                    glob.append(expand_to_nodes(cnn(grid.unsqueeze(1)), batch, fixed_order=cnn.kernel != 'torch'))
 
         def features():                                                    # the concatenated matrix, only where a caller needs it
             return torch.cat([x_comp] + [t.unsqueeze(-1) for t in (f, uu) if t is not None] + glob, dim=1).float()

@@ -54,6 +54,9 @@ def hot_path_opt(**overrides) -> dict:
         'gnn_inc_glob_feat_uu': False,      # params.py:117
         'gnn_normalize': False,             # params.py:118
         'global_feat_dim': 8,               # params.py:133
+        # not a reference key: what computes the global CNN features.  'torch': the Conv modules (MIOpen); 'hip': the one-launch
+        # kernels of features.global_cnn (images whose LDS copies fit 64 KB, else an error); 'auto': 'hip' where it fits
+        'glob_feat_kernel': 'torch',
         # model
         'conv_type': 'GRAND_plus',          # params.py:121
         'gat_plus_type': 'GAT_res_lap',     # params.py:122

@@ -610,6 +610,35 @@ int gadapt_adam_step_dev(float* param, const float* grad, float* exp_avg, float*
  * torch.distributed (its process group owns the communicator); this entry point is for callers that hold their own. */
 int gadapt_allreduce_flat(void* comm, float* bucket, int64_t n, int average, void* stream);
 
+/* ------------------------------------------------------------------ global CNN features of a field (features.GlobalFeatureExtractorCNN, kernel='hip')
+ * u / max|u| over the batch, four convolutions (3 taps at dim 1, 3 x 3 at dim 2; stride 1, zero padding 1; channels 1 -> mid -> mid -> mid ->
+ * out) with SELU, average pool (src/feature_extractors.py:6-34).  One image shape per call: u [n_meshes][n0][n1] fp32, n0 = 1 at dim 1.
+ * Weights as the Conv1d / Conv2d modules hold them: w_l [c_out][c_in][3] or [c_out][c_in][3][3], b_l [c_out]; nothing is copied or
+ * reshaped.  One workgroup per mesh with its images in LDS, channel-major planes of (n0 + 2)(n1 + 2) floats with a zero border: the
+ * forward holds 2 images of max(mid, out) planes, the backward 3, both beside a table of n0 n1 pixel offsets, and a call that needs
+ * more than 65 536 bytes (the LDS a launch gets without asking for more) is refused: *_lds_bytes return that size (-1: dim outside {1, 2}, a size below 1, n0 != 1 at dim 1), so
+ * at mid 8 / 16 / 32 / 64 the backward takes 2-D images up to 23 x 23 / 16 x 16 / 11 x 11 / 7 x 7.
+ * Every sum has a fixed order and there are no floating-point atomics: two runs give the same bits, and a mesh's row of feat does
+ * not depend on the other meshes of the batch beyond umax.  Argument checks run before anything is launched and need no GPU. */
+int64_t gadapt_cnn_forward_lds_bytes(int dim, int n0, int n1, int mid, int out);
+int64_t gadapt_cnn_backward_lds_bytes(int dim, int n0, int n1, int mid, int out);
+/* floats of the saved activations [4][n_meshes, c_l, n0 n1] (c_l = mid, mid, mid, out), and of the packed parameters
+ * w0, b0, w1, b1, w2, b2, w3, b3 */
+int64_t gadapt_cnn_workspace_floats(int n_meshes, int dim, int n0, int n1, int mid, int out);
+int gadapt_cnn_param_floats(int dim, int mid, int out);
+/* feat [n_meshes][out].  umax: DEVICE pointer to max|u| over the whole batch (one float; the launch divides by it - zero gives NaN
+ * like the reference).  acts (nullable): gadapt_cnn_workspace_floats floats, written for the backward. */
+int gadapt_cnn_forward(const float* u, const float* umax, int n_meshes, int dim, int n0, int n1, int mid, int out,
+                       const float* w0, const float* b0, const float* w1, const float* b1, const float* w2, const float* b2,
+                       const float* w3, const float* b3, float* feat, float* acts, void* stream);
+/* d_params [gadapt_cnn_param_floats]: the gradient of every weight and bias from d_feat [n_meshes][out] and the forward's acts, packed
+ * in the order above (overwritten, not accumulated).  partials [n_meshes][gadapt_cnn_param_floats]: the per-mesh gradients the launch
+ * leaves for the fixed-order sum over meshes, a second small launch (nullable at n_meshes = 1: the one mesh writes d_params itself).
+ * No gradient wrt u. */
+int gadapt_cnn_backward(const float* d_feat, const float* acts, const float* u, const float* umax, int n_meshes, int dim, int n0, int n1,
+                        int mid, int out, const float* w0, const float* b0, const float* w1, const float* b1, const float* w2,
+                        const float* b2, const float* w3, const float* b3, float* partials, float* d_params, void* stream);
+
 /* ------------------------------------------------------------------ timing (bench only)
  * When enabled, every launch of the three hot kernels is bracketed by hipEvents on its
  * stream; kernel_id 0 = forward, 1 = backward target pass, 2 = backward source pass.

@@ -9,7 +9,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ["gadapt_tu_fwd", "gadapt_tu_bwd_target", "gadapt_tu_bwd_source", "gadapt_tu_smallmesh"]   # the hot kernels' translation units
+UNITS = ["gadapt_tu_fwd", "gadapt_tu_bwd_target", "gadapt_tu_bwd_source", "gadapt_tu_smallmesh", "gadapt_tu_cnn"]   # the hot kernels' translation units
 flags = [a for a in sys.argv[1:] if a.startswith("-")]
 units = [a for a in sys.argv[1:] if not a.startswith("-")] or UNITS
 from concurrent.futures import ThreadPoolExecutor
@@ -38,7 +38,7 @@ for line in out.splitlines():
     elif cur and ":" in t:
         k, v = t.rsplit(":", 1)
         rec[k.strip()] = v.strip()
-        if k.strip().startswith("LDS Size") and ("grand_" in cur or "wide" in cur or "smallmesh" in cur):
+        if k.strip().startswith("LDS Size") and ("grand_" in cur or "wide" in cur or "smallmesh" in cur or "cnn" in cur):
             print("%-78s VGPR %4s  AGPR %3s  scratch %5s  spill %4s  waves/SIMD %s" % (
                 cur, rec.get("VGPRs"), rec.get("AGPRs"), rec.get("ScratchSize [bytes/lane]"), rec.get("VGPRs Spill"),
                 rec.get("Occupancy [waves/SIMD]")))
