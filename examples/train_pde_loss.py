@@ -4,7 +4,13 @@ FEM solve on the moved mesh, the reference's own `GNN` config (`src/params.py:10
 training meshes 15 and 20).  Prints the loss per epoch and ms per step, split into GNN forward / backward and FEM tail
 forward / backward.
 
+`--step captured` trains with `GraphedTrainStep` instead: the iteration is captured once per batch topology and replayed, with
+the new batch's fields, target and Gaussians fed in and no host synchronisation inside an epoch; it prints the loss per epoch
+and ms per step from HIP events around whole epochs.  `--adjoint wave` runs the backward's two lattice walks with a wave per
+node and per triangle (opt['fem_adjoint']); the gradients are the same, bit for bit.
+
     python examples/train_pde_loss.py --epochs 3 --num_train 32 --batch_size 8
+    python examples/train_pde_loss.py --step captured --adjoint wave --mesh 11 --batch_size 1
     python examples/train_pde_loss.py --mesh 64 --band window --num_train 4 --batch_size 2   # beyond 26 x 26: the windowed route
 """
 import argparse
@@ -15,7 +21,24 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from g_adaptivity_amd import GNN, MeshDataset, collate, fem_poisson, hot_path_opt, l1_loss   # noqa: E402
+from g_adaptivity_amd import GNN, GraphedTrainStep, MeshDataset, collate, fem_poisson, hot_path_opt, l1_loss   # noqa: E402
+from g_adaptivity_amd.optim import FlatAdam   # noqa: E402
+
+
+def train_captured(model, batches, a, n):
+    """The same training as one replayed hipGraph per step: nothing waits for the device inside an epoch."""
+    step = GraphedTrainStep(model, FlatAdam(model.parameters(), lr=a.lr, capturable=True), loss_fn=l1_loss)
+    step(batches[0])                                         # the capture (its warm-up iterations are undone) and one step
+    for epoch in range(a.epochs):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        tot = torch.zeros((), device=batches[0].x_comp.device)
+        t0.record()
+        for dd in batches:
+            tot += step(dd)                                  # the static loss tensor: accumulated on the device
+        t1.record()
+        t1.synchronize()
+        print(f"mesh {n}x{n} epoch {epoch}: loss {tot.item() / len(batches):.5f} | ms/step {t0.elapsed_time(t1) / len(batches):.3f} "
+              f"(captured, adjoint {a.adjoint})", flush=True)
 
 
 def main():
@@ -29,16 +52,23 @@ def main():
                     help="FEM route (opt['fem_band']): 'lds' keeps the banded factor in LDS (meshes up to 26 x 26), 'window' streams "
                          "it through a workspace (up to 81 x 81)")
     ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--step', choices=['eager', 'captured'], default='eager',
+                    help="'eager': the host-driven loop with its per-phase split; 'captured': GraphedTrainStep with FlatAdam(capturable=True)")
+    ap.add_argument('--adjoint', choices=['lane', 'wave'], default='lane',
+                    help="the backward's lattice walks (opt['fem_adjoint']): a lane or a wave per node and per triangle, the same bits")
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     for n in ([a.mesh] if a.mesh else a.mesh_dims_train):
         opt = hot_path_opt(mesh_dims=[n, n], hidden_dim=8, num_layers=4, time_step=0.1, loss_type='pde_loss', loss_fn='l1',
-                           device=str(dev), fem_band=a.band)
+                           device=str(dev), fem_band=a.band, fem_adjoint=a.adjoint)
         ds = MeshDataset([n, n], a.num_train, seed=n, pde_loss_fields=True)
         torch.manual_seed(0)
         model = GNN(ds, opt).to(dev).train()
-        optim = torch.optim.Adam(model.parameters(), lr=a.lr)
         batches = [collate(ds.samples[i:i + a.batch_size]).to(dev) for i in range(0, len(ds), a.batch_size)]
+        if a.step == 'captured':
+            train_captured(model, batches, a, n)
+            continue
+        optim = torch.optim.Adam(model.parameters(), lr=a.lr)
         ev = lambda: torch.cuda.Event(enable_timing=True)
         for epoch in range(a.epochs):
             tot, t = 0.0, {'gnn_fwd': 0.0, 'fem_fwd': 0.0, 'fem_bwd': 0.0, 'gnn_bwd': 0.0, 'step': 0.0}
@@ -53,7 +83,8 @@ def main():
                 e[1].record()
                 xd = x_phys.detach().requires_grad_(True)
                 counts = torch.bincount(dd.batch.cpu()).tolist()
-                coeffs, sol = fem_poisson(xd, dd.cells, dd.boundary_nodes, counts, dd.pde_params, model.quad_points, band=a.band)
+                coeffs, sol = fem_poisson(xd, dd.cells, dd.boundary_nodes, counts, dd.pde_params, model.quad_points, band=a.band,
+                                          adjoint=a.adjoint)
                 loss = l1_loss(sol.view(-1, 1), dd.u_true_fine_tensor.view(-1, 1))
                 e[2].record()
                 loss.backward()

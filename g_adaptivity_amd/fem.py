@@ -24,6 +24,15 @@ length: `gadapt_fem_factor_lds_bytes(n_int, band)` ('lds') or `gadapt_fem_window
 the 64 KB budget.  The sides quoted here are those of `square_mesh`'s row-major numbering (band n - 2).  A band of 79 is the
 windowed maximum for any mesh; a reference-style numbering (`mesh.coordinates.cell_node_map()`) with a wider band than
 row-major may be refused at a smaller size.  The nodes are not reordered here.
+
+adjoint='wave' (`fem_poisson`, `modular_loss_2d`, `PdeBatch`; opt['fem_adjoint'] = 'wave' for `gnn_pde_tail` and
+`gradient_meshpoints_2D`) runs the backward's two lattice walks with a wave per node and a wave per triangle instead of a lane
+each (gadapt_fem_backward_wave, gadapt_fem_backward_window_wave): the same gradient, bit for bit.  The default stays 'lane'.
+
+`PdeBatch` is the tail of one batch topology with everything a call would rebuild kept on the device - the topology, the lattice
+axes, the Gaussians' buffers: `gnn_pde_tail` on a batch that carries one (`data._pde_batch`) only launches, so it can be
+captured in a hipGraph, and `set_params` feeds the Gaussians of the next batch into the same buffers
+(`training.GraphedTrainStep` does both for a pde_loss model).
 """
 from __future__ import annotations
 
@@ -37,11 +46,12 @@ from . import _native_fem as _nf
 from ._native import NativeError, current_stream
 from .graph import content_fingerprint
 
-__all__ = ['FemTopology', 'fem_poisson', 'torch_FEM_2D', 'boundary_from_cells', 'gnn_pde_tail', 'gradient_meshpoints_2D',
+__all__ = ['FemTopology', 'PdeBatch', 'fem_poisson', 'torch_FEM_2D', 'boundary_from_cells', 'gnn_pde_tail', 'gradient_meshpoints_2D',
            'modular_loss_2d', 'simpson_points_per_dim', 'GRAD_TYPES_2D']
 
 
 BAND_ROUTES = ('lds', 'window')
+ADJOINTS = ('lane', 'wave')
 # appended to the refusals of the resident-band route
 WINDOW_HINT = ("; the evaluation (poisson_eval_errors, evaluate_model_fine) takes larger meshes with band='window' "
                "(opt['fem_band'] = 'window')")
@@ -171,9 +181,18 @@ def _check_route(what: str, band, tri_slab) -> int:
     return tri_slab
 
 
+def _check_adjoint(what: str, adjoint) -> str:
+    """The form of the backward's lattice walks, before anything is launched."""
+    if adjoint not in ADJOINTS:
+        raise ValueError(f"{what}: adjoint must be one of {ADJOINTS} (got {adjoint!r})")
+    return adjoint
+
+
 # operation -> route -> symbol of include/gadapt_fem.h (tests/test_fem_window_grad_host.py pins the pairing)
 ENTRY_POINTS = {op: {'lds': f'gadapt_fem_{op}', 'window': f'gadapt_fem_{op}_window'}
                 for op in ('forward', 'modular_forward', 'backward', 'eval_errors')}
+ENTRY_POINTS['backward_wave'] = {'lds': 'gadapt_fem_backward_wave', 'window': 'gadapt_fem_backward_window_wave'}
+_BACKWARD_OP = {'lane': 'backward', 'wave': 'backward_wave'}
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -186,8 +205,8 @@ def _solve_tail(topo: FemTopology, rhs, coeffs, factor, tri_slab: int) -> tuple:
     return (rhs.data_ptr(), coeffs.data_ptr(), _ptr(factor)) + ((tri_slab,) if topo.route == 'window' else ())
 
 
-def pack_gaussians(pde_params: Sequence[dict], device) -> Tuple[torch.Tensor, torch.Tensor]:
-    """gptr [B+1] int32 and gpar [G,4] fp32 = (c0, c1, s0, s1): per mesh its own number of Gaussians."""
+def _gaussian_rows(pde_params: Sequence[dict]) -> Tuple[np.ndarray, np.ndarray]:
+    """(cumulative counts [B+1] int32, rows [G,4] fp32 = (c0, c1, s0, s1)) on the host: per mesh its own number of Gaussians."""
     counts, rows = [0], []
     for p in pde_params:
         cs, ss = p['centers'], p['scales']
@@ -195,9 +214,13 @@ def pack_gaussians(pde_params: Sequence[dict], device) -> Tuple[torch.Tensor, to
             c, s = np.asarray(c, np.float32).reshape(-1), np.asarray(s, np.float32).reshape(-1)
             rows.append([c[0], c[1], s[0], s[1]])
         counts.append(len(cs))
-    gptr = torch.tensor(np.cumsum(counts), dtype=torch.int32, device=device)
-    gpar = torch.tensor(np.asarray(rows, np.float32).reshape(-1, 4), device=device)
-    return gptr, gpar
+    return np.cumsum(counts).astype(np.int32), np.asarray(rows, np.float32).reshape(-1, 4)
+
+
+def pack_gaussians(pde_params: Sequence[dict], device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """gptr [B+1] int32 and gpar [G,4] fp32 = (c0, c1, s0, s1): per mesh its own number of Gaussians."""
+    ptr, rows = _gaussian_rows(pde_params)
+    return torch.tensor(ptr, dtype=torch.int32, device=device), torch.tensor(rows, device=device)
 
 
 def lattice_axes(quad_points, device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -222,7 +245,7 @@ def lattice_axes(quad_points, device) -> Tuple[torch.Tensor, torch.Tensor]:
 
 class _FemPoisson(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, topo: FemTopology, gptr, gpar, lat_x, lat_y, tri_slab=0):
+    def forward(ctx, x, topo: FemTopology, gptr, gpar, lat_x, lat_y, tri_slab=0, adjoint='lane'):
         _require_gpu(x, 'FEM node coordinates')
         x = x.contiguous()
         dev, nlat = x.device, int(lat_x.numel())
@@ -231,7 +254,7 @@ class _FemPoisson(torch.autograd.Function):
         lfac = topo.factor_buffer(dev)                               # kept for the adjoint solve
         _nf.call(ENTRY_POINTS['forward'][topo.route], *topo.head(gptr, gpar, x, lat_x, lat_y, nlat),
                  *_solve_tail(topo, rhs, coeffs, lfac, tri_slab), sol.data_ptr(), current_stream(dev))
-        ctx.topo, ctx.nlat = topo, nlat
+        ctx.topo, ctx.nlat, ctx.adjoint = topo, nlat, adjoint
         ctx.save_for_backward(x, coeffs, lfac, gptr, gpar, lat_x, lat_y)
         return coeffs, sol
 
@@ -241,14 +264,15 @@ class _FemPoisson(torch.autograd.Function):
         topo, dev = ctx.topo, x.device
         g_coeffs = None if g_coeffs is None else g_coeffs.contiguous().float()
         g_sol = None if g_sol is None else g_sol.contiguous().float()
-        return _backward(topo, gptr, gpar, x, lat_x, lat_y, ctx.nlat, coeffs, lfac, g_coeffs, g_sol, current_stream(dev)), \
-            None, None, None, None, None, None
+        return _backward(topo, gptr, gpar, x, lat_x, lat_y, ctx.nlat, coeffs, lfac, g_coeffs, g_sol, current_stream(dev), ctx.adjoint), \
+            None, None, None, None, None, None, None
 
 
-def _backward(topo: FemTopology, gptr, gpar, x, lat_x, lat_y, nlat: int, coeffs, factor, g_coeffs, g_sol, stream) -> torch.Tensor:
-    """gadapt_fem_backward[_window] on the kept factor: d / d x [N,2] of what g_coeffs and g_sol (None: nothing) seed."""
+def _backward(topo: FemTopology, gptr, gpar, x, lat_x, lat_y, nlat: int, coeffs, factor, g_coeffs, g_sol, stream,
+              adjoint: str = 'lane') -> torch.Tensor:
+    """gadapt_fem_backward[_window][_wave] on the kept factor: d / d x [N,2] of what g_coeffs and g_sol (None: nothing) seed."""
     gc, mu, tgrad, gx = topo.backward_buffers(x.device)
-    _nf.call(ENTRY_POINTS['backward'][topo.route], *topo.head(gptr, gpar, x, lat_x, lat_y, nlat, tri_mesh=True, max_tris=False),
+    _nf.call(ENTRY_POINTS[_BACKWARD_OP[adjoint]][topo.route], *topo.head(gptr, gpar, x, lat_x, lat_y, nlat, tri_mesh=True, max_tris=False),
              coeffs.data_ptr(), factor.data_ptr(), _ptr(g_coeffs), _ptr(g_sol), gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(),
              gx.data_ptr(), stream)
     return gx
@@ -263,7 +287,7 @@ def _tri_counts(cells: torch.Tensor, node_counts: Sequence[int]) -> List[int]:
 
 def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
                 pde_params: Sequence[dict], quad_points, tri_counts: Optional[Sequence[int]] = None, band: str = 'lds',
-                tri_slab: int = 0):
+                tri_slab: int = 0, adjoint: str = 'lane'):
     """Batched P1 Poisson solve on the meshes of `x_phys` [N,2] (differentiable wrt x_phys).
 
     cells [T,3] global node ids, mesh by mesh; boundary [N] bool; node_counts per mesh; pde_params per mesh
@@ -275,8 +299,12 @@ def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
     vector; square meshes up to 81 x 81 nodes) with its workspace kept for an fp64 adjoint solve in the backward, and the
     lattice evaluated over slabs of `tri_slab` triangle ids (a multiple of 32; 0: the largest slab the LDS budget leaves).
     Where both routes take a mesh their results agree to the rounding of an fp32 solve, not bitwise; the windowed result
-    does not depend on `tri_slab`, bit for bit."""
+    does not depend on `tri_slab`, bit for bit.
+
+    adjoint: 'lane' walks the lattice in the backward with a lane per node and per triangle; 'wave' with a wave each
+    (gadapt_fem_backward[_window]_wave).  The gradient is the same, bit for bit."""
     tri_slab = _check_route('pde_loss FEM tail', band, tri_slab)
+    _check_adjoint('pde_loss FEM tail', adjoint)
     _require_gpu(x_phys, 'pde_loss FEM tail')
     if x_phys.dim() != 2 or x_phys.shape[1] != 2:
         raise NotImplementedError(f"pde_loss FEM tail: 2-D meshes only (x_phys {tuple(x_phys.shape)})")
@@ -286,7 +314,7 @@ def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
     topo = _topology(cells, boundary, node_counts, tri_counts, dev, band)
     gptr, gpar = pack_gaussians(pde_params, dev)
     lx, ly = lattice_axes(quad_points, dev)
-    coeffs, sol = _FemPoisson.apply(x_phys, topo, gptr, gpar, lx, ly, tri_slab)
+    coeffs, sol = _FemPoisson.apply(x_phys, topo, gptr, gpar, lx, ly, tri_slab, adjoint)
     return coeffs.unsqueeze(1), sol
 
 
@@ -308,29 +336,28 @@ def torch_FEM_2D(opt, mesh, mesh_points, quad_points, num_meshpoints, c_list, s_
     return coeffs, mesh_points, sol.view(shape)
 
 
-def gnn_pde_tail(model, data, x_phys: torch.Tensor):
-    """`GNN.forward`'s pde_loss branch (`src/GNN.py:307-342`) for a batch: (coeffs [N,1], x_phys, sol [B*Q]).
-    opt['fem_band'] = 'window' takes meshes beyond 26 x 26 nodes, up to 81 x 81 (`fem_poisson`)."""
-    o = model.opt
-    band = o.get('fem_band', 'lds')
-    _check_route("loss_type='pde_loss'", band, 0)
-    if model.dim != 2:
-        raise NotImplementedError("loss_type='pde_loss' is built for 2-D Poisson only; the 1-D tail (torch_FEM_1D) is out of scope")
-    if o.get('pde_type', 'Poisson') != 'Poisson':
-        raise NotImplementedError(f"loss_type='pde_loss' is built for 2-D Poisson only (pde_type={o.get('pde_type')!r})")
+def _batch_counts(data, x_phys: torch.Tensor) -> Tuple[int, List[int]]:
+    """(meshes, nodes per mesh) of a batch as `GNN.forward` is given it; reads `data.batch` back from the device."""
     batch = data.batch
     B = int(data.num_graphs) if hasattr(data, 'num_graphs') else int(batch.max()) + 1
     if batch is None:
-        node_counts = [x_phys.shape[0]]
-    else:
-        node_counts = torch.bincount(batch.detach().cpu(), minlength=B).tolist()
-    if o.get('data_type') == 'randg_mix' and hasattr(data, 'batch_dict'):
-        params = [data.batch_dict[i]['pde_params'] for i in range(B)]
-    else:
-        params = data.pde_params if isinstance(data.pde_params, (list, tuple)) else [data.pde_params]
+        return B, [x_phys.shape[0]]
+    return B, torch.bincount(batch.detach().cpu(), minlength=B).tolist()
+
+
+def batch_params(opt, data, B: int) -> list:
+    """The Gaussians of a batch, one dict per mesh: `data.batch_dict[i]['pde_params']` for randg_mix, else `data.pde_params`."""
+    if opt.get('data_type') == 'randg_mix' and hasattr(data, 'batch_dict'):
+        return [data.batch_dict[i]['pde_params'] for i in range(B)]
+    return data.pde_params if isinstance(data.pde_params, (list, tuple)) else [data.pde_params]
+
+
+def _batch_cells(model, data, node_counts: Sequence[int], B: int):
+    """(cells, boundary, tri_counts or None) of a batch: `data.cells` / `data.boundary_nodes`, else the per-mesh topology
+    objects (the reference's mesh / data.mesh[i]) and the edges that belong to one triangle."""
     cells = getattr(data, 'cells', None)
     tri_counts = None
-    if cells is None:                                    # per-mesh topology objects (the reference's mesh / data.mesh[i])
+    if cells is None:
         meshes = data.mesh if isinstance(getattr(data, 'mesh', None), (list, tuple)) else [model.dataset.mesh] * B
         parts, off = [], 0
         for m, n in zip(meshes, node_counts):
@@ -340,8 +367,116 @@ def gnn_pde_tail(model, data, x_phys: torch.Tensor):
     boundary = getattr(data, 'boundary_nodes', None)
     if boundary is None:
         boundary = torch.from_numpy(boundary_from_cells(cells.cpu().numpy(), sum(node_counts)))
-    coeffs, sol = fem_poisson(x_phys, cells, boundary, node_counts, params, model.quad_points, tri_counts=tri_counts, band=band)
+    return cells, boundary, tri_counts
+
+
+def _check_tail(model):
+    """(band, adjoint) of a model's pde_loss tail; refuses what it is not built for before anything is launched."""
+    o = model.opt
+    band, adjoint = o.get('fem_band', 'lds'), o.get('fem_adjoint', 'lane')
+    _check_route("loss_type='pde_loss'", band, 0)
+    _check_adjoint("loss_type='pde_loss' (opt['fem_adjoint'])", adjoint)
+    if model.dim != 2:
+        raise NotImplementedError("loss_type='pde_loss' is built for 2-D Poisson only; the 1-D tail (torch_FEM_1D) is out of scope")
+    if o.get('pde_type', 'Poisson') != 'Poisson':
+        raise NotImplementedError(f"loss_type='pde_loss' is built for 2-D Poisson only (pde_type={o.get('pde_type')!r})")
+    return band, adjoint
+
+
+def gnn_pde_tail(model, data, x_phys: torch.Tensor):
+    """`GNN.forward`'s pde_loss branch (`src/GNN.py:307-342`) for a batch: (coeffs [N,1], x_phys, sol [B*Q]).
+    opt['fem_band'] = 'window' takes meshes beyond 26 x 26 nodes, up to 81 x 81 (`fem_poisson`); opt['fem_adjoint'] = 'wave'
+    the wave-parallel backward.  A batch that carries a `PdeBatch` (`data._pde_batch`) is solved through it: the launches
+    alone, nothing read back from the device or sent to it (its route and Gaussians are the descriptor's)."""
+    band, adjoint = _check_tail(model)
+    pb = getattr(data, '_pde_batch', None)
+    if pb is not None:
+        coeffs, sol = pb.solve(x_phys)
+        return coeffs, x_phys, sol
+    B, node_counts = _batch_counts(data, x_phys)
+    params = batch_params(model.opt, data, B)
+    cells, boundary, tri_counts = _batch_cells(model, data, node_counts, B)
+    coeffs, sol = fem_poisson(x_phys, cells, boundary, node_counts, params, model.quad_points, tri_counts=tri_counts, band=band,
+                              adjoint=adjoint)
     return coeffs, x_phys, sol
+
+
+class PdeBatch:
+    """The pde_loss tail of ONE batch topology, ready to launch: the `FemTopology`, the lattice axes, the node and triangle
+    counts, and the Gaussians' device buffers `gptr` [B+1] int32 and `gpar` [cap,4] fp32 with a pinned host copy to stage
+    them in.  `solve` is `fem_poisson` without its per-call host work (no topology fingerprint, no tensors built from
+    Python lists, nothing read back): it can be stream-captured.  `set_params` feeds another batch's Gaussians into the
+    SAME device buffers, which is how a captured step sees them.
+
+        pb = PdeBatch.from_data(model, data)      # may synchronise, once
+        data._pde_batch = pb                      # `gnn_pde_tail` (GNN.forward) now solves through it
+        pb.set_params(next_batch.pde_params)
+    """
+
+    def __init__(self, topo: FemTopology, lat_x: torch.Tensor, lat_y: torch.Tensor, cap: int, adjoint: str = 'lane', tri_slab: int = 0):
+        _check_adjoint('PdeBatch', adjoint)
+        self.tri_slab = _check_route('PdeBatch', topo.route, tri_slab)
+        if int(cap) < 1:
+            raise ValueError(f"PdeBatch: room for {cap} Gaussians")
+        self.topo, self.lat_x, self.lat_y, self.adjoint = topo, lat_x, lat_y, adjoint
+        self.n_meshes, self.n_nodes, self.n_tris, self.cap = int(topo.n_meshes), int(topo.n_nodes), int(topo.n_tris), int(cap)
+        dev = lat_x.device
+        self.gptr = torch.zeros(self.n_meshes + 1, dtype=torch.int32, device=dev)
+        self.gpar = torch.zeros(self.cap, 4, dtype=torch.float32, device=dev)
+        pin = dev.type == 'cuda'
+        self.host_gptr = torch.zeros(self.n_meshes + 1, dtype=torch.int32, pin_memory=pin)
+        self.host_gpar = torch.zeros(self.cap, 4, dtype=torch.float32, pin_memory=pin)
+        self._staged = torch.cuda.Event() if pin else None       # recorded behind the copies out of the staging buffers
+
+    @classmethod
+    def from_data(cls, model, data, max_gauss: int = 8, adjoint: Optional[str] = None) -> 'PdeBatch':
+        """The descriptor of `data`'s topology for `model`'s tail (opt['fem_band'], and opt['fem_adjoint'] unless `adjoint`
+        is given), with room for `max_gauss` Gaussians per mesh; the batch's own Gaussians are set if it carries any."""
+        band, opt_adjoint = _check_tail(model)
+        dev = torch.device(model.opt['device'])
+        n = int(data.x_comp.shape[0])
+        B, node_counts = _batch_counts(data, data.x_comp)
+        cells, boundary, tri_counts = _batch_cells(model, data, node_counts, B)
+        if tri_counts is None:
+            tri_counts = _tri_counts(cells, node_counts)
+        topo = _topology(cells, boundary, node_counts, tri_counts, dev, band)
+        lx, ly = lattice_axes(model.quad_points, dev)
+        pb = cls(topo, lx, ly, B * int(max_gauss), adjoint if adjoint is not None else opt_adjoint)
+        if n != pb.n_nodes:
+            raise ValueError(f"PdeBatch: {n} nodes in the batch, {pb.n_nodes} in its topology")
+        try:
+            params = batch_params(model.opt, data, B)
+        except (AttributeError, KeyError):
+            params = None
+        if params is not None:
+            pb.set_params(params)
+        return pb
+
+    def set_params(self, pde_params: Sequence[dict]):
+        """The Gaussians of the next solve, `pack_gaussians`' layout and order: packed into the pinned buffers, then one
+        non-blocking copy each into `gptr` and `gpar` on the current stream (rows past the last Gaussian keep what they
+        held; nothing reads them)."""
+        if len(pde_params) != self.n_meshes:
+            raise ValueError(f"PdeBatch: Gaussians of {len(pde_params)} meshes for a batch of {self.n_meshes}")
+        ptr, rows = _gaussian_rows(pde_params)
+        if rows.shape[0] > self.cap:
+            raise ValueError(f"PdeBatch: {rows.shape[0]} Gaussians in the batch, room for {self.cap} (from_data's max_gauss per mesh)")
+        if self._staged is not None:
+            self._staged.synchronize()                           # the previous copies have left the staging buffers
+        self.host_gptr.copy_(torch.from_numpy(ptr))
+        self.host_gpar[:rows.shape[0]].copy_(torch.from_numpy(rows))
+        self.gptr.copy_(self.host_gptr, non_blocking=True)
+        self.gpar.copy_(self.host_gpar, non_blocking=True)
+        if self._staged is not None:
+            self._staged.record()
+
+    def solve(self, x_phys: torch.Tensor):
+        """(coeffs [N,1], sol [B*Q]) of `fem_poisson` on this topology and the Gaussians last set: the same entry points on
+        the same inputs, the same bits."""
+        if x_phys.dim() != 2 or x_phys.shape[1] != 2 or x_phys.shape[0] != self.n_nodes:
+            raise ValueError(f"PdeBatch: x_phys {tuple(x_phys.shape)} for a topology of {self.n_nodes} nodes in 2-D")
+        coeffs, sol = _FemPoisson.apply(x_phys, self.topo, self.gptr, self.gpar, self.lat_x, self.lat_y, self.tri_slab, self.adjoint)
+        return coeffs.unsqueeze(1), sol
 
 
 # ------------------------------------------------------------------------------------------------ the 2-D modular loss
@@ -361,7 +496,7 @@ def simpson_points_per_dim(N: int, dim: int = 2) -> int:
 def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
                     pde_params: Sequence[dict], n_lat: int, reduction: str, n_load: Optional[int] = None,
                     tri_counts: Optional[Sequence[int]] = None, band: str = 'lds',
-                    tri_slab: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+                    tri_slab: int = 0, adjoint: str = 'lane') -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-mesh 2-D modular loss and its gradient: (loss [B], x_grads [N,2]), x_grads on a node being the gradient of its
     own mesh's loss wrt all of that mesh's node coordinates.
 
@@ -369,8 +504,10 @@ def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.T
     and e = sol - u_true there: reduction 'mse' is mean e^2 (F.mse_loss), 'simpson' torchquad's composite Simpson rule of
     e^2 over [0,1]^2 (n_lat odd).  n_load: Simpson points per dimension of the load vector; only the compiled
     `gadapt_fem_simpson_points()` is built.  Five launches forward and backward, no autograd graph, no host wait.
-    band, tri_slab: as `fem_poisson` ('window': square meshes up to 81 x 81 nodes)."""
+    band, tri_slab, adjoint: as `fem_poisson` ('window': square meshes up to 81 x 81 nodes; 'wave': the wave-parallel lattice
+    walks of the backward, the same bits)."""
     tri_slab = _check_route('modular loss (2-D)', band, tri_slab)
+    _check_adjoint('modular loss (2-D)', adjoint)
     _require_gpu(x_phys, 'modular loss (2-D)')
     if x_phys.dim() != 2 or x_phys.shape[1] != 2:
         raise NotImplementedError(f"modular loss (2-D): x_phys must be [N,2] (got {tuple(x_phys.shape)})")
@@ -397,7 +534,7 @@ def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.T
     stream = current_stream(dev)
     _nf.call(ENTRY_POINTS['modular_forward'][topo.route], *topo.head(gptr, gpar, x, lat, lat, n_lat), _REDUCTIONS[reduction],
              *_solve_tail(topo, rhs, coeffs, lfac, tri_slab), sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(), stream)
-    return loss, _backward(topo, gptr, gpar, x, lat, lat, n_lat, coeffs, lfac, None, g_sol, stream)
+    return loss, _backward(topo, gptr, gpar, x, lat, lat, n_lat, coeffs, lfac, None, g_sol, stream, adjoint)
 
 
 def _modular_quadrature(opt, gt: str) -> Tuple[int, int, str]:
@@ -461,7 +598,8 @@ def gradient_meshpoints_2D(opt, data, x_phys):
     built for `gadapt_fem_simpson_points()` only (NotImplementedError otherwise), the loss lattice takes any count.
     Topology: data.cells (as collate offsets them), else data.mesh / data.mesh[i], else square_mesh(mesh_dims[0]).
     Limits as the pde_loss tail: 2-D Poisson, square meshes up to 26 x 26 nodes (the LDS budget of the banded factor), or
-    up to 81 x 81 with opt['fem_band'] = 'window' (`modular_loss_2d(band='window')`).
+    up to 81 x 81 with opt['fem_band'] = 'window' (`modular_loss_2d(band='window')`).  opt['fem_adjoint'] = 'wave': the
+    wave-parallel backward (`modular_loss_2d(adjoint='wave')`), the same bits.
     The reference's build_mass_matrix is called with three of its four arguments there (a TypeError as shipped); this
     builds the evident intent, the stiffness of torch_FEM_2D."""
     if 'grad_type' not in opt:
@@ -474,9 +612,10 @@ def gradient_meshpoints_2D(opt, data, x_phys):
                                   "1-D meshes take gradient_meshpoints_1D")
     band = opt.get('fem_band', 'lds')
     _check_route('gradient_meshpoints_2D', band, 0)
+    adjoint = _check_adjoint("gradient_meshpoints_2D (opt['fem_adjoint'])", opt.get('fem_adjoint', 'lane'))
     _require_gpu(x_phys.detach().float(), 'gradient_meshpoints_2D')
     n_load, n_lat, reduction = _modular_quadrature(opt, gt)
     cells, boundary, node_counts, tri_counts, params = _modular_batch(opt, data, x_phys.shape[0])
     loss, x_grads = modular_loss_2d(x_phys.detach().float(), cells, boundary, node_counts, params, n_lat, reduction,
-                                    n_load=n_load, tri_counts=tri_counts, band=band)
+                                    n_load=n_load, tri_counts=tri_counts, band=band, adjoint=adjoint)
     return loss.mean(), x_grads

@@ -25,7 +25,7 @@ struct FemBatch {
     const float *gpar, *x, *lat_x, *lat_y;
     int nlat, max_lds_bytes, max_tris;
 };
-// from the arguments of an entry point, which carry these names in all nine; tri_mesh and max_tris where it has them, else 0
+// from the arguments of an entry point, which carry these names in every one; tri_mesh and max_tris where it has them, else 0
 #define FEM_BATCH(tri_mesh_, max_tris_) \
     FemBatch { B, N, T, meta, cells, node_mesh, tri_mesh_, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, lat_x, lat_y, nlat, max_lds_bytes, max_tris_ }
 
@@ -39,9 +39,10 @@ struct FemPlan { int64_t solve_lds, eval_lds; int slab; };
 // load vector, solve, evaluation to sol, lattice loss and its derivative
 int fem_launch_modular_forward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, int reduction, float* sol, float* loss,
                                float* g_sol, hipStream_t s);
-// d L / d c, adjoint solve on the kept factor, per-triangle chain rule, per-node gather
+// d L / d c, adjoint solve on the kept factor, per-triangle chain rule, per-node gather; wave: the first and the third as a wave
+// per node and per triangle (fem_wave_grad_kernels.hip), with the lane kernels' bits
 int fem_launch_backward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, const float* g_coeffs, const float* g_sol,
-                        const FemAdjoint& a, hipStream_t s);
+                        const FemAdjoint& a, hipStream_t s, bool wave = false);
 
 // ---------------------------------------------------------------------------------------------------- 1-D
 // What the 1-D entry points receive under the same names; an entry point without Gaussians or quadrature leaves those 0.

@@ -599,9 +599,10 @@ __global__ void __launch_bounds__(256) fem_gather_kernel(int n_nodes, const int3
 
 // The route for meshes beyond the resident band (band='window') is compiled in this translation unit: its solve and slabbed
 // evaluation with their launch plan, then its adjoint solve.  Both call this file's device helpers; the entry points of
-// both routes follow below.
+// both routes follow below.  The wave-parallel form of the backward's two lattice walks (fem_adjoint='wave') comes last.
 #include "fem_window_kernels.hip"
 #include "fem_window_grad_kernels.hip"
+#include "fem_wave_grad_kernels.hip"
 
 // ---------------------------------------------------------------------------------------------------- checks
 // Every entry point: fill a FemBatch from the arguments, check (check_batch, make_plan and what only it checks, in the
@@ -704,16 +705,24 @@ int fem_launch_modular_forward(Band band, const FemBatch& b, const FemPlan& P, c
 }
 
 int fem_launch_backward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, const float* g_coeffs, const float* g_sol,
-                        const FemAdjoint& a, hipStream_t s) {
+                        const FemAdjoint& a, hipStream_t s, bool wave) {
     const int nb = (b.N + 255) / 256;
-    FEM_LAUNCH(fem_gc_kernel, nb, 256, 0, b.N, b.cells, b.node_mesh, b.nt_ptr, b.nt_idx, b.x, b.lat_x, b.lat_y, b.nlat, g_coeffs, g_sol, a.gc);
+    if (wave)                                                      // a wave per node (fem_wave_grad_kernels.hip): the same bits
+        FEM_LAUNCH(fem_gc_wave_kernel, b.N, FEM_WAVE, 0, b.N, b.cells, b.node_mesh, b.nt_ptr, b.nt_idx, b.x, b.lat_x, b.lat_y, b.nlat, g_coeffs,
+                   g_sol, a.gc);
+    else
+        FEM_LAUNCH(fem_gc_kernel, nb, 256, 0, b.N, b.cells, b.node_mesh, b.nt_ptr, b.nt_idx, b.x, b.lat_x, b.lat_y, b.nlat, g_coeffs, g_sol, a.gc);
     if (band == Band::window)
         FEM_LAUNCH(fem_window_adjoint_kernel, b.B, FEM_WIN_THREADS, (size_t)P.solve_lds, b.meta, b.int_idx, b.int_node, a.gc, a.mu,
                    reinterpret_cast<double*>(sc.factor), (int)P.solve_lds);
     else
         FEM_LAUNCH(fem_adjoint_kernel, b.B, FEM_SOLVE_THREADS, (size_t)P.solve_lds, b.meta, b.int_idx, b.int_node, sc.factor, a.gc, a.mu);
-    FEM_LAUNCH(fem_tri_bwd_kernel, (b.T + 255) / 256, 256, 0, b.T, b.cells, b.tri_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x,
-               b.lat_x, b.lat_y, b.nlat, sc.coeffs, a.mu, g_sol, a.tgrad);
+    if (wave)                                                      // a wave per triangle
+        FEM_LAUNCH(fem_tri_bwd_wave_kernel, b.T, FEM_WAVE, 0, b.T, b.cells, b.tri_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x,
+                   b.lat_x, b.lat_y, b.nlat, sc.coeffs, a.mu, g_sol, a.tgrad);
+    else
+        FEM_LAUNCH(fem_tri_bwd_kernel, (b.T + 255) / 256, 256, 0, b.T, b.cells, b.tri_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x,
+                   b.lat_x, b.lat_y, b.nlat, sc.coeffs, a.mu, g_sol, a.tgrad);
     FEM_LAUNCH(fem_gather_kernel, nb, 256, 0, b.N, b.nt_ptr, b.nt_idx, a.tgrad, a.gx);
     return GADAPT_FEM_OK;
 }
@@ -759,14 +768,15 @@ static int eval_errors(Band band, const char* who, const FemBatch& b, const FemS
     return launch_eval_errors(band, b, P, sc.coeffs, partials, err, s);
 }
 
-// sc.coeffs and, on Band::lds, sc.factor are only read; g_coeffs and g_sol may be NULL (no gradient flows in through them)
+// sc.coeffs and, on Band::lds, sc.factor are only read; g_coeffs and g_sol may be NULL (no gradient flows in through them).
+// wave: the *_wave entry points, the same checks and the wave-parallel lattice walks.
 static int backward(Band band, const char* who, const FemBatch& b, const FemScratch& sc, const float* g_coeffs, const float* g_sol,
-                    const FemAdjoint& a, hipStream_t s) {
+                    const FemAdjoint& a, hipStream_t s, bool wave = false) {
     FemPlan P;
     int rc = check_batch(who, b, NEED_TRI_MESH | (band == Band::window ? NEED_WORK : 0), {sc.coeffs, sc.factor, a.gc, a.mu, a.tgrad, a.gx},
                          sc.factor);
     if (rc || (rc = make_plan(band, who, b, 0, false, &P))) return rc;
-    return fem_launch_backward(band, b, P, sc, g_coeffs, g_sol, a, s);
+    return fem_launch_backward(band, b, P, sc, g_coeffs, g_sol, a, s, wave);
 }
 
 // The entry points fill the batch and the scratch from their positional arguments and do nothing else with them.
@@ -838,4 +848,24 @@ extern "C" int gadapt_fem_backward_window(int B, int N, int T, const int32_t* me
                                           void* stream) {
     return backward(Band::window, "gadapt_fem_backward_window", FEM_BATCH(tri_mesh, 0), {nullptr, const_cast<float*>(coeffs), work}, g_coeffs, g_sol,
                     {gc, mu, tgrad, gx}, (hipStream_t)stream);
+}
+
+extern "C" int gadapt_fem_backward_wave(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                        const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                                        const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
+                                        const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs, const float* lfac,
+                                        const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad, float* gx,
+                                        void* stream) {
+    return backward(Band::lds, "gadapt_fem_backward_wave", FEM_BATCH(tri_mesh, 0), {nullptr, const_cast<float*>(coeffs), const_cast<float*>(lfac)},
+                    g_coeffs, g_sol, {gc, mu, tgrad, gx}, (hipStream_t)stream, true);
+}
+
+extern "C" int gadapt_fem_backward_window_wave(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                               const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node,
+                                               const int32_t* nt_ptr, const int32_t* nt_idx, const int32_t* gptr, const float* gpar,
+                                               const float* x, const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes,
+                                               const float* coeffs, float* work, const float* g_coeffs, const float* g_sol, float* gc,
+                                               float* mu, float* tgrad, float* gx, void* stream) {
+    return backward(Band::window, "gadapt_fem_backward_window_wave", FEM_BATCH(tri_mesh, 0), {nullptr, const_cast<float*>(coeffs), work}, g_coeffs,
+                    g_sol, {gc, mu, tgrad, gx}, (hipStream_t)stream, true);
 }

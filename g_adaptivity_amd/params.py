@@ -41,6 +41,9 @@ def hot_path_opt(**overrides) -> dict:
         # tails (pde_loss, the 2-D modular loss, torch_FEM_2D).  'lds': the banded factor resident in LDS, 2-D meshes up to
         # 26 x 26; 'window': the windowed band solve, up to 81 x 81
         'fem_band': 'lds',
+        # not a reference key: the form of the two lattice walks in the backward of those tails.  'lane': a lane per node and per
+        # triangle; 'wave': a wave each (gadapt_fem_backward_wave), the same gradient bit for bit
+        'fem_adjoint': 'lane',
         # not a reference key: the route of the MMPDE5 target meshes that the examples build (`target_params={'solver':
         # {'route': ...}}` of the datasets).  'lane': one node per lane, 2-D meshes up to 32 x 32; 'strided': up to 81 x 81
         'mmpde5_route': 'lane',

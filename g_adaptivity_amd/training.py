@@ -12,6 +12,11 @@ The topology (edge list, masks, node count) is fixed per captured graph: a batch
 of an epoch - gets its own capture, keyed like the model's CSR cache (`graph.content_fingerprint`, memoised per tensor object, so
 loaders that share the topology tensors between batches pay a dictionary lookup).  `inference.GraphedForward` is the evaluation
 counterpart.
+
+loss_type='pde_loss' (2-D) is captured in the same way: the iteration is `coeffs, x_phys, sol = model(data); loss = loss_fn(
+sol.view(-1, 1), target.view(-1, 1))` (`src/run_GNN.py:108-110`, target `u_true_fine_tensor`), the static batch carries a
+`fem.PdeBatch` so that the FEM tail only launches, and besides the node fields and the target every call feeds the new batch's
+Gaussians into that descriptor's device buffers (`PdeBatch.set_params`) ahead of the replay.
 """
 from __future__ import annotations
 
@@ -268,12 +273,24 @@ class GraphedTrainStep:
     Under data parallelism every rank must call the step once per iteration (as with any all-reduce); WHEN a rank captures is its
     own business - a capture's warm-up issues no collective.  Hyper-parameters of the captured Adam launch (lr, betas, eps,
     weight_decay) are kernel arguments: a change of `optimizer.param_groups[0]` drops the captures and the next call re-captures.
+
+    A loss_type='pde_loss' model (2-D): `target_field` defaults to `u_true_fine_tensor` and `loss_fn` is given (sol [B*Q,1],
+    target [B*Q,1]).  Every batch must carry its Gaussians (`data.pde_params`, or `data.batch_dict[i]['pde_params']` for randg_mix),
+    at most `max_gauss` per mesh on average (the capacity of the captured buffers is fixed: meshes * max_gauss rows); the topology key
+    also covers `cells` and `boundary_nodes`.  Such a step is always the captured autograd iteration (`fused_reason` says so).
     """
 
-    def __init__(self, model, optimizer: FlatAdam, loss_fn: Callable = mse_loss, target_field: str = 'x_phys', warmup: int = 2,
-                 capture_optimizer: bool = True, max_graphs: int = 4, fused: bool = True, replay: str = 'auto'):
+    def __init__(self, model, optimizer: FlatAdam, loss_fn: Callable = mse_loss, target_field: Optional[str] = None, warmup: int = 2,
+                 capture_optimizer: bool = True, max_graphs: int = 4, fused: bool = True, replay: str = 'auto', max_gauss: int = 8):
         if replay not in ('auto', 'graph', 'eager'):
             raise ValueError("replay: 'auto', 'graph' or 'eager'")
+        self.pde = model.opt['loss_type'] == 'pde_loss'
+        if self.pde and model.dim != 2:
+            raise NotImplementedError("GraphedTrainStep: loss_type='pde_loss' is captured for 2-D Poisson models only; the 1-D tail "
+                                      "(torch_FEM_1D) is not built")
+        if target_field is None:                             # src/run_GNN.py:106 and :109
+            target_field = 'u_true_fine_tensor' if self.pde else 'x_phys'
+        self.max_gauss = int(max_gauss)
         if not isinstance(optimizer, FlatAdam) or not optimizer.capturable:
             raise TypeError("GraphedTrainStep needs FlatAdam(capturable=True): the step count must live on the device")
         if not model.training:
@@ -311,7 +328,10 @@ class GraphedTrainStep:
     def _iteration(self, data):
         self.optimizer.zero_grad()
         out = self.model(data)
-        loss = self.loss_fn(out, getattr(data, self.target_field))
+        if self.pde:                                         # (coeffs, x_phys, sol): the loss is on the lattice (src/run_GNN.py:108-110)
+            loss = self.loss_fn(out[2].view(-1, 1), getattr(data, self.target_field).view(-1, 1))
+        else:
+            loss = self.loss_fn(out, getattr(data, self.target_field))
         if self._root is not None:
             loss.backward(gradient=self._root)
         else:
@@ -361,7 +381,8 @@ class GraphedTrainStep:
                 o.step_count = state[3]
 
     def _key(self, data) -> Tuple:
-        tensors = [getattr(data, k) for k in TOPOLOGY_FIELDS if getattr(data, k, None) is not None]
+        fields = TOPOLOGY_FIELDS + (('cells', 'boundary_nodes') if self.pde else ())     # the FEM tail's topology too
+        tensors = [getattr(data, k) for k in fields if getattr(data, k, None) is not None]
         corners = getattr(data, 'corner_nodes', None)
         n_corner = 0 if corners is None else sum(len(c) for c in corners) if isinstance(corners, (list, tuple)) else len(corners)
         return (int(data.x_comp.shape[0]), n_corner, _graph_mod.content_fingerprint(tensors))
@@ -374,6 +395,11 @@ class GraphedTrainStep:
         # synchronisation - inside the capture (1-D models with global features have no corner list to count instead)
         if getattr(c.static, '_num_graphs', None) is None and getattr(data, 'batch', None) is not None:
             c.static._num_graphs = int(data.num_graphs)      # (one synchronisation, here, outside the capture)
+        if self.pde:
+            # ... and the FEM tail's descriptor: with it `gnn_pde_tail` only launches (no bincount, no topology fingerprint, no
+            # Gaussians packed from Python lists); the static batch's own Gaussians are in its buffers for the warm-up
+            from .fem import PdeBatch
+            c.static._pde_batch = PdeBatch.from_data(self.model, c.static, self.max_gauss)
         cur = torch.cuda.current_stream(dev)
         self._side.wait_stream(cur)
         with torch.cuda.stream(self._side):
@@ -510,8 +536,26 @@ class GraphedTrainStep:
         self._captured[key] = c                                      # (re-)inserted last = most recently used
         return c
 
+    def _pde_params(self, data) -> list:
+        """The Gaussians of a pde_loss batch, refused before anything is captured if there are none or too many."""
+        from .fem import batch_params
+        try:
+            params = batch_params(self.model.opt, data, int(data.num_graphs))
+        except (AttributeError, KeyError):
+            params = None
+        if params is None or any(not isinstance(p, dict) or 'centers' not in p or 'scales' not in p for p in params):
+            raise ValueError("GraphedTrainStep: a loss_type='pde_loss' batch must carry its Gaussians (data.pde_params, or "
+                             "data.batch_dict[i]['pde_params'] for randg_mix); this one has none (DeviceMeshLoader strips them)")
+        n, cap = sum(len(p['centers']) for p in params), len(params) * self.max_gauss
+        if n > cap:
+            raise ValueError(f"GraphedTrainStep: {n} Gaussians in the batch, room for {cap} ({len(params)} meshes x max_gauss = {self.max_gauss})")
+        return params
+
     def __call__(self, data) -> torch.Tensor:
+        params = self._pde_params(data) if self.pde else None
         c = self._lookup(data)
+        if params is not None:
+            c.static._pde_batch.set_params(params)           # on this stream, ahead of the replay: the same device buffers
         if data is not c.static:
             for name in INPUT_FIELDS + (self.target_field,):
                 src = getattr(data, name, None)

@@ -207,6 +207,37 @@ int gadapt_fem_backward_window(int n_meshes, int n_nodes, int n_tris, const int3
                                const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs, float* work,
                                const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad, float* gx, void* stream);
 
+/* The wave-parallel adjoint (fem_csrc/fem_wave_grad_kernels.hip; fem_adjoint='wave' in Python): gadapt_fem_backward and
+ * gadapt_fem_backward_window with their first and third launches - one lane per node, one lane per triangle, each walking
+ * every lattice point of its bounding boxes alone - replaced by a wave per node and a wave per triangle.  Arguments, checks
+ * and refusals are those of the entry point without the suffix (under this one's name); the adjoint solve and the gather
+ * are the same launches.  These entry points were added without changing GADAPT_FEM_ABI (no existing signature changed).
+ *
+ * Ordering contract: gc, tgrad and gx are those of gadapt_fem_backward[_window], bit for bit.  The library is built without
+ * FMA contraction, and each result is a chain of fp32 additions:
+ *   gc[v]      starts at g_coeffs[v] (0 without); v's incident (triangle, corner) pairs in CSR order; within one, the lattice
+ *              points of the triangle's bounding box, i outer, j inner; a point adds g_sol[p] * (inc / div), and a point
+ *              with ind == 0 or inc == 0 adds nothing (it is skipped, not added as zero).
+ *   tgrad[t]   six chains, (x, y) of the three vertices.  Each: the stiffness terms as one lane computes them; then per
+ *              interior corner l = 0, 1, 2 ONE addend, the sum from zero over the 9 x 9 Simpson points in (i, j) order
+ *              (ind == 0 skipped) of the aux_grad term that corner's rotation gives this vertex; then per lattice point of
+ *              the bounding box in (i, j) order (ind == 0 skipped) the terms of l = 0, 1, 2.
+ * The wave computes 64 addends at a time with the lane kernels' expressions, leaves them in LDS in point order, and one
+ * lane per chain adds the points the round's ballot marks, in increasing order.  A workgroup is one wave (static LDS 256 B
+ * and 4 680 B), so a box of any size is walked in rounds with the chains carried in registers.  No atomics, no scratch. */
+int gadapt_fem_backward_wave(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells,
+                             const int32_t* node_mesh, const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node,
+                             const int32_t* nt_ptr, const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x,
+                             const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, const float* coeffs,
+                             const float* lfac, const float* g_coeffs, const float* g_sol, float* gc, float* mu, float* tgrad,
+                             float* gx, void* stream);
+int gadapt_fem_backward_window_wave(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells,
+                                    const int32_t* node_mesh, const int32_t* tri_mesh, const int32_t* int_idx,
+                                    const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx, const int32_t* gptr,
+                                    const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
+                                    int max_lds_bytes, const float* coeffs, float* work, const float* g_coeffs,
+                                    const float* g_sol, float* gc, float* mu, float* tgrad, float* gx, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ 1-D tails
  * Differentiable 1-D P1 FEM of the reference's modular loss (firedrake_difFEM/difFEM_1d.py): semi-implicit Burgers steps
  * (torch_FEM_Burgers_1D, get_Burgers_initial_coeffs) and Poisson (torch_FEM_1D), with the reference's trapezoid inner

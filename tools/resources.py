@@ -2,6 +2,7 @@
 """Per-kernel register / scratch report of the hot kernels (hipcc -Rpass-analysis=kernel-resource-usage); `make resources`.
 
     python tools/resources.py [extra hipcc flags] [translation units, e.g. gadapt_tu_bwd_target]
+    python tools/resources.py -ffp-contract=off fem_csrc/fem_kernels     # a unit of another source directory: the FEM tails
 """
 import os
 import re
@@ -17,7 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 def remarks(unit):
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Iinclude", "-Ig_adaptivity_amd/csrc", *flags, "-c", "-o", "/dev/null",
-           f"g_adaptivity_amd/csrc/{unit}.hip", "-Rpass-analysis=kernel-resource-usage"]
+           f"g_adaptivity_amd/{unit if '/' in unit else 'csrc/' + unit}.hip", "-Rpass-analysis=kernel-resource-usage"]
     return subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True).stderr
 
 
@@ -38,7 +39,7 @@ for line in out.splitlines():
     elif cur and ":" in t:
         k, v = t.rsplit(":", 1)
         rec[k.strip()] = v.strip()
-        if k.strip().startswith("LDS Size") and ("grand_" in cur or "wide" in cur or "smallmesh" in cur or "cnn" in cur):
-            print("%-78s VGPR %4s  AGPR %3s  scratch %5s  spill %4s  waves/SIMD %s" % (
+        if k.strip().startswith("LDS Size") and ("grand_" in cur or "wide" in cur or "smallmesh" in cur or "cnn" in cur or "fem_" in cur):
+            print("%-78s VGPR %4s  AGPR %3s  scratch %5s  spill %4s  waves/SIMD %s  static LDS %s" % (
                 cur, rec.get("VGPRs"), rec.get("AGPRs"), rec.get("ScratchSize [bytes/lane]"), rec.get("VGPRs Spill"),
-                rec.get("Occupancy [waves/SIMD]")))
+                rec.get("Occupancy [waves/SIMD]"), v.strip()))
