@@ -47,12 +47,15 @@ PROTOTYPES = {
     'gadapt_fem1d_poisson_forward': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P] * 5),
     'gadapt_fem1d_poisson_eval_errors': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P] * 4),
     'gadapt_fem1d_poisson_backward': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P] * 6),
+    'gadapt_fem_poisson1d_loss_lds_bytes': (_L, [_I, _I]),
+    'gadapt_fem_poisson1d_loss': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P, _P, _I] + [_P] * 8),
     'gadapt_fem1d_expand': (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P]),
     'gadapt_fem1d_spline': (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     'gadapt_fem_descend': (_I, [_I, _I, _I] + [_P] * 14 + [_I, _I, _I, _I, _F] + [_P] * 16),
     'gadapt_fem1d_descend': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P, _I, _F, _I, _I] + [_P] * 11),
 }
 DESCEND_INTERNAL, DESCEND_ALL = 0, 1       # GADAPT_FEM1D_DESCEND_*
+FEM1D_LOSS_L1, FEM1D_LOSS_MSE = 0, 1       # GADAPT_FEM1D_LOSS_*
 SPLINE_OK, SPLINE_NOT_INCREASING, SPLINE_NOT_FINITE, SPLINE_BAD_COUNT = 0, 1, 2, 3   # GADAPT_SPLINE_S_*
 
 _lib = None

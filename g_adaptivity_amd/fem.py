@@ -376,8 +376,11 @@ def _check_tail(model):
     band, adjoint = o.get('fem_band', 'lds'), o.get('fem_adjoint', 'lane')
     _check_route("loss_type='pde_loss'", band, 0)
     _check_adjoint("loss_type='pde_loss' (opt['fem_adjoint'])", adjoint)
+    if model.dim == 1 and o.get('pde_loss_1d') and o.get('pde_type', 'Poisson') == 'Poisson':
+        return band, adjoint                                 # the 1-D tail (fem1d.gnn_pde_tail_1d): opt-in, one route
     if model.dim != 2:
-        raise NotImplementedError("loss_type='pde_loss' is built for 2-D Poisson only; the 1-D tail (torch_FEM_1D) is out of scope")
+        raise NotImplementedError("loss_type='pde_loss' is built for 2-D Poisson only; the 1-D tail (torch_FEM_1D) is out of scope "
+                                  "unless opt['pde_loss_1d'] is set (1-D Poisson)")
     if o.get('pde_type', 'Poisson') != 'Poisson':
         raise NotImplementedError(f"loss_type='pde_loss' is built for 2-D Poisson only (pde_type={o.get('pde_type')!r})")
     return band, adjoint
@@ -389,6 +392,9 @@ def gnn_pde_tail(model, data, x_phys: torch.Tensor):
     the wave-parallel backward.  A batch that carries a `PdeBatch` (`data._pde_batch`) is solved through it: the launches
     alone, nothing read back from the device or sent to it (its route and Gaussians are the descriptor's)."""
     band, adjoint = _check_tail(model)
+    if model.dim == 1:                                       # opt['pde_loss_1d']: torch_FEM_1D per mesh (src/GNN.py:319-325)
+        from .fem1d import gnn_pde_tail_1d
+        return gnn_pde_tail_1d(model, data, x_phys)
     pb = getattr(data, '_pde_batch', None)
     if pb is not None:
         coeffs, sol = pb.solve(x_phys)

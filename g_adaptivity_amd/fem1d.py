@@ -26,7 +26,8 @@ from . import _native_fem as _nf
 from ._native import NativeError, current_stream
 
 __all__ = ['burgers_1d', 'fem_poisson_1d', 'gradient_meshpoints_1D', 'torch_FEM_Burgers_1D', 'get_Burgers_initial_coeffs',
-           'burgers_project', 'fn_expansion', 'torch_FEM_1D', 'last_flags', 'GRAD_TYPES']
+           'burgers_project', 'fn_expansion', 'torch_FEM_1D', 'last_flags', 'GRAD_TYPES', 'poisson_loss_1d', 'Pde1dBatch',
+           'gnn_pde_tail_1d']
 
 GRAD_TYPES = ('PDE_loss_direct_mse', 'PDE_loss_direct_L2', 'burgers_timestep_loss_direct_mse')
 MAX_NODES = 1024                      # GADAPT_FEM1D_MAX_NODES
@@ -63,14 +64,9 @@ class _Batch:
         self.node_off = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32, device=device)
         self.gptr = self.gpar = None
         if pde_params is not None:
-            cnt, rows = [0], []
-            for p in pde_params:
-                for c, s in zip(p['centers'], p['scales']):
-                    rows.append([float(np.asarray(_host(c), np.float32).reshape(-1)[0]),
-                                 float(np.asarray(_host(s), np.float32).reshape(-1)[0])])
-                cnt.append(len(p['centers']))
-            self.gptr = torch.tensor(np.cumsum(cnt), dtype=torch.int32, device=device)
-            self.gpar = torch.tensor(np.asarray(rows, np.float32).reshape(-1, 2), device=device)
+            ptr, rows = _gaussian_rows(pde_params)
+            self.gptr = torch.tensor(ptr, dtype=torch.int32, device=device)
+            self.gpar = torch.tensor(rows, device=device)
         self._sizes = (self.B, self.nmax, self.node_off.data_ptr())
         self.gauss = (_ptr(self.gptr), _ptr(self.gpar))                  # (gptr, gpar), NULL without pde_params
 
@@ -88,6 +84,17 @@ class _Batch:
 
 def _host(v):
     return v.detach().cpu().numpy() if torch.is_tensor(v) else v
+
+
+def _gaussian_rows(pde_params: Sequence[dict]):
+    """(cumulative counts [B+1], rows [G,2] fp32 = (centre, scale)) on the host: per mesh its own number of Gaussians."""
+    cnt, rows = [0], []
+    for p in pde_params:
+        for c, s in zip(p['centers'], p['scales']):
+            rows.append([float(np.asarray(_host(c), np.float32).reshape(-1)[0]),
+                         float(np.asarray(_host(s), np.float32).reshape(-1)[0])])
+        cnt.append(len(p['centers']))
+    return np.cumsum(cnt).astype(np.int32), np.asarray(rows, np.float32).reshape(-1, 2)
 
 
 _last_flags: Optional[torch.Tensor] = None
@@ -110,6 +117,16 @@ def _watch_flags(flags: torch.Tensor):
         if bad:
             warnings.warn(f"WARNING: negative diffs in build_stiffness_matrix (meshes {bad})", RuntimeWarning, stacklevel=3)
     del _pending[:-64]
+
+
+def _keep_flags(flags: torch.Tensor, bt):
+    """`_watch_flags`, or for a descriptor that may be launched under stream capture (`Pde1dBatch`: `watch` False) only the
+    device tensor for `last_flags()`: no pinned copy and no event inside a capture."""
+    global _last_flags
+    if getattr(bt, 'watch', True):
+        _watch_flags(flags)
+    else:
+        _last_flags = flags
 
 
 def last_flags() -> Optional[torch.Tensor]:
@@ -203,7 +220,7 @@ class _Poisson(torch.autograd.Function):
         flags = torch.empty(B, dtype=torch.int32, device=dev)
         _nf.call('gadapt_fem1d_poisson_forward', *bt.head(x), k_load, k_stiff, P, pts.data_ptr(), coeffs.data_ptr(), sol.data_ptr(),
                  flags.data_ptr(), current_stream(dev))
-        _watch_flags(flags)
+        _keep_flags(flags, bt)
         ctx.bt, ctx.k = bt, (k_load, k_stiff)
         ctx.save_for_backward(x, pts, coeffs)
         return coeffs, sol
@@ -235,6 +252,197 @@ def fem_poisson_1d(x: torch.Tensor, node_counts: Sequence[int], pde_params: Sequ
     if x.dim() != 1:
         raise ValueError(f"fem_poisson_1d: x must be [N] (got {tuple(x.shape)})")
     return _poisson_on(_Batch(node_counts, pde_params, x.device), x, opt, points)
+
+
+# ---------------------------------------------------------------------------------------------- the 1-D pde_loss tail
+LOSS_KINDS = {'l1': _nf.FEM1D_LOSS_L1, 'mse': _nf.FEM1D_LOSS_MSE}
+_tickets = {}                         # (device, stream) -> the launch's ticket counter [1] int32, zero between launches
+
+
+def _check_loss_size(nmax: int, n_pts: int):
+    need, budget = int(_nf.lib().gadapt_fem_poisson1d_loss_lds_bytes(nmax, n_pts)), int(_nf.lib().gadapt_fem_lds_budget())
+    if need > budget:
+        raise NotImplementedError(f"fused 1-D Poisson tail: {nmax} nodes per mesh and {n_pts} evaluation points need {need} B of LDS "
+                                  f"(64 per node and the seed row), the budget is {budget} B; the split tail takes up to {MAX_NODES} nodes")
+
+
+class _PoissonLoss(torch.autograd.Function):
+    """gadapt_fem_poisson1d_loss: solve, loss and node gradient in one launch; backward is g * gx."""
+
+    @staticmethod
+    def forward(ctx, x, bt, k_load, k_stiff, pts, target, kind):
+        x = x.detach().contiguous()
+        dev, B, P = x.device, bt.B, pts.numel()
+        coeffs, gx = torch.empty_like(x), torch.empty_like(x)
+        sol = torch.empty(B * P, device=dev)
+        flags = torch.empty(B, dtype=torch.int32, device=dev)
+        partials, loss = torch.empty(B, device=dev), torch.empty((), device=dev)
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        ticket = _tickets.get(key)
+        if ticket is None:
+            ticket = _tickets[key] = torch.zeros(1, dtype=torch.int32, device=dev)
+        _nf.call('gadapt_fem_poisson1d_loss', *bt.head(x), k_load, k_stiff, P, pts.data_ptr(), target.data_ptr(), kind, coeffs.data_ptr(),
+                 sol.data_ptr(), gx.data_ptr(), flags.data_ptr(), partials.data_ptr(), loss.data_ptr(), ticket.data_ptr(),
+                 current_stream(dev))
+        _keep_flags(flags, bt)
+        ctx.save_for_backward(gx)
+        ctx.mark_non_differentiable(coeffs, sol, partials)
+        return loss, coeffs, sol, partials
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (gx,) = ctx.saved_tensors
+        from .functional import _unit_grads
+        unit = _unit_grads.get(g.device)
+        if unit is not None and g.data_ptr() == unit.data_ptr():
+            return (gx,) + (None,) * 6           # the caller passed unit_gradient(): nothing to multiply
+        return (gx * g,) + (None,) * 6
+
+
+def _poisson_loss_on(bt, x: torch.Tensor, target: torch.Tensor, k_load: int, k_stiff: int, pts: torch.Tensor, loss: str):
+    if loss not in LOSS_KINDS:
+        raise ValueError(f"fused 1-D Poisson tail: loss must be one of {sorted(LOSS_KINDS)} (got {loss!r})")
+    _require_gpu(x, 'poisson_loss_1d')
+    if min(bt.counts) < 3:
+        raise ValueError("poisson_loss_1d: every mesh needs at least 3 nodes")
+    target = target.detach().to(device=x.device, dtype=torch.float32).contiguous().view(-1)
+    if target.numel() != bt.B * pts.numel():
+        raise ValueError(f"poisson_loss_1d: target of {target.numel()} values for {bt.B} meshes x {pts.numel()} evaluation points")
+    _check_loss_size(bt.nmax, pts.numel())
+    return _PoissonLoss.apply(x.float(), bt, k_load, k_stiff, pts, target, LOSS_KINDS[loss])
+
+
+def poisson_loss_1d(x: torch.Tensor, node_counts: Sequence[int], pde_params: Sequence[dict], target: torch.Tensor, opt, loss: str = 'l1',
+                    points=None):
+    """`fem_poisson_1d`, the package's `l1_loss` / `mse_loss` of sol [B*P,1] against `target` [B*P] and that loss's backward
+    through the solve, in ONE launch (gadapt_fem_poisson1d_loss): (loss, coeffs [N], sol [B*P]).  `loss` is differentiable in x
+    (its backward is g * gx, gx written by the same launch); coeffs and sol are detached, with the bits of `fem_poisson_1d`, and
+    x.grad has the bits of the three launches.  The seed row shares the LDS with the solve: 1017 nodes per mesh at 101 points."""
+    if x.dim() != 1:
+        raise ValueError(f"poisson_loss_1d: x must be [N] (got {tuple(x.shape)})")
+    _require_gpu(x, 'poisson_loss_1d')
+    pts = _points(opt, x.device, points)
+    out = _poisson_loss_on(_Batch(node_counts, pde_params, x.device), x, target, int(opt.get('load_quad_points', 101)),
+                           int(opt.get('stiff_quad_points', 3)), pts, loss)
+    return out[0], out[1], out[2]
+
+
+class Pde1dBatch:
+    """The 1-D pde_loss tail of ONE batch shape, ready to launch (what `fem.PdeBatch` is in 2-D): the node counts, `node_off`, the
+    evaluation points and the quadrature counts, and the Gaussians' device buffers `gptr` [B+1] int32 and `gpar` [cap,2] fp32
+    (centre, scale) with a pinned host copy to stage them in.  `solve` / `solve_loss` are `fem_poisson_1d` / `poisson_loss_1d`
+    without their per-call host work, so they can be stream-captured: the flags stay on the device (`last_flags()`), no pinned
+    copy and no event.  `set_params` feeds another batch's Gaussians into the SAME device buffers."""
+
+    watch = False                     # `_keep_flags`: never `_watch_flags` (a pinned copy and an event) from a descriptor's launch
+    # (target field, 'l1' | 'mse'), set by training.GraphedTrainStep for opt['fem1d_tail'] = 'fused': `gnn_pde_tail_1d` then takes
+    # `solve_loss` against that field of the batch and leaves the loss in `loss`
+    fused = None
+    loss = None
+
+    def __init__(self, node_counts: Sequence[int], points: torch.Tensor, cap: int, device='cpu', k_load: int = 101, k_stiff: int = 3):
+        counts = [int(n) for n in node_counts]
+        if not counts or min(counts) < 3:
+            raise ValueError("Pde1dBatch: every mesh needs at least 3 nodes")
+        if max(counts) > MAX_NODES:
+            raise NotImplementedError(f"Pde1dBatch: {max(counts)} nodes per mesh; the limit is {MAX_NODES} (one lane per node)")
+        if int(cap) < 1:
+            raise ValueError(f"Pde1dBatch: room for {cap} Gaussians")
+        dev = torch.device(device)
+        self.counts, self.B, self.nmax, self.cap, self.device = counts, len(counts), max(counts), int(cap), dev
+        self.n_meshes, self.n_nodes = self.B, sum(counts)
+        self.k_load, self.k_stiff = int(k_load), int(k_stiff)
+        self.node_off = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32, device=dev)
+        self.pts = _points({}, dev, points)
+        self.gptr = torch.zeros(self.B + 1, dtype=torch.int32, device=dev)
+        self.gpar = torch.zeros(self.cap, 2, dtype=torch.float32, device=dev)
+        pin = dev.type == 'cuda'
+        self.host_gptr = torch.zeros(self.B + 1, dtype=torch.int32, pin_memory=pin)
+        self.host_gpar = torch.zeros(self.cap, 2, dtype=torch.float32, pin_memory=pin)
+        self._staged = torch.cuda.Event() if pin else None       # recorded behind the copies out of the staging buffers
+        self._sizes = (self.B, self.nmax, self.node_off.data_ptr())
+        self.gauss = (self.gptr.data_ptr(), self.gpar.data_ptr())
+        self.interior = _interior_index(counts, dev)             # positions of the coefficients GNN.forward returns
+
+    def head(self, x: torch.Tensor, gauss: bool = True) -> tuple:
+        return self._sizes + (x.data_ptr(),) + (self.gauss if gauss else ())
+
+    @classmethod
+    def from_data(cls, model, data, max_gauss: int = 8) -> 'Pde1dBatch':
+        """The descriptor of `data`'s node counts for `model`'s tail (its evaluation points and quadrature), with room for
+        `max_gauss` Gaussians per mesh; the batch's own Gaussians are set if it carries any.  May synchronise, once."""
+        from .fem import _batch_counts, _check_tail, batch_params
+        _check_tail(model)
+        o = model.opt
+        B, counts = _batch_counts(data, data.x_comp)
+        pb = cls(counts, model.quad_points, B * int(max_gauss), torch.device(o['device']), int(o.get('load_quad_points', 101)),
+                 int(o.get('stiff_quad_points', 3)))
+        try:
+            params = batch_params(o, data, B)
+        except (AttributeError, KeyError):
+            params = None
+        if params is not None:
+            pb.set_params(params)
+        return pb
+
+    def set_params(self, pde_params: Sequence[dict]):
+        """The Gaussians of the next solve: packed into the pinned buffers, then one non-blocking copy each into `gptr` and `gpar`
+        on the current stream (rows past the last Gaussian keep what they held; nothing reads them)."""
+        if len(pde_params) != self.B:
+            raise ValueError(f"PdeBatch: Gaussians of {len(pde_params)} meshes for a batch of {self.B}")
+        ptr, rows = _gaussian_rows(pde_params)
+        if rows.shape[0] > self.cap:
+            raise ValueError(f"PdeBatch: {rows.shape[0]} Gaussians in the batch, room for {self.cap} (from_data's max_gauss per mesh)")
+        if self._staged is not None:
+            self._staged.synchronize()                           # the previous copies have left the staging buffers
+        self.host_gptr.copy_(torch.from_numpy(ptr))
+        self.host_gpar[:rows.shape[0]].copy_(torch.from_numpy(rows))
+        self.gptr.copy_(self.host_gptr, non_blocking=True)
+        self.gpar.copy_(self.host_gpar, non_blocking=True)
+        if self._staged is not None:
+            self._staged.record()
+
+    def _x(self, x_phys: torch.Tensor) -> torch.Tensor:
+        if x_phys.numel() != self.n_nodes:
+            raise ValueError(f"Pde1dBatch: x_phys {tuple(x_phys.shape)} for a batch of {self.n_nodes} nodes in 1-D")
+        _require_gpu(x_phys, 'Pde1dBatch')
+        return x_phys.reshape(-1).float()
+
+    def solve(self, x_phys: torch.Tensor):
+        """(coeffs [N], sol [B*P]) of `fem_poisson_1d` on these node counts and the Gaussians last set: the same entry point on
+        the same inputs, the same bits."""
+        coeffs, sol = _Poisson.apply(self._x(x_phys), self, self.k_load, self.k_stiff, self.pts)
+        return coeffs, sol.view(-1)
+
+    def solve_loss(self, x_phys: torch.Tensor, target: torch.Tensor, loss: str = 'l1'):
+        """(loss, coeffs [N], sol [B*P]) of `poisson_loss_1d`: the one-launch tail."""
+        out = _poisson_loss_on(self, self._x(x_phys), target, self.k_load, self.k_stiff, self.pts, loss)
+        return out[0], out[1], out[2]
+
+
+def _interior_index(counts: Sequence[int], device) -> torch.Tensor:
+    """Positions of the interior nodes (1..n_b-2 of every mesh) in the concatenated batch."""
+    off = np.concatenate([[0], np.cumsum(counts)])
+    return torch.from_numpy(np.concatenate([o + np.arange(1, n - 1) for o, n in zip(off[:-1], counts)])).to(device, non_blocking=True)
+
+
+def gnn_pde_tail_1d(model, data, x_phys: torch.Tensor):
+    """`GNN.forward`'s pde_loss branch in 1-D (`src/GNN.py:319-325,338-342`): torch_FEM_1D per mesh, as one launch for the batch.
+    (coeffs [sum(n_b - 2), 1], the interior coefficients; x_phys [N]; sol [B*P]).  A batch that carries a `Pde1dBatch`
+    (`data._pde_batch`) is solved through it: the launch alone, nothing read back from the device or sent to it."""
+    from .fem import _batch_counts, batch_params
+    x = x_phys.reshape(-1)
+    pb = getattr(data, '_pde_batch', None)
+    if pb is not None:
+        if pb.fused is not None:
+            pb.loss, coeffs, sol = pb.solve_loss(x, getattr(data, pb.fused[0]), pb.fused[1])
+        else:
+            coeffs, sol = pb.solve(x)
+        return coeffs[pb.interior].unsqueeze(1), x, sol
+    B, counts = _batch_counts(data, x)
+    params = batch_params(model.opt, data, B)
+    coeffs, sol = _poisson_on(_Batch(counts, params, x.device), x, model.opt, model.quad_points)
+    return coeffs[_interior_index(counts, x.device)].unsqueeze(1), x, sol.view(-1)
 
 
 # ---------------------------------------------------------------------------------------------- the reference's names

@@ -26,6 +26,9 @@ struct Layout {
     // Poisson: a W1, one spare row so that the fp64 elimination (cp, rr: two fp64 rows) starts 8-aligned, and the three fp64
     // stiffness rows of the forward over the six fp32 rows Sl..t2, which it does not use otherwise
     static constexpr int POISSON_D64 = 12, POISSON_D64_ROWS = 2, POISSON_S64 = SL, POISSON_S64_ROWS = 3;
+    // The fused Poisson tail (poisson_loss_kernel): the Poisson layout and, behind its POISSON_ROWS fp32 rows, one row of n_pts
+    // floats (not of the node cap): sol - target per evaluation point, then the seed d loss / d sol
+    static constexpr int POISSON_ROWS = POISSON_D64 + 2 * POISSON_D64_ROWS;
     // fn_expansion: m, c.  The spline, on fp64 rows: x, y, M, the sweep's ratios.  The descent's step: the new nodes.
     static constexpr int EXPAND_ROWS = 2, SPLINE_ROWS = 4, DESCENT_ROWS = 1;
 
@@ -34,6 +37,7 @@ struct Layout {
     }
     static constexpr int64_t burgers_backward_bytes(int64_t max_nodes) { return 4 * BWD_ROWS * max_nodes; }
     static constexpr int64_t poisson_bytes(int64_t max_nodes) { return (4 * POISSON_D64 + 8 * POISSON_D64_ROWS) * max_nodes; }
+    static constexpr int64_t poisson_loss_bytes(int64_t max_nodes, int64_t n_pts) { return poisson_bytes(max_nodes) + 4 * n_pts; }
     static constexpr int64_t expand_bytes(int64_t max_nodes) { return 4 * EXPAND_ROWS * max_nodes; }
     static constexpr int64_t spline_bytes(int64_t max_nodes) { return 8 * SPLINE_ROWS * max_nodes; }
     static constexpr int64_t descent_step_bytes(int64_t max_nodes) { return 4 * DESCENT_ROWS * max_nodes; }
@@ -45,6 +49,10 @@ static_assert(Layout::POISSON_D64 >= Layout::W1_ROWS && Layout::POISSON_S64 + 2 
 static_assert(Layout::BWD_S0 + 4 == Layout::BWD_GXS && Layout::BWD_GXS + 1 == Layout::BWD_ROWS && Layout::BWD_ML + 3 == Layout::BWD_S0,
               "the backward's rows follow one another");
 static_assert(Layout::poisson_bytes(GADAPT_FEM1D_MAX_NODES) == GADAPT_FEM_LDS_BUDGET, "the Poisson layout at the node cap is the whole budget");
+static_assert(4 * Layout::POISSON_ROWS * GADAPT_FEM1D_MAX_NODES == Layout::poisson_bytes(GADAPT_FEM1D_MAX_NODES),
+              "the seed row of the fused Poisson tail starts where the Poisson layout ends");
+static_assert(Layout::poisson_loss_bytes(1017, 101) <= GADAPT_FEM_LDS_BUDGET && Layout::poisson_loss_bytes(1018, 101) > GADAPT_FEM_LDS_BUDGET,
+              "the fused Poisson tail with its seed row: 1017 nodes at 101 evaluation points, not the node cap");
 static_assert(Layout::burgers_backward_bytes(GADAPT_FEM1D_MAX_NODES) <= GADAPT_FEM_LDS_BUDGET, "the backward's rows fit at the node cap");
 static_assert(Layout::spline_bytes(GADAPT_FEM1D_MAX_NODES) <= GADAPT_FEM_LDS_BUDGET, "the spline's rows fit at the node cap");
 

@@ -812,6 +812,116 @@ __global__ void __launch_bounds__(F1_THREADS) poisson_bwd_kernel(
     }
 }
 
+// The 1-D pde_loss tail in one launch: poisson_solve, the loss of sol against `target` over the evaluation points and its
+// derivative in the nodes (gadapt_fem_poisson1d_loss).  sol has the bits of `evaluate`, the seed d loss / d sol the expressions of
+// the loss launch (loss_forward_kernel), and the backward below is poisson_bwd_kernel's statements with g_coeffs = NULL and g_sol
+// this mesh's seed row in LDS (copied, not shared: that kernel's machine code stays what it is), so gx has the bits of the three
+// launches.  A mesh's partial is summed by the first wave, lane l over points l, l + 64, ... and the lanes in a fixed butterfly
+// (as poisson_err_kernel: the order follows P alone, not the workgroup's size); the workgroup that takes the last ticket adds the
+// B partials in index order.  Barriers follow the reduction, so no lane leaves early.
+__global__ void __launch_bounds__(F1_THREADS) poisson_loss_kernel(
+    const int32_t* __restrict__ node_off, const float* __restrict__ x, const int32_t* __restrict__ gptr, const float* __restrict__ gpar,
+    int k_load, int k_stiff, int nmax, int P, const float* __restrict__ pts, const float* __restrict__ target, int l1,
+    float* __restrict__ coeffs, float* __restrict__ sol, float* __restrict__ gx, int32_t* __restrict__ flags, float* partials,
+    float* __restrict__ loss, unsigned* ticket) {
+    extern __shared__ float lds[];
+    const int b = blockIdx.x, t = threadIdx.x;
+    float* L = lds;
+    const W1 w = poisson_solve(L, b, node_off, x, gptr, gpar, k_load, k_stiff, nmax, flags);
+    const int off = node_off[b], n = w.n, g0 = gptr[b], g1 = gptr[b + 1];
+    float* seed = L + Layout::POISSON_ROWS * nmax;                 // [P]
+    const float inv = 1.0f / (float)((int64_t)gridDim.x * P);
+    // The coefficients leave w.r for w.c: the backward rebuilds the fp32 stiffness rows over the forward's fp64 ones (Sl..t2) and
+    // puts its right-hand side into w.r.  (poisson_solve ends with a barrier; w.c is not read by it.)
+    if (t < n) {
+        const float cv = w.r[t];
+        coeffs[off + t] = cv;
+        w.c[t] = cv;
+    }
+    __syncthreads();
+    for (int p = t; p < P; p += blockDim.x) {
+        const float v = pts[p];
+        const float u = expand(w.m, w.c, n, v, locate(w.m, n, v));
+        sol[(size_t)b * P + p] = u;
+        seed[p] = u - target[(size_t)b * P + p];
+    }
+    __syncthreads();
+    float part = 0.0f;
+    if (t < 64) {
+        for (int p = t; p < P; p += 64) {
+            const float d = seed[p];
+            part = part + (l1 ? fabsf(d) : d * d);
+        }
+        for (int o = 32; o > 0; o >>= 1) part = part + __shfl_xor(part, o, 64);
+    }
+    __syncthreads();                                               // the differences are read: the seed takes their place
+    for (int p = t; p < P; p += blockDim.x) {
+        const float d = seed[p];
+        seed[p] = l1 ? (d > 0.f ? inv : (d < 0.f ? -inv : 0.f)) : 2.0f * d * inv;
+    }
+    __syncthreads();
+    // ---- poisson_bwd_kernel from here on (the mesh and the coefficients are in w.m and w.c already)
+    float al, ad, au;
+    stiff_rows(w, k_stiff, al, ad, au);
+    poisson_matrix(w, al, ad, au);
+    float gxn = 0.0f;
+    if (t < n) {
+        float gc = 0.0f;
+        eval_adjoint_node(w.m, w.c, n, t, P, pts, seed, gc, gxn);
+        w.r[t] = (t == 0 || t == n - 1) ? 0.0f : gc;
+    }
+    __syncthreads();
+    if (t == 0) {
+        double* d64 = reinterpret_cast<double*>(L + Layout::POISSON_D64 * nmax);
+        thomas64(w.Sl, w.Sd, w.Su, w.r, d64, d64 + nmax, 1, n - 1, true);
+    }
+    __syncthreads();
+    const float* lam = w.r;
+    const float* c = w.c;
+    const float bc1 = c[0], bc2 = c[n - 1];
+    float ga = 0.0f, gb = 0.0f;
+    if (t < n - 1) {
+        const bool ia = t > 0, ib = t + 1 < n - 1;
+        float goff = (ia && ib) ? lam[t] * c[t + 1] + lam[t + 1] * c[t] : 0.0f;
+        if (t == 0) goff += lam[1] * bc1;
+        if (t == n - 2) goff += lam[n - 2] * bc2;
+        const float gdiag = (ia ? lam[t] * c[t] : 0.0f) + (ib ? lam[t + 1] * c[t + 1] : 0.0f);
+        const float d = w.m[t + 1] - w.m[t], i2 = 1.0f / (d * d);
+        const float gd = goff * i2 - gdiag * i2;
+        ga -= gd;
+        gb += gd;
+        const float wl = ib ? lam[t + 1] : 0.0f, wr = ia ? lam[t] : 0.0f;
+        auto Z = [&](int j, float xq, Phis ph) { return forcing(xq, gpar, g0, g1, nullptr) * (wl * ph.p + wr * ph.pr); };
+        auto Bk = [&](int j, float xq, Phis ph, float sz) {
+            float df;
+            forcing(xq, gpar, g0, g1, &df);
+            return sz * (wl * ph.p + wr * ph.pr) * df;
+        };
+        trapz_backward(w.m[t], d, k_load, Z, Bk, ga, gb);
+        w.t0[t] = ga;
+        w.t1[t] = gb;
+    }
+    __syncthreads();
+    if (t < n) {
+        float v = gxn;
+        if (t < n - 1) v += w.t0[t];
+        if (t > 0) v += w.t1[t - 1];
+        gx[off + t] = v;
+    }
+    // ---- the batch's loss: per-mesh partials, added in index order by the workgroup that finishes last
+    if (t == 0) {
+        __hip_atomic_store(partials + b, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+        if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+            __threadfence();
+            float v = 0.0f;
+            for (unsigned k = 0; k < gridDim.x; ++k) v = v + __hip_atomic_load(partials + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            loss[0] = v * inv;
+            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+        }
+    }
+}
+
 __global__ void __launch_bounds__(F1_THREADS) expand_kernel(const int32_t* __restrict__ node_off, const float* __restrict__ x,
                                                             const float* __restrict__ c, int nmax, int P, const float* __restrict__ pts,
                                                             float* __restrict__ sol) {
@@ -950,6 +1060,28 @@ extern "C" int gadapt_fem1d_poisson_backward(int n_meshes, int max_nodes, const 
     if (int rc = fem1d_check("gadapt_fem1d_poisson_backward", b, 3, true, !gptr || !gpar || !coeffs || !gx, "null pointer", P.lds_bytes))
         return rc;
     return fem1d_launch_poisson_backward(b, P, coeffs, g_coeffs, g_sol, gx, (hipStream_t)stream);
+}
+
+extern "C" int64_t gadapt_fem_poisson1d_loss_lds_bytes(int max_nodes, int n_pts) { return Layout::poisson_loss_bytes(max_nodes, n_pts); }
+
+// The Poisson launches' workgroup; the LDS is the Poisson layout's and the seed row's, so the node cap of this entry point lies
+// below GADAPT_FEM1D_MAX_NODES (1017 at 101 points) and the budget check is what refuses the sizes between.
+extern "C" int gadapt_fem_poisson1d_loss(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
+                                         const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts, const float* target,
+                                         int loss_kind, float* coeffs, float* sol, float* gx, int32_t* flags, float* partials, float* loss,
+                                         int32_t* ticket, void* stream) {
+    const Fem1dBatch b = FEM1D_BATCH(gptr, gpar, k_load, k_stiff);
+    Fem1dPlan P = fem1d_plan(Fem1dOp::poisson, max_nodes);
+    P.lds_bytes = Layout::poisson_loss_bytes(max_nodes, n_pts);
+    const bool own_bad = !gptr || !gpar || !target || !coeffs || !sol || !gx || !flags || !partials || !loss || !ticket || n_pts < 1 ||
+                         (loss_kind != GADAPT_FEM1D_LOSS_L1 && loss_kind != GADAPT_FEM1D_LOSS_MSE);
+    if (int rc = fem1d_check("gadapt_fem_poisson1d_loss", b, 3, true, own_bad, "null pointer, no evaluation points or unknown loss_kind",
+                             P.lds_bytes))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    FEM_LAUNCH(poisson_loss_kernel, n_meshes, P.threads, (size_t)P.lds_bytes, node_off, x, gptr, gpar, k_load, k_stiff, max_nodes, n_pts, pts,
+               target, loss_kind == GADAPT_FEM1D_LOSS_L1 ? 1 : 0, coeffs, sol, gx, flags, partials, loss, reinterpret_cast<unsigned*>(ticket));
+    return GADAPT_FEM_OK;
 }
 
 extern "C" int gadapt_fem1d_expand(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const float* c, int n_pts,

@@ -155,9 +155,12 @@ class GNN(nn.Module):
         if opt.get('learn_step'):
             self.steps = nn.ParameterList([nn.Parameter(torch.tensor([opt['time_step']]))
                                            for _ in range(opt['num_layers'])])       # GNN.py:179-180
-        if opt.get('loss_type') == 'pde_loss' and (self.dim != 2 or opt.get('pde_type', 'Poisson') != 'Poisson'):
+        one_d = self.dim == 1 and bool(opt.get('pde_loss_1d'))            # not a reference key: the 1-D Poisson tail, opt-in
+        if opt.get('loss_type') == 'pde_loss' and ((self.dim != 2 and not one_d) or opt.get('pde_type', 'Poisson') != 'Poisson'):
             raise NotImplementedError("loss_type='pde_loss' is built for 2-D Poisson only: the 1-D tail (torch_FEM_1D) and "
-                                      "Burgers are out of scope")
+                                      "Burgers are out of scope (1-D Poisson: opt['pde_loss_1d'])")
+        if opt.get('loss_type') == 'pde_loss' and one_d and opt.get('fem1d_tail', 'split') not in ('split', 'fused'):
+            raise ValueError(f"opt['fem1d_tail'] = {opt.get('fem1d_tail')!r}; 'split' or 'fused'")
         q = torch.linspace(0, 1, opt.get('eval_quad_points', 101))
         self.quad_points = q if self.dim == 1 else list(torch.meshgrid(q, q, indexing='ij'))
         self.end_MLmodel = None
@@ -297,7 +300,9 @@ class GNN(nn.Module):
         if not (Fn.SMALL_MESH_FORWARD and o['hidden_dim'] <= 32
                 and isinstance(self.enc, nn.Linear) and self.enc.bias is None and not self.enc.weight.requires_grad and x_comp.dtype == torch.float32
                 and all(t is None or (t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous() and not t.requires_grad) for t in (f, uu))
-                and not x_comp.requires_grad and o['loss_type'] in ('mesh_loss', 'modular')):
+                and not x_comp.requires_grad
+                # (the 1-D pde_loss tail, opt['pde_loss_1d'], takes x_phys from whatever route a mesh_loss model takes)
+                and (o['loss_type'] in ('mesh_loss', 'modular') or (o['loss_type'] == 'pde_loss' and self.dim == 1 and o.get('pde_loss_1d')))):
             return None
         if train and (o.get('learn_step') or o.get('softmax_temp_type') == 'learnable_a'):
             return None
@@ -391,6 +396,9 @@ class GNN(nn.Module):
             if not self.training and not torch.cuda.is_current_stream_capturing():
                 torch.cuda.current_stream(dev).synchronize()           # the stamp is read as a latency (utils_eval.py:201)
             self.end_MLmodel = time.time()                             # GNN.py:301
+            if o['loss_type'] == 'pde_loss':                           # (1-D, opt['pde_loss_1d']: _small_plan)
+                from .fem import gnn_pde_tail
+                return gnn_pde_tail(self, data, x)
             return x
         block = r.form in ('compact', 'dense')
         x_all, sliced, x0_cols = None, False, 0

@@ -270,8 +270,12 @@ def attach_fine_fields(d: MeshData, eval_quad_points: int = 101) -> MeshData:
     """The target of loss_type='pde_loss' (`src/data.py:234-267`, `run_GNN.py:108-110`): u_true on the evaluation lattice
     (`GNN.quad_points`, meshgrid(linspace(0,1,n), indexing='ij')), row-major: [n*n] with index i*n + j <-> (x_i, y_j)."""
     q = torch.linspace(0, 1, eval_quad_points).double()
-    X, Y = torch.meshgrid(q, q, indexing='ij')
-    u, _ = gaussian_fields(torch.stack([X.reshape(-1), Y.reshape(-1)], 1).numpy(), d.pde_params['centers'], d.pde_params['scales'])
+    if d.x_comp.dim() == 1:                                  # 1-D: [n] at linspace(0, 1, n) (`GNN.quad_points`, src/GNN.py:319-325)
+        pts = q[:, None]
+    else:
+        X, Y = torch.meshgrid(q, q, indexing='ij')
+        pts = torch.stack([X.reshape(-1), Y.reshape(-1)], 1)
+    u, _ = gaussian_fields(pts.numpy(), d.pde_params['centers'], d.pde_params['scales'])
     d.u_true_fine_tensor = torch.tensor(u, dtype=torch.float32)
     return d
 
@@ -433,9 +437,7 @@ def _set_targets(ds, target: str, target_params: Optional[dict]):
 
 def _add_pde_loss_fields(ds, eval_quad_points: int):
     """`mapping_tensor_fine` (identity: the fine lattice is already in lattice order) and per-sample `u_true_fine_tensor`."""
-    if ds.dim != 2:
-        raise NotImplementedError("pde_loss fields: 2-D datasets only")
-    ds.mapping_tensor_fine = torch.arange(eval_quad_points ** 2)
+    ds.mapping_tensor_fine = torch.arange(eval_quad_points ** ds.dim)
     for d in ds.samples:
         attach_fine_fields(d, eval_quad_points)
 

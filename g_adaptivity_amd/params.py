@@ -44,6 +44,12 @@ def hot_path_opt(**overrides) -> dict:
         # not a reference key: the form of the two lattice walks in the backward of those tails.  'lane': a lane per node and per
         # triangle; 'wave': a wave each (gadapt_fem_backward_wave), the same gradient bit for bit
         'fem_adjoint': 'lane',
+        # not a reference key: loss_type='pde_loss' on 1-D Poisson models (torch_FEM_1D per mesh, fem1d.gnn_pde_tail_1d).  False:
+        # such a model is refused, as before the tail was built
+        'pde_loss_1d': False,
+        # not a reference key: how training.GraphedTrainStep runs that tail.  'split': the solve, the loss launch and the adjoint
+        # solve (three launches); 'fused': gadapt_fem_poisson1d_loss, one launch, with the package's l1_loss / mse_loss only
+        'fem1d_tail': 'split',
         # not a reference key: the route of the MMPDE5 target meshes that the examples build (`target_params={'solver':
         # {'route': ...}}` of the datasets).  'lane': one node per lane, 2-D meshes up to 32 x 32; 'strided': up to 81 x 81
         'mmpde5_route': 'lane',

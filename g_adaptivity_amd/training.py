@@ -285,9 +285,17 @@ class GraphedTrainStep:
         if replay not in ('auto', 'graph', 'eager'):
             raise ValueError("replay: 'auto', 'graph' or 'eager'")
         self.pde = model.opt['loss_type'] == 'pde_loss'
-        if self.pde and model.dim != 2:
+        one_d = self.pde and model.dim == 1 and bool(model.opt.get('pde_loss_1d'))
+        if self.pde and model.dim != 2 and not one_d:
             raise NotImplementedError("GraphedTrainStep: loss_type='pde_loss' is captured for 2-D Poisson models only; the 1-D tail "
-                                      "(torch_FEM_1D) is not built")
+                                      "(torch_FEM_1D) is not built unless opt['pde_loss_1d'] is set")
+        # the 1-D tail: 'split' (solve, loss launch, adjoint solve) or 'fused' (gadapt_fem_poisson1d_loss: one launch, same gradient bits)
+        self.tail = model.opt.get('fem1d_tail', 'split') if one_d else None
+        if self.tail not in (None, 'split', 'fused'):
+            raise ValueError(f"GraphedTrainStep: opt['fem1d_tail'] = {self.tail!r}; 'split' or 'fused'")
+        if self.tail == 'fused' and loss_fn not in (mse_loss, l1_loss):
+            raise ValueError("GraphedTrainStep: opt['fem1d_tail'] = 'fused' computes the package's l1_loss or mse_loss inside the FEM "
+                             "launch; another loss_fn needs the 'split' tail")
         if target_field is None:                             # src/run_GNN.py:106 and :109
             target_field = 'u_true_fine_tensor' if self.pde else 'x_phys'
         self.max_gauss = int(max_gauss)
@@ -328,7 +336,10 @@ class GraphedTrainStep:
     def _iteration(self, data):
         self.optimizer.zero_grad()
         out = self.model(data)
-        if self.pde:                                         # (coeffs, x_phys, sol): the loss is on the lattice (src/run_GNN.py:108-110)
+        pb = getattr(data, '_pde_batch', None) if self.tail == 'fused' else None
+        if pb is not None and pb.fused is not None:          # the 1-D tail's launch has computed the loss (fem1d.gnn_pde_tail_1d)
+            loss = pb.loss
+        elif self.pde:                                       # (coeffs, x_phys, sol): the loss is on the lattice (src/run_GNN.py:108-110)
             loss = self.loss_fn(out[2].view(-1, 1), getattr(data, self.target_field).view(-1, 1))
         else:
             loss = self.loss_fn(out, getattr(data, self.target_field))
@@ -398,8 +409,14 @@ class GraphedTrainStep:
         if self.pde:
             # ... and the FEM tail's descriptor: with it `gnn_pde_tail` only launches (no bincount, no topology fingerprint, no
             # Gaussians packed from Python lists); the static batch's own Gaussians are in its buffers for the warm-up
-            from .fem import PdeBatch
-            c.static._pde_batch = PdeBatch.from_data(self.model, c.static, self.max_gauss)
+            if self.tail is not None:
+                from .fem1d import Pde1dBatch
+                c.static._pde_batch = Pde1dBatch.from_data(self.model, c.static, self.max_gauss)
+                if self.tail == 'fused':
+                    c.static._pde_batch.fused = (self.target_field, 'l1' if self.loss_fn is l1_loss else 'mse')
+            else:
+                from .fem import PdeBatch
+                c.static._pde_batch = PdeBatch.from_data(self.model, c.static, self.max_gauss)
         cur = torch.cuda.current_stream(dev)
         self._side.wait_stream(cur)
         with torch.cuda.stream(self._side):

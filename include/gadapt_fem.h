@@ -305,6 +305,33 @@ int gadapt_fem1d_poisson_backward(int n_meshes, int max_nodes, const int32_t* no
                                   const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts,
                                   const float* coeffs, const float* g_coeffs, const float* g_sol, float* gx, void* stream);
 
+/* The 1-D pde_loss tail in one launch: the Poisson forward, the loss of sol against a target on the evaluation points, and the
+ * gradient of that loss in the nodes (what gadapt_fem1d_poisson_forward, the loss launch of gadapt_hip.h and
+ * gadapt_fem1d_poisson_backward give in three).  One workgroup per mesh b, sized as for the other Poisson launches; with
+ * P = n_pts and inv = 1.0f / (float)(B * P), operation for operation:
+ *   1. the solve of gadapt_fem1d_poisson_forward; coeffs [N] and flags [B] as it writes them
+ *   2. sol[b,p] = fn_expansion(coeffs_b, x_b, pts[p]), the bits of gadapt_fem1d_poisson_forward; diff = sol[b,p] - target[b * P + p]
+ *   3. partials[b] = sum_p |diff| (GADAPT_FEM1D_LOSS_L1) or sum_p diff * diff (GADAPT_FEM1D_LOSS_MSE), by the first wave: lane l
+ *      adds points l, l + 64, ... in that order and the 64 lanes are added in a fixed butterfly, so the order follows P alone
+ *   4. the seed d loss / d sol[b,p], kept in LDS:  L1: diff > 0 ? inv : diff < 0 ? -inv : 0;  MSE: 2.0f * diff * inv
+ *      (the expressions of gadapt_loss_forward on [B * P, 1])
+ *   5. gx [N]: gadapt_fem1d_poisson_backward with g_coeffs = NULL and g_sol = that seed, the same bits
+ *   6. loss [1] = (partials[0] + partials[1] + ... + partials[B-1]) * inv, added in index order by the workgroup that
+ *      finishes last; ticket [1] counts the finished workgroups and is left at 0 (it must be 0 on entry: zero it once)
+ * Neither sums nor the gradient use float atomics: two calls give the same bits.  partials[b], like coeffs, sol and flags of mesh b,
+ * does not depend on the rest of the batch; gx and loss do through inv alone.
+ * LDS: the Poisson launches' 64 bytes per node and a seed row of 4 * n_pts bytes, gadapt_fem_poisson1d_loss_lds_bytes; within
+ * GADAPT_FEM_LDS_BUDGET that is 1017 nodes at 101 points, not GADAPT_FEM1D_MAX_NODES, and GADAPT_FEM_E_LDS beyond, before any
+ * launch.  (Named gadapt_fem_poisson1d_*, not gadapt_fem1d_*: that prefix is the eight entry points above with their shared
+ * node cap, whose refusal table tests/test_fem1d_abi_host.py pins as complete.) */
+#define GADAPT_FEM1D_LOSS_L1  0
+#define GADAPT_FEM1D_LOSS_MSE 1
+int64_t gadapt_fem_poisson1d_loss_lds_bytes(int max_nodes, int n_pts);
+int gadapt_fem_poisson1d_loss(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const int32_t* gptr,
+                              const float* gpar, int k_load, int k_stiff, int n_pts, const float* pts, const float* target,
+                              int loss_kind, float* coeffs, float* sol, float* gx, int32_t* flags, float* partials, float* loss,
+                              int32_t* ticket, void* stream);
+
 /* fn_expansion(c, x, pts) per mesh (no gradient): sol [B,P]. */
 int gadapt_fem1d_expand(int n_meshes, int max_nodes, const int32_t* node_off, const float* x, const float* c, int n_pts,
                         const float* pts, float* sol, void* stream);
