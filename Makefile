@@ -61,23 +61,24 @@ $(OBJDIR)/mmpde5_kernels.o: $(MESH_CSRC)/mmpde5_kernels.hip $(MESH_CSRC)/mesh_co
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
-# the Monge-Ampere target meshes (2-D): the same library and the same flags
-$(OBJDIR)/ma_kernels.o: $(MESH_CSRC)/ma_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
+# the Monge-Ampere target meshes (2-D): the same library and the same flags; the iteration and the batch check stated once
+MA_SHARED  := $(MESH_CSRC)/ma_iteration.h $(MESH_CSRC)/ma_host.h $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
+$(OBJDIR)/ma_kernels.o: $(MESH_CSRC)/ma_kernels.hip $(MA_SHARED)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
 # their strided route with an fp64 potential (up to 81 x 81): an object of its own, the same flags
-$(OBJDIR)/ma_strided_kernels.o: $(MESH_CSRC)/ma_strided_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
+$(OBJDIR)/ma_strided_kernels.o: $(MESH_CSRC)/ma_strided_kernels.hip $(MA_SHARED)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
 # the M2N 'slow' monitor (a P1 Poisson solve on the moving mesh inside the update loop, up to 24 x 24): the same flags
-$(OBJDIR)/ma_m2n_slow_kernels.o: $(MESH_CSRC)/ma_m2n_slow_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
+$(OBJDIR)/ma_m2n_slow_kernels.o: $(MESH_CSRC)/ma_m2n_slow_kernels.hip $(MA_SHARED)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 
 # Monge-Ampere meshes from a tabulated monitor, both routes: the same flags
-$(OBJDIR)/ma_table_kernels.o: $(MESH_CSRC)/ma_table_kernels.hip $(MESH_CSRC)/mesh_common.h include/gadapt_mesh.h
+$(OBJDIR)/ma_table_kernels.o: $(MESH_CSRC)/ma_table_kernels.hip $(MA_SHARED)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 

@@ -60,6 +60,17 @@ PROTOTYPES = {
     'gadapt_ma_table_batch_strided': (_I, [_I] + [_P] * 3 + [_D, _D, _I] + [_P] * 6),
 }
 
+# (getters, expected values, the message's wording with the values got and then those expected)
+LIMITS = [
+    (('gadapt_mmpde5_strided_max_side',), (STRIDED_MAX_SIDE,), "strided route up to {} a side, expected {}"),
+    (('gadapt_ma_max_side', 'gadapt_ma_max_gauss'), (MA_MAX_SIDE, MA_MAX_GAUSS),
+     "Monge-Ampere limits {} a side / {} Gaussians, expected {} / {}; rebuild it with `make`"),
+    (('gadapt_ma_strided_max_side',), (MA_STRIDED_MAX_SIDE,),
+     "strided Monge-Ampere route up to {} a side, expected {}; rebuild it with `make`"),
+    (('gadapt_ma_m2n_slow_max_side',), (MA_M2N_SLOW_MAX_SIDE,), "M2N 'slow' monitor up to {} a side, expected {}; rebuild it with `make`"),
+    (('gadapt_ma_table_max_side',), (MA_TABLE_MAX_SIDE,), "tabulated monitors up to {} a side, expected {}; rebuild it with `make`"),
+]
+
 _lib = None
 
 
@@ -78,20 +89,10 @@ def lib():
             if fn is None:                                             # same ABI number, older build: the ABI grows by addition
                 raise NativeError(f"{LIB_PATH} lacks {name}: a stale build; rebuild it with `make`")
             fn.restype, fn.argtypes = res, args
-        if handle.gadapt_mmpde5_strided_max_side() != STRIDED_MAX_SIDE:
-            raise NativeError(f"{LIB_PATH}: strided route up to {handle.gadapt_mmpde5_strided_max_side()} a side, expected {STRIDED_MAX_SIDE}")
-        if (handle.gadapt_ma_max_side(), handle.gadapt_ma_max_gauss()) != (MA_MAX_SIDE, MA_MAX_GAUSS):
-            raise NativeError(f"{LIB_PATH}: Monge-Ampere limits {handle.gadapt_ma_max_side()} a side / {handle.gadapt_ma_max_gauss()} "
-                              f"Gaussians, expected {MA_MAX_SIDE} / {MA_MAX_GAUSS}; rebuild it with `make`")
-        if handle.gadapt_ma_strided_max_side() != MA_STRIDED_MAX_SIDE:
-            raise NativeError(f"{LIB_PATH}: strided Monge-Ampere route up to {handle.gadapt_ma_strided_max_side()} a side, expected "
-                              f"{MA_STRIDED_MAX_SIDE}; rebuild it with `make`")
-        if handle.gadapt_ma_m2n_slow_max_side() != MA_M2N_SLOW_MAX_SIDE:
-            raise NativeError(f"{LIB_PATH}: M2N 'slow' monitor up to {handle.gadapt_ma_m2n_slow_max_side()} a side, expected "
-                              f"{MA_M2N_SLOW_MAX_SIDE}; rebuild it with `make`")
-        if handle.gadapt_ma_table_max_side() != MA_TABLE_MAX_SIDE:
-            raise NativeError(f"{LIB_PATH}: tabulated monitors up to {handle.gadapt_ma_table_max_side()} a side, expected "
-                              f"{MA_TABLE_MAX_SIDE}; rebuild it with `make`")
+        for got, want, text in LIMITS:                                 # the limits this module states are the library's
+            got = tuple(getattr(handle, g)() for g in got)
+            if got != want:
+                raise NativeError(f"{LIB_PATH}: " + text.format(*got, *want))
         _lib = handle
     return _lib
 

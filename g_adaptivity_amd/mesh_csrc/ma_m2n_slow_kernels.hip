@@ -2,8 +2,8 @@
 // (include/gadapt_mesh.h has the iteration): m = reg + alpha (u_h - u)^2 / max + beta F / max, with u_h the P1 solution of the
 // Poisson problem ON THE MOVING MESH, solved again inside the launch at every monitor evaluation.
 //
-// ma_m2n_slow_kernel is ma_m2n_kernel (ma_kernels.hip: one workgroup per mesh, one lane per node, phi in a register, two LDS
-// images) with a banded Cholesky solve between its first and second phase.  The phases of one update, each ended by a barrier
+// ma_m2n_slow_kernel is ma_m2n_kernel (ma_kernels.hip, on the lane route of ma_iteration.h: one workgroup per mesh, one lane per
+// node, phi in a register, two LDS images) with a banded Cholesky solve between its first and second phase.  The phases of one update, each ended by a barrier
 // that EVERY lane of the workgroup reaches (a mixed batch launches with the largest mesh's thread count, so the waves beyond a
 // small mesh's own walk the same loops: every trip count below depends on N alone, never on a lane):
 //   1  the image is complete and only read: x, y, det, lambda, u, f = -(u_xx + u_yy) and F of the lane's node; x, y, u, f go to
@@ -27,10 +27,9 @@
 // the node arrays are written in phase 1 and last read in phase 2 (u of the lane's own node stays in a register); the band and b
 // are written from phase 2 on and last read before the first barrier of phase 5.
 //
-// LDS: 4 * (6*16 + 8*8 + 4 + 6 nodes + (N-2)^2 (N-1) + (N-2)^2) bytes: six rows of wave partials, the Gaussians' constants, Cxy,
-// two images, four node arrays, the band (row r holds K[r][r-d] at r (w+1) + d, w = N - 2) and the right-hand side.  60 944 bytes
-// at 24 x 24, below the 64 KB that need no raised limit; 25 x 25 would take 68 556.  The pair table of fem_kernels.hip is not
-// needed: a lane has one pair.
+// LDS (ma_host.h, slow_lds_bytes): 4 * (6*16 + 8*8 + 4 + 6 nodes + (N-2)^2 (N-1) + (N-2)^2) bytes: six rows of wave partials, the
+// Gaussians' constants, Cxy, two images, four node arrays, the band and the right-hand side.  60 944 bytes at 24 x 24, below the
+// 64 KB that need no raised limit.  The pair table of fem_kernels.hip is not needed: a lane has one pair.
 //
 // expf / logf / sqrtf are the accurate ones; no FMA contraction (Makefile and the pragma below).  The arithmetic up to F is
 // ma_m2n_kernel's source, so alpha = 0 gives that kernel's bits (reg + 0 is exact).
@@ -38,34 +37,13 @@
 // ma_m2n_slow_kernel: 111 VGPRs, no AGPRs, 106 SGPRs, no scratch, no VGPR spills; 39 SGPRs are spilled to VGPR lanes, which
 // costs no memory traffic (hipcc -Rpass-analysis=kernel-resource-usage, gfx950).  __launch_bounds__(576): 9 waves a workgroup,
 // at most 3 on a SIMD, which allows 168 VGPRs.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-
-#include "gadapt_mesh.h"
-#include "mesh_common.h"
+#include "ma_iteration.h"                            // and through it ma_host.h, mesh_common.h, gadapt_mesh.h
 
 #pragma clang fp contract(off)
 
-using namespace gadapt_mesh_shared;                      // g_err, mesh_fail, wave_sum, wave_max, wave_min
+using namespace gadapt_ma;
 
 namespace {
-
-constexpr int MAX_SIDE = 24;
-constexpr int MAX_NODES = MAX_SIDE * MAX_SIDE;           // 576 lanes, 9 waves
-constexpr int ROW = 16;                                  // a row of wave partials, as in ma_kernels.hip
-constexpr int MAX_GAUSS = 8;
-constexpr int GAUSS_CONSTS = 8;                          // c0, c1, 1/q0, 1/q1, A0, B0, A1, B1
-constexpr int CXY = 6 * ROW + MAX_GAUSS * GAUSS_CONSTS;
-constexpr int LDS_HEAD = CXY + 4;
-
-__host__ __device__ inline int ma_threads(int nodes) { return (nodes + 63) & ~63; }
-
-__host__ __device__ inline int64_t slow_lds_floats(int N) {
-    const int64_t w = N - 2, n = w * w;
-    return LDS_HEAD + 6 * (int64_t)N * N + n * (w + 1) + n;
-}
 
 struct V2 { float x, y; };
 
@@ -107,7 +85,7 @@ __device__ __forceinline__ void tri_terms(int a, int b, bool up, int l, int N, i
     }
 }
 
-__global__ __launch_bounds__(MAX_NODES) void ma_m2n_slow_kernel(const int32_t* __restrict__ desc, const float* __restrict__ gauss,
+__global__ __launch_bounds__(SLOW_MAX_NODES) void ma_m2n_slow_kernel(const int32_t* __restrict__ desc, const float* __restrict__ gauss,
                                                                const float* __restrict__ mon, double cfl, float tol, int tol_zero,
                                                                int max_steps, float* __restrict__ xo, float* __restrict__ yo,
                                                                int32_t* __restrict__ steps_out, float* __restrict__ res_out,
@@ -116,13 +94,13 @@ __global__ __launch_bounds__(MAX_NODES) void ma_m2n_slow_kernel(const int32_t* _
     const int b = blockIdx.x;
     const int32_t* d = desc + GADAPT_MA_DESC * b;
     const int N = d[GADAPT_MA_D_N], noff = d[GADAPT_MA_D_NODE_OFF], goff = d[GADAPT_MA_D_GAUSS_OFF], ng = d[GADAPT_MA_D_GAUSS_N];
-    const int nodes = N * N, nw = ma_threads(nodes) >> 6;
+    const int nodes = N * N, nw = (nodes + 63) >> 6;     // whole waves: N <= 32 is within ma_threads' cap
     const int w = N - 2, n = w * w, ld = w + 1;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     float* red = lds;
     float* gc = lds + 6 * ROW;
-    float* img[2] = {lds + LDS_HEAD, lds + LDS_HEAD + nodes};
-    float* xs = lds + LDS_HEAD + 2 * nodes;
+    float* img[2] = {lds + SLOW_HEAD, lds + SLOW_HEAD + nodes};
+    float* xs = lds + SLOW_HEAD + 2 * nodes;
     float* ys = xs + nodes;
     float* us = ys + nodes;
     float* fs = us + nodes;
@@ -156,9 +134,9 @@ __global__ __launch_bounds__(MAX_NODES) void ma_m2n_slow_kernel(const int32_t* _
         float* o = gc + GAUSS_CONSTS * tid;
         o[0] = g[0], o[1] = g[1], o[2] = 1.0f / q0, o[3] = 1.0f / q1;
         o[4] = 4.0f / (q0 * q0), o[5] = 2.0f / q0, o[6] = 4.0f / (q1 * q1), o[7] = 2.0f / q1;
-        if (tid == ng - 1) lds[CXY] = (16.0f * o[2]) * o[3];   // u_xy is the LAST Gaussian's only, as in the reference
+        if (tid == ng - 1) lds[SLOW_HEAD - 4] = (16.0f * o[2]) * o[3];   // u_xy is the LAST Gaussian's only, as in the reference
     }
-    if (tid == 0 && ng == 0) lds[CXY] = 0.0f;           // read below whatever ng is: never an unwritten word
+    if (tid == 0 && ng == 0) lds[SLOW_HEAD - 4] = 0.0f;           // read below whatever ng is: never an unwritten word
     float phi = 0.0f, x = xi, y = xj, res = 0.0f, m = reg;
     if (own) img[0][c] = phi;
     int steps = 0, cur = 0, status;
@@ -187,7 +165,7 @@ __global__ __launch_bounds__(MAX_NODES) void ma_m2n_slow_kernel(const int32_t* _
             u = u + g;
             dxl = dx, dyl = dy, gl = g;                  // what is left after the loop is the last Gaussian's
         }
-        const float uxy = (lds[CXY] * (dxl * dyl)) * gl;
+        const float uxy = (lds[SLOW_HEAD - 4] * (dxl * dyl)) * gl;
         const float Fn = sqrtf((uxx * uxx + 2.0f * (uxy * uxy)) + uyy * uyy);
         if (own) xs[c] = x, ys[c] = y, us[c] = u, fs[c] = -(uxx + uyy);
         const float s_f = wave_max(own ? Fn : -INFINITY);
@@ -275,69 +253,30 @@ __global__ __launch_bounds__(MAX_NODES) void ma_m2n_slow_kernel(const int32_t* _
         yo[noff + c] = y;
         if (mon_out) mon_out[noff + c] = m;
     }
-    if (tid == 0) {
-        steps_out[b] = steps;
-        res_out[b] = res;
-        status_out[b] = status;
-    }
+    write_status(b, tid, steps, res, status, steps_out, res_out, status_out);
 }
 
 }  // namespace
 
-extern "C" int gadapt_ma_m2n_slow_max_side(void) { return MAX_SIDE; }
+extern "C" int gadapt_ma_m2n_slow_max_side(void) { return SLOW_MAX_SIDE; }
 
 extern "C" int64_t gadapt_ma_m2n_slow_lds_bytes(int nodes) {
     int N = 3;
     while (N * N < nodes) ++N;
-    if (nodes < 9 || nodes > MAX_NODES || N * N != nodes)
+    if (nodes < 9 || nodes > SLOW_MAX_NODES || N * N != nodes)
         return mesh_fail(GADAPT_MESH_E_SIZE, "gadapt_ma_m2n_slow_lds_bytes: N x N nodes, 3 <= N <= 24");
-    return 4 * slow_lds_floats(N);
+    return slow_lds_bytes(N);
 }
 
 // Everything is checked on desc_host before the one launch: the checks and codes of gadapt_ma_m2n_batch with this route's side limit.
 extern "C" int gadapt_ma_m2n_slow_batch(int n_mesh, const int32_t* desc_host, const int32_t* desc, const float* gauss, const float* mon3,
                                         double cfl, double tol, int max_steps, float* x, float* y, int32_t* steps, float* residual,
                                         int32_t* status, float* monitor_out, void* stream) {
-    const char* who = "gadapt_ma_m2n_slow_batch";
-    char msg[240];
-    if (n_mesh < 1 || !desc_host || !desc || !mon3 || !x || !y || !steps || !residual || !status) {
-        snprintf(msg, sizeof msg, "%s: empty batch or null pointer", who);
-        return mesh_fail(GADAPT_MESH_E_BADARG, msg);
-    }
-    if (!(cfl > 0.0) || !(tol >= 0.0) || !isfinite(cfl) || !isfinite(tol)) {
-        snprintf(msg, sizeof msg, "%s: need cfl > 0 and tol >= 0, both finite", who);
-        return mesh_fail(GADAPT_MESH_E_BADARG, msg);
-    }
-    if (max_steps < 0 || max_steps > GADAPT_MMPDE5_MAX_STEPS) {
-        snprintf(msg, sizeof msg, "%s: max_steps %d; 0..%d supported (the loop must end)", who, max_steps, GADAPT_MMPDE5_MAX_STEPS);
-        return mesh_fail(GADAPT_MESH_E_SIZE, msg);
-    }
-    int threads = 64, most = 3;
-    for (int b = 0; b < n_mesh; ++b) {
-        const int32_t* d = desc_host + GADAPT_MA_DESC * b;
-        const int N = d[GADAPT_MA_D_N], ng = d[GADAPT_MA_D_GAUSS_N];
-        if (N < 3 || d[GADAPT_MA_D_NODE_OFF] < 0 || d[GADAPT_MA_D_GAUSS_OFF] < 0 || ng < 0 || (ng > 0 && !gauss)) {
-            snprintf(msg, sizeof msg, "%s: mesh %d: N %d, offsets %d / %d, %d Gaussians", who, b, N, d[GADAPT_MA_D_NODE_OFF],
-                     d[GADAPT_MA_D_GAUSS_OFF], ng);
-            return mesh_fail(GADAPT_MESH_E_BADARG, msg);
-        }
-        if (N > MAX_SIDE || ng > MAX_GAUSS) {
-            snprintf(msg, sizeof msg, "%s: mesh %d: N = %d with %d Gaussians; N <= %d a side (the band of the P1 solve stays in LDS) "
-                     "and at most %d Gaussians", who, b, N, ng, MAX_SIDE, MAX_GAUSS);
-            return mesh_fail(GADAPT_MESH_E_SIZE, msg);
-        }
-        if ((int64_t)d[GADAPT_MA_D_NODE_OFF] + N * N > INT32_MAX) {
-            snprintf(msg, sizeof msg, "%s: more than 2^31 nodes in one batch", who);
-            return mesh_fail(GADAPT_MESH_E_SIZE, msg);
-        }
-        const int t = ma_threads(N * N);
-        threads = t > threads ? t : threads;
-        most = N > most ? N : most;
-    }
+    Geometry g;
+    const int rc = check_batch("gadapt_ma_m2n_slow_batch", SLOW_MAX_SIDE, BAND_IN_LDS, false, n_mesh, desc_host, desc, gauss, mon3, cfl,
+                               tol, max_steps, x, y, steps, residual, status, &g);
+    if (rc != GADAPT_MESH_OK) return rc;
     const float tol_f = (float)tol;
-    ma_m2n_slow_kernel<<<n_mesh, threads, (size_t)(4 * slow_lds_floats(most)), (hipStream_t)stream>>>(
-        desc, gauss, mon3, cfl, tol_f, tol_f == 0.0f, max_steps, x, y, steps, residual, status, monitor_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mesh_fail(GADAPT_MESH_E_LAUNCH, hipGetErrorString(e));
-    return GADAPT_MESH_OK;
+    return launch(ma_m2n_slow_kernel, n_mesh, g.threads, slow_lds_bytes(g.side), stream, desc, gauss, mon3, cfl, tol_f,
+                  (int)(tol_f == 0.0f), max_steps, x, y, steps, residual, status, monitor_out);
 }

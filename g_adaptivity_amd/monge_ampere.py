@@ -260,37 +260,22 @@ def _gaussians(b: int, params):
     return rows
 
 
-def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000, device=None,
-             route: str = 'lane', m2n_solve: Optional[str] = None):
-    """The host side of `ma_batch`: checks, the batch's descriptors and Gaussians on the GPU, the argument list.  Returns
-    (launch, collect): `launch()` issues the one kernel (it may be issued again), `collect()` gives the MAResult (the
-    MASlowResult under the 'slow' monitor)."""
+def _prepare_common(sizes: Sequence, fields: Sequence, fields_name: str, describe, *, cfl, tol, max_steps, device, route):
+    """What `_prepare` and `_prepare_table` share: the scalar checks, the sides, the device, the batch's descriptors and output
+    buffers on the GPU, the argument list and the (launch, collect) closures.  `describe(ns)` is the caller's own part, run after the
+    sides are checked and before a device is asked for: -> (word 3 of every descriptor, what word 2 advances by per mesh,
+    inputs(dev) -> the device tensors whose pointers follow the descriptors in the argument list, entry point, overflow text,
+    whether the monitor is written out)."""
     if route not in ROUTES:
         raise ValueError(f"route = {route!r}; one of {ROUTES}")
-    if len(sizes) == 0 or len(sizes) != len(pde_params):
-        raise ValueError(f"{len(sizes)} mesh sizes and {len(pde_params)} parameter sets")
+    if len(sizes) == 0 or len(sizes) != len(fields):
+        raise ValueError(f"{len(sizes)} mesh sizes and {len(fields)} {fields_name}")
     if not (0 <= int(max_steps) <= _native_mesh.MAX_STEPS):
         raise ValueError(f"max_steps = {max_steps}; 0..{_native_mesh.MAX_STEPS} (the loop has to end)")
     if not (0 < cfl < float('inf') and 0 <= tol < float('inf')):
         raise ValueError(f"cfl = {cfl}, tol = {tol}; cfl > 0 and tol >= 0 expected")
     ns = [_side(b, s, route) for b, s in enumerate(sizes)]
-    gauss = [_gaussians(b, p) for b, p in enumerate(pde_params)]
-    kinds = [monitor_kind(b, p, m2n_solve) for b, p in enumerate(pde_params)]
-    if len(set(kinds)) != 1:
-        if 'M2N slow' not in kinds:
-            raise ValueError(f"mesh_type 'ma' for {kinds.count('ma')} meshes and 'M2N' for {kinds.count('M2N')}: all meshes of one call "
-                             "share one monitor (one launch per call); split the batch")
-        raise ValueError("monitors " + ', '.join(f"{k!r} for {kinds.count(k)}" for k in sorted(set(kinds))) + " meshes: all meshes of one "
-                         "call share one monitor (one launch per call); split the batch")
-    m2n, slow = kinds[0] == 'M2N', kinds[0] == 'M2N slow'
-    if slow:
-        if route != 'lane':
-            raise ValueError(f"route = {route!r}: the M2N 'slow' monitor runs on route='lane' only (its band solve lives in LDS)")
-        for b, n in enumerate(ns):
-            if n > SLOW_MAX_SIDE:
-                raise ValueError(f"mesh {b}: N = {n}; the M2N 'slow' monitor goes up to {SLOW_MAX_SIDE} a side (the band of the P1 solve "
-                                 "stays in LDS)")
-    mon = [(m2n_slow_constants if slow else m2n_constants if m2n else monitor_constants)(p) for p in pde_params]
+    counts, strides, inputs, entry, overflow, slow = describe(ns)
     B = len(ns)
 
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device() if torch.cuda.is_available() else 0)
@@ -298,31 +283,24 @@ def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
         raise NativeError("Monge-Ampere meshes are built on the GPU only (libgadapt_mesh.so): no CUDA/HIP device is visible; "
                           "there is no CPU fallback")
 
-    desc, noff, goff = [], 0, 0
-    for n, g in zip(ns, gauss):
-        desc += [n, noff, goff, len(g)]
-        noff, goff = noff + n * n, goff + len(g)
-    if noff >= 2 ** 31:
-        raise ValueError("more than 2^31 nodes in one batch")
+    desc, noff, off = [], 0, 0
+    for n, count, stride in zip(ns, counts, strides):
+        desc += [n, noff, off, count]
+        noff, off = noff + n * n, off + stride
+    if noff >= 2 ** 31 or off >= 2 ** 31:
+        raise ValueError(overflow)
     desc_host = (C.c_int32 * len(desc))(*desc)
     desc_dev = torch.tensor(desc, dtype=torch.int32).to(dev)
-    rows = [r for g in gauss for r in g] or [[0.0] * 4]                  # never an empty allocation behind the pointer
-    gauss_dev = torch.tensor(rows, dtype=torch.float32).to(dev)
-    mon_dev = torch.tensor(mon, dtype=torch.float32).to(dev)
+    ins = inputs(dev)
     x = torch.empty(noff, dtype=torch.float32, device=dev)
     y = torch.empty_like(x)
     steps = torch.empty(B, dtype=torch.int32, device=dev)
     residual = torch.empty(B, dtype=torch.float32, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
     monitor = torch.empty_like(x) if slow else None
-    args = (B, C.cast(desc_host, C.c_void_p), desc_dev.data_ptr(), gauss_dev.data_ptr(), mon_dev.data_ptr(), float(cfl), float(tol),
-            int(max_steps), x.data_ptr(), y.data_ptr(), steps.data_ptr(), residual.data_ptr(), status.data_ptr())
-    keep = (desc_host, desc_dev, gauss_dev, mon_dev)                     # what the argument list points into
-
-    if slow:
-        args, entry = args + (monitor.data_ptr(),), 'gadapt_ma_m2n_slow_batch'
-    else:
-        entry = ('gadapt_ma_m2n_batch' if m2n else 'gadapt_ma_batch') + ('_strided' if route == 'strided' else '')
+    args = (B, C.cast(desc_host, C.c_void_p), desc_dev.data_ptr(), *(t.data_ptr() for t in ins), float(cfl), float(tol), int(max_steps),
+            x.data_ptr(), y.data_ptr(), steps.data_ptr(), residual.data_ptr(), status.data_ptr()) + ((monitor.data_ptr(),) if slow else ())
+    keep = (desc_host, desc_dev, ins)                                    # what the argument list points into
 
     def launch(_keep=keep):                                              # the closure keeps the inputs alive
         with torch.cuda.device(dev):
@@ -338,6 +316,41 @@ def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: fl
         return MASlowResult(out, steps, residual, status, mons) if slow else MAResult(out, steps, residual, status)
 
     return launch, collect
+
+
+def _prepare(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000, device=None,
+             route: str = 'lane', m2n_solve: Optional[str] = None):
+    """The host side of `ma_batch`: checks, the batch's descriptors and Gaussians on the GPU, the argument list.  Returns
+    (launch, collect): `launch()` issues the one kernel (it may be issued again), `collect()` gives the MAResult (the
+    MASlowResult under the 'slow' monitor)."""
+    def describe(ns):
+        gauss = [_gaussians(b, p) for b, p in enumerate(pde_params)]
+        kinds = [monitor_kind(b, p, m2n_solve) for b, p in enumerate(pde_params)]
+        if len(set(kinds)) != 1:
+            if 'M2N slow' not in kinds:
+                raise ValueError(f"mesh_type 'ma' for {kinds.count('ma')} meshes and 'M2N' for {kinds.count('M2N')}: all meshes of one call "
+                                 "share one monitor (one launch per call); split the batch")
+            raise ValueError("monitors " + ', '.join(f"{k!r} for {kinds.count(k)}" for k in sorted(set(kinds))) + " meshes: all meshes of one "
+                             "call share one monitor (one launch per call); split the batch")
+        m2n, slow = kinds[0] == 'M2N', kinds[0] == 'M2N slow'
+        if slow:
+            if route != 'lane':
+                raise ValueError(f"route = {route!r}: the M2N 'slow' monitor runs on route='lane' only (its band solve lives in LDS)")
+            for b, n in enumerate(ns):
+                if n > SLOW_MAX_SIDE:
+                    raise ValueError(f"mesh {b}: N = {n}; the M2N 'slow' monitor goes up to {SLOW_MAX_SIDE} a side (the band of the P1 solve "
+                                     "stays in LDS)")
+        mon = [(m2n_slow_constants if slow else m2n_constants if m2n else monitor_constants)(p) for p in pde_params]
+        rows = [r for g in gauss for r in g] or [[0.0] * 4]              # never an empty allocation behind the pointer
+        if slow:
+            entry = 'gadapt_ma_m2n_slow_batch'
+        else:
+            entry = ('gadapt_ma_m2n_batch' if m2n else 'gadapt_ma_batch') + ('_strided' if route == 'strided' else '')
+        counts = [len(g) for g in gauss]
+        return (counts, counts, lambda dev: (torch.tensor(rows, dtype=torch.float32).to(dev), torch.tensor(mon, dtype=torch.float32).to(dev)),
+                entry, "more than 2^31 nodes in one batch", slow)
+
+    return _prepare_common(sizes, pde_params, 'parameter sets', describe, cfl=cfl, tol=tol, max_steps=max_steps, device=device, route=route)
 
 
 def ma_batch(sizes: Sequence, pde_params: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000,
@@ -419,54 +432,13 @@ def _prepare_table(sizes: Sequence, tables: Sequence, *, cfl: float = 0.2, tol: 
                    route: str = 'lane'):
     """The host side of `ma_table_batch`, split like `_prepare`: checks, the batch's descriptors and tables on the GPU, the
     argument list.  Returns (launch, collect)."""
-    if route not in ROUTES:
-        raise ValueError(f"route = {route!r}; one of {ROUTES}")
-    if len(sizes) == 0 or len(sizes) != len(tables):
-        raise ValueError(f"{len(sizes)} mesh sizes and {len(tables)} monitor tables")
-    if not (0 <= int(max_steps) <= _native_mesh.MAX_STEPS):
-        raise ValueError(f"max_steps = {max_steps}; 0..{_native_mesh.MAX_STEPS} (the loop has to end)")
-    if not (0 < cfl < float('inf') and 0 <= tol < float('inf')):
-        raise ValueError(f"cfl = {cfl}, tol = {tol}; cfl > 0 and tol >= 0 expected")
-    ns = [_side(b, s, route) for b, s in enumerate(sizes)]
-    ts = [_table_side(b, t) for b, t in enumerate(tables)]
-    B = len(ns)
+    def describe(ns):
+        ts = [_table_side(b, t) for b, t in enumerate(tables)]
+        return (ts, [t * t for t in ts],
+                lambda dev: (torch.cat([t.detach().to(device=dev, dtype=torch.float32).reshape(-1) for t in tables]).contiguous(),),
+                'gadapt_ma_table_batch' + ('_strided' if route == 'strided' else ''), "more than 2^31 nodes or table entries in one batch", False)
 
-    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device() if torch.cuda.is_available() else 0)
-    if dev.type != 'cuda' or not torch.cuda.is_available():
-        raise NativeError("Monge-Ampere meshes are built on the GPU only (libgadapt_mesh.so): no CUDA/HIP device is visible; "
-                          "there is no CPU fallback")
-
-    desc, noff, toff = [], 0, 0
-    for n, t in zip(ns, ts):
-        desc += [n, noff, toff, t]
-        noff, toff = noff + n * n, toff + t * t
-    if noff >= 2 ** 31 or toff >= 2 ** 31:
-        raise ValueError("more than 2^31 nodes or table entries in one batch")
-    desc_host = (C.c_int32 * len(desc))(*desc)
-    desc_dev = torch.tensor(desc, dtype=torch.int32).to(dev)
-    tables_dev = torch.cat([t.detach().to(device=dev, dtype=torch.float32).reshape(-1) for t in tables]).contiguous()
-    x = torch.empty(noff, dtype=torch.float32, device=dev)
-    y = torch.empty_like(x)
-    steps = torch.empty(B, dtype=torch.int32, device=dev)
-    residual = torch.empty(B, dtype=torch.float32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev)
-    args = (B, C.cast(desc_host, C.c_void_p), desc_dev.data_ptr(), tables_dev.data_ptr(), float(cfl), float(tol), int(max_steps),
-            x.data_ptr(), y.data_ptr(), steps.data_ptr(), residual.data_ptr(), status.data_ptr())
-    keep = (desc_host, desc_dev, tables_dev)                             # what the argument list points into
-    entry = 'gadapt_ma_table_batch' + ('_strided' if route == 'strided' else '')
-
-    def launch(_keep=keep):                                              # the closure keeps the inputs alive
-        with torch.cuda.device(dev):
-            _native_mesh.check(getattr(_native_mesh.lib(), entry)(*args, current_stream(dev)), entry)
-
-    def collect():
-        out, o = [], 0
-        for n in ns:
-            out.append(torch.stack([x[o:o + n * n].view(n, n), y[o:o + n * n].view(n, n)]))
-            o += n * n
-        return MAResult(out, steps, residual, status)
-
-    return launch, collect
+    return _prepare_common(sizes, tables, 'monitor tables', describe, cfl=cfl, tol=tol, max_steps=max_steps, device=device, route=route)
 
 
 def ma_table_batch(sizes: Sequence, tables: Sequence, *, cfl: float = 0.2, tol: float = 1e-4, max_steps: int = 20000,

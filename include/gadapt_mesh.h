@@ -1,6 +1,8 @@
 /*
  * gadapt_mesh.h - C-ABI of the classical target-mesh generators: batched MMPDE5 and, further down, batched Monge-Ampere
  * (libgadapt_mesh.so; one node per lane up to 32 x 32, and a strided route with an fp64 potential up to 81 x 81).
+ * The Monge-Ampere iteration that the entry points below share is stated once in g_adaptivity_amd/mesh_csrc/ma_iteration.h
+ * (device side) and ma_host.h (the batch check and the launch geometry); a kernel file holds what is its monitor's own.
  *
  * The reference builds the target mesh `x_phys` of loss_type='mesh_loss' with the moving-mesh PDE "MMPDE5"
  * (classical_meshing/ma_mesh_1d.py:7-134, ma_mesh_2d.py:11-103, called from src/data.py:394-416): classical RK4 in
