@@ -82,6 +82,12 @@ def eval_lattice(n_eval: int) -> torch.Tensor:
     return torch.from_numpy(np.linspace(0, 1, int(n_eval)))
 
 
+def _require_gpu(t, what: str):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise NativeError(f"{what}: the FEM tail runs on the MI355X only (got a "
+                          f"{t.device if torch.is_tensor(t) else type(t).__name__} tensor); there is no CPU fallback")
+
+
 def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params: Sequence[dict], n_eval: int, *,
                         cells: Optional[torch.Tensor] = None, boundary: Optional[torch.Tensor] = None,
                         tri_counts: Optional[Sequence[int]] = None, opt: Optional[dict] = None, band: str = 'lds',
@@ -100,9 +106,7 @@ def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params:
     LDS budget leaves): square meshes up to 81 x 81 nodes.  The windowed route factors and substitutes in fp64 and evaluates
     the load vector's forcing in fp64 (fp32 missed the evaluation's accuracy rule from 27 x 27 on), so where both routes take
     a mesh their norms agree to the fp32 rounding of those, not bitwise; the result does not depend on `tri_slab`, bit for bit."""
-    if not torch.is_tensor(x) or not x.is_cuda:
-        raise NativeError(f"poisson_eval_errors: the FEM tail runs on the MI355X only (got a "
-                          f"{x.device if torch.is_tensor(x) else type(x).__name__} tensor); there is no CPU fallback")
+    _require_gpu(x, 'poisson_eval_errors')
     opt = opt or {}
     tri_slab = _check_route('poisson_eval_errors', band, tri_slab)
     n_eval = int(n_eval)

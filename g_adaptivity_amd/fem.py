@@ -33,6 +33,20 @@ each (gadapt_fem_backward_wave, gadapt_fem_backward_window_wave): the same gradi
 axes, the Gaussians' buffers: `gnn_pde_tail` on a batch that carries one (`data._pde_batch`) only launches, so it can be
 captured in a hipGraph, and `set_params` feeds the Gaussians of the next batch into the same buffers
 (`training.GraphedTrainStep` does both for a pde_loss model).
+
+The argument contract (`_check_batch_2d` and `_check_cells`, called by every public entry point before anything is allocated,
+before the device is looked at and before the library is loaded; tests/test_entry_contracts_host.py pins it row by row):
+
+    lengths   x_phys is [N,2] with N == sum(node_counts), which is the topology's n_nodes; node_counts is not empty and every
+              mesh has at least 3 nodes (one triangle); len(pde_params) == len(node_counts), and every Gaussian centre and
+              scale has two components; cells is [T,3] of an integer dtype (a [3,T] or 1-D array is refused, never reshaped),
+              T == sum(tri_counts) where those are given; boundary holds N flags
+    dtypes    coordinates are fp32 or TypeError - nothing is cast (`gradient_meshpoints_2D` alone, which is handed the training
+              loop's detached x_phys, takes any floating dtype and gives `modular_loss_2d` its fp32 cast; integer and complex
+              tensors are a TypeError there too); cells may be any integer dtype, boundary bool or any integer dtype
+    layouts   any strides and storage offset: what reaches a kernel is a contiguous tensor, and x_phys.grad has x_phys's shape
+    errors    ValueError for lengths, TypeError for dtypes, with the function's name and the two numbers that disagree
+              (an x_phys that is not [N,2] stays a NotImplementedError); a well-formed call on CPU tensors is a NativeError
 """
 from __future__ import annotations
 
@@ -60,8 +74,71 @@ WINDOW_HINT = ("; the evaluation (poisson_eval_errors, evaluate_model_fine) take
 def _require_gpu(t: torch.Tensor, what: str):
     if not t.is_cuda:
         raise NativeError(f"{what}: the FEM tail runs on the MI355X only (got a {t.device} tensor); there is no CPU fallback")
+    _check_fp32(what, t)
+
+
+def _check_fp32(what: str, t):
+    """The 2-D dtype rule, the one place it is enforced: fp32 coordinates or TypeError."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what}: the coordinates must be a tensor (got {type(t).__name__})")
     if t.dtype != torch.float32:
         raise TypeError(f"{what}: fp32 expected, got {t.dtype}")
+
+
+def _check_cells(what: str, cells, boundary, n_nodes: int, tri_counts: Optional[Sequence[int]] = None):
+    """cells [T,3] integer and boundary [N] (tensors or numpy arrays), on the host alone."""
+    shape = tuple(cells.shape)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"{what}: cells must be [T,3] (got {shape}); a [3,T] or flat array is not reshaped")
+    kind = cells.dtype.kind if isinstance(cells, np.ndarray) else ('f' if cells.dtype.is_floating_point or cells.dtype.is_complex
+                                                                   or cells.dtype == torch.bool else 'i')
+    if kind not in 'iu':
+        raise TypeError(f"{what}: cells must hold integer node ids (got {cells.dtype})")
+    if tri_counts is not None and shape[0] != int(sum(int(t) for t in tri_counts)):
+        raise ValueError(f"{what}: {shape[0]} cells for tri_counts summing to {int(sum(int(t) for t in tri_counts))}")
+    if boundary is not None:
+        bshape = tuple(boundary.shape)
+        if len(bshape) != 1 or bshape[0] != n_nodes:
+            raise ValueError(f"{what}: {bshape} boundary flags for {n_nodes} nodes")
+
+
+def _check_gaussians(what: str, pde_params: Sequence[dict], n_meshes: int):
+    if len(pde_params) != n_meshes:
+        raise ValueError(f"{what}: Gaussians of {len(pde_params)} meshes for node_counts of {n_meshes} meshes")
+    for b, p in enumerate(pde_params):
+        if len(p['centers']) != len(p['scales']):
+            raise ValueError(f"{what}: mesh {b} has {len(p['centers'])} centres and {len(p['scales'])} scales")
+        for name in ('centers', 'scales'):
+            for v in p[name]:
+                k = int(v.numel() if torch.is_tensor(v) else np.asarray(v).size)
+                if k != 2:
+                    raise ValueError(f"{what}: a Gaussian's {name[:-1]} of mesh {b} has {k} components; 2 in 2-D")
+
+
+def _check_batch_2d(what: str, x_phys, node_counts: Sequence[int], pde_params: Optional[Sequence[dict]] = None, cells=None,
+                    boundary=None, tri_counts: Optional[Sequence[int]] = None, cast: bool = False) -> list:
+    """The 2-D argument contract (module docstring), on the host alone: nothing is allocated, no device or library is touched.
+    `cast`: the caller casts a floating x_phys to fp32 (gradient_meshpoints_2D).  Returns the node counts as ints."""
+    if cast:
+        if not torch.is_tensor(x_phys) or not x_phys.dtype.is_floating_point:
+            raise TypeError(f"{what}: x_phys must be a floating-point tensor (got "
+                            f"{x_phys.dtype if torch.is_tensor(x_phys) else type(x_phys).__name__})")
+    else:
+        _check_fp32(what, x_phys)
+    if x_phys.dim() != 2 or x_phys.shape[1] != 2:
+        raise NotImplementedError(f"{what}: x_phys must be [N,2], 2-D meshes only (got {tuple(x_phys.shape)})")
+    counts = [int(n) for n in node_counts]
+    if not counts:
+        raise ValueError(f"{what}: node_counts is empty (0 meshes for {x_phys.shape[0]} coordinates)")
+    if min(counts) < 3:
+        raise ValueError(f"{what}: every mesh needs at least 3 nodes (got {min(counts)})")
+    if x_phys.shape[0] != sum(counts):
+        raise ValueError(f"{what}: {x_phys.shape[0]} coordinates for {sum(counts)} nodes (the sum of node_counts)")
+    if pde_params is not None:
+        _check_gaussians(what, pde_params, len(counts))
+    if cells is not None:
+        _check_cells(what, cells, boundary, sum(counts), tri_counts)
+    return counts
 
 
 def boundary_from_cells(cells: np.ndarray, n_nodes: int) -> np.ndarray:
@@ -85,10 +162,16 @@ class FemTopology:
         band='window': square meshes up to 81 x 81 nodes); `lds_bytes` is then the ring's."""
         if band not in BAND_ROUTES:
             raise ValueError(f"FEM topology: band must be one of {BAND_ROUTES} (got {band!r})")
-        lib = _nf.lib()
         B = len(node_counts)
-        cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
-        bnd = np.ascontiguousarray(boundary, dtype=np.uint8).reshape(-1)
+        if B < 1 or len(tri_counts) != B:
+            raise ValueError(f"FEM topology: node_counts of {B} meshes and tri_counts of {len(tri_counts)}")
+        cells, boundary = np.asarray(cells), np.asarray(boundary)
+        _check_cells('FEM topology', cells, None, int(np.sum(node_counts)))
+        if boundary.ndim != 1:
+            raise ValueError(f"FEM topology: boundary must be [N] (got {boundary.shape})")
+        lib = _nf.lib()
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        bnd = np.ascontiguousarray(boundary, dtype=np.uint8)
         node_off = np.zeros(B + 1, np.int32); node_off[1:] = np.cumsum(node_counts)
         tri_off = np.zeros(B + 1, np.int32); tri_off[1:] = np.cumsum(tri_counts)
         N, T = int(node_off[-1]), int(tri_off[-1])
@@ -137,7 +220,11 @@ class FemTopology:
 
     def head(self, gptr, gpar, x, lat_x, lat_y, nlat: int, tri_mesh: bool = False, max_tris: bool = True) -> tuple:
         """The arguments every 2-D entry point of include/gadapt_fem.h starts with, in its order: sizes, topology (with
-        tri_mesh where the entry point differentiates), Gaussians, coordinates, lattice, max_lds_bytes and max_tris."""
+        tri_mesh where the entry point differentiates), Gaussians, coordinates, lattice, max_lds_bytes and max_tris.
+        The last guard before the addresses leave: the kernels read gptr[b + 1] of every mesh and x[2 n + 1] of every node."""
+        if gptr.numel() != self.n_meshes + 1 or x.numel() != 2 * self.n_nodes or not x.is_contiguous():
+            raise ValueError(f"FEM topology of {self.n_meshes} meshes and {self.n_nodes} nodes: Gaussians of {gptr.numel() - 1} meshes, "
+                             f"{x.numel()} coordinate values{'' if x.is_contiguous() else ' (not contiguous)'}")
         return (self._head[tri_mesh] + (gptr.data_ptr(), gpar.data_ptr(), x.data_ptr(), lat_x.data_ptr(), lat_y.data_ptr(), nlat,
                                         self.lds_bytes) + ((self.max_tris,) if max_tris else ()))
 
@@ -205,13 +292,19 @@ def _solve_tail(topo: FemTopology, rhs, coeffs, factor, tri_slab: int) -> tuple:
     return (rhs.data_ptr(), coeffs.data_ptr(), _ptr(factor)) + ((tri_slab,) if topo.route == 'window' else ())
 
 
+def _host(v):
+    return v.detach().cpu().numpy() if torch.is_tensor(v) else v
+
+
 def _gaussian_rows(pde_params: Sequence[dict]) -> Tuple[np.ndarray, np.ndarray]:
     """(cumulative counts [B+1] int32, rows [G,4] fp32 = (c0, c1, s0, s1)) on the host: per mesh its own number of Gaussians."""
     counts, rows = [0], []
     for p in pde_params:
         cs, ss = p['centers'], p['scales']
         for c, s in zip(cs, ss):
-            c, s = np.asarray(c, np.float32).reshape(-1), np.asarray(s, np.float32).reshape(-1)
+            c, s = np.asarray(_host(c), np.float32).reshape(-1), np.asarray(_host(s), np.float32).reshape(-1)
+            if c.size != 2 or s.size != 2:
+                raise ValueError(f"2-D Gaussians: a centre of {c.size} and a scale of {s.size} components; 2 each")
             rows.append([c[0], c[1], s[0], s[1]])
         counts.append(len(cs))
     return np.cumsum(counts).astype(np.int32), np.asarray(rows, np.float32).reshape(-1, 4)
@@ -247,7 +340,7 @@ class _FemPoisson(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, topo: FemTopology, gptr, gpar, lat_x, lat_y, tri_slab=0, adjoint='lane'):
         _require_gpu(x, 'FEM node coordinates')
-        x = x.contiguous()
+        x = x.detach().contiguous()
         dev, nlat = x.device, int(lat_x.numel())
         rhs, coeffs = torch.empty(topo.n_nodes, device=dev), torch.empty(topo.n_nodes, device=dev)
         sol = torch.empty(topo.n_meshes * nlat * nlat, device=dev)
@@ -305,9 +398,8 @@ def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
     (gadapt_fem_backward[_window]_wave).  The gradient is the same, bit for bit."""
     tri_slab = _check_route('pde_loss FEM tail', band, tri_slab)
     _check_adjoint('pde_loss FEM tail', adjoint)
+    node_counts = _check_batch_2d('pde_loss FEM tail (fem_poisson)', x_phys, node_counts, pde_params, cells, boundary, tri_counts)
     _require_gpu(x_phys, 'pde_loss FEM tail')
-    if x_phys.dim() != 2 or x_phys.shape[1] != 2:
-        raise NotImplementedError(f"pde_loss FEM tail: 2-D meshes only (x_phys {tuple(x_phys.shape)})")
     dev = x_phys.device
     if tri_counts is None:
         tri_counts = _tri_counts(cells, node_counts)
@@ -479,6 +571,7 @@ class PdeBatch:
     def solve(self, x_phys: torch.Tensor):
         """(coeffs [N,1], sol [B*Q]) of `fem_poisson` on this topology and the Gaussians last set: the same entry points on
         the same inputs, the same bits."""
+        _check_fp32('PdeBatch', x_phys)
         if x_phys.dim() != 2 or x_phys.shape[1] != 2 or x_phys.shape[0] != self.n_nodes:
             raise ValueError(f"PdeBatch: x_phys {tuple(x_phys.shape)} for a topology of {self.n_nodes} nodes in 2-D")
         coeffs, sol = _FemPoisson.apply(x_phys, self.topo, self.gptr, self.gpar, self.lat_x, self.lat_y, self.tri_slab, self.adjoint)
@@ -514,19 +607,18 @@ def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.T
     walks of the backward, the same bits)."""
     tri_slab = _check_route('modular loss (2-D)', band, tri_slab)
     _check_adjoint('modular loss (2-D)', adjoint)
-    _require_gpu(x_phys, 'modular loss (2-D)')
-    if x_phys.dim() != 2 or x_phys.shape[1] != 2:
-        raise NotImplementedError(f"modular loss (2-D): x_phys must be [N,2] (got {tuple(x_phys.shape)})")
+    node_counts = _check_batch_2d('modular loss (2-D)', x_phys, node_counts, pde_params, cells, boundary, tri_counts)
     if reduction not in _REDUCTIONS:
         raise ValueError(f"modular loss (2-D): reduction must be one of {sorted(_REDUCTIONS)} (got {reduction!r})")
+    n_lat = int(n_lat)
+    if n_lat < 2 or (reduction == 'simpson' and (n_lat < 3 or n_lat % 2 == 0)):
+        raise ValueError(f"modular loss (2-D): {n_lat} lattice points per dimension for reduction {reduction!r}")
+    _require_gpu(x_phys, 'modular loss (2-D)')
     lib = _nf.lib()
     n_built = int(lib.gadapt_fem_simpson_points())
     if n_load is not None and int(n_load) != n_built:
         raise NotImplementedError(f"modular loss (2-D): the load vector's Simpson rule is built for {n_built} points per "
                                   f"dimension only (got {int(n_load)})")
-    n_lat = int(n_lat)
-    if n_lat < 2 or (reduction == 'simpson' and (n_lat < 3 or n_lat % 2 == 0)):
-        raise ValueError(f"modular loss (2-D): {n_lat} lattice points per dimension for reduction {reduction!r}")
     dev = x_phys.device
     x = x_phys.detach().contiguous()
     if tri_counts is None:
@@ -619,9 +711,9 @@ def gradient_meshpoints_2D(opt, data, x_phys):
     band = opt.get('fem_band', 'lds')
     _check_route('gradient_meshpoints_2D', band, 0)
     adjoint = _check_adjoint("gradient_meshpoints_2D (opt['fem_adjoint'])", opt.get('fem_adjoint', 'lane'))
-    _require_gpu(x_phys.detach().float(), 'gradient_meshpoints_2D')
     n_load, n_lat, reduction = _modular_quadrature(opt, gt)
     cells, boundary, node_counts, tri_counts, params = _modular_batch(opt, data, x_phys.shape[0])
+    _check_batch_2d('gradient_meshpoints_2D', x_phys, node_counts, params, cells, boundary, tri_counts, cast=True)
     loss, x_grads = modular_loss_2d(x_phys.detach().float(), cells, boundary, node_counts, params, n_lat, reduction,
                                     n_load=n_load, tri_counts=tri_counts, band=band, adjoint=adjoint)
     return loss.mean(), x_grads

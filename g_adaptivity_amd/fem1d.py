@@ -13,6 +13,20 @@ mesh, the mesh's state in LDS.
 
 Gradients are with respect to the node coordinates (and, for `torch_FEM_Burgers_1D`, the incoming coefficients).  The
 Burgers initial projection and the Poisson boundary values are detached, as in the reference.  There is no CPU fallback.
+
+The argument contract (`_check_batch`, called by every public entry point before anything is allocated, before the device is
+looked at and before the library is loaded; tests/test_entry_contracts_host.py pins it row by row):
+
+    lengths   x is [N] with N == sum(node_counts); node_counts is not empty and every count is at least the entry point's
+              minimum (2 for the Burgers steps, the projection and `fn_expansion`, 3 for the Poisson solves);
+              len(pde_params) == len(node_counts); u0, un_coeffs and coeffs hold N values; bc holds 2 per mesh; a target holds
+              B * P values; there is at least one evaluation point (the kernels' loops over P = 0 points would be empty, but
+              the [B, 0] result has no address to hand to the C-ABI, which refuses a null `sol`: P = 0 is refused here)
+    dtypes    every tensor argument is cast to fp32 (`_f32`: any floating dtype, fp32 is passed through untouched), and the
+              gradient returns in the caller's dtype; integer, bool and complex tensors are a TypeError
+    layouts   any strides and storage offset: what reaches a kernel is a contiguous fp32 tensor, and x.grad has x's shape
+    errors    ValueError for lengths, TypeError for dtypes, with the function's name and the two numbers that disagree; a
+              well-formed call on CPU tensors is a NativeError.  More than 1024 nodes per mesh stays a NotImplementedError.
 """
 from __future__ import annotations
 
@@ -45,12 +59,58 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _check_float(what: str, name: str, t):
+    """The 1-D dtype rule's refusing half: a tensor of a floating dtype, or TypeError."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what}: {name} must be a tensor (got {type(t).__name__})")
+    if not t.dtype.is_floating_point:
+        raise TypeError(f"{what}: {name} must be a floating-point tensor, which is cast to fp32 (got {t.dtype})")
+
+
+def _f32(t: torch.Tensor) -> torch.Tensor:
+    """The 1-D dtype rule's casting half, the one place it is done: fp32 of any floating dtype, differentiably, so that
+    autograd hands the gradient back in the caller's dtype.  An fp32 tensor is returned as it is."""
+    return t.float()
+
+
+def _check_batch(what: str, x, node_counts: Sequence[int], pde_params: Optional[Sequence[dict]] = None, *, min_nodes: int = 2,
+                 n_points: Optional[int] = None, **per_node) -> list:
+    """The 1-D argument contract (module docstring), on the host alone: nothing is allocated, no device or library is touched.
+    `per_node` are the tensors that hold one value per node (u0=..., un_coeffs=..., coeffs=...; None is skipped).  Returns the
+    node counts as a list of ints."""
+    _check_float(what, 'x', x)
+    if x.dim() != 1:
+        raise ValueError(f"{what}: x must be [N] (got {tuple(x.shape)})")
+    counts = [int(n) for n in node_counts]
+    if not counts:
+        raise ValueError(f"{what}: node_counts is empty (0 meshes for {x.shape[0]} coordinates)")
+    if min(counts) < min_nodes:
+        raise ValueError(f"{what}: every mesh needs at least {min_nodes} nodes (got {min(counts)})")
+    if x.shape[0] != sum(counts):
+        raise ValueError(f"{what}: {x.shape[0]} coordinates for node_counts summing to {sum(counts)}")
+    if pde_params is not None and len(pde_params) != len(counts):
+        raise ValueError(f"{what}: Gaussians of {len(pde_params)} meshes for node_counts of {len(counts)} meshes")
+    for name, t in per_node.items():
+        if t is None:
+            continue
+        _check_float(what, name, t)
+        if t.numel() != sum(counts):
+            raise ValueError(f"{what}: {name} holds {t.numel()} values for {sum(counts)} nodes")
+    if n_points is not None and n_points < 1:
+        raise ValueError(f"{what}: {n_points} evaluation points; at least 1 (a [B, 0] result has no address for the kernel)")
+    return counts
+
+
 class _Batch:
     """node_off, the node cap and the packed Gaussians of one call, on the device, and the arguments every 1-D entry point of
     include/gadapt_fem.h starts with (`head`).  The pointers of its own tensors are taken once, here."""
 
     def __init__(self, node_counts: Sequence[int], pde_params: Optional[Sequence[dict]], device, n_fine: int = 0):
         counts = [int(n) for n in node_counts]
+        if not counts:
+            raise ValueError("1-D FEM tail: node_counts is empty")
+        if pde_params is not None and len(pde_params) != len(counts):                # the kernels read gptr[b + 1] of every mesh
+            raise ValueError(f"1-D FEM tail: Gaussians of {len(pde_params)} meshes for node_counts of {len(counts)} meshes")
         self.counts, self.B, self.nmax, self.n_fine = counts, len(counts), max(counts), n_fine
         self.device = device
         lib = _nf.lib()
@@ -157,7 +217,7 @@ class _Burgers(torch.autograd.Function):
         sol = torch.empty(B, P, device=dev)
         fine = torch.empty(B, P, device=dev) if bt.n_fine > 1 else None
         flags = torch.empty(B, dtype=torch.int32, device=dev)
-        u0c = None if u0 is None else u0.detach().float().contiguous()
+        u0c = None if u0 is None else u0.detach().contiguous()
         _burgers_forward(bt, x, u0c, bc, cfg, T, pts, hist, sol, fine, flags)
         _watch_flags(flags)
         ctx.bt, ctx.cfg, ctx.has_u0 = bt, cfg, u0 is not None
@@ -196,17 +256,24 @@ def burgers_1d(x: torch.Tensor, node_counts: Sequence[int], pde_params: Optional
     (get_Burgers_initial_coeffs) and, with fine=True, runs the same steps on linspace(0, 1, num_fine_mesh_points).
     Returns coeffs [N] (u^T), sol [B,P] (u^T at the points, default linspace(0, 1, eval_quad_points)) and fine_sol [B,P]
     (or None).  Differentiable in x and u0."""
-    _require_gpu(x, 'burgers_1d')
-    if x.dim() != 1:
-        raise ValueError(f"burgers_1d: x must be [N] (got {tuple(x.shape)})")
+    pts = _points(opt, x.device if torch.is_tensor(x) else None, points)
+    counts = _check_batch('burgers_1d', x, node_counts, pde_params, n_points=pts.numel(), u0=u0)
     if int(n_steps) < 1:
         raise ValueError("burgers_1d: n_steps >= 1")
-    n_fine = int(opt.get('num_fine_mesh_points', 0)) if (fine and u0 is None) else 0
-    bt = _Batch(node_counts, pde_params if u0 is None or n_fine > 1 else None, x.device, n_fine)
-    pts = _points(opt, x.device, points)
+    if u0 is None and pde_params is None:
+        raise ValueError("burgers_1d: neither u0 nor pde_params: nothing to start from")
     if bc is not None:
-        bc = bc.detach().to(device=x.device, dtype=torch.float32).contiguous().view(bt.B, 2)
-    last, sol, fsol = _Burgers.apply(x.float(), u0, bt, _burgers_cfg(opt, n_steps), pts, bc)
+        _check_float('burgers_1d', 'bc', bc)
+        if bc.numel() != 2 * len(counts):
+            raise ValueError(f"burgers_1d: bc holds {bc.numel()} values for {len(counts)} meshes (2 per mesh)")
+    _require_gpu(x, 'burgers_1d')
+    n_fine = int(opt.get('num_fine_mesh_points', 0)) if (fine and u0 is None) else 0
+    bt = _Batch(counts, pde_params if u0 is None or n_fine > 1 else None, x.device, n_fine)
+    if bc is not None:
+        bc = _f32(bc.detach()).to(device=x.device).reshape(bt.B, 2).contiguous()
+    if u0 is not None:
+        u0 = _f32(u0).reshape(-1)
+    last, sol, fsol = _Burgers.apply(_f32(x), u0, bt, _burgers_cfg(opt, n_steps), pts, bc)
     return last, sol, fsol
 
 
@@ -242,16 +309,15 @@ def _poisson_on(bt: _Batch, x: torch.Tensor, opt, points=None):
     if min(bt.counts) < 3:
         raise ValueError("fem_poisson_1d: every mesh needs at least 3 nodes")
     pts = _points(opt, x.device, points)
-    return _Poisson.apply(x.float(), bt, int(opt.get('load_quad_points', 101)), int(opt.get('stiff_quad_points', 3)), pts)
+    return _Poisson.apply(_f32(x), bt, int(opt.get('load_quad_points', 101)), int(opt.get('stiff_quad_points', 3)), pts)
 
 
 def fem_poisson_1d(x: torch.Tensor, node_counts: Sequence[int], pde_params: Sequence[dict], opt, points=None):
     """torch_FEM_1D on every mesh of x [N]: coeffs [N] (u_true at the end nodes, detached; the solve inside) and sol [B,P].
-    Differentiable in x."""
+    Differentiable in x.  At least one evaluation point: P = 0 is refused (module docstring)."""
+    counts = _check_batch('fem_poisson_1d', x, node_counts, pde_params, min_nodes=3, n_points=_points(opt, None, points).numel())
     _require_gpu(x, 'fem_poisson_1d')
-    if x.dim() != 1:
-        raise ValueError(f"fem_poisson_1d: x must be [N] (got {tuple(x.shape)})")
-    return _poisson_on(_Batch(node_counts, pde_params, x.device), x, opt, points)
+    return _poisson_on(_Batch(counts, pde_params, x.device), x, opt, points)
 
 
 # ---------------------------------------------------------------------------------------------- the 1-D pde_loss tail
@@ -302,14 +368,19 @@ class _PoissonLoss(torch.autograd.Function):
 def _poisson_loss_on(bt, x: torch.Tensor, target: torch.Tensor, k_load: int, k_stiff: int, pts: torch.Tensor, loss: str):
     if loss not in LOSS_KINDS:
         raise ValueError(f"fused 1-D Poisson tail: loss must be one of {sorted(LOSS_KINDS)} (got {loss!r})")
-    _require_gpu(x, 'poisson_loss_1d')
     if min(bt.counts) < 3:
         raise ValueError("poisson_loss_1d: every mesh needs at least 3 nodes")
-    target = target.detach().to(device=x.device, dtype=torch.float32).contiguous().view(-1)
-    if target.numel() != bt.B * pts.numel():
-        raise ValueError(f"poisson_loss_1d: target of {target.numel()} values for {bt.B} meshes x {pts.numel()} evaluation points")
+    _check_target('poisson_loss_1d', target, bt.B, pts.numel())
+    _require_gpu(x, 'poisson_loss_1d')
+    target = _f32(target.detach()).to(device=x.device).reshape(-1).contiguous()
     _check_loss_size(bt.nmax, pts.numel())
-    return _PoissonLoss.apply(x.float(), bt, k_load, k_stiff, pts, target, LOSS_KINDS[loss])
+    return _PoissonLoss.apply(_f32(x), bt, k_load, k_stiff, pts, target, LOSS_KINDS[loss])
+
+
+def _check_target(what: str, target, B: int, P: int):
+    _check_float(what, 'target', target)
+    if target.numel() != B * P:
+        raise ValueError(f"{what}: target of {target.numel()} values for {B} meshes x {P} evaluation points")
 
 
 def poisson_loss_1d(x: torch.Tensor, node_counts: Sequence[int], pde_params: Sequence[dict], target: torch.Tensor, opt, loss: str = 'l1',
@@ -318,11 +389,13 @@ def poisson_loss_1d(x: torch.Tensor, node_counts: Sequence[int], pde_params: Seq
     through the solve, in ONE launch (gadapt_fem_poisson1d_loss): (loss, coeffs [N], sol [B*P]).  `loss` is differentiable in x
     (its backward is g * gx, gx written by the same launch); coeffs and sol are detached, with the bits of `fem_poisson_1d`, and
     x.grad has the bits of the three launches.  The seed row shares the LDS with the solve: 1017 nodes per mesh at 101 points."""
-    if x.dim() != 1:
-        raise ValueError(f"poisson_loss_1d: x must be [N] (got {tuple(x.shape)})")
+    pts = _points(opt, x.device if torch.is_tensor(x) else None, points)
+    counts = _check_batch('poisson_loss_1d', x, node_counts, pde_params, min_nodes=3, n_points=pts.numel())
+    if loss not in LOSS_KINDS:
+        raise ValueError(f"fused 1-D Poisson tail: loss must be one of {sorted(LOSS_KINDS)} (got {loss!r})")
+    _check_target('poisson_loss_1d', target, len(counts), pts.numel())
     _require_gpu(x, 'poisson_loss_1d')
-    pts = _points(opt, x.device, points)
-    out = _poisson_loss_on(_Batch(node_counts, pde_params, x.device), x, target, int(opt.get('load_quad_points', 101)),
+    out = _poisson_loss_on(_Batch(counts, pde_params, x.device), x, target, int(opt.get('load_quad_points', 101)),
                            int(opt.get('stiff_quad_points', 3)), pts, loss)
     return out[0], out[1], out[2]
 
@@ -403,10 +476,11 @@ class Pde1dBatch:
             self._staged.record()
 
     def _x(self, x_phys: torch.Tensor) -> torch.Tensor:
+        _check_float('Pde1dBatch', 'x_phys', x_phys)
         if x_phys.numel() != self.n_nodes:
             raise ValueError(f"Pde1dBatch: x_phys {tuple(x_phys.shape)} for a batch of {self.n_nodes} nodes in 1-D")
         _require_gpu(x_phys, 'Pde1dBatch')
-        return x_phys.reshape(-1).float()
+        return _f32(x_phys.reshape(-1))
 
     def solve(self, x_phys: torch.Tensor):
         """(coeffs [N], sol [B*P]) of `fem_poisson_1d` on these node counts and the Gaussians last set: the same entry point on
@@ -416,6 +490,7 @@ class Pde1dBatch:
 
     def solve_loss(self, x_phys: torch.Tensor, target: torch.Tensor, loss: str = 'l1'):
         """(loss, coeffs [N], sol [B*P]) of `poisson_loss_1d`: the one-launch tail."""
+        _check_target('Pde1dBatch.solve_loss', target, self.B, self.pts.numel())
         out = _poisson_loss_on(self, self._x(x_phys), target, self.k_load, self.k_stiff, self.pts, loss)
         return out[0], out[1], out[2]
 
@@ -441,6 +516,7 @@ def gnn_pde_tail_1d(model, data, x_phys: torch.Tensor):
         return coeffs[pb.interior].unsqueeze(1), x, sol
     B, counts = _batch_counts(data, x)
     params = batch_params(model.opt, data, B)
+    _check_batch('gnn_pde_tail_1d', x, counts, params, min_nodes=3)
     coeffs, sol = _poisson_on(_Batch(counts, params, x.device), x, model.opt, model.quad_points)
     return coeffs[_interior_index(counts, x.device)].unsqueeze(1), x, sol.view(-1)
 
@@ -454,14 +530,16 @@ def _params_of(c_list, s_list):
 def torch_FEM_Burgers_1D(opt, mesh_points, quad_points, num_meshpoints, un_coeffs, BC1=None, BC2=None):
     """One Burgers step from un_coeffs on one mesh (difFEM_1d.py's signature): (unp1_coeffs, mesh_points, sol, BC1, BC2).
     Differentiable in mesh_points and un_coeffs; explicit BC1/BC2 are taken as constants."""
+    _check_float('torch_FEM_Burgers_1D', 'un_coeffs', un_coeffs)
+    n = _check_batch('torch_FEM_Burgers_1D', mesh_points, [mesh_points.shape[0]] if torch.is_tensor(mesh_points) else [],
+                     n_points=_points(opt, None, quad_points).numel(), un_coeffs=un_coeffs)[0]
     _require_gpu(mesh_points, 'torch_FEM_Burgers_1D')
-    n = mesh_points.shape[0]
     bc = None
     if BC1 is not None or BC2 is not None:
         b1 = un_coeffs[0] if BC1 is None else torch.as_tensor(BC1, device=mesh_points.device).reshape(-1)[0]
         b2 = un_coeffs[-1] if BC2 is None else torch.as_tensor(BC2, device=mesh_points.device).reshape(-1)[0]
         bc = torch.stack([b1.detach().float(), b2.detach().float()])
-    unp1, sol, _ = burgers_1d(mesh_points, [n], None, opt, 1, points=quad_points, u0=un_coeffs.view(-1), bc=bc, fine=False)
+    unp1, sol, _ = burgers_1d(mesh_points, [n], None, opt, 1, points=quad_points, u0=un_coeffs.reshape(-1), bc=bc, fine=False)
     return unp1, mesh_points, sol.view(-1), (un_coeffs[0] if BC1 is None else BC1), (un_coeffs[-1] if BC2 is None else BC2)
 
 
@@ -469,19 +547,27 @@ def get_Burgers_initial_coeffs(fine_mesh_points, num_fine_meshpoints, mesh_point
     """(u0_coeffs, u0_coeffs_fine): the detached L2 projections of the initial state on the mesh (mass with eval_quad_points
     points) and on the fine mesh (10 * eval_quad_points).  u0 is the state's pde_params ({'centers', 'scales'}) or a
     (c_list, s_list) pair; it is scaled by opt['gauss_amplitude'] as the reference's u0 lambda is."""
-    _require_gpu(mesh_points, 'get_Burgers_initial_coeffs')
     if isinstance(u0, dict):
         params = [u0]
     elif isinstance(u0, (list, tuple)) and len(u0) == 1 and isinstance(u0[0], dict):
         params = list(u0)
     else:
         params = _params_of(*u0)
+    meshes = []
+    for name, pts in (('mesh_points', mesh_points), ('fine_mesh_points', fine_mesh_points)):
+        what = f'get_Burgers_initial_coeffs ({name})'
+        pts = torch.as_tensor(pts)
+        _check_float(what, name, pts)
+        x = pts.detach().reshape(-1)
+        _check_batch(what, x, [x.shape[0]], params)
+        meshes.append(x)
+    _require_gpu(mesh_points, 'get_Burgers_initial_coeffs')
     o = dict(opt)
     o['load_quad_points'] = int(load_quad_points)
     ev = int(opt.get('eval_quad_points', 101))
     out = []
-    for pts, kp in ((mesh_points, ev), (fine_mesh_points, 10 * ev)):
-        x = torch.as_tensor(pts, device=mesh_points.device).detach().float().view(-1)
+    for x, kp in zip(meshes, (ev, 10 * ev)):
+        x = _f32(x).to(mesh_points.device)
         out.append(_project(x, [x.shape[0]], params, o, kp)[0])
     return out[0], out[1]
 
@@ -493,6 +579,8 @@ def _project(x: torch.Tensor, counts: Sequence[int], params: Sequence[dict], opt
     x = x.contiguous()
     bt = _Batch(counts, params, dev)
     N = x.shape[0]
+    if x.dim() != 1 or N != sum(bt.counts):
+        raise ValueError(f"1-D Burgers projection: x {tuple(x.shape)} for node_counts summing to {sum(bt.counts)}")
     hist, sol = torch.empty(2 * N, device=dev), torch.empty(bt.B, 1, device=dev)
     flags, p1 = torch.empty(bt.B, dtype=torch.int32, device=dev), torch.zeros(1, device=dev)
     _burgers_forward(bt, x, None, None, _burgers_cfg(opt, 1, k_proj=k_proj), 1, p1, hist, sol, None, flags)
@@ -506,8 +594,9 @@ def burgers_project(x: torch.Tensor, counts: Sequence[int], params: Sequence[dic
     gauss_amplitude * sum exp(-(x-c)^2/s^2) of each mesh's own Gaussians on its mesh, [N] concatenated.  The mass matrix
     takes `k_proj` points per interval (eval_quad_points, as for a coarse mesh, unless given; the reference's fine mesh takes
     10 * eval_quad_points)."""
+    counts = _check_batch('burgers_project', x, counts, params)
     _require_gpu(x, 'burgers_project')
-    u0, flags = _project(x.detach().float(), counts, params, opt, k_proj)
+    u0, flags = _project(_f32(x.detach()), counts, params, opt, k_proj)
     _watch_flags(flags)
     return u0
 
@@ -515,10 +604,13 @@ def burgers_project(x: torch.Tensor, counts: Sequence[int], params: Sequence[dic
 def fn_expansion(coeffs, mesh, quad_points, num_solpoints=None):
     """Piecewise-linear expansion of coeffs on mesh at quad_points (values only, no gradient), with the reference's
     searchsorted point location."""
+    _check_float('fn_expansion', 'mesh', mesh)
+    coeffs = torch.as_tensor(coeffs)
+    pts = _points({}, mesh.device, quad_points)
+    _check_batch('fn_expansion', mesh.reshape(-1), [mesh.numel()], n_points=pts.numel(), coeffs=coeffs)
     _require_gpu(mesh, 'fn_expansion')
-    x = mesh.detach().float().contiguous().view(-1)
-    c = torch.as_tensor(coeffs, device=x.device).detach().float().contiguous().view(-1)
-    pts = _points({}, x.device, quad_points)
+    x = _f32(mesh.detach()).reshape(-1).contiguous()
+    c = _f32(coeffs.detach()).to(x.device).reshape(-1).contiguous()
     bt = _Batch([x.shape[0]], None, x.device)
     sol = torch.empty(pts.numel(), device=x.device)
     _nf.call('gadapt_fem1d_expand', *bt.head(x, gauss=False), c.data_ptr(), pts.numel(), pts.data_ptr(), sol.data_ptr(),
@@ -529,9 +621,11 @@ def fn_expansion(coeffs, mesh, quad_points, num_solpoints=None):
 def torch_FEM_1D(opt, mesh_points, quad_points, num_meshpoints, c_list, s_list):
     """The reference's 1-D Poisson solve on one mesh: (coeffs [N-2,1], mesh_points, sol, BC1, BC2), differentiable in
     mesh_points; BC1/BC2 are u_true at the end nodes (detached)."""
+    params = _params_of(c_list, s_list)
+    n = _check_batch('torch_FEM_1D', mesh_points, [mesh_points.shape[0]] if torch.is_tensor(mesh_points) else [], params, min_nodes=3,
+                     n_points=_points(opt, None, quad_points).numel())[0]
     _require_gpu(mesh_points, 'torch_FEM_1D')
-    n = mesh_points.shape[0]
-    coeffs, sol = fem_poisson_1d(mesh_points, [n], _params_of(c_list, s_list), opt, points=quad_points)
+    coeffs, sol = fem_poisson_1d(mesh_points, [n], params, opt, points=quad_points)
     return coeffs[1:-1].unsqueeze(1), mesh_points, sol.view(-1), coeffs[:1].detach(), coeffs[-1:].detach()
 
 
@@ -562,18 +656,22 @@ def gradient_meshpoints_1D(opt, data, x_phys):
     gt = opt['grad_type']
     if gt not in GRAD_TYPES:
         raise ValueError("Error: opt['grad_type'] incorrectly specified")
-    x = x_phys.detach()
-    _require_gpu(x, 'gradient_meshpoints_1D')
-    x = x.float().reshape(-1)
+    _check_float('gradient_meshpoints_1D', 'x_phys', x_phys)
+    x = x_phys.detach().reshape(-1)
     pp = data.pde_params
     B = int(data.__dict__.get('_num_graphs') or (len(pp) if isinstance(pp, (list, tuple)) else getattr(data, 'num_graphs', 1)))
     n = int(opt['mesh_dims'][0]) if 'mesh_dims' in opt else x.shape[0] // B
     if B * n == x.shape[0]:
         counts = [n] * B
-    else:
+    elif getattr(data, 'batch', None) is not None:
         counts = torch.bincount(data.batch.detach().cpu(), minlength=B).tolist()
+    else:
+        raise ValueError(f"gradient_meshpoints_1D: {x.shape[0]} coordinates for {B} meshes of {n} nodes, and the batch carries no "
+                         "`batch` vector to count them by")
     params = _split_params(pp, B)
-    x = x.requires_grad_(True)
+    counts = _check_batch('gradient_meshpoints_1D', x, counts, params, min_nodes=2 if gt == 'burgers_timestep_loss_direct_mse' else 3)
+    _require_gpu(x, 'gradient_meshpoints_1D')
+    x = _f32(x).requires_grad_(True)
     pts = _points(opt, x.device)
     with torch.enable_grad():
         if gt == 'burgers_timestep_loss_direct_mse':
@@ -588,4 +686,4 @@ def gradient_meshpoints_1D(opt, data, x_phys):
             else:
                 per_mesh = torch.trapezoid(err.abs() ** 2, pts, dim=1)
         per_mesh.sum().backward()
-    return per_mesh.detach().mean(), x.grad
+    return per_mesh.detach().mean(), x.grad.to(x_phys.dtype)                      # the gradient in the caller's dtype
