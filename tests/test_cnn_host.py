@@ -8,7 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from cnn_cases import BACKWARD_LIMITS, CASES, FLOOR, PAST, make_inputs, params_of, reference, rel, run_restatement
+from cnn_cases import (BACKWARD_LIMITS, BACKWARD_LIMITS_1D, CASES, FLOOR, FORWARD_LIMITS, FORWARD_ONLY, PAST, PAST_FORWARD, PLANTS, make_inputs,
+                       params_of, reference, rel, run_restatement)
 from g_adaptivity_amd import GNN, MeshDataset, _native as nv, hot_path_opt
 from g_adaptivity_amd.features import LDS_BUDGET, GlobalFeatureExtractorCNN, global_cnn, hip_limit
 from oracle.pyg_restatement import _GlobalCNN
@@ -55,6 +56,35 @@ def test_backward_limits_are_the_largest_that_fit():
         assert lib.gadapt_cnn_backward_lds_bytes(2, n, n, mid, 8) <= LDS_BUDGET < lib.gadapt_cnn_backward_lds_bytes(2, n + 1, n + 1, mid, 8), mid
         assert lib.gadapt_cnn_forward_lds_bytes(2, n + 1, n + 1, mid, 8) <= LDS_BUDGET          # the forward admits more
     assert lib.gadapt_cnn_backward_lds_bytes(2, 23, 23, 8, 8) == 60000 + 4 * 529
+    assert lib.gadapt_cnn_backward_lds_bytes(2, 11, 11, 32, 8) == 65380 and lib.gadapt_cnn_backward_lds_bytes(2, 7, 7, 64, 8) == 62404
+
+
+def test_1d_backward_limits_are_the_longest_that_fit():
+    lib = nv.lib()
+    for mid, n in BACKWARD_LIMITS_1D.items():
+        assert lib.gadapt_cnn_backward_lds_bytes(1, 1, n, mid, 8) <= LDS_BUDGET < lib.gadapt_cnn_backward_lds_bytes(1, 1, n + 1, mid, 8), mid
+        assert lib.gadapt_cnn_forward_lds_bytes(1, 1, n + 1, mid, 8) <= LDS_BUDGET              # the forward admits more
+        assert hip_limit(1, 1, n, mid, 8) is None and 'backward' in hip_limit(1, 1, n + 1, mid, 8)
+    assert lib.gadapt_cnn_backward_lds_bytes(1, 1, 222, 8, 8) == 65400 and lib.gadapt_cnn_backward_lds_bytes(1, 1, 111, 16, 8) == 65532
+
+
+def test_forward_limits_are_the_largest_that_fit():
+    lib = nv.lib()
+    for mid, n in FORWARD_LIMITS.items():
+        assert lib.gadapt_cnn_forward_lds_bytes(2, n, n, mid, 8) <= LDS_BUDGET < lib.gadapt_cnn_forward_lds_bytes(2, n + 1, n + 1, mid, 8), mid
+        assert n > BACKWARD_LIMITS[mid]
+    assert lib.gadapt_cnn_forward_lds_bytes(2, 29, 29, 8, 8) == 64868 and lib.gadapt_cnn_forward_lds_bytes(2, 30, 30, 8, 8) == 69136
+
+
+def test_forward_only_rows_fit_the_forward_alone():
+    """FORWARD_ONLY: refused for a call that records for a backward, taken without one; PAST_FORWARD: refused either way, and the
+    sentence names the launch that does not fit."""
+    for name, (dim, n0, n1, mid, out, B) in FORWARD_ONLY.items():
+        assert hip_limit(dim, n0, n1, mid, out, training=False) is None, name
+        assert 'backward' in hip_limit(dim, n0, n1, mid, out, training=True), name
+    for name, (dim, n0, n1, mid, out, B) in PAST_FORWARD.items():
+        assert 'forward' in hip_limit(dim, n0, n1, mid, out, training=False) and 'backward' not in hip_limit(dim, n0, n1, mid, out, training=False), name
+        assert 'backward' in hip_limit(dim, n0, n1, mid, out, training=True), name
 
 
 def test_size_functions_refuse_bad_sizes():
@@ -75,10 +105,14 @@ SIZES = [({'n_meshes': 0}, 'n_meshes < 1'), ({'dim': 0}, 'dim must be 1 or 2'), 
          ({'n1': -1}, '1 <= n0, n1'), ({'dim': 1}, '(n0 = 1 when dim = 1)'), ({'mid': 0}, '1 <= mid, out'), ({'out': 0}, '1 <= mid, out')]
 REFUSALS = [('gadapt_cnn_forward', FWD_OK, b, t) for b, t in NULL_F + SIZES + [
                 ({'n0': 40, 'n1': 40}, 'cnn_forward: 2 LDS images'), ({'n0': 12, 'n1': 12, 'mid': 64}, 'above the 65536-byte LDS budget'),
-                ({'acts': None, 'dim': 3}, 'dim must be 1 or 2')]] + \
+                ({'acts': None, 'dim': 3}, 'dim must be 1 or 2'),
+                ({'n0': 30, 'n1': 30}, 'cnn_forward: 2 LDS images'), ({'n0': 30, 'n1': 30}, '= 69136 bytes, above the 65536-byte LDS budget')]] + \
            [('gadapt_cnn_backward', BWD_OK, b, t) for b, t in NULL_B + SIZES + [
                 ({'n0': 24, 'n1': 24}, 'cnn_backward: 3 LDS images'), ({'n0': 24, 'n1': 24}, '= 67200 bytes, above the 65536-byte LDS budget'),
-                ({'n0': 17, 'n1': 17, 'mid': 16}, 'above the 65536-byte LDS budget'), ({'partials': None, 'n_meshes': 1, 'dim': 3}, 'dim must be 1 or 2')]]
+                ({'n0': 17, 'n1': 17, 'mid': 16}, 'above the 65536-byte LDS budget'),
+                ({'dim': 1, 'n0': 1, 'n1': 223}, '= 65692 bytes, above the 65536-byte LDS budget'),
+                ({'dim': 1, 'n0': 1, 'n1': 112, 'mid': 16}, 'cnn_backward: 3 LDS images'), ({'n0': 12, 'n1': 12, 'mid': 32}, 'cnn_backward: 3 LDS images'),
+                ({'n0': 8, 'n1': 8, 'mid': 64}, 'cnn_backward: 3 LDS images'), ({'partials': None, 'n_meshes': 1, 'dim': 3}, 'dim must be 1 or 2')]]
 
 
 @pytest.mark.parametrize('entry,ok,breaks,text', REFUSALS, ids=[f"{e[11:]}-{'+'.join(f'{k}={v}' for k, v in b.items())}" for e, _, b, _ in REFUSALS])
@@ -168,3 +202,99 @@ def test_restatement_is_the_oracle_in_fp64_and_quiet_in_fp32(name):
     neg = torch.cat([a.flatten() for a in ref['acts']])
     assert 0.2 < (neg < 0).double().mean().item() < 0.8                 # both SELU branches
     assert max(ref['noise']) < FLOOR, ref['noise']                      # the yardstick is quiet: the floor decides the bar
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_cases_meet_their_conditions_on_the_fp64_restatement(name):
+    """What tests/cnn_cases.py promises of every row, from the fp64 restatement alone: no gradient is small enough for a relative error
+    to hide in (max|g| >= 1e-3 for each of the eight), and both SELU branches run - in every layer of four or more channels between 5 %
+    and 95 % of the activations before the pool are negative; narrower layers may be one-sided, the network as a whole is not."""
+    dim, n0, n1, mid, out, B = CASES[name]
+    ref = reference(name)
+    for label, g in zip([f'convs.{k}.{t}' for k in range(4) for t in ('weight', 'bias')], ref['grads']):
+        assert g.abs().max().item() >= 1e-3, label
+    for l, a in enumerate(ref['acts']):
+        assert a.shape == (B, out if l == 3 else mid, n0 * n1)
+        if a.shape[1] >= 4:
+            assert 0.05 <= (a < 0).double().mean().item() <= 0.95, l
+    everything = torch.cat([a.flatten() for a in ref['acts']])
+    assert (everything < 0).any() and (everything > 0).any()
+    if name in PLANTS:                                                  # the batch maximum sits where the row says, with that sign
+        mesh, pixel, factor = PLANTS[name]
+        u = ref['u']
+        assert u.abs().argmax().item() == mesh * n0 * n1 + pixel and (u.flatten()[u.abs().argmax()] < 0) == (factor < 0)
+        assert u.max().item() < 0.5 * u.abs().max().item()              # max u is NOT the scale
+
+
+def _plan(case):
+    """csrc/gadapt_cnn_plan.h restated: pixels; per layer width c the groups of four channels, ceil(c / 4), and whether the last group is
+    clamped (c no multiple of 4); units of the widest layer; the workgroup sizes of the forward and the backward by threads_for."""
+    dim, n0, n1, mid, out, B = case
+    def threads_for(units):
+        waves = min(max(units, 4), 16)
+        return 64 * ((waves + 3) // 4 * 4)
+    pixels = n0 * n1
+    units = -(-pixels // 64) * -(-max(mid, out) // 4)
+    entries = (mid * mid * 3 ** dim + mid + 63) // 64
+    return {'pixels': pixels, 'mid_groups': -(-mid // 4), 'mid_tail': mid % 4, 'out_groups': -(-out // 4), 'out_tail': out % 4, 'units': units,
+            'forward_threads': threads_for(units), 'backward_threads': threads_for(max(entries, units))}
+
+
+# What each row claims about its launch: (pixels, groups of the mid-wide layers, live channels of their clamped tail group or 0, the same two
+# for the top layer, units, forward threads, backward threads).  A later edit of a row cannot silently stop it from reaching its edge.
+CLAIMS = {
+    '2d-5x5-m8-b1': (25, 2, 0, 2, 0, 2, 256, 768),
+    '1d-21-m16-b1': (21, 4, 0, 2, 0, 4, 256, 1024),
+    '2d-5x5-m4-o8': (25, 1, 0, 2, 0, 2, 256, 256),
+    '2d-5x5-m12-o16': (25, 3, 0, 4, 0, 4, 256, 1024),
+    '2d-6x5-m3-o5': (30, 1, 3, 2, 1, 2, 256, 256),
+    '2d-7x4-m6-o2': (28, 2, 2, 1, 2, 2, 256, 512),
+    '2d-5x5-m5-o8': (25, 2, 1, 2, 0, 2, 256, 256),
+    '2d-3x3-m1-o1': (9, 1, 1, 1, 1, 1, 256, 256),
+    '2d-3x3-m2-o1': (9, 1, 2, 1, 1, 1, 256, 256),
+    '2d-1x9-m8': (9, 2, 0, 2, 0, 2, 256, 768),
+    '2d-9x1-m8': (9, 2, 0, 2, 0, 2, 256, 768),
+    '2d-1x1-m8': (1, 2, 0, 2, 0, 2, 256, 768),
+    '2d-2x33-m8': (66, 2, 0, 2, 0, 4, 256, 768),
+    '2d-33x2-m8': (66, 2, 0, 2, 0, 4, 256, 768),
+    '2d-11x11-m32': (121, 8, 0, 2, 0, 16, 1024, 1024),
+    '2d-7x7-m64': (49, 16, 0, 2, 0, 16, 1024, 1024),
+    '1d-1-m8': (1, 2, 0, 2, 0, 2, 256, 256),
+    '1d-2-m8': (2, 2, 0, 2, 0, 2, 256, 256),
+    '1d-64-m8': (64, 2, 0, 2, 0, 2, 256, 256),
+    '1d-65-m8': (65, 2, 0, 2, 0, 4, 256, 256),
+    '1d-101-m16': (101, 4, 0, 2, 0, 8, 512, 1024),
+    '1d-222-m8': (222, 2, 0, 2, 0, 8, 512, 512),
+    '1d-111-m16': (111, 4, 0, 2, 0, 8, 512, 1024),
+    '2d-3x3-m8-b65': (9, 2, 0, 2, 0, 2, 256, 768),
+    '2d-5x5-m8-negmax': (25, 2, 0, 2, 0, 2, 256, 768),
+}
+
+
+@pytest.mark.parametrize('name', list(CLAIMS))
+def test_rows_reach_the_launch_plan_they_claim(name):
+    assert tuple(_plan(CASES[name]).values()) == CLAIMS[name]
+
+
+def test_the_rows_cover_the_edges_of_the_launch_plan():
+    plans = {name: _plan(case) for name, case in CASES.items()}
+    assert plans['1d-64-m8']['pixels'] == 64 and plans['1d-65-m8']['pixels'] == 65
+    assert plans['2d-2x33-m8']['pixels'] == 66 == plans['2d-33x2-m8']['pixels']
+    assert CASES['2d-6x5-m3-o5'][1] > CASES['2d-6x5-m3-o5'][2] and CASES['2d-7x4-m6-o2'][1] > CASES['2d-7x4-m6-o2'][2]         # n0 > n1
+    tails = {name: (p['mid_groups'], p['mid_tail']) for name, p in plans.items()}
+    assert tails['2d-3x3-m1-o1'] == (1, 1) and tails['2d-3x3-m2-o1'] == (1, 2)          # a tail group and nothing else
+    assert tails['2d-6x5-m3-o5'] == (1, 3)
+    assert tails['2d-5x5-m5-o8'] == (2, 1) and tails['2d-7x4-m6-o2'] == (2, 2)          # a full group and a tail
+    assert tails['2d-5x5-m12-o16'] == (3, 0) and plans['2d-5x5-m12-o16']['out_groups'] == 4      # more than one group each, out > mid
+    assert (plans['2d-6x5-m3-o5']['out_groups'], plans['2d-6x5-m3-o5']['out_tail']) == (2, 1)
+    for name in ('2d-5x5-m4-o8', '2d-5x5-m12-o16', '2d-6x5-m3-o5', '2d-5x5-m5-o8'):
+        assert CASES[name][4] > CASES[name][3], name                                      # out > mid
+    assert {name for name, case in CASES.items() if case[5] == 1} == {'2d-5x5-m8-b1', '1d-21-m16-b1'}
+    assert CASES['2d-3x3-m8-b65'][5] == 65
+    sizes = {p['forward_threads'] for p in plans.values()} | {p['backward_threads'] for p in plans.values()}
+    assert {256, 1024} <= sizes and any(256 < s < 1024 for s in sizes) and sizes <= {256, 512, 768, 1024}
+    lib = nv.lib()                                                       # the limit rows sit AT their limits
+    for name in ('2d-11x11-m32', '2d-7x7-m64', '1d-222-m8', '1d-111-m16'):
+        dim, n0, n1, mid, out, B = CASES[name]
+        grown = (n0 + 1, n1 + 1) if dim == 2 else (1, n1 + 1)
+        assert lib.gadapt_cnn_backward_lds_bytes(dim, n0, n1, mid, out) <= LDS_BUDGET < lib.gadapt_cnn_backward_lds_bytes(dim, *grown, mid, out), name
