@@ -30,7 +30,7 @@ all: $(LIB) $(FEM_LIB) $(MESH_LIB)
 $(FEM_LIB): $(FEM_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(FEM_OBJS)
 
-$(OBJDIR)/fem_kernels.o: $(FEM_CSRC)/fem_kernels.hip $(FEM_CSRC)/fem_window_kernels.hip $(FEM_CSRC)/fem_window_grad_kernels.hip $(FEM_CSRC)/fem_wave_grad_kernels.hip $(FEM_CSRC)/fem_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
+$(OBJDIR)/fem_kernels.o: $(FEM_CSRC)/fem_kernels.hip $(FEM_CSRC)/fem_window_kernels.hip $(FEM_CSRC)/fem_window_grad_kernels.hip $(FEM_CSRC)/fem_wave_grad_kernels.hip $(FEM_CSRC)/fem_wave_fwd_kernels.hip $(FEM_CSRC)/fem_common.h $(FEM_CSRC)/fem_host.h include/gadapt_fem.h
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c -o $@ $<
 

@@ -5,6 +5,7 @@ pseudo-loss sum(x_phys * x_grads) with Adam.  GRAND_plus, hidden 8, 11 x 11 mesh
 batch 1 by default (the reference's defaults).  Prints the loss per epoch.
 
     python examples/train_modular_2d.py --epochs 5 --num_train 8 --batch_size 1
+    python examples/train_modular_2d.py --forward wave                                   # the wave-parallel FEM forward (--band lds)
     python examples/train_modular_2d.py --mesh_dim 64 --band window --num_train 2       # beyond 26 x 26: the windowed route
 """
 import argparse
@@ -28,13 +29,16 @@ def main():
     ap.add_argument('--band', choices=['lds', 'window'], default='lds',
                     help="FEM route (opt['fem_band']): 'lds' keeps the banded factor in LDS (meshes up to 26 x 26), 'window' streams "
                          "it through a workspace (up to 81 x 81)")
+    ap.add_argument('--forward', choices=['lane', 'wave'], default='lane',
+                    help="the forward's load vector and evaluation (opt['fem_forward']): 'wave' is the wave-parallel form on "
+                         "--band lds, the same bits")
     ap.add_argument('--lr', type=float, default=1e-3)
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     n = a.mesh_dim
     opt = hot_path_opt(mesh_dims=[n, n], conv_type='GRAND_plus', hidden_dim=8, num_layers=4, time_step=0.1,
                        loss_type='modular', grad_type=a.grad_type, eval_quad_points=101, load_quad_points=101, device=str(dev),
-                       fem_band=a.band)
+                       fem_band=a.band, fem_forward=a.forward)
     ds = MeshDataset([n, n], a.num_train, seed=n)
     torch.manual_seed(0)
     model = GNN(ds, opt).to(dev).train()

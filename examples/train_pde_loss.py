@@ -7,10 +7,13 @@ forward / backward.
 `--step captured` trains with `GraphedTrainStep` instead: the iteration is captured once per batch topology and replayed, with
 the new batch's fields, target and Gaussians fed in and no host synchronisation inside an epoch; it prints the loss per epoch
 and ms per step from HIP events around whole epochs.  `--adjoint wave` runs the backward's two lattice walks with a wave per
-node and per triangle (opt['fem_adjoint']); the gradients are the same, bit for bit.
+node and per triangle (opt['fem_adjoint']); the gradients are the same, bit for bit.  `--forward wave` runs the forward's load
+vector with a wave per node and its evaluation with a wave per chunk of the lattice (opt['fem_forward'], `--band lds` only);
+coeffs and sol are the same, bit for bit.
 
     python examples/train_pde_loss.py --epochs 3 --num_train 32 --batch_size 8
     python examples/train_pde_loss.py --step captured --adjoint wave --mesh 11 --batch_size 1
+    python examples/train_pde_loss.py --step captured --adjoint wave --forward wave --mesh 11 --batch_size 1
     python examples/train_pde_loss.py --mesh 64 --band window --num_train 4 --batch_size 2   # beyond 26 x 26: the windowed route
 """
 import argparse
@@ -38,7 +41,7 @@ def train_captured(model, batches, a, n):
         t1.record()
         t1.synchronize()
         print(f"mesh {n}x{n} epoch {epoch}: loss {tot.item() / len(batches):.5f} | ms/step {t0.elapsed_time(t1) / len(batches):.3f} "
-              f"(captured, adjoint {a.adjoint})", flush=True)
+              f"(captured, adjoint {a.adjoint}, forward {a.forward})", flush=True)
 
 
 def main():
@@ -56,11 +59,14 @@ def main():
                     help="'eager': the host-driven loop with its per-phase split; 'captured': GraphedTrainStep with FlatAdam(capturable=True)")
     ap.add_argument('--adjoint', choices=['lane', 'wave'], default='lane',
                     help="the backward's lattice walks (opt['fem_adjoint']): a lane or a wave per node and per triangle, the same bits")
+    ap.add_argument('--forward', choices=['lane', 'wave'], default='lane',
+                    help="the forward's load vector and evaluation (opt['fem_forward']): a lane per node and five lattice points per "
+                         "lane, or a wave per node and per chunk of the lattice (--band lds only), the same bits")
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     for n in ([a.mesh] if a.mesh else a.mesh_dims_train):
         opt = hot_path_opt(mesh_dims=[n, n], hidden_dim=8, num_layers=4, time_step=0.1, loss_type='pde_loss', loss_fn='l1',
-                           device=str(dev), fem_band=a.band, fem_adjoint=a.adjoint)
+                           device=str(dev), fem_band=a.band, fem_adjoint=a.adjoint, fem_forward=a.forward)
         ds = MeshDataset([n, n], a.num_train, seed=n, pde_loss_fields=True)
         torch.manual_seed(0)
         model = GNN(ds, opt).to(dev).train()
@@ -84,7 +90,7 @@ def main():
                 xd = x_phys.detach().requires_grad_(True)
                 counts = torch.bincount(dd.batch.cpu()).tolist()
                 coeffs, sol = fem_poisson(xd, dd.cells, dd.boundary_nodes, counts, dd.pde_params, model.quad_points, band=a.band,
-                                          adjoint=a.adjoint)
+                                          adjoint=a.adjoint, forward=a.forward)
                 loss = l1_loss(sol.view(-1, 1), dd.u_true_fine_tensor.view(-1, 1))
                 e[2].record()
                 loss.backward()

@@ -41,6 +41,8 @@ PROTOTYPES = {
     'gadapt_fem_backward_window': (_I, [_I, _I, _I] + [_P] * 13 + [_I, _I] + [_P] * 9),
     'gadapt_fem_backward_wave': (_I, [_I, _I, _I] + [_P] * 13 + [_I, _I] + [_P] * 9),
     'gadapt_fem_backward_window_wave': (_I, [_I, _I, _I] + [_P] * 13 + [_I, _I] + [_P] * 9),
+    'gadapt_fem_forward_wave': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 5),
+    'gadapt_fem_modular_forward_wave': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I, _I] + [_P] * 7),
     'gadapt_fem1d_lds_bytes': (_L, [_I, _I]),
     'gadapt_fem1d_burgers_forward': (_I, [_I, _I] + [_P] * 6 + [_F] * 3 + [_I] * 7 + [_P] * 6),
     'gadapt_fem1d_burgers_backward': (_I, [_I, _I, _P, _P, _P, _F, _F, _I, _I, _I, _I] + [_P] * 7),

@@ -29,6 +29,11 @@ adjoint='wave' (`fem_poisson`, `modular_loss_2d`, `PdeBatch`; opt['fem_adjoint']
 `gradient_meshpoints_2D`) runs the backward's two lattice walks with a wave per node and a wave per triangle instead of a lane
 each (gadapt_fem_backward_wave, gadapt_fem_backward_window_wave): the same gradient, bit for bit.  The default stays 'lane'.
 
+forward='wave' (the same functions; opt['fem_forward'] = 'wave' for `torch_FEM_2D`, `gnn_pde_tail`, `gradient_meshpoints_2D` and
+`PdeBatch.from_data`) runs the load vector with a wave per node and the evaluation with a wave per chunk of the lattice and two
+phases per point (gadapt_fem_forward_wave, gadapt_fem_modular_forward_wave): the same rhs, coeffs, factor and sol, bit for bit.
+band='lds' only: with band='window' it is a ValueError.  The default stays 'lane'.
+
 `PdeBatch` is the tail of one batch topology with everything a call would rebuild kept on the device - the topology, the lattice
 axes, the Gaussians' buffers: `gnn_pde_tail` on a batch that carries one (`data._pde_batch`) only launches, so it can be
 captured in a hipGraph, and `set_params` feeds the Gaussians of the next batch into the same buffers
@@ -66,6 +71,7 @@ __all__ = ['FemTopology', 'PdeBatch', 'fem_poisson', 'torch_FEM_2D', 'boundary_f
 
 BAND_ROUTES = ('lds', 'window')
 ADJOINTS = ('lane', 'wave')
+FORWARDS = ('lane', 'wave')
 # appended to the refusals of the resident-band route
 WINDOW_HINT = ("; the evaluation (poisson_eval_errors, evaluate_model_fine) takes larger meshes with band='window' "
                "(opt['fem_band'] = 'window')")
@@ -275,11 +281,25 @@ def _check_adjoint(what: str, adjoint) -> str:
     return adjoint
 
 
+def _check_forward(what: str, forward, band) -> str:
+    """The form of the forward's load vector and evaluation, before anything is launched; 'wave' is built for band='lds'."""
+    if forward not in FORWARDS:
+        raise ValueError(f"{what}: forward must be one of {FORWARDS} (got {forward!r})")
+    if forward == 'wave' and band == 'window':
+        raise ValueError(f"{what}: forward='wave' is built for band='lds' only; band='window' has its own load-vector and "
+                         "evaluation kernels (use forward='lane')")
+    return forward
+
+
 # operation -> route -> symbol of include/gadapt_fem.h (tests/test_fem_window_grad_host.py pins the pairing)
 ENTRY_POINTS = {op: {'lds': f'gadapt_fem_{op}', 'window': f'gadapt_fem_{op}_window'}
                 for op in ('forward', 'modular_forward', 'backward', 'eval_errors')}
 ENTRY_POINTS['backward_wave'] = {'lds': 'gadapt_fem_backward_wave', 'window': 'gadapt_fem_backward_window_wave'}
+ENTRY_POINTS['forward_wave'] = {'lds': 'gadapt_fem_forward_wave'}
+ENTRY_POINTS['modular_forward_wave'] = {'lds': 'gadapt_fem_modular_forward_wave'}
 _BACKWARD_OP = {'lane': 'backward', 'wave': 'backward_wave'}
+_FORWARD_OP = {'lane': 'forward', 'wave': 'forward_wave'}
+_MODULAR_OP = {'lane': 'modular_forward', 'wave': 'modular_forward_wave'}
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -338,14 +358,14 @@ def lattice_axes(quad_points, device) -> Tuple[torch.Tensor, torch.Tensor]:
 
 class _FemPoisson(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, topo: FemTopology, gptr, gpar, lat_x, lat_y, tri_slab=0, adjoint='lane'):
+    def forward(ctx, x, topo: FemTopology, gptr, gpar, lat_x, lat_y, tri_slab=0, adjoint='lane', fwd='lane'):
         _require_gpu(x, 'FEM node coordinates')
         x = x.detach().contiguous()
         dev, nlat = x.device, int(lat_x.numel())
         rhs, coeffs = torch.empty(topo.n_nodes, device=dev), torch.empty(topo.n_nodes, device=dev)
         sol = torch.empty(topo.n_meshes * nlat * nlat, device=dev)
         lfac = topo.factor_buffer(dev)                               # kept for the adjoint solve
-        _nf.call(ENTRY_POINTS['forward'][topo.route], *topo.head(gptr, gpar, x, lat_x, lat_y, nlat),
+        _nf.call(ENTRY_POINTS[_FORWARD_OP[fwd]][topo.route], *topo.head(gptr, gpar, x, lat_x, lat_y, nlat),
                  *_solve_tail(topo, rhs, coeffs, lfac, tri_slab), sol.data_ptr(), current_stream(dev))
         ctx.topo, ctx.nlat, ctx.adjoint = topo, nlat, adjoint
         ctx.save_for_backward(x, coeffs, lfac, gptr, gpar, lat_x, lat_y)
@@ -358,7 +378,7 @@ class _FemPoisson(torch.autograd.Function):
         g_coeffs = None if g_coeffs is None else g_coeffs.contiguous().float()
         g_sol = None if g_sol is None else g_sol.contiguous().float()
         return _backward(topo, gptr, gpar, x, lat_x, lat_y, ctx.nlat, coeffs, lfac, g_coeffs, g_sol, current_stream(dev), ctx.adjoint), \
-            None, None, None, None, None, None, None
+            None, None, None, None, None, None, None, None
 
 
 def _backward(topo: FemTopology, gptr, gpar, x, lat_x, lat_y, nlat: int, coeffs, factor, g_coeffs, g_sol, stream,
@@ -380,7 +400,7 @@ def _tri_counts(cells: torch.Tensor, node_counts: Sequence[int]) -> List[int]:
 
 def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
                 pde_params: Sequence[dict], quad_points, tri_counts: Optional[Sequence[int]] = None, band: str = 'lds',
-                tri_slab: int = 0, adjoint: str = 'lane'):
+                tri_slab: int = 0, adjoint: str = 'lane', *, forward: str = 'lane'):
     """Batched P1 Poisson solve on the meshes of `x_phys` [N,2] (differentiable wrt x_phys).
 
     cells [T,3] global node ids, mesh by mesh; boundary [N] bool; node_counts per mesh; pde_params per mesh
@@ -395,9 +415,14 @@ def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
     does not depend on `tri_slab`, bit for bit.
 
     adjoint: 'lane' walks the lattice in the backward with a lane per node and per triangle; 'wave' with a wave each
-    (gadapt_fem_backward[_window]_wave).  The gradient is the same, bit for bit."""
+    (gadapt_fem_backward[_window]_wave).  The gradient is the same, bit for bit.
+
+    forward: 'lane' computes the load vector with a lane per node and the evaluation with five lattice points per lane; 'wave'
+    (band='lds' only) with a wave per node and a wave per chunk of the lattice, two phases per point
+    (gadapt_fem_forward_wave).  coeffs, sol and the factor the backward reads are the same, bit for bit."""
     tri_slab = _check_route('pde_loss FEM tail', band, tri_slab)
     _check_adjoint('pde_loss FEM tail', adjoint)
+    _check_forward('pde_loss FEM tail', forward, band)
     node_counts = _check_batch_2d('pde_loss FEM tail (fem_poisson)', x_phys, node_counts, pde_params, cells, boundary, tri_counts)
     _require_gpu(x_phys, 'pde_loss FEM tail')
     dev = x_phys.device
@@ -406,15 +431,17 @@ def fem_poisson(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
     topo = _topology(cells, boundary, node_counts, tri_counts, dev, band)
     gptr, gpar = pack_gaussians(pde_params, dev)
     lx, ly = lattice_axes(quad_points, dev)
-    coeffs, sol = _FemPoisson.apply(x_phys, topo, gptr, gpar, lx, ly, tri_slab, adjoint)
+    coeffs, sol = _FemPoisson.apply(x_phys, topo, gptr, gpar, lx, ly, tri_slab, adjoint, forward)
     return coeffs.unsqueeze(1), sol
 
 
 def torch_FEM_2D(opt, mesh, mesh_points, quad_points, num_meshpoints, c_list, s_list):
     """The reference's entry point (`difFEM_2d.py:320-372`) on one mesh: (coeffs [N,1], mesh_points, sol shaped as
-    quad_points[0]).  opt['fem_band'] = 'window' takes meshes beyond 26 x 26 nodes, up to 81 x 81 (`fem_poisson`)."""
+    quad_points[0]).  opt['fem_band'] = 'window' takes meshes beyond 26 x 26 nodes, up to 81 x 81 (`fem_poisson`);
+    opt['fem_forward'] = 'wave' the wave-parallel forward (band 'lds')."""
     band = opt.get('fem_band', 'lds')
     _check_route('torch_FEM_2D', band, 0)
+    forward = _check_forward("torch_FEM_2D (opt['fem_forward'])", opt.get('fem_forward', 'lane'), band)
     cells_np = np.asarray(mesh.coordinates.cell_node_map().values, dtype=np.int64)
     n = mesh_points.shape[0]
     if n != num_meshpoints ** 2:
@@ -423,7 +450,8 @@ def torch_FEM_2D(opt, mesh, mesh_points, quad_points, num_meshpoints, c_list, s_
     boundary = torch.from_numpy(boundary_from_cells(cells_np, n))
     params = [{'centers': [np.asarray(c.detach().cpu() if torch.is_tensor(c) else c, np.float32) for c in c_list],
                'scales': [np.asarray(s.detach().cpu() if torch.is_tensor(s) else s, np.float32) for s in s_list]}]
-    coeffs, sol = fem_poisson(mesh_points, cells, boundary, [n], params, quad_points, tri_counts=[cells_np.shape[0]], band=band)
+    coeffs, sol = fem_poisson(mesh_points, cells, boundary, [n], params, quad_points, tri_counts=[cells_np.shape[0]], band=band,
+                              forward=forward)
     shape = quad_points[0].shape if quad_points[0].dim() == 2 else (quad_points[0].numel(), quad_points[1].numel())
     return coeffs, mesh_points, sol.view(shape)
 
@@ -468,6 +496,7 @@ def _check_tail(model):
     band, adjoint = o.get('fem_band', 'lds'), o.get('fem_adjoint', 'lane')
     _check_route("loss_type='pde_loss'", band, 0)
     _check_adjoint("loss_type='pde_loss' (opt['fem_adjoint'])", adjoint)
+    _check_forward("loss_type='pde_loss' (opt['fem_forward'])", o.get('fem_forward', 'lane'), band)
     if model.dim == 1 and o.get('pde_loss_1d') and o.get('pde_type', 'Poisson') == 'Poisson':
         return band, adjoint                                 # the 1-D tail (fem1d.gnn_pde_tail_1d): opt-in, one route
     if model.dim != 2:
@@ -481,8 +510,9 @@ def _check_tail(model):
 def gnn_pde_tail(model, data, x_phys: torch.Tensor):
     """`GNN.forward`'s pde_loss branch (`src/GNN.py:307-342`) for a batch: (coeffs [N,1], x_phys, sol [B*Q]).
     opt['fem_band'] = 'window' takes meshes beyond 26 x 26 nodes, up to 81 x 81 (`fem_poisson`); opt['fem_adjoint'] = 'wave'
-    the wave-parallel backward.  A batch that carries a `PdeBatch` (`data._pde_batch`) is solved through it: the launches
-    alone, nothing read back from the device or sent to it (its route and Gaussians are the descriptor's)."""
+    the wave-parallel backward, opt['fem_forward'] = 'wave' the wave-parallel forward (band 'lds').  A batch that carries a
+    `PdeBatch` (`data._pde_batch`) is solved through it: the launches alone, nothing read back from the device or sent to it
+    (its route and Gaussians are the descriptor's)."""
     band, adjoint = _check_tail(model)
     if model.dim == 1:                                       # opt['pde_loss_1d']: torch_FEM_1D per mesh (src/GNN.py:319-325)
         from .fem1d import gnn_pde_tail_1d
@@ -495,7 +525,7 @@ def gnn_pde_tail(model, data, x_phys: torch.Tensor):
     params = batch_params(model.opt, data, B)
     cells, boundary, tri_counts = _batch_cells(model, data, node_counts, B)
     coeffs, sol = fem_poisson(x_phys, cells, boundary, node_counts, params, model.quad_points, tri_counts=tri_counts, band=band,
-                              adjoint=adjoint)
+                              adjoint=adjoint, forward=model.opt.get('fem_forward', 'lane'))
     return coeffs, x_phys, sol
 
 
@@ -511,9 +541,11 @@ class PdeBatch:
         pb.set_params(next_batch.pde_params)
     """
 
-    def __init__(self, topo: FemTopology, lat_x: torch.Tensor, lat_y: torch.Tensor, cap: int, adjoint: str = 'lane', tri_slab: int = 0):
+    def __init__(self, topo: FemTopology, lat_x: torch.Tensor, lat_y: torch.Tensor, cap: int, adjoint: str = 'lane', tri_slab: int = 0, *,
+                 forward: str = 'lane'):
         _check_adjoint('PdeBatch', adjoint)
         self.tri_slab = _check_route('PdeBatch', topo.route, tri_slab)
+        self.forward = _check_forward('PdeBatch', forward, topo.route)
         if int(cap) < 1:
             raise ValueError(f"PdeBatch: room for {cap} Gaussians")
         self.topo, self.lat_x, self.lat_y, self.adjoint = topo, lat_x, lat_y, adjoint
@@ -527,9 +559,10 @@ class PdeBatch:
         self._staged = torch.cuda.Event() if pin else None       # recorded behind the copies out of the staging buffers
 
     @classmethod
-    def from_data(cls, model, data, max_gauss: int = 8, adjoint: Optional[str] = None) -> 'PdeBatch':
-        """The descriptor of `data`'s topology for `model`'s tail (opt['fem_band'], and opt['fem_adjoint'] unless `adjoint`
-        is given), with room for `max_gauss` Gaussians per mesh; the batch's own Gaussians are set if it carries any."""
+    def from_data(cls, model, data, max_gauss: int = 8, adjoint: Optional[str] = None, forward: Optional[str] = None) -> 'PdeBatch':
+        """The descriptor of `data`'s topology for `model`'s tail (opt['fem_band'], and opt['fem_adjoint'] and opt['fem_forward']
+        unless `adjoint` and `forward` are given), with room for `max_gauss` Gaussians per mesh; the batch's own Gaussians are
+        set if it carries any."""
         band, opt_adjoint = _check_tail(model)
         dev = torch.device(model.opt['device'])
         n = int(data.x_comp.shape[0])
@@ -539,7 +572,8 @@ class PdeBatch:
             tri_counts = _tri_counts(cells, node_counts)
         topo = _topology(cells, boundary, node_counts, tri_counts, dev, band)
         lx, ly = lattice_axes(model.quad_points, dev)
-        pb = cls(topo, lx, ly, B * int(max_gauss), adjoint if adjoint is not None else opt_adjoint)
+        pb = cls(topo, lx, ly, B * int(max_gauss), adjoint if adjoint is not None else opt_adjoint,
+                 forward=forward if forward is not None else model.opt.get('fem_forward', 'lane'))
         if n != pb.n_nodes:
             raise ValueError(f"PdeBatch: {n} nodes in the batch, {pb.n_nodes} in its topology")
         try:
@@ -574,7 +608,8 @@ class PdeBatch:
         _check_fp32('PdeBatch', x_phys)
         if x_phys.dim() != 2 or x_phys.shape[1] != 2 or x_phys.shape[0] != self.n_nodes:
             raise ValueError(f"PdeBatch: x_phys {tuple(x_phys.shape)} for a topology of {self.n_nodes} nodes in 2-D")
-        coeffs, sol = _FemPoisson.apply(x_phys, self.topo, self.gptr, self.gpar, self.lat_x, self.lat_y, self.tri_slab, self.adjoint)
+        coeffs, sol = _FemPoisson.apply(x_phys, self.topo, self.gptr, self.gpar, self.lat_x, self.lat_y, self.tri_slab, self.adjoint,
+                                        self.forward)
         return coeffs.unsqueeze(1), sol
 
 
@@ -595,7 +630,7 @@ def simpson_points_per_dim(N: int, dim: int = 2) -> int:
 def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
                     pde_params: Sequence[dict], n_lat: int, reduction: str, n_load: Optional[int] = None,
                     tri_counts: Optional[Sequence[int]] = None, band: str = 'lds',
-                    tri_slab: int = 0, adjoint: str = 'lane') -> Tuple[torch.Tensor, torch.Tensor]:
+                    tri_slab: int = 0, adjoint: str = 'lane', *, forward: str = 'lane') -> Tuple[torch.Tensor, torch.Tensor]:
     """Per-mesh 2-D modular loss and its gradient: (loss [B], x_grads [N,2]), x_grads on a node being the gradient of its
     own mesh's loss wrt all of that mesh's node coordinates.
 
@@ -604,9 +639,11 @@ def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.T
     e^2 over [0,1]^2 (n_lat odd).  n_load: Simpson points per dimension of the load vector; only the compiled
     `gadapt_fem_simpson_points()` is built.  Five launches forward and backward, no autograd graph, no host wait.
     band, tri_slab, adjoint: as `fem_poisson` ('window': square meshes up to 81 x 81 nodes; 'wave': the wave-parallel lattice
-    walks of the backward, the same bits)."""
+    walks of the backward, the same bits).  forward: as `fem_poisson` ('wave', band='lds' only: gadapt_fem_modular_forward_wave,
+    the same loss and gradient bits)."""
     tri_slab = _check_route('modular loss (2-D)', band, tri_slab)
     _check_adjoint('modular loss (2-D)', adjoint)
+    _check_forward('modular loss (2-D)', forward, band)
     node_counts = _check_batch_2d('modular loss (2-D)', x_phys, node_counts, pde_params, cells, boundary, tri_counts)
     if reduction not in _REDUCTIONS:
         raise ValueError(f"modular loss (2-D): reduction must be one of {sorted(_REDUCTIONS)} (got {reduction!r})")
@@ -630,7 +667,7 @@ def modular_loss_2d(x_phys: torch.Tensor, cells: torch.Tensor, boundary: torch.T
     rhs, coeffs, lfac = torch.empty(N, device=dev), torch.empty(N, device=dev), topo.factor_buffer(dev)
     sol, g_sol, loss = torch.empty(Q, device=dev), torch.empty(Q, device=dev), torch.empty(topo.n_meshes, device=dev)
     stream = current_stream(dev)
-    _nf.call(ENTRY_POINTS['modular_forward'][topo.route], *topo.head(gptr, gpar, x, lat, lat, n_lat), _REDUCTIONS[reduction],
+    _nf.call(ENTRY_POINTS[_MODULAR_OP[forward]][topo.route], *topo.head(gptr, gpar, x, lat, lat, n_lat), _REDUCTIONS[reduction],
              *_solve_tail(topo, rhs, coeffs, lfac, tri_slab), sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(), stream)
     return loss, _backward(topo, gptr, gpar, x, lat, lat, n_lat, coeffs, lfac, None, g_sol, stream, adjoint)
 
@@ -697,7 +734,8 @@ def gradient_meshpoints_2D(opt, data, x_phys):
     Topology: data.cells (as collate offsets them), else data.mesh / data.mesh[i], else square_mesh(mesh_dims[0]).
     Limits as the pde_loss tail: 2-D Poisson, square meshes up to 26 x 26 nodes (the LDS budget of the banded factor), or
     up to 81 x 81 with opt['fem_band'] = 'window' (`modular_loss_2d(band='window')`).  opt['fem_adjoint'] = 'wave': the
-    wave-parallel backward (`modular_loss_2d(adjoint='wave')`), the same bits.
+    wave-parallel backward (`modular_loss_2d(adjoint='wave')`), the same bits; opt['fem_forward'] = 'wave': the wave-parallel
+    forward (`modular_loss_2d(forward='wave')`, band 'lds'), the same bits.
     The reference's build_mass_matrix is called with three of its four arguments there (a TypeError as shipped); this
     builds the evident intent, the stiffness of torch_FEM_2D."""
     if 'grad_type' not in opt:
@@ -711,9 +749,11 @@ def gradient_meshpoints_2D(opt, data, x_phys):
     band = opt.get('fem_band', 'lds')
     _check_route('gradient_meshpoints_2D', band, 0)
     adjoint = _check_adjoint("gradient_meshpoints_2D (opt['fem_adjoint'])", opt.get('fem_adjoint', 'lane'))
+    forward = _check_forward("gradient_meshpoints_2D (opt['fem_forward'])", opt.get('fem_forward', 'lane'), band)
     n_load, n_lat, reduction = _modular_quadrature(opt, gt)
     cells, boundary, node_counts, tri_counts, params = _modular_batch(opt, data, x_phys.shape[0])
     _check_batch_2d('gradient_meshpoints_2D', x_phys, node_counts, params, cells, boundary, tri_counts, cast=True)
     loss, x_grads = modular_loss_2d(x_phys.detach().float(), cells, boundary, node_counts, params, n_lat, reduction,
-                                    n_load=n_load, tri_counts=tri_counts, band=band, adjoint=adjoint)
+                                    n_load=n_load, tri_counts=tri_counts, band=band, adjoint=adjoint,
+                                    forward=forward)
     return loss.mean(), x_grads

@@ -36,9 +36,10 @@ struct FemAdjoint { float *gc, *mu, *tgrad, *gx; };
 struct FemPlan { int64_t solve_lds, eval_lds; int slab; };
 
 // What the descent shares with the entry points (fem_kernels.hip), four launches each; the caller has checked everything.
-// load vector, solve, evaluation to sol, lattice loss and its derivative
+// load vector, solve, evaluation to sol, lattice loss and its derivative; wave (Band::lds alone): the first as a wave per node
+// and the third as a wave per chunk with two phases per point (fem_wave_fwd_kernels.hip), with the lane kernels' bits
 int fem_launch_modular_forward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, int reduction, float* sol, float* loss,
-                               float* g_sol, hipStream_t s);
+                               float* g_sol, hipStream_t s, bool wave = false);
 // d L / d c, adjoint solve on the kept factor, per-triangle chain rule, per-node gather; wave: the first and the third as a wave
 // per node and per triangle (fem_wave_grad_kernels.hip), with the lane kernels' bits
 int fem_launch_backward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, const float* g_coeffs, const float* g_sol,

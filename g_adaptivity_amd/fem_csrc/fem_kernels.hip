@@ -599,10 +599,12 @@ __global__ void __launch_bounds__(256) fem_gather_kernel(int n_nodes, const int3
 
 // The route for meshes beyond the resident band (band='window') is compiled in this translation unit: its solve and slabbed
 // evaluation with their launch plan, then its adjoint solve.  Both call this file's device helpers; the entry points of
-// both routes follow below.  The wave-parallel form of the backward's two lattice walks (fem_adjoint='wave') comes last.
+// both routes follow below.  The wave-parallel forms come last: the backward's two lattice walks (fem_adjoint='wave'), then
+// the resident-band forward's load vector and evaluation (fem_forward='wave').
 #include "fem_window_kernels.hip"
 #include "fem_window_grad_kernels.hip"
 #include "fem_wave_grad_kernels.hip"
+#include "fem_wave_fwd_kernels.hip"
 
 // ---------------------------------------------------------------------------------------------------- checks
 // Every entry point: fill a FemBatch from the arguments, check (check_batch, make_plan and what only it checks, in the
@@ -651,27 +653,35 @@ static int make_plan(Band band, const char* who, const FemBatch& b, int tri_slab
 
 // ---------------------------------------------------------------------------------------------------- launch sequences
 // Each takes the stream as `s` (FEM_LAUNCH) and returns at the first launch that fails.
-// load vector and banded Cholesky solve -> coeffs; the factor goes to sc.factor (Band::lds: may be NULL, it is not kept then)
-static int launch_solve(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, hipStream_t s) {
+// load vector and banded Cholesky solve -> coeffs; the factor goes to sc.factor (Band::lds: may be NULL, it is not kept then).
+// wave (Band::lds alone): the load vector as a wave per node (fem_wave_fwd_kernels.hip), the same bits
+static int launch_solve(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, hipStream_t s, bool wave = false) {
     const int nb = (b.N + 255) / 256;
     if (band == Band::window) {
         FEM_LAUNCH(fem_window_rhs_kernel, nb, 256, 0, b.N, b.cells, b.node_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x, sc.rhs);
         FEM_LAUNCH(fem_window_solve_kernel, b.B, FEM_WIN_THREADS, (size_t)P.solve_lds, b.meta, b.cells, b.int_idx, b.int_node, b.nt_ptr, b.nt_idx,
                    b.x, sc.rhs, sc.coeffs, reinterpret_cast<double*>(sc.factor), (int)P.solve_lds);
     } else {
-        FEM_LAUNCH(fem_rhs_kernel, nb, 256, 0, b.N, b.cells, b.node_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x, sc.rhs);
+        if (wave)
+            FEM_LAUNCH(fem_rhs_wave_kernel, b.N, FEM_WAVE, 0, b.N, b.cells, b.node_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x, sc.rhs);
+        else
+            FEM_LAUNCH(fem_rhs_kernel, nb, 256, 0, b.N, b.cells, b.node_mesh, b.int_idx, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x, sc.rhs);
         FEM_LAUNCH(fem_factor_kernel, b.B, FEM_SOLVE_THREADS, (size_t)P.solve_lds, b.meta, b.cells, b.int_idx, b.int_node, b.nt_ptr, b.nt_idx, b.x,
                    sc.rhs, sc.coeffs, sc.factor);
     }
     return GADAPT_FEM_OK;
 }
 
-// the solution on the lattice -> sol
-static int launch_eval(Band band, const FemBatch& b, const FemPlan& P, const float* coeffs, float* sol, hipStream_t s) {
+// the solution on the lattice -> sol.  wave (Band::lds alone): a wave per chunk, two phases per point, the same bits and
+// the same LDS (the bin mask)
+static int launch_eval(Band band, const FemBatch& b, const FemPlan& P, const float* coeffs, float* sol, hipStream_t s, bool wave = false) {
     const dim3 grid(b.B, FEM_EVAL_CHUNKS);
     if (band == Band::window)
         FEM_LAUNCH(fem_eval_slab_kernel, grid, FEM_EVAL_THREADS, (size_t)P.eval_lds, b.meta, b.cells, b.nt_ptr, b.nt_idx, b.x, coeffs, b.lat_x,
                    b.lat_y, b.nlat, P.slab, sol);
+    else if (wave)
+        FEM_LAUNCH(fem_eval_wave_kernel, dim3(b.B, eval_wave_chunks(b.B, b.nlat)), FEM_WAVE, (size_t)P.eval_lds, b.meta, b.cells, b.nt_ptr, b.nt_idx,
+                   b.x, coeffs, b.lat_x, b.lat_y, b.nlat, sol);
     else
         FEM_LAUNCH(fem_eval_kernel, grid, FEM_EVAL_THREADS, (size_t)P.eval_lds, b.meta, b.cells, b.nt_ptr, b.nt_idx, b.x, coeffs, b.lat_x, b.lat_y,
                    b.nlat, sol);
@@ -691,14 +701,14 @@ static int launch_eval_errors(Band band, const FemBatch& b, const FemPlan& P, co
     return GADAPT_FEM_OK;
 }
 
-static int launch_forward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, float* sol, hipStream_t s) {
-    const int rc = launch_solve(band, b, P, sc, s);
-    return rc ? rc : launch_eval(band, b, P, sc.coeffs, sol, s);
+static int launch_forward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, float* sol, hipStream_t s, bool wave = false) {
+    const int rc = launch_solve(band, b, P, sc, s, wave);
+    return rc ? rc : launch_eval(band, b, P, sc.coeffs, sol, s, wave);
 }
 
 int fem_launch_modular_forward(Band band, const FemBatch& b, const FemPlan& P, const FemScratch& sc, int reduction, float* sol, float* loss,
-                               float* g_sol, hipStream_t s) {
-    const int rc = launch_forward(band, b, P, sc, sol, s);
+                               float* g_sol, hipStream_t s, bool wave) {
+    const int rc = launch_forward(band, b, P, sc, sol, s, wave);
     if (rc) return rc;
     FEM_LAUNCH(fem_loss_kernel, b.B, FEM_LOSS_THREADS, (size_t)b.nlat * 4, b.gptr, b.gpar, b.lat_x, b.lat_y, b.nlat, reduction, sol, loss, g_sol);
     return GADAPT_FEM_OK;
@@ -740,19 +750,20 @@ static int check_forward(Band band, const char* who, const FemBatch& b, const Fe
     return !sc.factor || !sol ? fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size") : GADAPT_FEM_OK;
 }
 
-static int forward(Band band, const char* who, const FemBatch& b, const FemScratch& sc, int tri_slab, float* sol, hipStream_t s) {
+// wave: the *_wave entry points (Band::lds), the same checks and the wave-parallel load vector and evaluation
+static int forward(Band band, const char* who, const FemBatch& b, const FemScratch& sc, int tri_slab, float* sol, hipStream_t s, bool wave = false) {
     FemPlan P;
     const int rc = check_forward(band, who, b, sc, tri_slab, sol, &P);
-    return rc ? rc : launch_forward(band, b, P, sc, sol, s);
+    return rc ? rc : launch_forward(band, b, P, sc, sol, s, wave);
 }
 
-// the loss arguments first; Band::lds has always reported the shared ones under gadapt_fem_forward's name
+// the loss arguments first; Band::lds has always reported the shared ones under gadapt_fem_forward's name, with `wave` too
 static int modular_forward(Band band, const char* who, const FemBatch& b, const FemScratch& sc, int reduction, int tri_slab, float* sol,
-                           float* loss, float* g_sol, hipStream_t s) {
+                           float* loss, float* g_sol, hipStream_t s, bool wave = false) {
     FemPlan P;
     int rc = check_loss(who, b, reduction, loss, g_sol);
     if (rc || (rc = check_forward(band, band == Band::lds ? "gadapt_fem_forward" : who, b, sc, tri_slab, sol, &P))) return rc;
-    return fem_launch_modular_forward(band, b, P, sc, reduction, sol, loss, g_sol, s);
+    return fem_launch_modular_forward(band, b, P, sc, reduction, sol, loss, g_sol, s, wave);
 }
 
 // Band::lds takes a NULL lfac (the factor is not kept), refuses partials and err only after the LDS, and nlat's range last
@@ -868,4 +879,21 @@ extern "C" int gadapt_fem_backward_window_wave(int B, int N, int T, const int32_
                                                float* mu, float* tgrad, float* gx, void* stream) {
     return backward(Band::window, "gadapt_fem_backward_window_wave", FEM_BATCH(tri_mesh, 0), {nullptr, const_cast<float*>(coeffs), work}, g_coeffs,
                     g_sol, {gc, mu, tgrad, gx}, (hipStream_t)stream, true);
+}
+
+extern "C" int gadapt_fem_forward_wave(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                       const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                                       const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y,
+                                       int nlat, int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* sol,
+                                       void* stream) {
+    return forward(Band::lds, "gadapt_fem_forward_wave", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, lfac}, 0, sol, (hipStream_t)stream, true);
+}
+
+extern "C" int gadapt_fem_modular_forward_wave(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                               const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                                               const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
+                                               const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int reduction, float* rhs,
+                                               float* coeffs, float* lfac, float* sol, float* loss, float* g_sol, void* stream) {
+    return modular_forward(Band::lds, "gadapt_fem_modular_forward_wave", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, lfac}, reduction, 0, sol, loss,
+                           g_sol, (hipStream_t)stream, true);
 }

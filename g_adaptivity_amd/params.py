@@ -44,6 +44,10 @@ def hot_path_opt(**overrides) -> dict:
         # not a reference key: the form of the two lattice walks in the backward of those tails.  'lane': a lane per node and per
         # triangle; 'wave': a wave each (gadapt_fem_backward_wave), the same gradient bit for bit
         'fem_adjoint': 'lane',
+        # not a reference key: the form of the load vector and the lattice evaluation in the forward of those tails, on
+        # fem_band='lds'.  'lane': a lane per node and five lattice points per lane; 'wave': a wave per node and per chunk of the
+        # lattice (gadapt_fem_forward_wave), the same coeffs, factor and sol bit for bit.  'wave' with fem_band='window' is refused
+        'fem_forward': 'lane',
         # not a reference key: loss_type='pde_loss' on 1-D Poisson models (torch_FEM_1D per mesh, fem1d.gnn_pde_tail_1d).  False:
         # such a model is refused, as before the tail was built
         'pde_loss_1d': False,

@@ -238,6 +238,38 @@ int gadapt_fem_backward_window_wave(int n_meshes, int n_nodes, int n_tris, const
                                     int max_lds_bytes, const float* coeffs, float* work, const float* g_coeffs,
                                     const float* g_sol, float* gc, float* mu, float* tgrad, float* gx, void* stream);
 
+/* The wave-parallel forward of the resident-band route (fem_csrc/fem_wave_fwd_kernels.hip; fem_forward='wave' in Python):
+ * gadapt_fem_forward and gadapt_fem_modular_forward with their first and third launches replaced.  Arguments, checks, their
+ * order and the refusals are those of the entry point without the suffix, before any launch (under this one's name where that
+ * one reports under its own; gadapt_fem_modular_forward reports the shared checks under gadapt_fem_forward's name, and so does
+ * gadapt_fem_modular_forward_wave); the factor launch and the loss launch are the same launches.  There is no windowed form.
+ * These entry points were added without changing GADAPT_FEM_ABI (no existing signature changed).
+ *
+ * Ordering contract: rhs, coeffs, lfac, sol, loss and g_sol are those of the entry point without the suffix, bit for bit, for
+ * every input it accepts.  The library is built without FMA contraction, and each result is a chain of fp32 operations in a
+ * fixed order on addends that do not depend on each other:
+ *   rhs[m]     on an interior node the 9 x 9 integrand values f(i, j) = out / div * forcing, each from its own point alone; nine
+ *              y-rule sums s_i, each from zero over k = 0, 2, 4, 6 of hy3 * (f(i,k) + 4 f(i,k+1) + f(i,k+2)); the x-rule sum of
+ *              the s_i in the same form.  A wave per node computes the 81 values on its lanes (64 + 17) into LDS, nine lanes
+ *              form the s_i, one lane the result (372 B of static LDS).  A boundary node is u_true on one lane.
+ *   sol[p]     from zero, over the triangles of p's bin in increasing id that contain p, over their corners l = 0, 1, 2 with
+ *              inc != 0: coeffs[v] * (inc / div).  A lane scans the bin with the containment test alone and notes the
+ *              containing triangles in four registers, then adds their terms in the noted order; a lane that meets a fifth
+ *              adds the four first and goes on, so any number of overlapping triangles gives the same chain.  The lanes of a
+ *              wave so run the expensive terms together.  A workgroup is one wave, and the lattice of a mesh is cut into
+ *              min(ceil(nlat^2 / 64), max(2048 / n_meshes, 1)) chunks (sol[p] does not depend on the cut): one point per lane
+ *              for a small batch.  The LDS is the bin mask of gadapt_fem_eval_lds_bytes, as for gadapt_fem_forward.
+ * No float atomics, no scratch; a mesh's result does not depend on its batch. */
+int gadapt_fem_forward_wave(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                            const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                            const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
+                            int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* sol, void* stream);
+int gadapt_fem_modular_forward_wave(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells,
+                                    const int32_t* node_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                                    const int32_t* nt_idx, const int32_t* gptr, const float* gpar, const float* x, const float* lat_x,
+                                    const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int reduction, float* rhs,
+                                    float* coeffs, float* lfac, float* sol, float* loss, float* g_sol, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ 1-D tails
  * Differentiable 1-D P1 FEM of the reference's modular loss (firedrake_difFEM/difFEM_1d.py): semi-implicit Burgers steps
  * (torch_FEM_Burgers_1D, get_Burgers_initial_coeffs) and Poisson (torch_FEM_1D), with the reference's trapezoid inner
