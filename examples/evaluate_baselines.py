@@ -5,6 +5,8 @@ baselines: the fixed mesh and backFEM, the gradient descent of the mesh nodes on
     python examples/evaluate_baselines.py                        # 2-D, 11 x 11: GNN, fixed_mesh_2D, backFEM_2D
     python examples/evaluate_baselines.py --dim 1 --mesh 21       # 1-D
     python examples/evaluate_baselines.py --time                 # ms per sample of the descent, one call against the Python loop
+    python examples/evaluate_baselines.py --forward wave --adjoint wave   # the evaluation and backFEM_2D's descent on the
+                                                                 # wave-parallel FEM kernels: the same tables (2-D)
 
 `--time` measures `mesh_descent_2d` (1-D: `mesh_descent_1d`), every epoch enqueued by one call, against the loop it replaces,
 written with the public functions (`modular_loss_2d`, 1-D `gradient_meshpoints_1D`, plus a torch update): at batch 1 and at
@@ -58,12 +60,13 @@ def time_descent(dim, data, opt, batch, windows, reps):
         tri = [data.cells.shape[0] // batch] * batch         # topology on the host for both variants: it is looked up, not rebuilt
         args = (data.cells.cpu(), data.boundary_nodes.cpu(), [n] * batch, params)
         interior = ~data.boundary_nodes
-        one_call = lambda: mesh_descent_2d(x0, *args, epochs, lr, tri_counts=tri)
+        routes = dict(forward=opt.get('fem_forward', 'lane'), adjoint=opt.get('fem_adjoint', 'lane'))
+        one_call = lambda: mesh_descent_2d(x0, *args, epochs, lr, tri_counts=tri, **routes)
 
         def loop():
             x = x0.clone()
             for _ in range(epochs):
-                _, gx = modular_loss_2d(x, *args, 9, 'simpson', tri_counts=tri)
+                _, gx = modular_loss_2d(x, *args, 9, 'simpson', tri_counts=tri, **routes)
                 x[interior] = x[interior] - lr * gx[interior]
             return x
         per_epoch = LAUNCHES_PER_EPOCH_2D
@@ -99,17 +102,23 @@ if __name__ == '__main__':
     ap.add_argument('--epochs', type=int, default=None, help="the descent's epochs (default: the reference's, 200 in 2-D, 10 in 1-D)")
     ap.add_argument('--batch_size', type=int, default=1, help='model batch of the evaluation')
     ap.add_argument('--time', action='store_true', help='time the descent instead of printing the tables')
+    ap.add_argument('--forward', choices=('lane', 'wave'), default='lane',
+                    help="2-D: the load vector and lattice evaluation of the error norms and of the descent's epochs (opt['fem_forward'])")
+    ap.add_argument('--adjoint', choices=('lane', 'wave'), default='lane',
+                    help="2-D: the two lattice walks of the backward in the descent's epochs (opt['fem_adjoint'])")
     ap.add_argument('--windows', type=int, default=5)
     ap.add_argument('--reps', type=int, default=3)
     a = ap.parse_args()
     mesh = a.mesh or (11 if a.dim == 2 else 21)
     dims, suffix = [mesh] * a.dim, f'{a.dim}D'
-    common = dict(mesh_dims=dims, device='cuda:0', solver='torch_FEM', evaler='analytical', eval_quad_points=101)
+    common = dict(mesh_dims=dims, device='cuda:0', solver='torch_FEM', evaler='analytical', eval_quad_points=101,
+                  fem_forward=a.forward, fem_adjoint=a.adjoint)
     over = {} if a.epochs is None else {'epochs': a.epochs}
     test = MeshDataset(dims, a.num_test, seed=1, target='mmpde5')
     if a.time:
         opt = hot_path_opt(model='backFEM_' + suffix, **common, **over)
-        print(f"backFEM_{suffix}, {mesh} nodes per dimension, {opt['epochs']} epochs, lr {opt['lr']}")
+        routes = f", forward '{a.forward}', adjoint '{a.adjoint}'" if a.dim == 2 else ''
+        print(f"backFEM_{suffix}, {mesh} nodes per dimension, {opt['epochs']} epochs, lr {opt['lr']}{routes}")
         for batch in (1, a.num_test):
             time_descent(a.dim, collate(test.samples[:batch]).to(opt['device']), opt, batch, a.windows, a.reps)
         sys.exit(0)

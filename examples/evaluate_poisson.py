@@ -7,6 +7,7 @@ error reduction of the last two, with the model's time per sample.
     python examples/evaluate_poisson.py --dim 1 --mesh 21
     python examples/evaluate_poisson.py --state model.pt         # a saved state_dict instead of the brief training
     python examples/evaluate_poisson.py --mesh 64 --band window  # beyond 26 x 26: the windowed band solve
+    python examples/evaluate_poisson.py --forward wave           # the wave-parallel load vector and evaluation: the same tables
     python examples/evaluate_poisson.py --mesh 64 --band window --mmpde5_route strided --mmpde5_cfl 0.5 --mmpde5_max_steps 40000
                                                                  # ... with real MMPDE5 targets beyond 32 x 32
     python examples/evaluate_poisson.py --target monge_ampere    # the MA columns on Monge-Ampere meshes (2-D, at most 32 x 32)
@@ -60,6 +61,10 @@ if __name__ == '__main__':
     ap.add_argument('--mesh', type=int, default=11, help="nodes per dimension (2-D: at most 26, with --band window 81)")
     ap.add_argument('--band', choices=('lds', 'window'), default='lds',
                     help="FEM route of the 2-D evaluation: 'lds' keeps the banded factor in LDS, 'window' streams it (opt['fem_band'])")
+    ap.add_argument('--forward', choices=('lane', 'wave'), default='lane',
+                    help="the load vector and lattice evaluation of the 2-D error norms (opt['fem_forward']): a lane per node and five "
+                         "lattice points per lane, or a wave per node and per chunk of the lattice (--band lds only); the same norms, "
+                         "bit for bit")
     ap.add_argument('--mmpde5_route', choices=('lane', 'strided'), default='lane',
                     help="MMPDE5 targets: 'lane' stops at 32 a side in 2-D (beyond it the noise stand-in is used), 'strided' at 81")
     ap.add_argument('--mmpde5_cfl', type=float, default=None, help='RK4 step of MMPDE5 is cfl / N^3 (default: the reference 0.05)')
@@ -98,7 +103,7 @@ if __name__ == '__main__':
     dims = [a.mesh] * a.dim
     opt = hot_path_opt(mesh_dims=dims, hidden_dim=8, num_layers=4, batch_size=8, device='cuda:0', lr=1e-2, loss_type='mesh_loss',
                        solver='torch_FEM', evaler='analytical', eval_quad_points=101, load_quad_points=101,
-                       fem_band=a.band, mmpde5_route=a.mmpde5_route, ma_route=a.ma_route)
+                       fem_band=a.band, fem_forward=a.forward, mmpde5_route=a.mmpde5_route, ma_route=a.ma_route)
     # the default route of the batched MMPDE5 generator stops at 32 nodes a side in 2-D: beyond it the "MA" columns are those of
     # the stand-in target unless --mmpde5_route strided is given (81 a side)
     target = 'mmpde5' if a.dim == 1 or a.mesh <= (81 if opt['mmpde5_route'] == 'strided' else 32) else 'noise'

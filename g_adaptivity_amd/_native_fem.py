@@ -43,6 +43,7 @@ PROTOTYPES = {
     'gadapt_fem_backward_window_wave': (_I, [_I, _I, _I] + [_P] * 13 + [_I, _I] + [_P] * 9),
     'gadapt_fem_forward_wave': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 5),
     'gadapt_fem_modular_forward_wave': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I, _I] + [_P] * 7),
+    'gadapt_fem_eval_errors_wave': (_I, [_I, _I, _I] + [_P] * 12 + [_I, _I, _I] + [_P] * 7),
     'gadapt_fem1d_lds_bytes': (_L, [_I, _I]),
     'gadapt_fem1d_burgers_forward': (_I, [_I, _I] + [_P] * 6 + [_F] * 3 + [_I] * 7 + [_P] * 6),
     'gadapt_fem1d_burgers_backward': (_I, [_I, _I, _P, _P, _P, _F, _F, _I, _I, _I, _I] + [_P] * 7),
@@ -54,9 +55,11 @@ PROTOTYPES = {
     'gadapt_fem1d_expand': (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _P]),
     'gadapt_fem1d_spline': (_I, [_I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P]),
     'gadapt_fem_descend': (_I, [_I, _I, _I] + [_P] * 14 + [_I, _I, _I, _I, _F] + [_P] * 16),
+    'gadapt_fem_descend_wave': (_I, [_I, _I, _I] + [_P] * 14 + [_I, _I, _I, _I, _F] + [_P] * 15 + [_I, _P]),
     'gadapt_fem1d_descend': (_I, [_I, _I] + [_P] * 4 + [_I] * 3 + [_P, _I, _F, _I, _I] + [_P] * 11),
 }
 DESCEND_INTERNAL, DESCEND_ALL = 0, 1       # GADAPT_FEM1D_DESCEND_*
+ROUTE_WAVE_FORWARD, ROUTE_WAVE_ADJOINT = 1, 2   # GADAPT_FEM_ROUTE_WAVE_*
 FEM1D_LOSS_L1, FEM1D_LOSS_MSE = 0, 1       # GADAPT_FEM1D_LOSS_*
 SPLINE_OK, SPLINE_NOT_INCREASING, SPLINE_NOT_FINITE, SPLINE_BAD_COUNT = 0, 1, 2, 3   # GADAPT_SPLINE_S_*
 

@@ -54,7 +54,8 @@ class backFEM_2D(_Baseline):
     coeffs are those of the last epoch's solve, on the mesh before the last step, as the reference returns them.
     `loss_list` is [E,B] and `mesh_list` [E,N,2] of the last call (device tensors), `first_tangled` / `min_area` its
     tangling watch (`descent.DescentResult`).  Quadrature: torchquad's points per dimension of `load_quad_points` for the
-    load vector and the loss (101 -> 9, the built rule)."""
+    load vector and the loss (101 -> 9, the built rule).  opt['fem_forward'] / opt['fem_adjoint'] = 'wave' run the epochs on the
+    wave-parallel kernels (`mesh_descent_2d(forward=..., adjoint=...)`), the same meshes bit for bit."""
 
     def __init__(self, opt):
         super().__init__(opt)
@@ -66,7 +67,8 @@ class backFEM_2D(_Baseline):
         n = simpson_points_per_dim(self.opt.get('load_quad_points', 101))
         cells, boundary, node_counts, tri_counts, params = _modular_batch(self.opt, data, x0.shape[0])
         res = mesh_descent_2d(x0, cells, boundary, node_counts, params, int(self.epochs), float(self.lr), n_lat=n, n_load=n,
-                              keep_meshes=True, tri_counts=tri_counts)
+                              keep_meshes=True, tri_counts=tri_counts, forward=self.opt.get('fem_forward', 'lane'),
+                              adjoint=self.opt.get('fem_adjoint', 'lane'))
         self.loss_list, self.mesh_list = res.loss_hist, res.mesh_hist
         self.first_tangled, self.min_area = res.first_tangled, res.min_area
         self._stamp(res.x)

@@ -2,7 +2,7 @@
 
 The reference's `backFEM_*` baselines move the mesh points themselves by SGD on the L2 error of the Poisson solve, with no
 network: `train_step_adjoint` (`firedrake_difFEM/difFEM_2d.py:593-685`) and `train_step_vec` (`difFEM_1d.py:241-292`).  Here
-a whole batch descends at once and the loop lives behind the C-ABI (`gadapt_fem_descend`, `gadapt_fem1d_descend`;
+a whole batch descends at once and the loop lives behind the C-ABI (`gadapt_fem_descend[_wave]`, `gadapt_fem1d_descend`;
 fem_csrc/descent_kernels.hip): per epoch the launches of the modular loss (`modular_loss_2d`: nine; 1-D: forward, L2 seed,
 backward) and one step launch that does the optimizer's update, keeps the epoch's loss and mesh and watches for tangling.
 Nothing waits for the device between epochs or at the end.
@@ -21,7 +21,7 @@ import torch
 
 from . import _native_fem as _nf
 from ._native import NativeError, current_stream
-from .fem import _ptr, _topology, _tri_counts, pack_gaussians
+from .fem import _check_adjoint, _check_forward, _ptr, _topology, _tri_counts, pack_gaussians
 from .fem1d import _Batch, _points, _watch_flags
 
 __all__ = ['DescentResult', 'mesh_descent_2d', 'mesh_descent_1d', 'LAUNCHES_PER_EPOCH_2D', 'LAUNCHES_PER_EPOCH_1D']
@@ -63,7 +63,7 @@ def _require_gpu(t, what: str):
 def mesh_descent_2d(x0: torch.Tensor, cells: torch.Tensor, boundary: torch.Tensor, node_counts: Sequence[int],
                     pde_params: Sequence[dict], epochs: int, lr: float, n_lat: Optional[int] = None, n_load: Optional[int] = None,
                     x_ref: Optional[torch.Tensor] = None, keep_meshes: bool = False,
-                    tri_counts: Optional[Sequence[int]] = None) -> DescentResult:
+                    tri_counts: Optional[Sequence[int]] = None, *, forward: str = 'lane', adjoint: str = 'lane') -> DescentResult:
     """`epochs` steps of x[interior] -= lr * d loss_b / d x on every mesh of x0 [N,2] at once, loss_b the Simpson L2 error of
     mesh b's Poisson solve against its own Gaussians (`modular_loss_2d(..., n_lat, 'simpson')`; n_lat defaults to the
     reference's 9 points per dimension, what torchquad makes of load_quad_points = 101).  Bit-identical to that loop written
@@ -71,7 +71,14 @@ def mesh_descent_2d(x0: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
 
     x_ref: the mesh whose triangle orientations count as untangled (default x0).  keep_meshes: also return every epoch's
     mesh.  Refuses what `modular_loss_2d` refuses: meshes beyond the LDS budget (26 x 26 nodes), a load rule other than the
-    built one.  epochs == 0 is valid."""
+    built one.  epochs == 0 is valid.
+
+    forward, adjoint: 'lane' (the default: `gadapt_fem_descend`) or 'wave', the wave-parallel form of every epoch's load
+    vector and evaluation (`modular_loss_2d(forward='wave')`) and of its backward's two lattice walks
+    (`modular_loss_2d(adjoint='wave')`), through `gadapt_fem_descend_wave` when either is 'wave'.  Every field of the result
+    has the same bits whichever pair is chosen."""
+    _check_forward('mesh_descent_2d', forward, 'lds')
+    _check_adjoint('mesh_descent_2d', adjoint)
     _require_gpu(x0, 'mesh_descent_2d')
     if x0.dtype != torch.float32:
         raise TypeError(f"mesh_descent_2d: fp32 expected, got {x0.dtype}")
@@ -113,10 +120,15 @@ def mesh_descent_2d(x0: torch.Tensor, cells: torch.Tensor, boundary: torch.Tenso
     min_area = f(B)
     sign = torch.empty(T, dtype=torch.int8, device=dev)
     head = topo.head(gptr, gpar, x, lat, lat, n_lat, tri_mesh=True)
-    _nf.call('gadapt_fem_descend', *head[:-5], _ptr(x_ref), *head[-5:],        # x_ref comes after x, before the lattice
-             epochs, float(lr), rhs.data_ptr(), coeffs.data_ptr(), lfac.data_ptr(), sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(),
-             gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), loss_hist.data_ptr() if epochs else None, _ptr(mesh_hist),
-             first_tangled.data_ptr(), min_area.data_ptr(), sign.data_ptr(), current_stream(dev))
+    routes = (_nf.ROUTE_WAVE_FORWARD if forward == 'wave' else 0) | (_nf.ROUTE_WAVE_ADJOINT if adjoint == 'wave' else 0)
+    args = (*head[:-5], _ptr(x_ref), *head[-5:],                                # x_ref comes after x, before the lattice
+            epochs, float(lr), rhs.data_ptr(), coeffs.data_ptr(), lfac.data_ptr(), sol.data_ptr(), loss.data_ptr(), g_sol.data_ptr(),
+            gc.data_ptr(), mu.data_ptr(), tgrad.data_ptr(), gx.data_ptr(), loss_hist.data_ptr() if epochs else None, _ptr(mesh_hist),
+            first_tangled.data_ptr(), min_area.data_ptr(), sign.data_ptr())
+    if routes:
+        _nf.call('gadapt_fem_descend_wave', *args, routes, current_stream(dev))
+    else:
+        _nf.call('gadapt_fem_descend', *args, current_stream(dev))
     return DescentResult(x=x, coeffs=coeffs if epochs else None, loss_hist=loss_hist, mesh_hist=mesh_hist,
                          first_tangled=first_tangled, min_area=min_area)
 

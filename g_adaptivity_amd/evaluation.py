@@ -15,7 +15,9 @@ mesher and of the model, with the model's time per sample.  This is the referenc
 Cholesky launches of `fem_poisson`, then the lattice evaluation fused with the reduction of the two norms and a last launch
 that adds each mesh's chunk partials (`gadapt_fem_eval_errors`, four launches); in 1-D one launch, one workgroup per mesh
 (`gadapt_fem1d_poisson_eval_errors`).  The solution on the lattice is never written to memory and nothing waits for the
-device.  A mesh's pair of norms does not depend on what else is in the batch.  The 1-D launch assembles its stiffness matrix
+device.  forward='wave' (opt['fem_forward'] = 'wave' for `evaluate_model_fine` and `eval_grid_MMPDE_MA`; band 'lds') runs the
+wave-parallel load vector and evaluation of `fem_poisson(forward='wave')` instead, five launches with the solution written to a
+workspace (`gadapt_fem_eval_errors_wave`): the same norms, bit for bit.  A mesh's pair of norms does not depend on what else is in the batch.  The 1-D launch assembles its stiffness matrix
 in fp64 (the fp32 matrix of `fem_poisson_1d` moves these norms by up to 3e-4: docs/measurements.md), the rest is that forward.
 
 Limits: `solver='torch_FEM'` with `evaler='analytical'` only (the others need Firedrake); `fine_eval=True` only; the FEM
@@ -33,7 +35,7 @@ import torch
 
 from . import _native_fem as _nf
 from ._native import NativeError, current_stream
-from .fem import ENTRY_POINTS, _check_route, _solve_tail, _topology, _tri_counts, pack_gaussians, simpson_points_per_dim
+from .fem import ENTRY_POINTS, _check_forward, _check_route, _solve_tail, _topology, _tri_counts, pack_gaussians, simpson_points_per_dim
 from .fem1d import _Batch, _split_params, _watch_flags
 from .mesh_graph import MeshData, MeshLoader, Mixed_DataLoader
 
@@ -91,7 +93,7 @@ def _require_gpu(t, what: str):
 def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params: Sequence[dict], n_eval: int, *,
                         cells: Optional[torch.Tensor] = None, boundary: Optional[torch.Tensor] = None,
                         tri_counts: Optional[Sequence[int]] = None, opt: Optional[dict] = None, band: str = 'lds',
-                        tri_slab: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+                        tri_slab: int = 0, forward: str = 'lane') -> Tuple[torch.Tensor, torch.Tensor]:
     """(L1 [B], L2 [B]) on the device: per mesh, the P1 Poisson solve with its own Gaussians, expanded on the lattice
     linspace(0, 1, n_eval) per dimension, and the trapezium norms of sol - u_true there.
 
@@ -105,7 +107,15 @@ def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params:
     2 MB per 64 x 64 mesh), and takes the triangles in slabs of `tri_slab` ids (a multiple of 32; 0: the largest slab the
     LDS budget leaves): square meshes up to 81 x 81 nodes.  The windowed route factors and substitutes in fp64 and evaluates
     the load vector's forcing in fp64 (fp32 missed the evaluation's accuracy rule from 27 x 27 on), so where both routes take
-    a mesh their norms agree to the fp32 rounding of those, not bitwise; the result does not depend on `tri_slab`, bit for bit."""
+    a mesh their norms agree to the fp32 rounding of those, not bitwise; the result does not depend on `tri_slab`, bit for bit.
+
+    forward (2-D only; 1-D input does not read it): 'lane' is the four launches above.  'wave' (band='lds' only; with
+    band='window' a ValueError) runs the load vector with a wave per node and the evaluation with a wave per chunk of the
+    lattice (`fem_poisson(forward='wave')`) into a workspace allocated here (4 * n_eval^2 bytes a mesh: on this route the
+    solution on the lattice does reach memory), then the lane route's reduction reading it: five launches
+    (`gadapt_fem_eval_errors_wave`), and the same L1 and L2, bit for bit."""
+    if torch.is_tensor(x) and x.dim() == 2 and x.shape[1] == 2:
+        _check_forward('poisson_eval_errors', forward, band)
     _require_gpu(x, 'poisson_eval_errors')
     opt = opt or {}
     tri_slab = _check_route('poisson_eval_errors', band, tri_slab)
@@ -136,8 +146,13 @@ def poisson_eval_errors(x: torch.Tensor, node_counts: Sequence[int], pde_params:
         rhs, coeffs = torch.empty(topo.n_nodes, device=dev), torch.empty(topo.n_nodes, device=dev)
         partials = torch.empty(int(lib.gadapt_fem_eval_partials_floats(B)), device=dev)
         work = topo.factor_buffer(dev) if band == 'window' else None           # 'lds': the factor is not kept
-        _nf.call(ENTRY_POINTS['eval_errors'][band], *topo.head(gptr, gpar, x, lat, lat, n_eval),
-                 *_solve_tail(topo, rhs, coeffs, work, tri_slab), partials.data_ptr(), err.data_ptr(), stream)
+        if forward == 'wave':
+            sol_work = torch.empty(B * n_eval * n_eval, device=dev)            # the wave evaluation's sol, read by the reduction
+            _nf.call(ENTRY_POINTS['eval_errors_wave'][band], *topo.head(gptr, gpar, x, lat, lat, n_eval),
+                     *_solve_tail(topo, rhs, coeffs, work, tri_slab), sol_work.data_ptr(), partials.data_ptr(), err.data_ptr(), stream)
+        else:
+            _nf.call(ENTRY_POINTS['eval_errors'][band], *topo.head(gptr, gpar, x, lat, lat, n_eval),
+                     *_solve_tail(topo, rhs, coeffs, work, tri_slab), partials.data_ptr(), err.data_ptr(), stream)
     elif x.dim() == 1 or (x.dim() == 2 and x.shape[1] == 1):
         x = x.reshape(-1).contiguous()
         if sum(int(n) for n in node_counts) != x.shape[0]:
@@ -208,11 +223,15 @@ def _samples_of(dataset_or_batch) -> List[MeshData]:
 
 
 def _errors_of(coords: Sequence[torch.Tensor], samples: Sequence[MeshData], n_eval: int, opt, dev) -> torch.Tensor:
-    """[M,2] (L1, L2) of mesh k = coords[k] on the topology and Gaussians of samples[k]: ONE poisson_eval_errors call."""
+    """[M,2] (L1, L2) of mesh k = coords[k] on the topology and Gaussians of samples[k]: ONE poisson_eval_errors call.
+    2-D meshes take the route from opt['fem_band'] and opt['fem_forward'] ('wave' with 'window' is refused before anything moves
+    to the device, as by every other reader of the key); 1-D meshes read neither."""
     counts = [int(c.shape[0]) for c in coords]
+    band, forward = opt.get('fem_band', 'lds'), opt.get('fem_forward', 'lane')
+    if coords[0].dim() == 2 and coords[0].shape[1] == 2:
+        _check_forward("evaluation (opt['fem_forward'])", forward, band)
     x = torch.cat([c.detach().to(dev, non_blocking=True).float().reshape(c.shape[0], -1) for c in coords], 0)
     params = [s.pde_params for s in samples]
-    band = opt.get('fem_band', 'lds')
     if x.shape[1] == 1:
         l1, l2 = poisson_eval_errors(x, counts, params, n_eval, opt=opt)
     else:
@@ -220,7 +239,8 @@ def _errors_of(coords: Sequence[torch.Tensor], samples: Sequence[MeshData], n_ev
         cells = torch.cat([s.cells.cpu() + int(o) for s, o in zip(samples, off[:-1])], 0)
         boundary = torch.cat([s.boundary_nodes.cpu() for s in samples], 0)
         l1, l2 = poisson_eval_errors(x, counts, params, n_eval, cells=cells, boundary=boundary,
-                                     tri_counts=[int(s.cells.shape[0]) for s in samples], opt=opt, band=band)
+                                     tri_counts=[int(s.cells.shape[0]) for s in samples], opt=opt, band=band,
+                                     forward=forward)
     return torch.stack([l1, l2], 1)
 
 
@@ -300,7 +320,8 @@ def evaluate_model_fine(model, dataset, opt, fine_eval: bool = True, batch_size:
 
     The model runs in eval mode without gradients through `MeshLoader`, or `Mixed_DataLoader` for
     `opt['data_type'] == 'randg_mix'`; `opt.get('fem_band', 'lds')` picks the FEM route of every `poisson_eval_errors` call
-    here and in `eval_grid_MMPDE_MA` ('window': meshes beyond 26 x 26 nodes); `loss_type` 'mesh_loss' and 'modular' return the coordinates, 'pde_loss' the triple
+    here and in `eval_grid_MMPDE_MA` ('window': meshes beyond 26 x 26 nodes) and `opt.get('fem_forward', 'lane')` the form of its
+    load vector and evaluation ('wave': the wave-parallel kernels, band 'lds' only, the same columns bit for bit); `loss_type` 'mesh_loss' and 'modular' return the coordinates, 'pde_loss' the triple
     whose second entry they are.  `opt['overfit_num']`, when set, lists the sample indices to evaluate.  With `batch_size=1`
     the model is called once per sample and `MLmodel_time` is `model.end_MLmodel - start` as in the reference (the forward
     waits for the device before it stamps); with a larger `batch_size` it is the batch's time divided by the batch's size.

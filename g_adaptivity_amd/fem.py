@@ -32,7 +32,9 @@ each (gadapt_fem_backward_wave, gadapt_fem_backward_window_wave): the same gradi
 forward='wave' (the same functions; opt['fem_forward'] = 'wave' for `torch_FEM_2D`, `gnn_pde_tail`, `gradient_meshpoints_2D` and
 `PdeBatch.from_data`) runs the load vector with a wave per node and the evaluation with a wave per chunk of the lattice and two
 phases per point (gadapt_fem_forward_wave, gadapt_fem_modular_forward_wave): the same rhs, coeffs, factor and sol, bit for bit.
-band='lds' only: with band='window' it is a ValueError.  The default stays 'lane'.
+band='lds' only: with band='window' it is a ValueError.  The default stays 'lane'.  The same two keys reach the evaluation
+(`evaluation.poisson_eval_errors(forward='wave')`, gadapt_fem_eval_errors_wave) and the mesh descent
+(`descent.mesh_descent_2d(forward=..., adjoint=...)`, gadapt_fem_descend_wave), with the lane routes' bits.
 
 `PdeBatch` is the tail of one batch topology with everything a call would rebuild kept on the device - the topology, the lattice
 axes, the Gaussians' buffers: `gnn_pde_tail` on a batch that carries one (`data._pde_batch`) only launches, so it can be
@@ -297,6 +299,7 @@ ENTRY_POINTS = {op: {'lds': f'gadapt_fem_{op}', 'window': f'gadapt_fem_{op}_wind
 ENTRY_POINTS['backward_wave'] = {'lds': 'gadapt_fem_backward_wave', 'window': 'gadapt_fem_backward_window_wave'}
 ENTRY_POINTS['forward_wave'] = {'lds': 'gadapt_fem_forward_wave'}
 ENTRY_POINTS['modular_forward_wave'] = {'lds': 'gadapt_fem_modular_forward_wave'}
+ENTRY_POINTS['eval_errors_wave'] = {'lds': 'gadapt_fem_eval_errors_wave'}
 _BACKWARD_OP = {'lane': 'backward', 'wave': 'backward_wave'}
 _FORWARD_OP = {'lane': 'forward', 'wave': 'forward_wave'}
 _MODULAR_OP = {'lane': 'modular_forward', 'wave': 'modular_forward_wave'}

@@ -103,20 +103,21 @@ __global__ void __launch_bounds__(DESC_THREADS) fem_descent_step_kernel(const in
     if (threadIdx.x == 0) record_epoch(b, n_meshes, epoch, m, loss, loss_hist, first_tangled, min_area);
 }
 
-extern "C" int gadapt_fem_descend(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
-                                  const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
-                                  const int32_t* nt_idx, const int32_t* gptr, const float* gpar, float* x, const float* x_ref,
-                                  const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int epochs, float lr,
-                                  float* rhs, float* coeffs, float* lfac, float* sol, float* loss, float* g_sol, float* gc, float* mu,
-                                  float* tgrad, float* gx, float* loss_hist, float* mesh_hist, int32_t* first_tangled, float* min_area,
-                                  int8_t* sign, void* stream) {
+// Both 2-D entry points, under the name `who`.  routes: GADAPT_FEM_ROUTE_WAVE_FORWARD and _ADJOINT select the wave-parallel
+// form of an epoch's forward and backward launches (fem_host.h), which have the lane kernels' bits; 0 is gadapt_fem_descend.
+static int descend_2d(const char* who, int routes, int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                      const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                      const int32_t* nt_idx, const int32_t* gptr, const float* gpar, float* x, const float* x_ref, const float* lat_x,
+                      const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int epochs, float lr, float* rhs, float* coeffs,
+                      float* lfac, float* sol, float* loss, float* g_sol, float* gc, float* mu, float* tgrad, float* gx, float* loss_hist,
+                      float* mesh_hist, int32_t* first_tangled, float* min_area, int8_t* sign, void* stream) {
     if (B <= 0 || N <= 0 || T <= 0 || epochs < 0 || !meta || !cells || !node_mesh || !tri_mesh || !int_idx || !int_node || !nt_ptr ||
         !nt_idx || !gptr || !gpar || !x || !lat_x || !lat_y || !rhs || !coeffs || !lfac || !sol || !loss || !g_sol || !gc || !mu ||
         !tgrad || !gx || !first_tangled || !min_area || !sign || (epochs > 0 && !loss_hist) || max_tris <= 0)
-        return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem_descend: null pointer or bad size");
-    if (nlat < 3 || !(nlat & 1)) return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem_descend: the Simpson rule needs an odd nlat >= 3");
+        return fem_fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size");
+    if (nlat < 3 || !(nlat & 1)) return fem_fail_as(GADAPT_FEM_E_BADARG, who, "the Simpson rule needs an odd nlat >= 3");
     if (max_lds_bytes <= 0 || max_lds_bytes > GADAPT_FEM_LDS_BUDGET || gadapt_fem_eval_lds_bytes(max_tris) > GADAPT_FEM_LDS_BUDGET)
-        return fem_fail(GADAPT_FEM_E_LDS, "gadapt_fem_descend: band factor or triangle bin mask outside the LDS budget");
+        return fem_fail_as(GADAPT_FEM_E_LDS, who, "band factor or triangle bin mask outside the LDS budget");
     // the lattice loss's row sums, as gadapt_fem_modular_forward refuses them in an epoch (and under its name)
     if (epochs > 0 && (int64_t)nlat * 4 > GADAPT_FEM_LDS_BUDGET)
         return fem_fail(GADAPT_FEM_E_LDS, "gadapt_fem_modular_forward: the lattice's row sums exceed the LDS budget");
@@ -125,17 +126,46 @@ extern "C" int gadapt_fem_descend(int B, int N, int T, const int32_t* meta, cons
     const FemAdjoint adj{gc, mu, tgrad, gx};
     const FemPlan P{max_lds_bytes, gadapt_fem_eval_lds_bytes(max_tris), 0};
     hipStream_t s = (hipStream_t)stream;
+    const bool wave_forward = routes & GADAPT_FEM_ROUTE_WAVE_FORWARD, wave_adjoint = routes & GADAPT_FEM_ROUTE_WAVE_ADJOINT;
     const int n_init = T > B ? T : B;
     FEM_LAUNCH(fem_descent_sign_kernel, (n_init + DESC_THREADS - 1) / DESC_THREADS, DESC_THREADS, 0, T, B, cells, x_ref ? x_ref : x, sign,
                first_tangled, min_area);
     for (int j = 0; j < epochs; ++j) {
-        int rc = fem_launch_modular_forward(Band::lds, b, P, sc, GADAPT_FEM_LOSS_SIMPSON, sol, loss, g_sol, s);
-        if (rc || (rc = fem_launch_backward(Band::lds, b, P, sc, nullptr, g_sol, adj, s))) return rc;
+        int rc = fem_launch_modular_forward(Band::lds, b, P, sc, GADAPT_FEM_LOSS_SIMPSON, sol, loss, g_sol, s, wave_forward);
+        if (rc || (rc = fem_launch_backward(Band::lds, b, P, sc, nullptr, g_sol, adj, s, wave_adjoint))) return rc;
         FEM_LAUNCH(fem_descent_step_kernel, B, DESC_THREADS, 0, meta, cells, int_idx, sign, gx, loss, lr, j, B, N, x, loss_hist, mesh_hist,
                    first_tangled, min_area);
     }
     return GADAPT_FEM_OK;
 }
+
+#define DESCEND_ARGS                                                                                                                       \
+    B, N, T, meta, cells, node_mesh, tri_mesh, int_idx, int_node, nt_ptr, nt_idx, gptr, gpar, x, x_ref, lat_x, lat_y, nlat, max_lds_bytes, \
+        max_tris, epochs, lr, rhs, coeffs, lfac, sol, loss, g_sol, gc, mu, tgrad, gx, loss_hist, mesh_hist, first_tangled, min_area, sign, stream
+
+extern "C" int gadapt_fem_descend(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                  const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                                  const int32_t* nt_idx, const int32_t* gptr, const float* gpar, float* x, const float* x_ref,
+                                  const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int epochs, float lr,
+                                  float* rhs, float* coeffs, float* lfac, float* sol, float* loss, float* g_sol, float* gc, float* mu,
+                                  float* tgrad, float* gx, float* loss_hist, float* mesh_hist, int32_t* first_tangled, float* min_area,
+                                  int8_t* sign, void* stream) {
+    return descend_2d("gadapt_fem_descend", 0, DESCEND_ARGS);
+}
+
+// routes is checked first: a value with other bits set selects nothing that is built
+extern "C" int gadapt_fem_descend_wave(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                       const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                                       const int32_t* nt_idx, const int32_t* gptr, const float* gpar, float* x, const float* x_ref,
+                                       const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int epochs,
+                                       float lr, float* rhs, float* coeffs, float* lfac, float* sol, float* loss, float* g_sol, float* gc,
+                                       float* mu, float* tgrad, float* gx, float* loss_hist, float* mesh_hist, int32_t* first_tangled,
+                                       float* min_area, int8_t* sign, int routes, void* stream) {
+    if (routes & ~(GADAPT_FEM_ROUTE_WAVE_FORWARD | GADAPT_FEM_ROUTE_WAVE_ADJOINT))
+        return fem_fail(GADAPT_FEM_E_BADARG, "gadapt_fem_descend_wave: routes takes bit 0 (wave forward) and bit 1 (wave adjoint) only");
+    return descend_2d("gadapt_fem_descend_wave", routes, DESCEND_ARGS);
+}
+#undef DESCEND_ARGS
 
 // ---------------------------------------------------------------------------------------------------- 1-D
 // u_true is f1::gauss, the one the 1-D tail evaluates (fem1d_common.h)

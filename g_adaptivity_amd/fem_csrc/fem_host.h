@@ -9,6 +9,7 @@
 #include "gadapt_fem.h"
 
 int fem_fail(int code, const char* msg);   // leaves msg in gadapt_fem_last_error()'s slot and returns code
+int fem_fail_as(int code, const char* who, const char* what);   // the same with "<who>: <what>" as the message
 int fem_launched(const char* what);        // after a launch: GADAPT_FEM_OK, or GADAPT_FEM_E_LAUNCH with "<what>: <error>" in the slot
 // kernel<<<grid, block, lds, s>>>(...) on the stream `s` of the calling function, which returns fem_launched's code if that fails
 #define FEM_LAUNCH(kernel, grid, block, lds, ...)                 \

@@ -25,7 +25,7 @@ int fem_fail(int code, const char* msg) {
 }
 
 // "<who>: <what>", who being the entry point that refuses
-static int fail_as(int code, const char* who, const char* what) {
+int fem_fail_as(int code, const char* who, const char* what) {
     char msg[200];
     snprintf(msg, sizeof msg, "%s: %s", who, what);
     return fem_fail(code, msg);
@@ -621,20 +621,20 @@ static int check_batch(const char* who, const FemBatch& b, unsigned needs, std::
     bad |= (needs & NEED_MAX_TRIS) && b.max_tris <= 0;
     bad |= (needs & NEED_WORK) && (!work || ((uintptr_t)work & 7));
     for (const void* p : required) bad |= !p;
-    if (bad) return fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size");
+    if (bad) return fem_fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size");
     if (!b.lat_x || !b.lat_y || b.nlat < 2) return fem_fail(GADAPT_FEM_E_BADARG, "evaluation lattice: need lat_x, lat_y and nlat >= 2");
-    if ((needs & NLAT_RANGE) && b.nlat > 46340) return fail_as(GADAPT_FEM_E_BADARG, who, "nlat * nlat exceeds the int range");
+    if ((needs & NLAT_RANGE) && b.nlat > 46340) return fem_fail_as(GADAPT_FEM_E_BADARG, who, "nlat * nlat exceeds the int range");
     return GADAPT_FEM_OK;
 }
 
 // what a modular forward checks of its loss arguments, before the shared ones
 static int check_loss(const char* who, const FemBatch& b, int reduction, const float* loss, const float* g_sol) {
     if (b.B <= 0 || !loss || !g_sol || (reduction != GADAPT_FEM_LOSS_MSE && reduction != GADAPT_FEM_LOSS_SIMPSON))
-        return fail_as(GADAPT_FEM_E_BADARG, who, "null output or unknown reduction");
+        return fem_fail_as(GADAPT_FEM_E_BADARG, who, "null output or unknown reduction");
     if (reduction == GADAPT_FEM_LOSS_SIMPSON && (b.nlat < 3 || !(b.nlat & 1)))
-        return fail_as(GADAPT_FEM_E_BADARG, who, "the Simpson rule needs an odd nlat >= 3");
+        return fem_fail_as(GADAPT_FEM_E_BADARG, who, "the Simpson rule needs an odd nlat >= 3");
     if (b.nlat > 0 && (int64_t)b.nlat * 4 > GADAPT_FEM_LDS_BUDGET)
-        return fail_as(GADAPT_FEM_E_LDS, who, "the lattice's row sums exceed the LDS budget");
+        return fem_fail_as(GADAPT_FEM_E_LDS, who, "the lattice's row sums exceed the LDS budget");
     return GADAPT_FEM_OK;
 }
 
@@ -688,13 +688,18 @@ static int launch_eval(Band band, const FemBatch& b, const FemPlan& P, const flo
     return GADAPT_FEM_OK;
 }
 
-// the lattice evaluation fused with the two error norms' chunk partials, then their sum -> err
-static int launch_eval_errors(Band band, const FemBatch& b, const FemPlan& P, const float* coeffs, float* partials, float* err, hipStream_t s) {
+// the lattice evaluation fused with the two error norms' chunk partials, then their sum -> err.  sol_work (Band::lds alone,
+// gadapt_fem_eval_errors_wave): the wave evaluation into it, then the lane kernel's sums read from it, the same partials
+static int launch_eval_errors(Band band, const FemBatch& b, const FemPlan& P, const float* coeffs, float* partials, float* err, hipStream_t s,
+                              float* sol_work = nullptr) {
     const dim3 grid(b.B, FEM_EVAL_CHUNKS);
     if (band == Band::window)
         FEM_LAUNCH(fem_eval_err_slab_kernel, grid, FEM_EVAL_THREADS, (size_t)P.eval_lds, b.meta, b.cells, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x,
                    coeffs, b.lat_x, b.lat_y, b.nlat, P.slab, partials);
-    else
+    else if (sol_work) {
+        if (int rc = launch_eval(band, b, P, coeffs, sol_work, s, true)) return rc;
+        FEM_LAUNCH(fem_err_lattice_kernel, grid, FEM_EVAL_THREADS, 0, b.gptr, b.gpar, b.lat_x, b.lat_y, b.nlat, sol_work, partials);
+    } else
         FEM_LAUNCH(fem_eval_err_kernel, grid, FEM_EVAL_THREADS, (size_t)P.eval_lds, b.meta, b.cells, b.nt_ptr, b.nt_idx, b.gptr, b.gpar, b.x, coeffs,
                    b.lat_x, b.lat_y, b.nlat, partials);
     FEM_LAUNCH(fem_err_finish_kernel, (b.B + 255) / 256, 256, 0, b.B, FEM_EVAL_CHUNKS, b.lat_x, b.lat_y, b.nlat, partials, err);
@@ -747,7 +752,7 @@ static int check_forward(Band band, const char* who, const FemBatch& b, const Fe
     int rc = band == Band::window ? check_batch(who, b, NEED_MAX_TRIS | NEED_WORK | NLAT_RANGE, {sc.rhs, sc.coeffs, sol}, sc.factor)
                                   : check_batch(who, b, NEED_MAX_TRIS, {sc.rhs, sc.coeffs});
     if (rc || (rc = make_plan(band, who, b, tri_slab, true, P))) return rc;
-    return !sc.factor || !sol ? fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size") : GADAPT_FEM_OK;
+    return !sc.factor || !sol ? fem_fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size") : GADAPT_FEM_OK;
 }
 
 // wave: the *_wave entry points (Band::lds), the same checks and the wave-parallel load vector and evaluation
@@ -766,17 +771,19 @@ static int modular_forward(Band band, const char* who, const FemBatch& b, const 
     return fem_launch_modular_forward(band, b, P, sc, reduction, sol, loss, g_sol, s, wave);
 }
 
-// Band::lds takes a NULL lfac (the factor is not kept), refuses partials and err only after the LDS, and nlat's range last
+// Band::lds takes a NULL lfac (the factor is not kept), refuses partials and err only after the LDS, and nlat's range last.
+// wave: gadapt_fem_eval_errors_wave (Band::lds), the same checks, sol_work refused with partials and err, and the
+// wave-parallel load vector and evaluation
 static int eval_errors(Band band, const char* who, const FemBatch& b, const FemScratch& sc, int tri_slab, float* partials, float* err,
-                       hipStream_t s) {
+                       hipStream_t s, bool wave = false, float* sol_work = nullptr) {
     FemPlan P;
     int rc = band == Band::window ? check_batch(who, b, NEED_MAX_TRIS | NEED_WORK | NLAT_RANGE, {sc.rhs, sc.coeffs, partials, err}, sc.factor)
                                   : check_batch(who, b, NEED_MAX_TRIS, {sc.rhs, sc.coeffs});
     if (rc || (rc = make_plan(band, who, b, tri_slab, true, &P))) return rc;
-    if (!partials || !err) return fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size");
-    if (b.nlat > 46340) return fail_as(GADAPT_FEM_E_BADARG, who, "nlat * nlat exceeds the int range");
-    if ((rc = launch_solve(band, b, P, sc, s))) return rc;
-    return launch_eval_errors(band, b, P, sc.coeffs, partials, err, s);
+    if (!partials || !err || (wave && !sol_work)) return fem_fail_as(GADAPT_FEM_E_BADARG, who, "null pointer or bad size");
+    if (b.nlat > 46340) return fem_fail_as(GADAPT_FEM_E_BADARG, who, "nlat * nlat exceeds the int range");
+    if ((rc = launch_solve(band, b, P, sc, s, wave))) return rc;
+    return launch_eval_errors(band, b, P, sc.coeffs, partials, err, s, wave ? sol_work : nullptr);
 }
 
 // sc.coeffs and, on Band::lds, sc.factor are only read; g_coeffs and g_sol may be NULL (no gradient flows in through them).
@@ -896,4 +903,13 @@ extern "C" int gadapt_fem_modular_forward_wave(int B, int N, int T, const int32_
                                                float* coeffs, float* lfac, float* sol, float* loss, float* g_sol, void* stream) {
     return modular_forward(Band::lds, "gadapt_fem_modular_forward_wave", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, lfac}, reduction, 0, sol, loss,
                            g_sol, (hipStream_t)stream, true);
+}
+
+extern "C" int gadapt_fem_eval_errors_wave(int B, int N, int T, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                           const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                                           const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y,
+                                           int nlat, int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* sol_work,
+                                           float* partials, float* err, void* stream) {
+    return eval_errors(Band::lds, "gadapt_fem_eval_errors_wave", FEM_BATCH(nullptr, max_tris), {rhs, coeffs, lfac}, 0, partials, err,
+                       (hipStream_t)stream, true, sol_work);
 }

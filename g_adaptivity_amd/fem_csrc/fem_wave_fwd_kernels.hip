@@ -1,5 +1,6 @@
 // fem_wave_fwd_kernels.hip - the wave-parallel form of the forward's load vector and lattice evaluation on the resident-band
-// route (fem_forward='wave': gadapt_fem_forward_wave, gadapt_fem_modular_forward_wave in include/gadapt_fem.h).
+// route (fem_forward='wave': gadapt_fem_forward_wave, gadapt_fem_modular_forward_wave in include/gadapt_fem.h), and at the
+// file's end the error norms of the evaluation on them (gadapt_fem_eval_errors_wave).
 //
 // This file is compiled inside fem_kernels.hip's translation unit, after fem_wave_grad_kernels.hip: it calls
 // fem_kernels.hip's simpson_box, eval_frame, build_bin_mask and bin_of and the fem:: helpers, and takes FEM_WAVE from the
@@ -151,4 +152,50 @@ static int eval_wave_chunks(int n_meshes, int nlat) {
     const int64_t per_lane = ((int64_t)nlat * nlat + FEM_WAVE - 1) / FEM_WAVE;
     const int64_t room = FEM_EVALW_GROUPS / n_meshes > 1 ? FEM_EVALW_GROUPS / n_meshes : 1;
     return (int)(per_lane < room ? per_lane : room);
+}
+
+// ---------------------------------------------------------------------------------------------------- error norms
+// gadapt_fem_eval_errors_wave: the evaluation's norms on the wave-parallel walk.  fem_eval_err_kernel fuses eval_point with the
+// sums of the two norms, and the order of those sums is tied to its cut of the lattice (FEM_EVAL_CHUNKS chunks of
+// FEM_EVAL_THREADS lanes), which fem_eval_wave_kernel's cut is not.  So the wave route takes two launches: fem_eval_wave_kernel
+// writes sol to a workspace (sol_work: 4 * nlat * nlat bytes a mesh, 40 KB at 101 points - on this route sol DOES reach
+// memory; the lane route's "sol never written" stays true of the lane route), and the kernel below is fem_eval_err_kernel's
+// loop, statement for statement, with eval_point's value read from there.  sol_work carries eval_point's bits, so the
+// partials and err are the lane route's, bit for bit, in any batch.  grid (n_meshes, FEM_EVAL_CHUNKS), FEM_EVAL_THREADS
+// lanes; 2 * waves floats of static LDS for the wave sums and no dynamic LDS.  Nothing returns before the two barriers:
+// every lane reaches both.  No float atomics.
+__global__ void __launch_bounds__(FEM_EVAL_THREADS) fem_err_lattice_kernel(const int32_t* __restrict__ gptr, const float* __restrict__ gpar,
+                                                                           const float* __restrict__ lat_x, const float* __restrict__ lat_y,
+                                                                           int nlat, const float* __restrict__ sol_work,
+                                                                           float* __restrict__ partials) {
+    constexpr int waves = FEM_EVAL_THREADS / 64;
+    __shared__ float red[2 * waves];
+    const int b = blockIdx.x;
+    const int g0 = gptr[b], g1 = gptr[b + 1];
+    const int Q = nlat * nlat;
+    const int q0 = (int)((int64_t)Q * blockIdx.y / gridDim.y), q1 = (int)((int64_t)Q * (blockIdx.y + 1) / gridDim.y);
+    float s1 = 0.0f, s2 = 0.0f;
+    for (int q = q0 + threadIdx.x; q < q1; q += FEM_EVAL_THREADS) {
+        const int i = q / nlat, j = q % nlat;
+        const float px = lat_x[i], py = lat_y[j];
+        const float e = sol_work[(int64_t)b * Q + q] - fem::u_true(px, py, gpar, g0, g1);
+        const float w = ((i == 0 || i == nlat - 1) ? 0.5f : 1.0f) * ((j == 0 || j == nlat - 1) ? 0.5f : 1.0f);
+        s1 = s1 + w * fabsf(e);
+        s2 = s2 + w * (e * e);
+    }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    __syncthreads();                                               // fem_eval_err_kernel's barrier, kept: the same two on every lane
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = s1;
+        red[waves + (threadIdx.x >> 6)] = s2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float a1 = red[0], a2 = red[waves];
+        for (int k = 1; k < waves; ++k) { a1 = a1 + red[k]; a2 = a2 + red[waves + k]; }
+        float* out = partials + ((int64_t)b * gridDim.y + blockIdx.y) * 2;
+        out[0] = a1;
+        out[1] = a2;
+    }
 }

@@ -419,7 +419,7 @@ static int win_ring_plan(int max_lds_bytes, int64_t* solve_lds) {
 }
 
 static int win_plan(const char* who, int nlat, int max_lds_bytes, int max_tris, int tri_slab, FemPlan* P) {
-    if (tri_slab < 0 || (tri_slab & 31)) return fail_as(GADAPT_FEM_E_BADARG, who, "tri_slab must be 0 or a positive multiple of 32");
+    if (tri_slab < 0 || (tri_slab & 31)) return fem_fail_as(GADAPT_FEM_E_BADARG, who, "tri_slab must be 0 or a positive multiple of 32");
     int rc = win_ring_plan(max_lds_bytes, &P->solve_lds);
     if (rc) return rc;
     // the slab: acc and the mask share the budget

@@ -42,11 +42,14 @@ def hot_path_opt(**overrides) -> dict:
         # 26 x 26; 'window': the windowed band solve, up to 81 x 81
         'fem_band': 'lds',
         # not a reference key: the form of the two lattice walks in the backward of those tails.  'lane': a lane per node and per
-        # triangle; 'wave': a wave each (gadapt_fem_backward_wave), the same gradient bit for bit
+        # triangle; 'wave': a wave each (gadapt_fem_backward_wave), the same gradient bit for bit.  backFEM_2D's mesh descent
+        # reads it too (mesh_descent_2d(adjoint=...), gadapt_fem_descend_wave)
         'fem_adjoint': 'lane',
         # not a reference key: the form of the load vector and the lattice evaluation in the forward of those tails, on
         # fem_band='lds'.  'lane': a lane per node and five lattice points per lane; 'wave': a wave per node and per chunk of the
-        # lattice (gadapt_fem_forward_wave), the same coeffs, factor and sol bit for bit.  'wave' with fem_band='window' is refused
+        # lattice (gadapt_fem_forward_wave), the same coeffs, factor and sol bit for bit.  'wave' with fem_band='window' is refused.
+        # The evaluation (evaluate_model_fine, eval_grid_MMPDE_MA: poisson_eval_errors(forward=...), gadapt_fem_eval_errors_wave)
+        # and backFEM_2D's mesh descent (mesh_descent_2d(forward=...)) read it too, with the same error norms and meshes
         'fem_forward': 'lane',
         # not a reference key: loss_type='pde_loss' on 1-D Poisson models (torch_FEM_1D per mesh, fem1d.gnn_pde_tail_1d).  False:
         # such a model is refused, as before the tail was built

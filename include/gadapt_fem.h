@@ -270,6 +270,22 @@ int gadapt_fem_modular_forward_wave(int n_meshes, int n_nodes, int n_tris, const
                                     const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int reduction, float* rhs,
                                     float* coeffs, float* lfac, float* sol, float* loss, float* g_sol, void* stream);
 
+/* gadapt_fem_eval_errors on the wave-parallel kernels (fem_forward='wave' in the Python evaluation), resident band only, five
+ * launches: the wave load vector, the factor launch as it is, the wave evaluation into sol_work, then fem_eval_err_kernel's
+ * reduction reading sol_work (fem_err_lattice_kernel: the same cut of the lattice into chunks and lanes, the same statements,
+ * the same butterfly and wave order), then the sum of the chunk partials as it is.
+ *   sol_work [B * nlat * nlat]  caller-owned work buffer, no initialisation needed.  On this route sol DOES reach memory (40 KB a
+ *                               mesh at nlat 101); gadapt_fem_eval_errors still never writes it.
+ * The other arguments, the checks, their order and the refusals are gadapt_fem_eval_errors's, under this entry point's name;
+ * a NULL sol_work is refused where a NULL partials or err is (after the LDS checks).  sol_work holds gadapt_fem_forward's sol
+ * bit for bit, so rhs, coeffs, partials and err are gadapt_fem_eval_errors's, bit for bit, in any batch.  No float atomics.
+ * Added without changing GADAPT_FEM_ABI (no existing signature changed). */
+int gadapt_fem_eval_errors_wave(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                                const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr, const int32_t* nt_idx,
+                                const int32_t* gptr, const float* gpar, const float* x, const float* lat_x, const float* lat_y, int nlat,
+                                int max_lds_bytes, int max_tris, float* rhs, float* coeffs, float* lfac, float* sol_work, float* partials,
+                                float* err, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ 1-D tails
  * Differentiable 1-D P1 FEM of the reference's modular loss (firedrake_difFEM/difFEM_1d.py): semi-implicit Burgers steps
  * (torch_FEM_Burgers_1D, get_Burgers_initial_coeffs) and Poisson (torch_FEM_1D), with the reference's trapezoid inner
@@ -414,6 +430,21 @@ int gadapt_fem_descend(int n_meshes, int n_nodes, int n_tris, const int32_t* met
                        const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int epochs, float lr, float* rhs, float* coeffs,
                        float* lfac, float* sol, float* loss, float* g_sol, float* gc, float* mu, float* tgrad, float* gx,
                        float* loss_hist, float* mesh_hist, int32_t* first_tangled, float* min_area, int8_t* sign, void* stream);
+
+/* gadapt_fem_descend with the wave-parallel kernels in its epochs.  routes: bit 0 (GADAPT_FEM_ROUTE_WAVE_FORWARD) runs an
+ * epoch's forward as gadapt_fem_modular_forward_wave does, bit 1 (GADAPT_FEM_ROUTE_WAVE_ADJOINT) its backward as
+ * gadapt_fem_backward_wave does; any other bit is GADAPT_FEM_E_BADARG, refused first.  routes == 0 is gadapt_fem_descend.  The
+ * other arguments and the refusals are gadapt_fem_descend's, in its order, under this entry point's name where that one's
+ * appears.  Every output has gadapt_fem_descend's bits for every value of routes.  Added without changing GADAPT_FEM_ABI. */
+#define GADAPT_FEM_ROUTE_WAVE_FORWARD 1
+#define GADAPT_FEM_ROUTE_WAVE_ADJOINT 2
+int gadapt_fem_descend_wave(int n_meshes, int n_nodes, int n_tris, const int32_t* meta, const int32_t* cells, const int32_t* node_mesh,
+                            const int32_t* tri_mesh, const int32_t* int_idx, const int32_t* int_node, const int32_t* nt_ptr,
+                            const int32_t* nt_idx, const int32_t* gptr, const float* gpar, float* x, const float* x_ref,
+                            const float* lat_x, const float* lat_y, int nlat, int max_lds_bytes, int max_tris, int epochs, float lr,
+                            float* rhs, float* coeffs, float* lfac, float* sol, float* loss, float* g_sol, float* gc, float* mu,
+                            float* tgrad, float* gx, float* loss_hist, float* mesh_hist, int32_t* first_tangled, float* min_area,
+                            int8_t* sign, int routes, void* stream);
 
 /* 1-D.  Epoch j: gadapt_fem1d_poisson_forward, the seed launch (loss [B] = torch.trapezoid((sol - u_true)^2, pts), the loss of
  * gradient_meshpoints_1D's PDE_loss_direct_L2, and g_sol [B,P] = d loss / d sol), gadapt_fem1d_poisson_backward, the step.
